@@ -2,7 +2,7 @@
 """bench.py — headline benchmark of the hot path: TaylorPoly mul f64 (dense truncated N-d
 polynomial product, src/multivariate_taylor.rs:971-1072) in GMAC/s on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|small]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|small] [--dump-outputs DIR]
 
 A "step" is one full product z = x (*) y of the workload with x, y already resident in HBM
 (synthetic splitmix64 inputs, SURVEY §8d).  N > 1: one process per GPU (torchrun / RANK env);
@@ -134,6 +134,35 @@ def cpu_baseline_all_cores(shape, x, y, max_threads=64):
         "sample": f"leading-axis output slabs k0 in [{slabs[0]}, {slabs[-1]}] of the same product, one per thread "
                   f"({macs:.3e} MACs, {wall:.1f} s wall, host has {os.cpu_count()} cores)",
     }
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all, .npy headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each {name: array} of the timed path's last step as out_dir/<name>.npy (float32 stays float32, the
+    rest is written as float64), so that two builds can be compared output for output.  An array larger than its share of
+    DUMP_BUDGET_BYTES is replaced by a fixed sample, the same in every run: the flat (row-major) indices
+    np.random.default_rng(DUMP_SAMPLE_SEED).choice(size, k, replace=False), sorted ascending, written as a 1-d array of k
+    values.  Returns what was written, for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    header = 4096  # generous bound on one .npy header
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        rec = {"file": name + ".npy", "shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes + header > share:
+            n, k = a.size, (share - header) // a.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+            a = a.reshape(-1)[idx]
+            rec["sample"] = (f"{k} of {n} elements: flat indices np.random.default_rng({DUMP_SAMPLE_SEED}).choice({n}, {k}, "
+                             "replace=False), sorted")
+        np.save(os.path.join(out_dir, rec["file"]), a)
+        written[name] = rec
+    return {"dir": out_dir, "arrays": written}
 
 
 PROFILE_ROUNDS = ("r06", "r05", "r04", "r03", "r02", "r01")  # newest first
@@ -438,7 +467,11 @@ def main():
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end seconds of the NeurIPS'23 programs (N = 1 only)")
     ap.add_argument("--conv-mode", type=int, default=0, help="0 auto, 1 reference-order kernel, 2 tiled kernel")
     ap.add_argument("--no-clock", action="store_true", help="do not sample the shader clock under load (rocm-smi)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the product of the last timed step to DIR/z.npy (float64; a fixed sample above 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # (before anything initialises the GPU: see start_clock_helper / ensure_oracle — nothing below spawns a process)
     have_oracle = ensure_oracle() if int(os.environ.get("RANK", "0")) == 0 else os.path.exists(os.path.join(ROOT, "oracle", "liborc.so"))
@@ -577,6 +610,8 @@ def main():
             during = timed_loop_samples(clock_helper, clock_helper.stdout.readline())
         except Exception:  # noqa: BLE001
             during = None
+    # --dump-outputs: the product of the last timed step, copied before anything below runs the product again
+    last_z = z.cpu().numpy() if args.dump_outputs and rank == 0 else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -710,6 +745,8 @@ def main():
         out["e2e"] = e2e_seconds(oracle_available=have_oracle)
         if out["e2e"].pop("parity_failed"):
             out["parity_failed"] = True
+    if last_z is not None:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, {"z": last_z})
     bad = bool(out.get("parity_failed")) or any(t < 0 for t in kern_ms)
     if rank == 0:
         print(json.dumps(out))

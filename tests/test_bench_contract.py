@@ -77,3 +77,44 @@ def test_contract_keys_are_present():
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"steps"', '"warmup"', '"ms_per_step"', '"higher_is_better"', '"scaling"',
                 '"vs_baseline"', '"dtype"', '"data"', '"config"', '"roofline"', '"cpu_baseline"', '"bound"', '"achieved"', '"peak"', '"frac"', '"traffic"'):
         assert key in src, key
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_writes_the_arrays_within_budget(tmp_path, monkeypatch):
+    import numpy as np
+
+    bench = _bench_module()
+    small = np.arange(24, dtype=np.float64).reshape(2, 3, 4)
+    rec = bench.dump_outputs(str(tmp_path / "a"), {"z": small})
+    assert np.array_equal(np.load(tmp_path / "a" / "z.npy"), small) and "sample" not in rec["arrays"]["z"]
+
+    # an array above its share of the budget becomes a fixed sample: the same values in every run, within the budget
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 64 * 1024)
+    big = np.random.default_rng(7).random((64, 64, 8))
+    for d in ("b", "c"):
+        rec = bench.dump_outputs(str(tmp_path / d), {"z": big, "w": big.astype(np.float32)})
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_BUDGET_BYTES
+    for name, dtype in (("z", np.float64), ("w", np.float32)):
+        got = np.load(tmp_path / "b" / f"{name}.npy")
+        assert got.dtype == dtype and got.ndim == 1 and 0 < got.size < big.size and "sample" in rec["arrays"][name]
+        assert np.array_equal(got, np.load(tmp_path / "c" / f"{name}.npy"))
+        k = got.size
+        idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(big.size, k, replace=False))
+        assert np.array_equal(got, big.astype(dtype).reshape(-1)[idx])
+
+
+def test_dump_outputs_takes_the_last_timed_step():
+    """The snapshot is taken after the timed loop and before the untimed steps (clock sample, CPU parity) run the product again."""
+    src = _bench_source()
+    main = src[src.index("def main():"):]
+    timed = main.index("for _ in range(args.steps):")
+    snap = main.index("last_z = z.cpu()")
+    assert timed < snap < main.index("sclk_under_load(") and snap < main.index("cpu_baseline(shape")
