@@ -224,9 +224,7 @@ struct Runtime {
     bool defer = true;             // GFT_DEFER=0 / "defer": one launch per elementwise operation (A/B, bisecting)
     size_t horner_loop_max = (size_t)1 << 40;  // elements of the final tensor up to which the whole Horner loop is one launch
     static constexpr bool fuse_horner = true;  // (the fused / speculative Horner loop; the generic loop is horner_exact)
-    static constexpr bool div2d = true;  // (the last two axes of the division recurrence in one launch; the host-driven recursion is the fallback for shapes outside the kernels' domains)
     bool div_wavefront = true;     // GFT_DIV_WAVEFRONT=0 / "div_wavefront": the blocked recurrence instead of the one-launch row wavefront
-    static constexpr bool rows_wavefront = true;  // (rank-2 recurrences with rows > 64 as a coefficient-level wavefront)
     bool exp_right = true;         // GFT_EXP_RIGHT=0 / "exp_right": left-looking exp steps everywhere (A/B and bisecting)
     // Shallow products (round 4): a plain product whose outputs receive at most this many terms each (prod_i min(xs_i, ys_i):
     // one operand is a stencil — the substitutions of `+~ Binomial(other, p)` statements are 3-6 coefficients) runs on the

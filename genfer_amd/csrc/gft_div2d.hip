@@ -688,29 +688,7 @@ template bool K<EIv>::div_1d(hipStream_t, const double*, size_t, unsigned, const
 // on all CUs.  A row product keeps one coefficient per lane: the source row's coefficient j reaches all lanes by
 // v_readlane, the divisor row slides by one DPP wave shift per step (zeros enter at lane 0: the truncation).  Same
 // operations in the same order per coefficient as the host-driven recursion => the same bits (GFT_DIV_WAVEFRONT=0 A/B).
-struct DivWfArgs {
-    int L;                    // leading axes (tasks); the last axis is the row
-    unsigned n[3], m[3], xn[3];   // extents of res / ys / xs on the leading axes
-    unsigned nr, mr, xnr;     // row lengths
-    size_t rstr[3], ystr[3], xstr[3];  // strides of the leading axes (rows are contiguous)
-    unsigned ntasks;
-    unsigned* flags;          // [rows] row done; zeroed before the launch
-    unsigned* counter;        // next task; zeroed before the launch
-    // log_mode (mt:1335-1386): res = log(xs) for the slabs k0 >= 1 (slab 0, a log one dimension down, is the caller's).
-    //   level 0:  S = sum_{j0 = max(k0 + 1 - xn0, 1)}^{k0 - 1} sum_{j' lexicographic} rowproduct(xs[k0 - j0, j'], j0 * res[j0, k - j'])
-    //             r = (-S) + k0 * xs[K]
-    //   levels >= 1 and the row division: the division of the slab by xs[0] — as above with ys = xs[0], on the rows q of
-    //             the slab's own quotient (kept in `qb`); finally res[K] = q / k0.
-    // log_mode == 2: res = exp(xs) for the slabs k0 >= 1 (mt:1271-1300; slab 0, an exp one dimension down, is the caller's):
-    //   res[K] = ( sum_{j0 = 1}^{min(k0, xn0 - 1)} sum_{j' lexicographic} rowproduct(j0 * xs[j0, j'], res[k0 - j0, k - j']) ) / k0
-    int log_mode;
-    int rev;                  // log_mode 2: the source SLABS in descending j0 — the order in which they become available (1e-10 contract,
-                              // see k_rows_wavefront); set by the caller where it would otherwise take the right-looking tiled form
-    const unsigned* order;    // task t works on row order[t] of the task rows (anti-diagonal order, see dwf_order); null: t
-    int pack;                 // rows <= 32: two source rows per wave (GFT_DWF_PACK=0: one, for A/B)
-    double* qb;               // log_mode: the quotient rows before the division by k0 (same layout as res)
-    size_t qbp;
-};
+// (the launch arguments: DivWfArgs in gft_wavefront_plan.hpp)
 
 template <class E>
 __device__ inline typename E::V ld_coherent(const double* p, size_t plane, size_t i);
@@ -766,7 +744,6 @@ struct DwfCfg {
 // coefficient is an 8-byte store); the per-row flags (release / acquire) remain the authority when a row keeps looking
 // unwritten, so a genuine coefficient of that pattern only costs time.
 constexpr unsigned long long DWF_EMPTY = 0x7ff8dead0badf00dull;
-static const int dwf_pack = 1;
 __global__ void __launch_bounds__(256) k_fill_bits(double* p, size_t n, unsigned long long bits) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         reinterpret_cast<unsigned long long*>(p)[i] = bits;
@@ -1358,49 +1335,6 @@ __global__ void __launch_bounds__(64 * QNW) k_div_wavefront_q(const double* __re
     }
 }
 
-template <class E>
-static void launch_dwf(hipStream_t st, unsigned blocks, const double* xs, size_t xp, const double* ys, size_t yp, double* res, size_t rp, const DivWfArgs& g) {
-    // f64 rows of 33 .. 64 coefficients: four source rows per wave, four coefficients per lane (k_div_wavefront_q)
-    static const int quad_on = 1;
-    // (where a row has thousands of source rows — 64^3 div 4.8 -> 4.0 ms, 24^4 7.7 -> 6.2; thin or small quotients, whose time is the
-    // chain of rows, lose to its larger batches: 1000 x 32 6.2 -> 8.0 ms, 32^3 0.53 -> 0.62 — they keep one or two rows per wave)
-    size_t max_sources = 1;
-    for (int a = 0; a < g.L; ++a) max_sources *= g.n[a];
-    if constexpr (E::W == 1) {
-        if (quad_on && g.nr >= 8 && g.nr <= 64 && (max_sources >= 2048 || quad_on == 2)) {
-            const bool wide = g.nr > 32;
-            const size_t lds = wide ? sizeof(double) * (2 * QCfg<16>::QS * 64 + (size_t)QNW * QCfg<16>::NG * QCfg<16>::QSTG)
-                                    : sizeof(double) * (2 * QCfg<8>::QS * 64 + (size_t)QNW * QCfg<8>::NG * QCfg<8>::QSTG);
-            static bool attr_set = false;
-            bool ok = true;
-            if (!attr_set) {
-                auto set = [](const void* f) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess; };
-                ok = set((const void*)k_div_wavefront_q<1, 16>) && set((const void*)k_div_wavefront_q<2, 16>) && set((const void*)k_div_wavefront_q<3, 16>) &&
-                     set((const void*)k_div_wavefront_q<1, 8>) && set((const void*)k_div_wavefront_q<2, 8>) && set((const void*)k_div_wavefront_q<3, 8>);
-                if (!ok) (void)hipGetLastError();
-                attr_set = ok;
-            }
-            if (ok) {
-                const dim3 qgrid(blocks), qblock(64 * QNW);
-                if (wide) {
-                    if (g.L == 1) GFT_LAUNCH((k_div_wavefront_q<1, 16>), qgrid, qblock, lds, st, xs, xp, ys, yp, res, rp, g);
-                    else if (g.L == 2) GFT_LAUNCH((k_div_wavefront_q<2, 16>), qgrid, qblock, lds, st, xs, xp, ys, yp, res, rp, g);
-                    else GFT_LAUNCH((k_div_wavefront_q<3, 16>), qgrid, qblock, lds, st, xs, xp, ys, yp, res, rp, g);
-                } else {
-                    if (g.L == 1) GFT_LAUNCH((k_div_wavefront_q<1, 8>), qgrid, qblock, lds, st, xs, xp, ys, yp, res, rp, g);
-                    else if (g.L == 2) GFT_LAUNCH((k_div_wavefront_q<2, 8>), qgrid, qblock, lds, st, xs, xp, ys, yp, res, rp, g);
-                    else GFT_LAUNCH((k_div_wavefront_q<3, 8>), qgrid, qblock, lds, st, xs, xp, ys, yp, res, rp, g);
-                }
-                return;
-            }
-        }
-    }
-    const dim3 grid(blocks), block(64 * DwfCfg<E>::NW);
-    if (g.L == 1) GFT_LAUNCH((k_div_wavefront<E, 1>), grid, block, 0, st, xs, xp, ys, yp, res, rp, g);
-    else if (g.L == 2) GFT_LAUNCH((k_div_wavefront<E, 2>), grid, block, 0, st, xs, xp, ys, yp, res, rp, g);
-    else GFT_LAUNCH((k_div_wavefront<E, 3>), grid, block, 0, st, xs, xp, ys, yp, res, rp, g);
-}
-
 // Claim order of the tasks.  Any order in which a row comes after the rows it reads is deadlock-free (a claimed task only
 // waits for tasks claimed before it, and those belong to running workgroups).  Lexicographic order has every row wait for
 // the row claimed just before it — (k0, k1 - 1) is the LAST source of (k0, k1), so the rows of a slab run as a chain of
@@ -1415,10 +1349,9 @@ static std::map<DwfOrderKey, unsigned*>& dwf_orders() {
     static std::map<DwfOrderKey, unsigned*> m;
     return m;
 }
-static const int dwf_diag = 1;
 // rows (k0 >= first, k1, ..) of an n[0] x .. x n[L-1] grid, task-relative index (row index - first * rows per slab)
 static const unsigned* dwf_order(int L, const unsigned* n, unsigned first) {
-    if (!dwf_diag || L < 2) return nullptr;
+    if (L < 2) return nullptr;
     DwfOrderKey key;
     std::memset(&key, 0, sizeof(key));
     key.L = (unsigned)L;
@@ -1463,144 +1396,6 @@ void dwf_release_orders() {
     for (auto& kv : dwf_orders()) (void)hipFree(kv.second);
     dwf_orders().clear();
 }
-
-template <class E>
-bool K<E>::div_wavefront(hipStream_t st, const double* xs, size_t x_plane, const unsigned* xshape, const double* ys, size_t y_plane,
-                         const unsigned* yshape, double* res, size_t r_plane, const unsigned* rshape, int nd, unsigned* flags_and_counter) {
-    if (nd < 2 || nd > 4) return false;
-    DivWfArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.L = nd - 1;
-    g.pack = dwf_pack;
-    g.nr = rshape[nd - 1];
-    g.mr = yshape[nd - 1];
-    g.xnr = xshape[nd - 1];
-    if (g.nr < 2 || g.nr > 64 || g.mr > g.nr || g.xnr > g.nr) return false;
-    size_t rs = g.nr, ysd = g.mr, xsd = g.xnr, ntasks = 1;
-    for (int a = g.L - 1; a >= 0; --a) {
-        g.n[a] = rshape[a];
-        g.m[a] = yshape[a];
-        g.xn[a] = xshape[a];
-        if (g.m[a] > g.n[a] || g.xn[a] > g.n[a] || g.n[a] == 0) return false;
-        g.rstr[a] = rs;
-        g.ystr[a] = ysd;
-        g.xstr[a] = xsd;
-        rs *= rshape[a];
-        ysd *= yshape[a];
-        xsd *= xshape[a];
-        ntasks *= rshape[a];
-    }
-    if (ntasks > 0x7fffffffu) return false;
-    g.ntasks = (unsigned)ntasks;
-    g.flags = flags_and_counter;
-    g.counter = flags_and_counter + ntasks;
-    g.order = dwf_order(g.L, g.n, 0);
-    // enough waves to keep every SIMD busy with several tasks; all of them persistent (they claim tasks until none is left)
-    // persistent workgroups (they claim tasks until none is left): a few per CU so that the SIMDs stay busy while some wait
-    const unsigned blocks = (unsigned)std::min<size_t>(ntasks, (size_t)256 * 2);
-    for (int pl = 0; pl < E::W; ++pl) {
-        const size_t nel = ntasks * g.nr;
-        GFT_LAUNCH(k_fill_bits, dim3((unsigned)std::min<size_t>((nel + 255) / 256, 2048)), dim3(256), 0, st, res + (size_t)pl * r_plane, nel, DWF_EMPTY);
-    }
-    launch_dwf<E>(st, blocks, xs, x_plane, ys, y_plane, res, r_plane, g);
-    return true;
-}
-// res[1..] = log(xs)[1..] (slabs k0 >= 1; mt:1335-1386) as the same row wavefront.  `qbuf`: a tensor like res for the slab
-// quotients before the division by k0; `flags_and_counter`: (rows of res + 1) zeroed words.
-template <class E>
-bool K<E>::log_wavefront(hipStream_t st, const double* xs, size_t x_plane, const unsigned* xshape, double* res, size_t r_plane,
-                         const unsigned* rshape, int nd, double* qbuf, size_t q_plane, unsigned* flags_and_counter) {
-    if (nd < 2 || nd > 4) return false;
-    DivWfArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.L = nd - 1;
-    g.pack = dwf_pack;
-    g.log_mode = 1;
-    g.nr = rshape[nd - 1];
-    g.xnr = xshape[nd - 1];
-    g.mr = g.xnr;  // the divisor of the slab divisions is xs[0]
-    if (g.nr < 2 || g.nr > 64 || g.xnr > g.nr || rshape[0] < 2) return false;
-    size_t rs = g.nr, xsd = g.xnr, rows = 1;
-    for (int a = g.L - 1; a >= 0; --a) {
-        g.n[a] = rshape[a];
-        g.xn[a] = xshape[a];
-        g.m[a] = xshape[a];
-        if (g.xn[a] > g.n[a] || g.n[a] == 0 || g.xn[a] == 0) return false;
-        g.rstr[a] = rs;
-        g.xstr[a] = xsd;
-        g.ystr[a] = xsd;
-        rs *= rshape[a];
-        xsd *= xshape[a];
-        rows *= rshape[a];
-    }
-    const size_t slab_rows = rows / rshape[0], ntasks = rows - slab_rows;
-    if (rows > 0x7fffffffu) return false;
-    g.ntasks = (unsigned)ntasks;
-    g.flags = flags_and_counter;
-    g.counter = flags_and_counter + rows;
-    g.order = dwf_order(g.L, g.n, 1);
-    g.qb = qbuf;
-    g.qbp = q_plane;
-    const size_t slab_el = slab_rows * g.nr, nel = ntasks * g.nr;
-    for (int pl = 0; pl < E::W; ++pl) {
-        const unsigned fb = (unsigned)std::min<size_t>((nel + 255) / 256, 2048);
-        GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, res + (size_t)pl * r_plane + slab_el, nel, DWF_EMPTY);
-        GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, qbuf + (size_t)pl * q_plane + slab_el, nel, DWF_EMPTY);
-    }
-    const unsigned blocks = (unsigned)std::min<size_t>(ntasks, (size_t)256 * 2);
-    launch_dwf<E>(st, blocks, xs, x_plane, xs, x_plane, res, r_plane, g);
-    return true;
-}
-// res[1..] = exp(xs)[1..] (slabs k0 >= 1; mt:1271-1300) as the same row wavefront: no division, the row sum / k0.
-template <class E>
-bool K<E>::exp_wavefront(hipStream_t st, const double* xs, size_t x_plane, const unsigned* xshape, double* res, size_t r_plane,
-                         const unsigned* rshape, int nd, unsigned* flags_and_counter, int arrival_order) {
-    if (nd < 2 || nd > 4) return false;
-    DivWfArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.rev = arrival_order;
-    g.L = nd - 1;
-    g.pack = dwf_pack;
-    g.log_mode = 2;
-    g.nr = rshape[nd - 1];
-    g.xnr = xshape[nd - 1];
-    g.mr = g.xnr;
-    if (g.nr < 2 || g.nr > 64 || g.xnr > g.nr || rshape[0] < 2) return false;
-    size_t rs = g.nr, xsd = g.xnr, rows = 1;
-    for (int a = g.L - 1; a >= 0; --a) {
-        g.n[a] = rshape[a];
-        g.xn[a] = xshape[a];
-        g.m[a] = xshape[a];
-        if (g.xn[a] > g.n[a] || g.n[a] == 0 || g.xn[a] == 0) return false;
-        g.rstr[a] = rs;
-        g.xstr[a] = xsd;
-        g.ystr[a] = xsd;
-        rs *= rshape[a];
-        xsd *= xshape[a];
-        rows *= rshape[a];
-    }
-    const size_t slab_rows = rows / rshape[0], ntasks = rows - slab_rows;
-    if (rows > 0x7fffffffu) return false;
-    g.ntasks = (unsigned)ntasks;
-    g.flags = flags_and_counter;
-    g.counter = flags_and_counter + rows;
-    g.order = dwf_order(g.L, g.n, 1);
-    const size_t slab_el = slab_rows * g.nr, nel = ntasks * g.nr;
-    for (int pl = 0; pl < E::W; ++pl)
-        GFT_LAUNCH(k_fill_bits, dim3((unsigned)std::min<size_t>((nel + 255) / 256, 2048)), dim3(256), 0, st, res + (size_t)pl * r_plane + slab_el, nel, DWF_EMPTY);
-    const unsigned blocks = (unsigned)std::min<size_t>(ntasks, (size_t)256 * 2);
-    launch_dwf<E>(st, blocks, xs, x_plane, xs, x_plane, res, r_plane, g);
-    return true;
-}
-template bool K<EF64>::exp_wavefront(hipStream_t, const double*, size_t, const unsigned*, double*, size_t, const unsigned*, int, unsigned*, int);
-template bool K<EIv>::exp_wavefront(hipStream_t, const double*, size_t, const unsigned*, double*, size_t, const unsigned*, int, unsigned*, int);
-template bool K<EF64>::log_wavefront(hipStream_t, const double*, size_t, const unsigned*, double*, size_t, const unsigned*, int, double*, size_t, unsigned*);
-template bool K<EIv>::log_wavefront(hipStream_t, const double*, size_t, const unsigned*, double*, size_t, const unsigned*, int, double*, size_t, unsigned*);
-
-template bool K<EF64>::div_wavefront(hipStream_t, const double*, size_t, const unsigned*, const double*, size_t, const unsigned*, double*, size_t,
-                                     const unsigned*, int, unsigned*);
-template bool K<EIv>::div_wavefront(hipStream_t, const double*, size_t, const unsigned*, const double*, size_t, const unsigned*, double*, size_t,
-                                    const unsigned*, int, unsigned*);
 
 template <class E>
 bool K<E>::div_2d(hipStream_t st, const double* x, size_t x_plane, unsigned nx1, unsigned nx2, size_t x_rstride, const double* y,
@@ -1687,17 +1482,7 @@ template bool K<EIv>::div_2d(hipStream_t, const double*, size_t, unsigned, unsig
 // `rev` takes the source rows in descending j0 — the oldest result row first, the order in which they become available,
 // the right-looking tiled form's order of arrival — under that form's contract (1e-10, measured ~1e-15: all terms of an
 // exponential's recurrence carry the same sign pattern as the series itself); the caller sets it exactly where it would
-// otherwise take the right-looking tiled form (f64, `exp_right`).
-struct RowsWfArgs {
-    unsigned n0, nr, m0, mr, xn0, xnr;   // rows / row lengths of res, ys (mode 0), xs
-    unsigned nseg, ntasks, first_row;
-    int mode;
-    unsigned* flags;                     // [n0 * nseg] segment stored; zeroed before the launch
-    unsigned* counter;                   // next task; zeroed before the launch
-    double* qb;                          // mode 1: the quotient rows before the division by k0
-    size_t qbp;
-    int rev;                             // mode 2: take the source rows in DESCENDING j0 (see k_rows_wavefront)
-};
+// otherwise take the right-looking tiled form (f64, `exp_right`).  (The launch arguments: RowsWfArgs in gft_wavefront_plan.hpp.)
 
 // inner += sum_{i < 64} a[i] * bwin[64 + l - i]   (bwin = {bprev[64], bcur[64]}), ascending i — one chunk of a row product.
 // jbase = 64 t (the chunk's first j), c = the lane's coefficient, alen / blen = the rows' lengths: positions outside the
@@ -1942,54 +1727,6 @@ __global__ void __launch_bounds__(64 * DwfCfg<E>::NW) k_rows_wavefront(const dou
     }
 }
 
-// mode 0: res = xs / ys;  1: rows >= 1 of log(xs) (qbuf: a tensor like res);  2: rows >= 1 of exp(xs).  Rank 2, rows of
-// 65 .. 4096 coefficients.  `flags_and_counter`: n0 * ceil(nr / 64) + 1 zeroed words.  false: outside the kernel's domain,
-// nothing launched.
-template <class E>
-bool K<E>::rows_wavefront(hipStream_t st, int mode, const double* xs, size_t x_plane, const unsigned* xshape, const double* ys, size_t y_plane,
-                          const unsigned* yshape, double* res, size_t r_plane, const unsigned* rshape, double* qbuf, size_t q_plane,
-                          unsigned* flags_and_counter) {
-    RowsWfArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.rev = (mode & 4) ? 1 : 0;  // mode 2 | 4: exp with the source rows in descending order (1e-10 contract)
-    mode &= 3;
-    g.mode = mode;
-    g.n0 = rshape[0];
-    g.nr = rshape[1];
-    g.xn0 = xshape[0];
-    g.xnr = xshape[1];
-    g.m0 = mode == 0 ? yshape[0] : xshape[0];
-    g.mr = mode == 0 ? yshape[1] : xshape[1];
-    if (g.nr <= 64 || g.nr > 4096 || g.n0 == 0 || g.xn0 == 0 || g.xnr == 0 || g.m0 == 0 || g.mr == 0) return false;
-    if (g.xn0 > g.n0 || g.xnr > g.nr || g.m0 > g.n0 || g.mr > g.nr) return false;
-    g.first_row = mode == 0 ? 0u : 1u;
-    if (g.n0 <= g.first_row) return false;
-    g.nseg = (g.nr + 63u) / 64u;
-    const size_t ntasks = (size_t)(g.n0 - g.first_row) * g.nseg;
-    if (ntasks > 0x7fffffffu) return false;
-    g.ntasks = (unsigned)ntasks;
-    g.flags = flags_and_counter;
-    g.counter = flags_and_counter + (size_t)g.n0 * g.nseg;
-    g.qb = qbuf;
-    g.qbp = q_plane;
-    if (mode == 1 && !qbuf) return false;
-    const size_t skip = (size_t)g.first_row * g.nr, nel = (size_t)(g.n0 - g.first_row) * g.nr;
-    for (int pl = 0; pl < E::W; ++pl) {
-        const unsigned fb = (unsigned)std::min<size_t>((nel + 255) / 256, 2048);
-        GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, res + (size_t)pl * r_plane + skip, nel, DWF_EMPTY);
-        if (mode == 1) GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, qbuf + (size_t)pl * q_plane + skip, nel, DWF_EMPTY);
-    }
-    // persistent workgroups (they claim tasks until none is left): two per CU so that the SIMDs stay busy while some wait
-    const unsigned blocks = (unsigned)std::min<size_t>(ntasks, (size_t)256 * 2);
-    GFT_LAUNCH((k_rows_wavefront<E>), dim3(blocks), dim3(64 * DwfCfg<E>::NW), 0, st, xs, x_plane, mode == 0 ? ys : xs, mode == 0 ? y_plane : x_plane,
-               res, r_plane, g);
-    return true;
-}
-template bool K<EF64>::rows_wavefront(hipStream_t, int, const double*, size_t, const unsigned*, const double*, size_t, const unsigned*, double*, size_t,
-                                      const unsigned*, double*, size_t, unsigned*);
-template bool K<EIv>::rows_wavefront(hipStream_t, int, const double*, size_t, const unsigned*, const double*, size_t, const unsigned*, double*, size_t,
-                                     const unsigned*, double*, size_t, unsigned*);
-
 // ------------------------------------------------------------------------------------------
 // Quotients / logarithms of rank 3 and 4 with LONG rows (round 6): the segment wavefront with leading axes
 // ------------------------------------------------------------------------------------------
@@ -2070,19 +1807,7 @@ __device__ inline typename E::V seg_chunk_mac_sa(typename E::V inner, typename E
     }
     return inner;
 }
-struct SegWfArgs {
-    int L;
-    unsigned n[3], m[3], xn[3];
-    unsigned nr, mr, xnr;
-    size_t rstr[3], ystr[3], xstr[3];
-    unsigned nseg, sl, ntasks;    // segments per row, coefficients per segment (<= 64: rows are cut EVENLY — a 65-long row is 33 + 32, not 64 + 1)
-    unsigned* flags;              // [all rows of res][nseg], zeroed before the launch
-    unsigned* counter;
-    int log_mode;
-    const unsigned* order;        // task row t works on row order[t] of the task rows (dwf_order); null: t
-    double* qb;
-    size_t qbp;
-};
+// (the launch arguments: SegWfArgs in gft_wavefront_plan.hpp)
 template <class E, int L>
 __global__ void __launch_bounds__(64 * DwfCfg<E>::NW) k_seg_wavefront(const double* __restrict__ xs, size_t xp, const double* __restrict__ ys, size_t yp,
                                                                double* res, size_t rp, SegWfArgs g) {
@@ -2342,66 +2067,76 @@ __global__ void __launch_bounds__(64 * DwfCfg<E>::NW) k_seg_wavefront(const doub
     }
 }
 
-// mode 0: res = xs / ys; mode 1: slabs k0 >= 1 of res = log(xs) (slab 0 is the caller's; qbuf: a tensor like res).  Ranks 3 and 4,
-// rows of 65 .. 4096 coefficients.  `flags_and_counter`: (rows of res) * ceil(row length / 64) + 1 zeroed words.  false: outside
-// the kernel's domain, nothing launched.
+// The recurrence wavefront the plan names (plan_wavefront: the domain is checked there): the result rows it computes start
+// EMPTY, then one persistent launch.
 template <class E>
-bool K<E>::seg_wavefront(hipStream_t st, int mode, const double* xs, size_t x_plane, const unsigned* xshape, const double* ys, size_t y_plane,
-                         const unsigned* yshape, double* res, size_t r_plane, const unsigned* rshape, int nd, double* qbuf, size_t q_plane,
-                         unsigned* flags_and_counter) {
-    if (nd < 3 || nd > 4 || (mode != 0 && mode != 1)) return false;
-    SegWfArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.L = nd - 1;
-    g.log_mode = mode;
-    g.nr = rshape[nd - 1];
-    g.xnr = xshape[nd - 1];
-    g.mr = mode == 0 ? yshape[nd - 1] : g.xnr;
-    if (g.nr <= 64 || g.nr > 4096 || g.mr == 0 || g.xnr == 0 || g.mr > g.nr || g.xnr > g.nr) return false;
-    if (mode == 1 && (!qbuf || rshape[0] < 2)) return false;
-    size_t rs = g.nr, ysd = g.mr, xsd = g.xnr, rows = 1;
-    for (int a = g.L - 1; a >= 0; --a) {
-        g.n[a] = rshape[a];
-        g.xn[a] = xshape[a];
-        g.m[a] = mode == 0 ? yshape[a] : xshape[a];
-        if (g.m[a] > g.n[a] || g.xn[a] > g.n[a] || g.n[a] == 0 || g.m[a] == 0 || g.xn[a] == 0) return false;
-        g.rstr[a] = rs;
-        g.ystr[a] = ysd;
-        g.xstr[a] = xsd;
-        rs *= rshape[a];
-        ysd *= g.m[a];
-        xsd *= xshape[a];
-        rows *= rshape[a];
-    }
-    g.nseg = (g.nr + 63u) / 64u;
-    g.sl = (g.nr + g.nseg - 1u) / g.nseg;  // even cut: the work of a row is nseg (nseg + 1) / 2 chunk products of sl steps each
-    const size_t slab_rows = rows / rshape[0];
-    const size_t task_rows = mode == 1 ? rows - slab_rows : rows;
-    const size_t ntasks = task_rows * g.nseg;
-    if (rows * g.nseg > 0x7fffffffu || task_rows == 0) return false;
-    g.ntasks = (unsigned)ntasks;
-    g.flags = flags_and_counter;
-    g.counter = flags_and_counter + rows * g.nseg;
-    g.order = dwf_order(g.L, g.n, mode == 1 ? 1u : 0u);
-    g.qb = qbuf;
-    g.qbp = q_plane;
-    const size_t skip = mode == 1 ? slab_rows * g.nr : 0, nel = task_rows * g.nr;
+void K<E>::recur_wavefront(hipStream_t st, const WfPlan& p, const double* xs, size_t x_plane, const double* ys, size_t y_plane, double* res,
+                           size_t r_plane, double* qb, size_t q_plane, unsigned* flags) {
+    const unsigned* order = nullptr;
+    if (p.family == WF_SEG) order = dwf_order(p.L, p.seg.n, p.first);
+    else if (p.family != WF_ROWS_2D) order = dwf_order(p.L, p.row.n, p.first);
+    const unsigned fb = (unsigned)std::min<size_t>((p.fill_count + 255) / 256, 2048);
     for (int pl = 0; pl < E::W; ++pl) {
-        const unsigned fb = (unsigned)std::min<size_t>((nel + 255) / 256, 2048);
-        GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, res + (size_t)pl * r_plane + skip, nel, DWF_EMPTY);
-        if (mode == 1) GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, qbuf + (size_t)pl * q_plane + skip, nel, DWF_EMPTY);
+        GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, res + (size_t)pl * r_plane + p.fill_offset, p.fill_count, DWF_EMPTY);
+        if (p.needs_qbuf) GFT_LAUNCH(k_fill_bits, dim3(fb), dim3(256), 0, st, qb + (size_t)pl * q_plane + p.fill_offset, p.fill_count, DWF_EMPTY);
     }
-    const dim3 grid((unsigned)std::min<size_t>(ntasks, (size_t)256 * 2)), block(64 * DwfCfg<E>::NW);
-    const double* yarg = mode == 0 ? ys : xs;
-    const size_t yplane = mode == 0 ? y_plane : x_plane;
-    if (g.L == 2) GFT_LAUNCH((k_seg_wavefront<E, 2>), grid, block, 0, st, xs, x_plane, yarg, yplane, res, r_plane, g);
-    else GFT_LAUNCH((k_seg_wavefront<E, 3>), grid, block, 0, st, xs, x_plane, yarg, yplane, res, r_plane, g);
-    return true;
+    auto wire = [&](auto g) {
+        g.flags = flags;
+        g.counter = flags + p.flag_words - 1;
+        g.qb = qb;
+        g.qbp = q_plane;
+        return g;
+    };
+    const dim3 grid(p.blocks), block(64 * DwfCfg<E>::NW);
+    if (p.family == WF_ROWS_2D) {
+        GFT_LAUNCH((k_rows_wavefront<E>), grid, block, 0, st, xs, x_plane, ys, y_plane, res, r_plane, wire(p.rows));
+        return;
+    }
+    if (p.family == WF_SEG) {
+        SegWfArgs g = wire(p.seg);
+        g.order = order;
+        if (p.L == 2) GFT_LAUNCH((k_seg_wavefront<E, 2>), grid, block, 0, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+        else GFT_LAUNCH((k_seg_wavefront<E, 3>), grid, block, 0, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+        return;
+    }
+    DivWfArgs g = wire(p.row);
+    g.order = order;
+    if constexpr (E::W == 1) {
+        if (p.family == WF_ROW_QUAD16 || p.family == WF_ROW_QUAD8) {
+            // the quad kernels' LDS exceeds the default limit; if it cannot be raised they stay unused (the plain row kernel runs)
+            static bool attr_set = false;
+            bool ok = true;
+            if (!attr_set) {
+                auto set = [](const void* f) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess; };
+                ok = set((const void*)k_div_wavefront_q<1, 16>) && set((const void*)k_div_wavefront_q<2, 16>) && set((const void*)k_div_wavefront_q<3, 16>) &&
+                     set((const void*)k_div_wavefront_q<1, 8>) && set((const void*)k_div_wavefront_q<2, 8>) && set((const void*)k_div_wavefront_q<3, 8>);
+                if (!ok) (void)hipGetLastError();
+                attr_set = ok;
+            }
+            if (ok) {
+                const bool wide = p.family == WF_ROW_QUAD16;
+                const size_t lds = wide ? sizeof(double) * (2 * QCfg<16>::QS * 64 + (size_t)QNW * QCfg<16>::NG * QCfg<16>::QSTG)
+                                        : sizeof(double) * (2 * QCfg<8>::QS * 64 + (size_t)QNW * QCfg<8>::NG * QCfg<8>::QSTG);
+                const dim3 qblock(64 * QNW);
+                if (wide) {
+                    if (p.L == 1) GFT_LAUNCH((k_div_wavefront_q<1, 16>), grid, qblock, lds, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+                    else if (p.L == 2) GFT_LAUNCH((k_div_wavefront_q<2, 16>), grid, qblock, lds, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+                    else GFT_LAUNCH((k_div_wavefront_q<3, 16>), grid, qblock, lds, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+                } else {
+                    if (p.L == 1) GFT_LAUNCH((k_div_wavefront_q<1, 8>), grid, qblock, lds, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+                    else if (p.L == 2) GFT_LAUNCH((k_div_wavefront_q<2, 8>), grid, qblock, lds, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+                    else GFT_LAUNCH((k_div_wavefront_q<3, 8>), grid, qblock, lds, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+                }
+                return;
+            }
+        }
+    }
+    if (p.L == 1) GFT_LAUNCH((k_div_wavefront<E, 1>), grid, block, 0, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+    else if (p.L == 2) GFT_LAUNCH((k_div_wavefront<E, 2>), grid, block, 0, st, xs, x_plane, ys, y_plane, res, r_plane, g);
+    else GFT_LAUNCH((k_div_wavefront<E, 3>), grid, block, 0, st, xs, x_plane, ys, y_plane, res, r_plane, g);
 }
-template bool K<EF64>::seg_wavefront(hipStream_t, int, const double*, size_t, const unsigned*, const double*, size_t, const unsigned*, double*, size_t,
-                                     const unsigned*, int, double*, size_t, unsigned*);
-template bool K<EIv>::seg_wavefront(hipStream_t, int, const double*, size_t, const unsigned*, const double*, size_t, const unsigned*, double*, size_t,
-                                    const unsigned*, int, double*, size_t, unsigned*);
+template void K<EF64>::recur_wavefront(hipStream_t, const WfPlan&, const double*, size_t, const double*, size_t, double*, size_t, double*, size_t, unsigned*);
+template void K<EIv>::recur_wavefront(hipStream_t, const WfPlan&, const double*, size_t, const double*, size_t, double*, size_t, double*, size_t, unsigned*);
 
 
 }  // namespace gft

@@ -10,6 +10,7 @@
 
 #include "gft_elem.hpp"
 #include "gft_launch.hpp"  // GFT_LAUNCH: every kernel launch of the library (counted, issued by the launch thread)
+#include "gft_wavefront_plan.hpp"
 
 namespace gft {
 
@@ -397,31 +398,11 @@ struct K {
     static bool div_2d(hipStream_t st, const double* x, size_t x_plane, unsigned nx1, unsigned nx2, size_t x_rstride, const double* y,
                        size_t y_plane, unsigned ny1, unsigned ny2, double* res, size_t r_plane, unsigned n1, unsigned n2, int fused,
                        unsigned log_k = 0, double* res2 = nullptr, size_t r2_plane = 0);
-    // The whole quotient res = xs / ys (ranks 2-4, rows of at most 64 coefficients) as a row wavefront in ONE launch
-    // (gft_div2d.hip): bit-identical to the host-driven recursion.  `flags_and_counter`: (rows + 1) zeroed device words.
-    // false: shape outside the kernel's domain, nothing launched.
-    static bool div_wavefront(hipStream_t st, const double* xs, size_t x_plane, const unsigned* xshape, const double* ys, size_t y_plane,
-                              const unsigned* yshape, double* res, size_t r_plane, const unsigned* rshape, int nd, unsigned* flags_and_counter);
-    // res[1..] = log(xs)[1..]: the slabs k0 >= 1 of the log recurrence as the same row wavefront (slab 0 is the caller's)
-    static bool log_wavefront(hipStream_t st, const double* xs, size_t x_plane, const unsigned* xshape, double* res, size_t r_plane,
-                              const unsigned* rshape, int nd, double* qbuf, size_t q_plane, unsigned* flags_and_counter);
-    // res[1..] = exp(xs)[1..] likewise (slab 0, an exp one dimension down, is the caller's and complete in stream order)
-    // `arrival_order`: the source slabs of each row's sum in descending j0 (1e-10 contract instead of the reference's order)
-    static bool exp_wavefront(hipStream_t st, const double* xs, size_t x_plane, const unsigned* xshape, double* res, size_t r_plane,
-                              const unsigned* rshape, int nd, unsigned* flags_and_counter, int arrival_order = 0);
-    // Rank-2 quotient (mode 0), or the rows >= 1 of a rank-2 log (1) / exp (2), with rows of 65 .. 4096 coefficients as a
-    // coefficient-level wavefront in ONE launch (gft_div2d.hip k_rows_wavefront): tasks are 64-coefficient segments of rows,
-    // bit-identical to the host-driven recursion.  `flags_and_counter`: rows * ceil(row length / 64) + 1 zeroed words;
-    // `qbuf` (mode 1): a tensor like res.  false: outside the kernel's domain, nothing launched.
-    static bool rows_wavefront(hipStream_t st, int mode, const double* xs, size_t x_plane, const unsigned* xshape, const double* ys,
-                               size_t y_plane, const unsigned* yshape, double* res, size_t r_plane, const unsigned* rshape, double* qbuf,
-                               size_t q_plane, unsigned* flags_and_counter);
-    // Quotients (mode 0) and the slabs k0 >= 1 of logarithms (mode 1) of rank 3 / 4 with rows of 65 .. 4096 coefficients: the segment
-    // wavefront with leading axes (gft_div2d.hip k_seg_wavefront), bit-identical to the host-driven recursion.
-    // `flags_and_counter`: (rows of res) * ceil(row length / 64) + 1 zeroed words; `qbuf` (mode 1): a tensor like res.
-    static bool seg_wavefront(hipStream_t st, int mode, const double* xs, size_t x_plane, const unsigned* xshape, const double* ys, size_t y_plane,
-                              const unsigned* yshape, double* res, size_t r_plane, const unsigned* rshape, int nd, double* qbuf, size_t q_plane,
-                              unsigned* flags_and_counter);
+    // A division res = xs / ys, or the slabs k0 >= 1 of log(xs) / exp(xs) (ys = xs; slab 0 is the caller's, complete in stream
+    // order), as the persistent wavefront `plan` names (plan_wavefront, gft_wavefront_plan.hpp) in ONE launch.  `qb` (log): a
+    // tensor like res; `flags`: plan.flag_words zeroed device words.
+    static void recur_wavefront(hipStream_t st, const WfPlan& plan, const double* xs, size_t x_plane, const double* ys, size_t y_plane,
+                                double* res, size_t r_plane, double* qb, size_t q_plane, unsigned* flags);
     // factor tables computed on device in the reference's operation order (mt:472-478, 499-506, 557-565)
     static void factor_table(hipStream_t st, int op, unsigned n, unsigned len, const double* m, size_t m_plane,
                              double* tab, size_t tab_plane);

@@ -113,7 +113,7 @@
                              res.plane, (unsigned)res.shape[0]);
             return;
         }
-        if (!host && R.div2d && res.shape.size() == 2 &&
+        if (!host && res.shape.size() == 2 &&
             K<E>::div_2d(R.stream, xs.p, xs.plane, (unsigned)xs.shape[0], (unsigned)xs.shape[1], xs.shape[1], ys.p, ys.plane,
                          (unsigned)ys.shape[0], (unsigned)ys.shape[1], res.p, res.plane, (unsigned)res.shape[0], (unsigned)res.shape[1], 0))
             return;  // the last two axes in one launch (gft_div2d.hip), same bits
@@ -126,7 +126,7 @@
         // the bits are the reference's; what changes is that a step is a product of m slabs wide — hundreds of
         // workgroups instead of four.  Steps of at least recur_tiled_min_macs multiply-adds may take the tiled kernel
         // (different summation order: 1e-10 contract), smaller ones keep the reference order.
-        const bool right = !host && R.div2d;
+        const bool right = !host;
         Dims rest(res.shape.begin() + 1, res.shape.end()), yrest(ys.shape.begin() + 1, ys.shape.end());
         if (right) {
             zero_elems(false, res.p, res.numel());
@@ -152,7 +152,7 @@
                     right_update(xk, ym, zm, m);
                 }
             } scatter{res, ys, cur, rest, yrest, k, n0, right};
-            if (!host && R.div2d && cur.shape.size() == 2) {
+            if (!host && cur.shape.size() == 2) {
                 // neg, += xs[k], copy and the whole 2-d division of the slab fused into one launch
                 const bool have_x = k < xs.shape[0];
                 HV xk = have_x ? xs.index0(k) : HV{nullptr, 0, Dims{0, 0}, false};
@@ -161,7 +161,7 @@
                                  (unsigned)cur.shape[0], (unsigned)cur.shape[1], 1))
                     continue;
             }
-            if (!host && R.div2d && cur.shape.size() == 1) {
+            if (!host && cur.shape.size() == 1) {
                 // 2-d quotient whose rows do not fit the slab kernel: row by row, each row's neg, += xs[k], copy and 1-d
                 // division in one launch
                 const bool have_x = k < xs.shape[0];
@@ -197,53 +197,32 @@
             if (rs[i] == UMAX) throw Error("div: untruncated result shape (degrees_p1 == usize::MAX)");
         const bool host = tier_host(prod(rs), self, other) && est_macs(rs, other.shape, rs) <= R.host_max_macs;
         P out = make(rs, deg, host);
-        if (!host && div_wavefront(self, other, out)) return out;
+        if (!host) {  // (dropped axes have extent 1 in the result, hence in both operands: shapes never exceed the result's)
+            Dims keep = collapse_mask({&out.shape}, false);
+            HV x{dp<E>(self), self.numel, pick(self.shape, keep), false}, y{dp<E>(other), other.numel, pick(other.shape, keep), false},
+                z{dp<E>(out), out.numel, pick(out.shape, keep), false};
+            if (recur_wavefront(WF_DIV, x, y, z)) return out;
+        }
         div_rec(view(self, host), view(other, host), view(out, host));
         return seal(out);
     }
-    // The whole quotient in one launch (gft_div2d.hip k_div_wavefront): every row a task of one wave, consumed in the
-    // reference's order, dependencies through per-row flags.  Ranks 2-4 (after dropping the axes on which all three
-    // tensors are trivial) with rows of at most 64 coefficients and enough rows to be worth a persistent launch.
-    static bool div_wavefront(const P& self, const P& other, const P& out) {
-        if (!R.div_wavefront || !R.div2d) return false;
-        Dims keep = collapse_mask({&out.shape}, false);
-        if (keep.size() < 2 || keep.size() > 4) return false;
-        // dropped axes have extent 1 in the result, hence in both operands (shapes never exceed the result's)
-        HV x{dp<E>(self), self.numel, pick(self.shape, keep), false}, y{dp<E>(other), other.numel, pick(other.shape, keep), false},
-            z{dp<E>(out), out.numel, pick(out.shape, keep), false};
-        return div_wavefront_hv(x, y, z);
-    }
-    // (contiguous views of rank 2-4, no unit axes to drop)
-    static bool div_wavefront_hv(const HV& x, const HV& y, const HV& z) {
-        if (!R.div_wavefront || !R.div2d) return false;
+    // The whole recurrence in one persistent launch, the kernel and its geometry chosen by plan_wavefront (gft_wavefront_plan.hpp):
+    // every result row (or 64-coefficient segment of one) a task, its terms consumed in the reference's order — or, exp with
+    // `arrival_order`, in the order they become available — with dependencies through per-segment flags.  x, y, z: contiguous
+    // device views of one rank (log / exp: y = x, and the slabs k0 >= 1 of z).  false: no wavefront for this shape, nothing
+    // allocated or launched.
+    static bool recur_wavefront(WfOp op, const HV& x, const HV& y, const HV& z, bool arrival_order = false) {
         const size_t nd = z.shape.size();
-        if (nd < 2 || nd > 4) return false;
-        unsigned xs[4], ys[4], zs[4];
-        size_t rows = 1;
-        for (size_t i = 0; i < nd; ++i) {
-            xs[i] = (unsigned)x.shape[i];
-            ys[i] = (unsigned)y.shape[i];
-            zs[i] = (unsigned)z.shape[i];
-            if (i + 1 < nd) rows *= zs[i];
-        }
-        if (nd == 2 && zs[1] > 64 && zs[1] <= 4096 && rows >= 8 && R.rows_wavefront) {
-            // long rows, rank 2: the coefficient-level wavefront (tasks are 64-coefficient segments of rows)
-            const size_t words = rows * ((zs[1] + 63) / 64) + 1;
-            Rc<Buf> fl = alloc_doubles((words + 1) / 2 + 1);
-            zero_elems(false, fl->p, (words + 1) / 2 + 1);
-            return K<E>::rows_wavefront(R.stream, 0, x.p, x.plane, xs, y.p, y.plane, ys, z.p, z.plane, zs, nullptr, 0, reinterpret_cast<unsigned*>(fl->p));
-        }
-        if (nd >= 3 && zs[nd - 1] > 64 && zs[nd - 1] <= 4096 && rows >= 8) {
-            // long rows, rank 3 / 4 (round 6): the segment wavefront with leading axes — one launch instead of the slab-by-slab form
-            const size_t words = rows * ((zs[nd - 1] + 63) / 64) + 1;
-            Rc<Buf> fl = alloc_doubles((words + 1) / 2 + 1);
-            zero_elems(false, fl->p, (words + 1) / 2 + 1);
-            return K<E>::seg_wavefront(R.stream, 0, x.p, x.plane, xs, y.p, y.plane, ys, z.p, z.plane, zs, (int)nd, nullptr, 0, reinterpret_cast<unsigned*>(fl->p));
-        }
-        if (zs[nd - 1] > 64 || zs[nd - 1] < 2 || rows < 64) return false;
-        Rc<Buf> fl = alloc_doubles((rows + 1 + 1) / 2 + 1);
-        zero_elems(false, fl->p, (rows + 1 + 1) / 2 + 1);
-        return K<E>::div_wavefront(R.stream, x.p, x.plane, xs, y.p, y.plane, ys, z.p, z.plane, zs, (int)nd, reinterpret_cast<unsigned*>(fl->p));
+        if (!R.div_wavefront || x.shape.size() != nd || y.shape.size() != nd) return false;
+        const WfPlan p = plan_wavefront(op, W, (int)nd, z.shape.data(), x.shape.data(), y.shape.data(), arrival_order);
+        if (p.family == WF_NONE) return false;
+        Rc<Buf> qb = p.needs_qbuf ? alloc_doubles(z.numel() * W) : Rc<Buf>();
+        const size_t fl_doubles = (p.flag_words + 1) / 2 + 1;
+        Rc<Buf> fl = alloc_doubles(fl_doubles);
+        zero_elems(false, fl->p, fl_doubles);
+        K<E>::recur_wavefront(R.stream, p, x.p, x.plane, y.p, y.plane, z.p, z.plane, qb ? qb->p : nullptr, qb ? z.numel() : 0,
+                              reinterpret_cast<unsigned*>(fl->p));
+        return true;
     }
     // ---- exp / log (mt:406-430, 1270-1386) ---------------------------------------------------------------------
     // xs scaled slab-wise by T::from(j) along axis 0 (mt:1308-1310): xs[j] * j
@@ -318,8 +297,8 @@
         // form — 400^2: see profiles/r04/recurrences.txt)
         // rank 2 where the right-looking tiled form would be taken: the wavefront kernels with each row's terms in the order of
         // their ARRIVAL (that form's order, same 1e-10 contract) — 400^2 62 -> 4.5 ms, 1000 x 32 10.6 -> see recurrences.txt
-        const bool wf_2d = res.shape.size() == 2 && res.shape[1] <= 4096 && R.rows_wavefront;
-        if (!res.host && (!right_tiled || wf_2d) && exp_wavefront(xs, res, right_tiled)) return;
+        const bool wf_2d = res.shape.size() == 2 && res.shape[1] <= 4096;
+        if (!res.host && (!right_tiled || wf_2d) && recur_wavefront(WF_EXP, xs, xs, res, right_tiled)) return;
         HV xsc;
         Rc<Buf> hold = scaled_by_index(xs, &xsc);
         // Large f64 exponentials (their slab steps would take the tiled kernel anyway, i.e. the 1e-10 contract, not the
@@ -352,32 +331,6 @@
             conv(xsc, res, res, k, k + 1, false, true, 1, 0, 0);
             x_map_inplace(cur, MAP_DIV_U32, (unsigned)k);
         }
-    }
-    // `arrival_order`: the caller would otherwise take the right-looking tiled form (1e-10 contract) — the long-row kernel may
-    // then add each row's terms in the order the source rows become available instead of the reference's
-    static bool exp_wavefront(const HV& xs, const HV& res, bool arrival_order = false) {
-        if (!R.div_wavefront || !R.div2d) return false;
-        const size_t nd = res.shape.size();
-        if (nd < 2 || nd > 4 || xs.shape.size() != nd) return false;
-        unsigned xsh[4], rsh[4];
-        size_t rows = 1;
-        for (size_t i = 0; i < nd; ++i) {
-            if (res.shape[i] < 2 || xs.shape[i] > res.shape[i] || xs.shape[i] == 0 || res.shape[i] > 0x7fffffffu) return false;
-            xsh[i] = (unsigned)xs.shape[i];
-            rsh[i] = (unsigned)res.shape[i];
-            if (i + 1 < nd) rows *= res.shape[i];
-        }
-        if (nd == 2 && rsh[1] > 64 && rsh[1] <= 4096 && rows >= 8 && R.rows_wavefront) {  // long rows: the coefficient-level wavefront
-            const size_t words = rows * ((rsh[1] + 63) / 64) + 1;
-            Rc<Buf> fl = alloc_doubles((words + 1) / 2 + 1);
-            zero_elems(false, fl->p, (words + 1) / 2 + 1);
-            return K<E>::rows_wavefront(R.stream, arrival_order ? 2 | 4 : 2, xs.p, xs.plane, xsh, xs.p, xs.plane, xsh, res.p, res.plane, rsh, nullptr, 0,
-                                        reinterpret_cast<unsigned*>(fl->p));
-        }
-        if (rsh[nd - 1] > 64 || rows < 8) return false;  // (the alternative is two launches per slab)
-        Rc<Buf> fl = alloc_doubles((rows + 2) / 2 + 1);
-        zero_elems(false, fl->p, (rows + 2) / 2 + 1);
-        return K<E>::exp_wavefront(R.stream, xs.p, xs.plane, xsh, res.p, res.plane, rsh, (int)nd, reinterpret_cast<unsigned*>(fl->p), arrival_order ? 1 : 0);
     }
     static Dims explog_shape(const P& a) {
         Dims rs = a.deg;
@@ -423,7 +376,7 @@
         log_rec(xs.index0(0), res.index0(0), seed);
         size_t n0 = res.shape[0];
         if (n0 <= 1) return;
-        if (!host && log_wavefront(xs, res)) return;
+        if (!host && recur_wavefront(WF_LOG, xs, xs, res)) return;
         // rs[j] = res[j] * j, filled slab by slab as res becomes known (mt:1362-1365)
         Rc<Buf> rsbuf = alloc_tier(host, res.numel() * W);
         HV rs{rsbuf->p, res.numel(), res.shape, host};
@@ -432,7 +385,7 @@
         HV x0 = xs.index0(0);
         // device tier: right-looking accumulation like div_rec — once rs[k] = res[k] * k is known, one product adds
         // xs[1..m] (*) rs[k] into the m slabs that follow (terms arrive in ascending j, as in the reference)
-        const bool right = !host && R.div2d;
+        const bool right = !host;
         Dims xrest(xs.shape.begin() + 1, xs.shape.end());
         if (right) {
             HV tail{res.p + prod(sub), res.plane, res.shape, false};
@@ -480,46 +433,6 @@
             }
         }
         if (right) join_side();
-    }
-    // The slabs k0 >= 1 of the log recurrence in one launch (gft_div2d.hip k_div_wavefront, log_mode): every row a task,
-    // consumed in the reference's order (mt:1335-1386), same bits.  Shapes: no unit axes in the result, rows of at most 64
-    // coefficients, a divisor xs[0] with more than one coefficient (Div's general path, mt:1194-1231), enough rows.
-    static bool log_wavefront(const HV& xs, const HV& res) {
-        if (!R.div_wavefront || !R.div2d) return false;
-        const size_t nd = res.shape.size();
-        if (nd < 2 || nd > 4 || xs.shape.size() != nd) return false;
-        unsigned xsh[4], rsh[4];
-        size_t rows = 1, x0n = 1;
-        for (size_t i = 0; i < nd; ++i) {
-            if (res.shape[i] < 2 || xs.shape[i] > res.shape[i] || res.shape[i] > 0x7fffffffu) return false;
-            xsh[i] = (unsigned)xs.shape[i];
-            rsh[i] = (unsigned)res.shape[i];
-            if (i + 1 < nd) rows *= res.shape[i];
-            if (i > 0) x0n *= xs.shape[i];
-        }
-        if (nd == 2 && rsh[1] > 64 && rsh[1] <= 4096 && rows >= 8 && x0n >= 2 && nonunit_axes(xs.shape) >= 2 && R.rows_wavefront) {
-            // long rows: the coefficient-level wavefront
-            Rc<Buf> qb = alloc_doubles(res.numel() * W);
-            const size_t words = rows * ((rsh[1] + 63) / 64) + 1;
-            Rc<Buf> fl = alloc_doubles((words + 1) / 2 + 1);
-            zero_elems(false, fl->p, (words + 1) / 2 + 1);
-            return K<E>::rows_wavefront(R.stream, 1, xs.p, xs.plane, xsh, xs.p, xs.plane, xsh, res.p, res.plane, rsh, qb->p, res.numel(),
-                                        reinterpret_cast<unsigned*>(fl->p));
-        }
-        if (nd >= 3 && rsh[nd - 1] > 64 && rsh[nd - 1] <= 4096 && rows >= 8 && x0n >= 2 && nonunit_axes(xs.shape) >= 2) {
-            // long rows, rank 3 / 4 (round 6): the segment wavefront with leading axes
-            Rc<Buf> qb = alloc_doubles(res.numel() * W);
-            const size_t words = rows * ((rsh[nd - 1] + 63) / 64) + 1;
-            Rc<Buf> fl = alloc_doubles((words + 1) / 2 + 1);
-            zero_elems(false, fl->p, (words + 1) / 2 + 1);
-            return K<E>::seg_wavefront(R.stream, 1, xs.p, xs.plane, xsh, xs.p, xs.plane, xsh, res.p, res.plane, rsh, (int)nd, qb->p, res.numel(),
-                                       reinterpret_cast<unsigned*>(fl->p));
-        }
-        if (rsh[nd - 1] > 64 || rows < 8 || x0n < 2 || nonunit_axes(xs.shape) < 2) return false;  // (the alternative is 2+ launches per slab)
-        Rc<Buf> qb = alloc_doubles(res.numel() * W);
-        Rc<Buf> fl = alloc_doubles((rows + 2) / 2 + 1);
-        zero_elems(false, fl->p, (rows + 2) / 2 + 1);
-        return K<E>::log_wavefront(R.stream, xs.p, xs.plane, xsh, res.p, res.plane, rsh, (int)nd, qb->p, res.numel(), reinterpret_cast<unsigned*>(fl->p));
     }
     // Div's dispatcher (mt:1194-1231) for the slab division inside log.  tp<E>() serves a device caller whatever side
     // the quotient is on; a host caller needs it in host memory.
