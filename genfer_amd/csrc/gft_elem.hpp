@@ -283,4 +283,79 @@ struct EIv {
     }
 };
 
+// ---- BigFloat (src/number/big_float.rs) ---------------------------------------------------------------------------
+// {factor, exponent}: factor in +-[1, 2), or 0, or non-finite; value factor * 2^exponent.  Stored as two planes like
+// Interval<F64>: the factors, then the exponents as (exactly representable, integral) doubles.  The exponent stays a
+// double in registers too: every sum or difference of two exponents with |e| < 2^52 is exact, so no 64-bit integer
+// arithmetic is needed on the device.  Exponent differences of 2^31 or more are unsupported (the reference truncates
+// them with `as i32`).
+struct Bf {
+    double f, e;
+};
+
+// powi(2, n) as this repository lowers f64::powi (__builtin_powi: repeated squaring, the reciprocal for n < 0):
+// exactly 2^n for -1023 <= n <= 1023, +0 below, +inf above.  ldexp plus range selects — no pow call on the device.
+GFT_HD inline double bf_pow2(double n) {
+    const int k = (int)__builtin_fmax(__builtin_fmin(n, 1024.0), -1024.0);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double p = __builtin_amdgcn_ldexp(1.0, k);
+#else
+    const double p = std::ldexp(1.0, k);
+#endif
+    const double inf = bits_f64(0x7ff0000000000000LL);
+    return n <= -1024.0 ? 0.0 : (n >= 1024.0 ? inf : p);
+}
+
+struct EBig {
+    typedef Bf V;
+    static constexpr int W = 2;
+    GFT_HD static V ld(const double* p, size_t plane, size_t i) { return Bf{p[i], p[plane + i]}; }
+    GFT_HD static void st(double* p, size_t plane, size_t i, V v) {
+        p[i] = v.f;
+        p[plane + i] = v.e;
+    }
+    GFT_HD static V from(Scalar2 s) { return Bf{s.a, s.b}; }
+    GFT_HD static V zero() { return Bf{0.0, 0.0}; }  // :84-90
+    GFT_HD static V one() { return Bf{1.0, 0.0}; }   // :98-104
+    // normalize(factor, exponent) (:60-75 with extract_exponent :24-43): a zero factor (either sign) gives {+0, 0}; a
+    // non-finite factor keeps the exponent it was given; otherwise the factor is rescaled into +-[1, 2) exactly
+    // (subnormals included: frexp's mantissa of a subnormal is exact), which is what extract_exponent computes.
+    GFT_HD static V normalize(double f, double e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const double m = __builtin_amdgcn_frexp_mant(f);  // v_frexp_mant_f64: [0.5, 1)
+        const int x = __builtin_amdgcn_frexp_exp(f);      // v_frexp_exp_i32_f64
+#else
+        int x;
+        const double m = std::frexp(f, &x);
+#endif
+        const bool fin = finite_d(f), z = f == 0.0;
+        V r;
+        r.f = fin ? m * 2.0 : f;  // (m * 2 is exact)
+        r.e = fin ? e + (double)(x - 1) : e;
+        r.f = z ? 0.0 : r.f;
+        r.e = z ? 0.0 : r.e;
+        return r;
+    }
+    GFT_HD static V from_u32(unsigned u) { return normalize((double)u, 0.0); }  // :107-112
+    GFT_HD static bool is_zero(V x) { return x.f == 0.0; }                      // :92-95
+    GFT_HD static bool eq(V a, V b) { return a.f == b.f && a.e == b.e; }        // derived PartialEq
+    GFT_HD static V neg(V a) { return Bf{-a.f, a.e}; }                          // :338 (keeps {-0, 0})
+    // :267-276.  The operand with the larger exponent is "bigger" (self on a tie); the other factor is scaled by
+    // powi(2, diff) — which is 0 for diff <= -1024, so x + 0 and 0 + x are {0, 0} when x.exponent <= -1024.
+    GFT_HD static V add(V a, V b) {
+        const bool sa = a.e >= b.e;
+        const double bf = sa ? a.f : b.f, be = sa ? a.e : b.e;
+        const double sf = sa ? b.f : a.f, se = sa ? b.e : a.e;
+        return normalize(bf + sf * bf_pow2(se - be), be);
+    }
+    GFT_HD static V sub(V a, V b) { return add(a, neg(b)); }                       // :289-294
+    GFT_HD static V mul(V a, V b) { return normalize(a.f * b.f, a.e + b.e); }      // :302-307
+    GFT_HD static V div(V a, V b) { return normalize(a.f / b.f, a.e - b.e); }      // :318-323
+    GFT_HD static V mac(V acc, V a, V b) { return add(acc, mul(a, b)); }
+    GFT_HD static V mulw(V a, V b) { return mul(a, b); }
+    GFT_HD static V addw(V a, V b) { return add(a, b); }
+    GFT_HD static V add0(V b) { return add(zero(), b); }  // the real 0 + b: it drops b when b.exponent <= -1024
+    static constexpr bool HAS_POS = false;
+};
+
 }  // namespace gft

@@ -1,6 +1,6 @@
 // `genfer` — the reference's command line (src/main.rs:22-131) over the host interpreter and the MI355X Taylor
 // core:   genfer [flags] <file.sgcl>
-// Same flags (f64 and `--bounds` Taylor paths), same report on stdout, same `--json <path>` file, so the reference's
+// Same flags (f64, `--bounds` and `--big-float` Taylor paths), same report on stdout, same `--json <path>` file, so the reference's
 // own harnesses (benchmarks/neurips2023/exact/bench.py:44-105 spawns `genfer <flags> <path>` and parses
 // "Total inference time") can drive it unchanged.  The TaylorPoly backend is libgftaylor.so (HIP, gfx950) next to
 // this binary's directory; GENFER_BACKEND=<lib>[:prefix] selects another library exporting the C ABI of
@@ -27,11 +27,12 @@ int main(int argc, char** argv) {
     // exported wins.  Must happen before the backend library brings up HIP.
     setenv("HIP_FORCE_DEV_KERNARG", "1", 0);
     std::string file, flags;
-    bool bounds = false;
+    bool bounds = false, big_float = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         const bool takes_value = a == "-l" || a == "--limit" || a == "-u" || a == "--unroll" || a == "--json" || a == "-p" || a == "--precision";
         if (a == "-b" || a == "--bounds") bounds = true;
+        if (a == "--big-float") big_float = true;
         if (!a.empty() && a[0] == '-') {
             flags += a + " ";
             if (takes_value && i + 1 < argc) flags += std::string(argv[++i]) + " ";
@@ -58,14 +59,16 @@ int main(int argc, char** argv) {
     if (stem.find_last_of('.') != std::string::npos && stem.find_last_of('.') > 0) stem = stem.substr(0, stem.find_last_of('.'));
     flags += "--model-name " + stem + " ";
 
-    std::string lib, prefix = bounds ? "gfti_" : "gft_";
+    // element family: f64 -> <pfx>_, Interval<F64> -> <pfx>i_, BigFloat -> <pfx>b_ (--big-float --bounds is refused by gfh_run)
+    const char* family = bounds ? "i_" : (big_float ? "b_" : "_");
+    std::string lib, prefix = std::string("gft") + family;
     if (const char* e = getenv("GENFER_BACKEND")) {
         lib = e;
         size_t c = lib.find(':');
         if (c != std::string::npos) {
             std::string pfx = lib.substr(c + 1);
             lib = lib.substr(0, c);
-            prefix = bounds ? pfx + "i_" : pfx + "_";  // e.g. "orc" -> orc_ / orci_
+            prefix = pfx + family;  // e.g. "orc" -> orc_ / orci_ / orcb_
         }
     } else {
         char exe[4096];

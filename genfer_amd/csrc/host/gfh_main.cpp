@@ -5,7 +5,7 @@
 // C entry point:  int gfh_run(const char* source, const char* flags, const char* backend_lib,
 //                             const char* backend_prefix, char** out_text, char** out_timings_json)
 // `backend_lib`/`backend_prefix` select the library that implements the TaylorPoly C ABI
-// (include/gftaylor.h): the product passes libgftaylor.so + "gft_" (or "gfti_" with --bounds).
+// (include/gftaylor.h): the product passes libgftaylor.so + "gft_" (or "gfti_" with --bounds, "gftb_" with --big-float).
 #include <charconv>
 #include <chrono>
 #include <cmath>
@@ -22,7 +22,7 @@ using namespace gfh;
 namespace {
 
 struct Args {
-    bool bounds = false, no_simplify_gf = false, no_timing = false, no_probs = false;
+    bool bounds = false, big_float = false, no_simplify_gf = false, no_timing = false, no_probs = false;
     size_t unroll = 8;
     bool has_limit = false;
     size_t limit = 0;
@@ -53,11 +53,14 @@ Args parse_flags(const std::string& flags) {
         else if (tok == "--json") { if (!(is >> a.json_path)) throw std::runtime_error("missing value for --json"); }
         else if (tok.rfind("--json=", 0) == 0) a.json_path = tok.substr(7);
         else if (tok == "--model-name") { if (!(is >> a.model_name)) throw std::runtime_error("missing value for --model-name"); }
-        else if (tok == "-r" || tok == "--rational" || tok == "-s" || tok == "--symbolic" || tok == "--big-float" || tok == "-p" ||
+        else if (tok == "--big-float") a.big_float = true;
+        else if (tok == "-r" || tok == "--rational" || tok == "-s" || tok == "--symbolic" || tok == "-p" ||
                  tok == "--precision" || tok == "--print-program")
-            throw std::runtime_error("flag " + tok + " selects a part of the reference that is out of scope here (f64 / interval Taylor path only)");
+            throw std::runtime_error("flag " + tok + " selects a part of the reference that is out of scope here (f64 / interval / BigFloat Taylor paths only)");
         else throw std::runtime_error("unknown flag " + tok);
     }
+    if (a.bounds && a.big_float)  // Interval<BigFloat> tensors (main.rs:123-124)
+        throw std::runtime_error("--big-float together with --bounds (Interval<BigFloat> tensors) is out of scope here");
     return a;
 }
 
@@ -108,32 +111,36 @@ struct Report {
     }
 };
 
-std::string in_interval(const Interval& iv, bool print_intervals) {  // main.rs:291-299
-    F64 x;
+template <class IV, class B = typename IV::Bound>
+std::string in_interval(const IV& iv, bool print_intervals) {  // main.rs:291-299
+    B x;
     if (iv.extract_point(x)) return "= " + x.str();
     if (!print_intervals) return "= " + iv.center().str();
     return "∈ [" + iv.lo.str() + ", " + iv.hi.str() + "]";
 }
 
-bool support_to_interval(const SupportSet& s, Interval& out) {  // support.rs:267-288
+template <class IV, class B = typename IV::Bound>
+bool support_to_interval(const SupportSet& s, IV& out) {  // support.rs:267-288
     if (s.kind == SupportSet::EMPTY) return false;
     if (s.kind == SupportSet::RANGE) {
-        out = Interval::exact(F64::from_u32(s.start), s.end ? F64::from_u32(*s.end) : F64::infinity());
+        out = IV::exact(B::from_u32(s.start), s.end ? B::from_u32(*s.end) : B::infinity());
         return true;
     }
     int64_t n; uint64_t d;
     s.istart.to_ratio(n, d);
-    F64 lo = F64::from_ratio((uint64_t)n, d);
-    F64 hi = F64::infinity();
-    if (!s.iend.is_infinite()) { s.iend.to_ratio(n, d); hi = F64::from_ratio((uint64_t)n, d); }
-    out = Interval::exact(lo, hi);
+    B lo = B::from_ratio((uint64_t)n, d);
+    B hi = B::infinity();
+    if (!s.iend.is_infinite()) { s.iend.to_ratio(n, d); hi = B::from_ratio((uint64_t)n, d); }
+    out = IV::exact(lo, hi);
     return true;
 }
 
-struct Moments { Interval total, mean, raw2nd, raw3rd, raw4th, variance, stddev, central3rd, central4th, skewness, kurtosis; };
+template <class IV>
+struct MomentsT { IV total, mean, raw2nd, raw3rd, raw4th, variance, stddev, central3rd, central4th, skewness, kurtosis; };
 
-Moments moments_to_struct(const Interval& total, const std::vector<Interval>& m) {  // main.rs:512-546
-    Moments r;
+template <class IV, class B = typename IV::Bound>
+MomentsT<IV> moments_to_struct(const IV& total, const std::vector<IV>& m) {  // main.rs:512-546
+    MomentsT<IV> r;
     r.total = total;
     r.raw2nd = m[1]; r.raw3rd = m[2]; r.raw4th = m[3];
     auto cm = moments_to_central_moments(m);
@@ -143,13 +150,14 @@ Moments moments_to_struct(const Interval& total, const std::vector<Interval>& m)
     r.variance = sm.first;
     r.skewness = sm.second[0]; r.kurtosis = sm.second[1];
     r.stddev = r.variance.sqrt();
-    for (auto& x : m) if (!x.not_less_than(Interval::zero())) throw std::runtime_error("moments must be non-negative for distributions supported on the natural numbers");
-    if (!r.variance.not_less_than(Interval::zero())) throw std::runtime_error("variance must be non-negative");
-    if (!r.kurtosis.not_less_than(Interval::zero())) throw std::runtime_error("kurtosis must be non-negative");
+    for (auto& x : m) if (!x.not_less_than(IV::zero())) throw std::runtime_error("moments must be non-negative for distributions supported on the natural numbers");
+    if (!r.variance.not_less_than(IV::zero())) throw std::runtime_error("variance must be non-negative");
+    if (!r.kurtosis.not_less_than(IV::zero())) throw std::runtime_error("kurtosis must be non-negative");
     return r;
 }
 
-void print_moments(Report& R, const Moments& m, bool pi) {  // main.rs:548-577
+template <class IV, class B = typename IV::Bound>
+void print_moments(Report& R, const MomentsT<IV>& m, bool pi) {  // main.rs:548-577
     auto& o = R.out;
     o << "Total measure:             Z " << in_interval(m.total, pi) << "\n";
     o << "Expected value:            E " << in_interval(m.mean, pi) << "\n";
@@ -166,12 +174,13 @@ void print_moments(Report& R, const Moments& m, bool pi) {  // main.rs:548-577
 
 const size_t MAX_PROB_LIMIT = 1000;
 
-std::vector<Interval> print_probs(Report& R, const Interval& rest, const Interval& total_without_rest, const std::vector<Interval>& moments,
+template <class IV, class B = typename IV::Bound>
+std::vector<IV> print_probs(Report& R, const IV& rest, const IV& total_without_rest, const std::vector<IV>& moments,
                  const SupportSet& var_info, const SupportSet& rest_info, bool uses_observe,
-                 const std::function<std::vector<Interval>(size_t)>& probs_fn, Clock::time_point probs_start) {  // main.rs:384-473
+                 const std::function<std::vector<IV>(size_t)>& probs_fn, Clock::time_point probs_start) {  // main.rs:384-473
     auto& o = R.out;
     o << "\n";
-    Interval total = (total_without_rest + rest).ensure_upper_bound(F64::one());
+    IV total = (total_without_rest + rest).ensure_upper_bound(B::one());
     size_t limit;
     uint32_t lo, hi;
     if (R.args.has_limit) limit = R.args.limit;
@@ -191,29 +200,29 @@ std::vector<Interval> print_probs(Report& R, const Interval& rest, const Interva
     }
     o << "Computing probabilities up to " << limit << "...\n";
     bool is_normalized = !uses_observe || total.is_one();
-    Interval mass_missing = total_without_rest;
-    std::vector<Interval> probs = probs_fn(limit);
+    IV mass_missing = total_without_rest;
+    std::vector<IV> probs = probs_fn(limit);
     bool pi = R.args.bounds || !rest.is_zero();
     for (size_t i = 0; i < limit; ++i) {
-        Interval p = probs[i];
+        IV p = probs[i];
         mass_missing = mass_missing - p;
         if (rest_info.contains((uint32_t)i)) p = p + rest;
-        if (p < Interval::zero() || p > Interval::one())
+        if (p < IV::zero() || p > IV::one())
             throw std::runtime_error("p(" + std::to_string(i) + ") = " + p.str() + " is not a probability");
-        p = p.ensure_lower_bound(F64::zero()).ensure_upper_bound(F64::one());
+        p = p.ensure_lower_bound(B::zero()).ensure_upper_bound(B::one());
         probs[i] = p;
         if (is_normalized) o << "p(" << i << ") " << in_interval(p, pi) << "\n";
         else {
-            Interval np = (p / total).ensure_lower_bound(F64::zero()).ensure_upper_bound(F64::one());
+            IV np = (p / total).ensure_lower_bound(B::zero()).ensure_upper_bound(B::one());
             o << "Unnormalized: p(" << i << ")     " << in_interval(p, pi) << "\n";
             o << "Normalized:   p(" << i << ") / Z " << in_interval(np, pi) << "\n";
         }
     }
     SupportSet up_to = SupportSet::range(0, (uint32_t)(limit - 1));
     if (!rest_info.is_subset_of(up_to)) mass_missing = mass_missing + rest;
-    if (var_info.is_subset_of(up_to)) mass_missing = Interval::zero();
-    F64 mm_un = mass_missing.hi.max(F64::zero()).min(F64::one());
-    F64 mm_n = (mass_missing / total).hi.max(F64::zero()).min(F64::one());
+    if (var_info.is_subset_of(up_to)) mass_missing = IV::zero();
+    B mm_un = mass_missing.hi.max(B::zero()).min(B::one());
+    B mm_n = (mass_missing / total).hi.max(B::zero()).min(B::one());
     if (is_normalized) o << "p(n) <= " << mm_un.str() << " for all n >= " << limit << "\n";
     else {
         o << "Unnormalized: p(n)     <= " << mm_un.str() << " for all n >= " << limit << "\n";
@@ -223,39 +232,40 @@ std::vector<Interval> print_probs(Report& R, const Interval& rest, const Interva
     return probs;
 }
 
-void print_moments_and_probs_interval(Report& R, const std::function<Interval()>& rest_fn,
-                                      const std::function<std::pair<Interval, std::vector<Interval>>(size_t)>& moments_fn,
-                                      const std::function<std::vector<Interval>(size_t)>& probs_fn, const SupportSet& var_info,
+template <class IV, class B = typename IV::Bound>
+void print_moments_and_probs_interval(Report& R, const std::function<IV()>& rest_fn,
+                                      const std::function<std::pair<IV, std::vector<IV>>(size_t)>& moments_fn,
+                                      const std::function<std::vector<IV>(size_t)>& probs_fn, const SupportSet& var_info,
                                       const SupportSet& rest_info, bool uses_observe, Clock::time_point inference_start) {  // main.rs:301-382
     auto& o = R.out;
     o << "Support is a subset of: " << var_info.str() << "\n\n";
     o << "Computing moments...\n";
-    Interval rest = rest_fn().ensure_lower_bound(F64::zero()).ensure_upper_bound(F64::one()).unite(F64::zero());
+    IV rest = rest_fn().ensure_lower_bound(B::zero()).ensure_upper_bound(B::one()).unite(B::zero());
     auto moment_start = Clock::now();
     auto tm = moments_fn(5);
-    Interval total = tm.first.ensure_lower_bound(F64::zero()).ensure_upper_bound(F64::one());
-    Interval total_without_rest = total;
-    Interval max_rest = Interval::one() - total_without_rest;
+    IV total = tm.first.ensure_lower_bound(B::zero()).ensure_upper_bound(B::one());
+    IV total_without_rest = total;
+    IV max_rest = IV::one() - total_without_rest;
     rest = rest.ensure_upper_bound(max_rest.hi);
-    total = (total + rest).ensure_upper_bound(F64::one());
-    std::vector<Interval> moments;
-    for (auto& x : tm.second) moments.push_back(x.ensure_lower_bound(F64::zero()));
-    Interval range;
+    total = (total + rest).ensure_upper_bound(B::one());
+    std::vector<IV> moments;
+    for (auto& x : tm.second) moments.push_back(x.ensure_lower_bound(B::zero()));
+    IV range;
     if (support_to_interval(rest_info, range)) {
         for (size_t i = 0; i < moments.size(); ++i) {
-            F64 added = rest.hi * range.hi.pow((uint32_t)i + 1);
-            moments[i] = moments[i] + Interval::exact(F64::zero(), added);
+            B added = rest.hi * range.hi.pow((uint32_t)i + 1);
+            moments[i] = moments[i] + IV::exact(B::zero(), added);
         }
     }
-    Moments ms = moments_to_struct(total, moments);
-    ms.variance = ms.variance.ensure_lower_bound(F64::zero());
-    ms.stddev = ms.stddev.ensure_lower_bound(F64::zero());
-    ms.kurtosis = ms.kurtosis.ensure_lower_bound(F64::zero());
+    MomentsT<IV> ms = moments_to_struct(total, moments);
+    ms.variance = ms.variance.ensure_lower_bound(B::zero());
+    ms.stddev = ms.stddev.ensure_lower_bound(B::zero());
+    ms.kurtosis = ms.kurtosis.ensure_lower_bound(B::zero());
     print_moments(R, ms, R.args.bounds || !rest.is_zero());
     R.elapsed(moment_start, "Time to compute moments: ", &R.t_moments);
-    std::vector<Interval> probs;
+    std::vector<IV> probs;
     if (!(R.args.no_probs || !var_info.is_discrete() || total.is_zero()))
-        probs = print_probs(R, rest, total_without_rest, moments, var_info, rest_info, uses_observe, probs_fn, Clock::now());
+        probs = print_probs<IV>(R, rest, total_without_rest, moments, var_info, rest_info, uses_observe, probs_fn, Clock::now());
     R.elapsed(inference_start, "Total inference time: ", &R.t_total);
     if (!R.args.json_path.empty()) {  // main.rs:364-382: point values (interval centres), only without loop bounds
         if (rest.is_zero()) {
@@ -304,7 +314,7 @@ void run_f64(Report& R, const Program& program) {  // main.rs:187-227 + 256-289
     bool uses_observe = program.uses_observe();
     GfTranslation<F64> t = translate<F64>(R, program);
     size_t res = program.result;
-    print_moments_and_probs_interval(
+    print_moments_and_probs_interval<Interval>(
         R, [&] { return Interval::precisely(t.rest.eval(std::vector<F64>(t.var_info.num_vars(), F64::zero()), 1).constant_term()); },
         [&](size_t limit) {
             auto tm = moments_taylor(t.gf, res, t.var_info, limit);
@@ -325,10 +335,41 @@ void run_interval(Report& R, const Program& program) {  // main.rs:145-185
     bool uses_observe = program.uses_observe();
     GfTranslation<Interval> t = translate<Interval>(R, program);
     size_t res = program.result;
-    print_moments_and_probs_interval(
+    print_moments_and_probs_interval<Interval>(
         R, [&] { return t.rest.eval(std::vector<Interval>(t.var_info.num_vars(), Interval::zero()), 1).constant_term(); },
         [&](size_t limit) { return moments_taylor(t.gf, res, t.var_info, limit); },
         [&](size_t limit) { return probs_taylor(t.gf, res, t.var_info, limit); }, t.var_info[res], t.rest_info[res], uses_observe, start);
+}
+
+void run_bigfloat(Report& R, const Program& program) {  // main.rs:137-138: run_program::<BigFloat>
+    auto start = Clock::now();
+    bool uses_observe = program.uses_observe();
+    GfTranslation<BigFloat> t = translate<BigFloat>(R, program);
+    size_t res = program.result;
+    print_moments_and_probs_interval<BfInterval>(
+        R, [&] { return BfInterval::precisely(t.rest.eval(std::vector<BigFloat>(t.var_info.num_vars(), BigFloat::zero()), 1).constant_term()); },
+        [&](size_t limit) {
+            auto tm = moments_taylor(t.gf, res, t.var_info, limit);
+            std::vector<BfInterval> ms;
+            for (auto& m : tm.second) ms.push_back(BfInterval::precisely(m));
+            return std::make_pair(BfInterval::precisely(tm.first), ms);
+        },
+        [&](size_t limit) {
+            std::vector<BfInterval> ps;
+            for (auto& p : probs_taylor(t.gf, res, t.var_info, limit)) ps.push_back(BfInterval::precisely(p));
+            return ps;
+        },
+        t.var_info[res], t.rest_info[res], uses_observe, start);
+}
+
+// Whether `lib` exports the TaylorPoly family `prefix` (its `<prefix>width` entry point); a library that cannot be
+// loaded is left to Api::load to report.
+bool exports_family(const char* lib, const char* prefix) {
+    void* h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL);
+    if (!h) return true;
+    const bool found = dlsym(h, (std::string(prefix) + "width").c_str()) != nullptr;
+    dlclose(h);
+    return found;
 }
 
 char* dup(const std::string& s) {
@@ -354,10 +395,17 @@ int gfh_run(const char* source, const char* flags, const char* backend_lib, cons
     try {
         R.args = parse_flags(flags ? flags : "");
         Program program = parse_program(source);
+        if (R.args.big_float && !exports_family(backend_lib, backend_prefix))
+            throw std::runtime_error(std::string("flag --big-float is out of scope for this backend: ") + backend_lib +
+                                     " has no BigFloat TaylorPoly family (" + backend_prefix +
+                                     "*); libgftaylor does not provide one yet, GENFER_BACKEND=<lib>:<pfx> selects a library whose <pfx>b_ family does");
         auto api = Api::load(backend_lib, backend_prefix);
         if (R.args.bounds) {
             Poly<Interval>::bind(api);
             run_interval(R, program);
+        } else if (R.args.big_float) {
+            Poly<BigFloat>::bind(api);
+            run_bigfloat(R, program);
         } else {
             Poly<F64>::bind(api);
             run_f64(R, program);
@@ -379,6 +427,37 @@ int gfh_run(const char* source, const char* flags, const char* backend_lib, cons
 }
 
 void gfh_free(char* p) { free(p); }
+
+// One raw BigFloat operation of the interpreter's own number type (gfh_number.hpp, big_float.rs): op 0 add, 1 sub,
+// 2 mul, 3 div, 4 neg, 5 exp, 6 log, 7 normalize(a.factor, a.exponent), 8 to_f64 (into out[0]), 9 sqrt,
+// 10 next_up, 11 next_down, 12 partial_cmp (into out[0]: -1, 0, 1, or 2 for unordered), 13 min, 14 max, 15 abs,
+// 16 pow(a, (uint32_t)b.factor).  Scalars are {factor, exponent}.  tests/test_bigfloat_cpu.py pins it bit for bit against
+// the kernels' EBig (gft_elem.hpp) and the test oracle's BigFloat.
+int gfh_bigfloat_op(int op, const double* a, const double* b, double* out) {
+    BigFloat x = BigFloat::load(a), y = b ? BigFloat::load(b) : BigFloat(), r;
+    switch (op) {
+        case 0: r = x + y; break;
+        case 1: r = x - y; break;
+        case 2: r = x * y; break;
+        case 3: r = x / y; break;
+        case 4: r = -x; break;
+        case 5: r = x.exp(); break;
+        case 6: r = x.log(); break;
+        case 7: r = BigFloat::normalize(x.f, x.e); break;
+        case 8: out[0] = x.to_f64(); out[1] = 0.0; return 0;
+        case 9: r = x.sqrt(); break;
+        case 10: r = x.next_up(); break;
+        case 11: r = x.next_down(); break;
+        case 12: out[0] = x.cmp(y); out[1] = 0.0; return 0;
+        case 13: r = x.min(y); break;
+        case 14: r = x.max(y); break;
+        case 15: r = x.abs(); break;
+        case 16: r = x.pow((uint32_t)b[0]); break;
+        default: return -1;
+    }
+    r.store(out);
+    return 0;
+}
 
 // One raw Interval<F64> operation of the interpreter's own number type (gfh_number.hpp, interval.rs:117-234,
 // 264-276): op 0 add, 1 sub, 2 mul, 3 div, 4 neg, 5 exp, 6 log.  Used by tests/test_interval_pins.py to check that
