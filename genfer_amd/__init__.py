@@ -61,6 +61,7 @@ def _declare_runtime(L):
     L.gft_shutdown.restype, L.gft_shutdown.argtypes = None, []
     L.gft_set_stream.restype, L.gft_set_stream.argtypes = c.c_int, [c.c_void_p]
     L.gft_get_stream.restype, L.gft_get_stream.argtypes = c.c_void_p, []
+    L.gft_device.restype, L.gft_device.argtypes = c.c_int, []
     L.gft_synchronize.restype, L.gft_synchronize.argtypes = c.c_int, []
     L.gft_last_error.restype, L.gft_last_error.argtypes = c.c_char_p, []
     L.gft_pool_stats.restype, L.gft_pool_stats.argtypes = None, [sz]

@@ -32,6 +32,7 @@
 #include "gft_small_alloc.hpp"
 #include "gft_host.hpp"
 #include "gft_fmt.hpp"
+#include "gft_interop.hpp"
 
 using namespace gft;
 static const size_t UMAX = SIZE_MAX;
@@ -209,6 +210,9 @@ struct Runtime {
     double* d_mail = nullptr;    // the same slot as the device sees it
     unsigned long long mail_seq = 0;
     hipEvent_t events[64] = {};
+    static constexpr int IO_EVENTS = 16;
+    hipEvent_t io_events[IO_EVENTS] = {};  // the device interop's stream joins (interop_event), created on first use
+    int io_next = 0;
     int conv_mode = 0;
     static constexpr int pairs_first = 1;  // small plain f64 products ask the row-pair form before the tiled kernel ("pairs_first", GFT_PAIRS_FIRST)
     double pairs_first_max = 1.0e7, pairs_first_max_rank2 = 2.0e8;  // ... up to this many multiply-adds (rank >= 3 / rank 2)
@@ -1322,6 +1326,10 @@ void gft_shutdown(void) {
     (void)hipHostFree(R.h_mail);
     R.h_mail = R.d_mail = nullptr;
     for (auto& ev : R.events) (void)hipEventDestroy(ev);
+    for (auto& ev : R.io_events) {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
     (void)hipStreamDestroy(R.own_stream);
     if (R.side) (void)hipStreamDestroy(R.side);
     if (R.ev_main) (void)hipEventDestroy(R.ev_main);
@@ -1340,6 +1348,9 @@ int gft_set_stream(void* s) {
     });
 }
 void* gft_get_stream(void) { return (void*)R.stream; }
+int gft_device(void) {
+    return guard_int([&] { return R.device; });
+}
 int gft_synchronize(void) {
     return guard_int([&] {
         HIP_OK(hipStreamSynchronize(R.stream));
@@ -1738,6 +1749,122 @@ int gft_plan_slabs(size_t n0, int world, int rank, size_t out[4]) {
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
+// device interop: gft_from_device / gft_to_device (the kernels: gft_interop.hip)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// The caller's memory must be device memory of the library's GPU: hipPointerGetAttributes says what it is.
+static void check_device_ptr(const void* p, const char* what) {
+    if (!p) throw Error(std::string(what) + " is a null pointer, but the tensor has elements");
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        throw Error(std::string(what) + " is not device memory (pageable host memory, or an address HIP does not know)");
+    }
+    if (at.type == hipMemoryTypeHost) throw Error(std::string(what) + " is pinned host memory, not device memory");
+    if (at.type == hipMemoryTypeUnregistered) throw Error(std::string(what) + " is pageable host memory, not device memory");
+    if (at.type != hipMemoryTypeDevice || at.isManaged) throw Error(std::string(what) + " is not plain device memory (managed or array memory)");
+    if (at.device != R.device)
+        throw Error(std::string(what) + " is memory of GPU " + std::to_string(at.device) + ", but the library runs on GPU " + std::to_string(R.device));
+}
+
+// Stream joins with the caller's stream: the copy runs after everything issued so far on both streams and before everything
+// issued later on either.  Events come from a small ring (a wait is bound to the record it follows, so an event may be
+// recorded again once later calls have moved on).  The wrapped hipEventRecord / hipStreamWaitEvent (gft_launch.hpp) drain the
+// launch thread first: the caller's record happens on this thread, now, and the caller's wait follows the copy's record.
+static hipEvent_t interop_event() {
+    hipEvent_t& ev = R.io_events[R.io_next];
+    R.io_next = (R.io_next + 1) % Runtime::IO_EVENTS;
+    if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return ev;
+}
+static void join_caller_in(hipStream_t cs) {
+    if (cs == R.stream) return;
+    hipEvent_t ev = interop_event();
+    HIP_OK(hipEventRecord(ev, cs));
+    HIP_OK(hipStreamWaitEvent(R.stream, ev, 0));
+}
+static void join_caller_out(hipStream_t cs) {
+    if (cs == R.stream) return;
+    hipEvent_t ev = interop_event();
+    HIP_OK(hipEventRecord(ev, R.stream));
+    HIP_OK(hipStreamWaitEvent(cs, ev, 0));
+}
+
+// The copy geometry between a handle of `shape` (W planes, compact) and a strided tensor: W == 2 puts the plane axis first.
+template <class E>
+static gft::CopyGeom compact_geom(const Dims& shape, size_t numel) {
+    gft::CopyGeom g;
+    g.nd = 0;
+    const Dims cst = c_strides(shape);
+    if (E::W == 2) {
+        g.ext[0] = 2;
+        g.ss[0] = g.ds[0] = numel;
+        g.nd = 1;
+    }
+    for (size_t i = 0; i < shape.size(); ++i, ++g.nd) {
+        g.ext[g.nd] = shape[i];
+        g.ss[g.nd] = g.ds[g.nd] = cst[i];
+    }
+    return g;
+}
+
+template <class E>
+static gft_poly from_device(const double* src, const int64_t* strides, const size_t* sh, const size_t* dg, size_t nd, void* stream) {
+    const Dims shape = dims(sh, nd), deg = dims(dg, nd);
+    check_invariants(shape, deg);
+    const size_t n = prod(shape);
+    gft::CopyGeom g = compact_geom<E>(shape, n);  // ds: the handle's buffer
+    if (strides)
+        for (int a = 0; a < g.nd; ++a) {
+            if (strides[a] < 0) throw Error("from_device: negative strides are not supported (axis " + std::to_string(a) + ")");
+            g.ss[a] = (size_t)strides[a];
+        }
+    check_device_ptr(src, "from_device: the source");
+    // a plain device tensor: no host tier, no affine shortcut, nothing read on the host, no facts about its values
+    gft_poly r = Ops<E>::make(shape, deg, false);
+    double* dst = dp<E>(r);
+    const hipStream_t cs = (hipStream_t)stream;
+    join_caller_in(cs);
+    gft::interop_copy(R.stream, src, dst, g);
+    join_caller_out(cs);
+    return r;
+}
+
+template <class E>
+static int to_device(const gft_poly& p, double* dst, const int64_t* strides, void* stream) {
+    gft::CopyGeom g = compact_geom<E>(p.shape, p.numel);  // ss: the handle's buffer
+    if (strides) {
+        for (int a = 0; a < g.nd; ++a) {
+            if (strides[a] < 0) throw Error("to_device: negative strides are not supported (axis " + std::to_string(a) + ")");
+            if (strides[a] == 0 && g.ext[a] > 1) throw Error("to_device: the destination has a zero stride (axis " + std::to_string(a) + "): its elements overlap");
+            g.ds[a] = (size_t)strides[a];
+        }
+        // no two elements on one address: sorted by stride, every axis steps over the whole extent of the ones below it
+        int ax[32 + 1];
+        int k = 0;
+        for (int a = 0; a < g.nd; ++a)
+            if (g.ext[a] > 1) ax[k++] = a;
+        std::sort(ax, ax + k, [&](int u, int v) { return g.ds[u] < g.ds[v]; });
+        for (int i = 1; i < k; ++i)
+            if (g.ds[ax[i]] / g.ext[ax[i - 1]] < g.ds[ax[i - 1]])
+                throw Error("to_device: the destination's elements overlap (strides do not separate the axes)");
+    }
+    check_device_ptr(dst, "to_device: the destination");
+    // lazy scalars / affine values, host-tier tensors, deferred chains and graph recordings become a device tensor first
+    const double* src = dp<E>(p);
+    const hipStream_t cs = (hipStream_t)stream;
+    join_caller_in(cs);
+    gft::interop_copy(R.stream, src, dst, g);
+    join_caller_out(cs);
+    return 0;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
 // C ABI — handle API, generated for both element types
 // ------------------------------------------------------------------------------------------
 #define GFT_API(PFX, E)                                                                                       \
@@ -1763,6 +1890,13 @@ int gft_plan_slabs(size_t n0, int world, int rank, size_t out[4]) {
             HIP_OK(hipStreamSynchronize(R.stream));                                                           \
             return r;                                                                                         \
         });                                                                                                   \
+    }                                                                                                         \
+    gft_poly* PFX##from_device(const double* src, const int64_t* strides, const size_t* sh, const size_t* dg, size_t nd, \
+                               void* stream) {                                                                \
+        return guard([&] { return from_device<E>(src, strides, sh, dg, nd, stream); });                       \
+    }                                                                                                         \
+    int PFX##to_device(const gft_poly* p, double* dst, const int64_t* strides, void* stream) {                \
+        return guard_int([&] { return to_device<E>(*p, dst, strides, stream); });                             \
     }                                                                                                         \
     gft_poly* PFX##scalar(const double* x) { return guard([&] { return Ops<E>::scalar(x); }); }               \
     gft_poly* PFX##from_u32(uint32_t c) {                                                                     \

@@ -92,6 +92,15 @@ HANDLE_API = {
 }
 
 
+# Device interop (include/gftaylor.h: <prefix>from_device / <prefix>to_device, plus the runtime's gft_device).  Not part of
+# HANDLE_API: a backend without device memory (the CPU oracle) does not export them, and its classes refuse the methods.
+_I64P = C.POINTER(C.c_int64)
+DEVICE_API = {
+    "from_device": (_VP, [_VP, _I64P, _SP, _SP, C.c_size_t, _VP]),
+    "to_device": (C.c_int, [_VP, _VP, _I64P, _VP]),
+}
+
+
 class _Fn:
     """Prefix-bound, signature-checked view of one library."""
 
@@ -102,6 +111,14 @@ class _Fn:
             f.restype, f.argtypes = res, args
             setattr(self, name, f)
         self.W = int(self.width())
+        self.device_interop = hasattr(lib, "gft_device") and all(hasattr(lib, prefix + n) for n in DEVICE_API)
+        if self.device_interop:
+            for name, (res, args) in DEVICE_API.items():
+                f = getattr(lib, prefix + name)
+                f.restype, f.argtypes = res, args
+                setattr(self, name, f)
+            self.device = lib.gft_device
+            self.device.restype, self.device.argtypes = C.c_int, []
 
 
 def bind(lib: C.CDLL, prefix: str):
@@ -120,6 +137,36 @@ def bind(lib: C.CDLL, prefix: str):
 
     def unscal(buf):
         return float(buf[0]) if W == 1 else (float(buf[0]), float(buf[1]))
+
+    def interop(what: str):
+        """torch, for from_torch / to_torch; refuses a backend without device interop."""
+        if not fn.device_interop:
+            raise TaylorError(f"{what}: the backend bound to prefix {prefix!r} has no device interop ({prefix}from_device / {prefix}to_device)")
+        import torch  # (lazily: the package works without torch)
+
+        return torch
+
+    def lib_device() -> int:
+        dev = int(fn.device())
+        if dev < 0:
+            raise TaylorError((fn.last_error() or b"no usable HIP device").decode())
+        return dev
+
+    def check_tensor(torch, t, what: str):
+        """dtype and placement, all before any call into the library"""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float64:
+            raise TaylorError(f"{what}: the tensor is {t.dtype}; only torch.float64 is accepted (no implicit conversion)")
+        if t.device.type != "cuda":
+            raise TaylorError(f"{what}: the tensor is on {t.device}; it must be in device memory of the library's GPU")
+        dev = lib_device()
+        if t.device.index != dev:
+            raise TaylorError(f"{what}: the tensor is on {t.device}, but the library runs on cuda:{dev}")
+
+    def strides_of(t):
+        st = list(t.stride())
+        return (C.c_int64 * max(len(st), 1))(*st)
 
     class TaylorPoly:
         __slots__ = ("_h",)
@@ -150,6 +197,22 @@ def bind(lib: C.CDLL, prefix: str):
             if nd != nd2:
                 raise TaylorError("invariant: ndim != degrees_p1.len()")
             return cls(fn.from_host(a.ctypes.data_as(_DP), sh, dg, nd))
+
+        @classmethod
+        def from_torch(cls, t, degrees_p1: Optional[Sequence[int]] = None):
+            """A handle holding a copy of the float64 device tensor ``t`` (``[*shape]``, or ``[2, *shape]`` = (lo, hi) for
+            intervals; any strides).  Stream-ordered with torch's current stream of ``t``'s device; no host memory."""
+            torch = interop("from_torch")
+            check_tensor(torch, t, "from_torch")
+            if W == 2 and (t.dim() == 0 or t.shape[0] != 2):
+                raise TaylorError("from_torch: interval coefficients must be stacked as [2, ...] = (lo, hi)")
+            shape = tuple(t.shape[1:]) if W == 2 else tuple(t.shape)
+            sh, nd = _sz(shape)
+            dg, nd2 = _sz(shape if degrees_p1 is None else degrees_p1)
+            if nd != nd2:
+                raise TaylorError("invariant: ndim != degrees_p1.len()")
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            return cls(fn.from_device(C.c_void_p(t.data_ptr()), strides_of(t), sh, dg, nd, C.c_void_p(stream)))
 
         @classmethod
         def from_coeffs(cls, coeffs):
@@ -226,6 +289,23 @@ def bind(lib: C.CDLL, prefix: str):
             if fn.to_host(self._h, out.ctypes.data_as(_DP)) != 0:
                 raise TaylorError((fn.last_error() or b"").decode())
             return out.reshape(((2,) + sh) if W == 2 else sh)
+
+        def to_torch(self, out=None):
+            """The stored (compact) coefficients as a float64 tensor on the library's GPU (intervals stacked [2, ...]), or
+            written into ``out`` (that shape, any non-overlapping strides).  Written on torch's current stream; no host memory."""
+            torch = interop("to_torch")
+            sh = self.coeffs_shape()
+            full = ((2,) + sh) if W == 2 else sh
+            if out is None:
+                out = torch.empty(full, dtype=torch.float64, device=torch.device("cuda", lib_device()))
+            else:
+                check_tensor(torch, out, "to_torch")
+                if tuple(out.shape) != full:
+                    raise TaylorError(f"to_torch: out has shape {tuple(out.shape)}, the coefficients have {full}")
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+            if fn.to_device(self._h, C.c_void_p(out.data_ptr()), strides_of(out), C.c_void_p(stream)) != 0:
+                raise TaylorError((fn.last_error() or b"").decode())
+            return out
 
         def is_constant(self) -> bool:
             return bool(fn.is_constant(self._h))

@@ -62,6 +62,8 @@ void gft_shutdown(void);
 /* Adopt an existing hipStream_t (e.g. torch's current stream); NULL restores the library's own. */
 int gft_set_stream(void* hip_stream);
 void* gft_get_stream(void);
+/* The HIP device ordinal the library runs on (gft_init(-1) first if nothing has initialised it); -1 on failure. */
+int gft_device(void);
 int gft_synchronize(void);
 const char* gft_last_error(void);
 /* Device-memory statistics in bytes: {in_use, cached, peak_in_use}.  in_use and peak include the kernels' grow-only
@@ -168,6 +170,18 @@ int gft_conv_raw_sharded(const double* x, const size_t* xshape, const double* y,
 /* ---- constructors ------------------------------------------------------------------------- */
 gft_poly* gft_from_host(const double* coeffs, const size_t* shape, const size_t* degrees_p1,
                         size_t ndim);                                   /* TaylorPoly::new        mt:33-41   */
+/* Copy a caller-owned DEVICE tensor into a new handle (TaylorPoly::new, mt:33-46; the handle owns a copy in its own pool
+ * block).  `strides` are element strides (not bytes), ndim of them for gft_, ndim + 1 for gfti_ (the first is the lo -> hi
+ * plane stride: interval data stacked as [2, *shape]); NULL = C-contiguous with the planes back to back, the gft_to_host
+ * layout.  Stride 0 (a broadcast view) is accepted, negative strides are not.  `src` must be device memory of the library's
+ * GPU.  Shape and degrees are validated as gft_from_host validates them.  Nothing is read on the host: the result is a
+ * plain device tensor (no host tier, no affine shortcut).
+ * Stream contract: `stream` is the caller's hipStream_t (0 = the HIP null stream, which is torch's default stream on
+ * ROCm).  The copy is ordered after all work issued so far on the caller's stream and the library's, and before all work
+ * issued later on either; the call does not wait for the copy.  `src` may be freed and reused on the caller's stream as
+ * soon as the call returns. */
+gft_poly* gft_from_device(const double* src, const int64_t* strides, const size_t* shape, const size_t* degrees_p1,
+                          size_t ndim, void* stream);
 gft_poly* gft_scalar(const double* x);                                  /* From<T>                mt:626-630 */
 gft_poly* gft_from_u32(uint32_t c);                                     /* from_u32               mt:219-225 */
 gft_poly* gft_zero_with(const size_t* degrees_p1, size_t ndim);         /* zero_with              mt:208-216 */
@@ -185,6 +199,13 @@ size_t gft_numel(const gft_poly* p);                                    /* coeff
 void gft_shape(const gft_poly* p, size_t* out);                         /* coeffs.shape() (compact)          */
 void gft_degrees_p1(const gft_poly* p, size_t* out);                    /* shape()                mt:53-56   */
 int gft_to_host(const gft_poly* p, double* out);                        /* array()/into_array     mt:58-66   */
+/* Write the handle's coefficients, in its compact shape as gft_to_host gives them, into caller-owned DEVICE memory with the
+ * given element strides (NULL = C-contiguous, planes back to back; gfti_ takes the plane stride first).  Zero strides on an
+ * axis longer than 1, negative strides and destinations whose elements overlap are refused.  Lazy scalars, host-tier
+ * tensors, deferred chains and recorded launch graphs are materialised on the device first.  Same stream contract as
+ * gft_from_device: ordered after earlier work on both streams (torch kernels still reading or writing `dst` included),
+ * before later work on both; 0 on success. */
+int gft_to_device(const gft_poly* p, double* dst, const int64_t* strides, void* stream);
 size_t gft_len_of(const gft_poly* p, size_t v);                         /* len_of                 mt:72-79   */
 int gft_is_constant(const gft_poly* p);                                 /* is_constant            mt:68-70   */
 int gft_is_zero(const gft_poly* p);                                     /* Zero::is_zero          mt:643-645 */
@@ -250,6 +271,8 @@ gft_poly* gft_mul_linear(const gft_poly* a, const double* c, const double* m, si
 const char* gfti_last_error(void);
 int gfti_width(void);
 gft_poly* gfti_from_host(const double* planes, const size_t* shape, const size_t* degrees_p1, size_t ndim);
+gft_poly* gfti_from_device(const double* src, const int64_t* strides, const size_t* shape, const size_t* degrees_p1,
+                           size_t ndim, void* stream);
 gft_poly* gfti_scalar(const double* x);
 gft_poly* gfti_from_u32(uint32_t c);
 gft_poly* gfti_zero_with(const size_t* degrees_p1, size_t ndim);
@@ -263,6 +286,7 @@ size_t gfti_numel(const gft_poly* p);
 void gfti_shape(const gft_poly* p, size_t* out);
 void gfti_degrees_p1(const gft_poly* p, size_t* out);
 int gfti_to_host(const gft_poly* p, double* out);
+int gfti_to_device(const gft_poly* p, double* dst, const int64_t* strides, void* stream);
 size_t gfti_len_of(const gft_poly* p, size_t v);
 int gfti_is_constant(const gft_poly* p);
 int gfti_is_zero(const gft_poly* p);

@@ -12,7 +12,8 @@ DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED extern block (tools/gen_rust_extern.py) -->", "<!-- END GENERATED extern block -->"
 
 TYPES = {
-    "int": "c_int", "long": "c_long", "size_t": "usize", "double": "f64", "float": "f32", "uint32_t": "u32",
+    "int": "c_int", "long": "c_long", "size_t": "usize", "double": "f64", "float": "f32", "uint32_t": "u32", "int64_t": "i64",
+    "const int64_t*": "*const i64",
     "const double*": "*const f64", "double*": "*mut f64", "const size_t*": "*const usize", "size_t*": "*mut usize",
     "const gft_poly*": "*const GftPoly", "gft_poly*": "*mut GftPoly", "void*": "*mut c_void", "const void*": "*const c_void",
     "const char*": "*const c_char", "char*": "*mut c_char",
