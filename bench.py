@@ -2,7 +2,7 @@
 """bench.py — headline benchmark of the hot path: TaylorPoly mul f64 (dense truncated N-d
 polynomial product, src/multivariate_taylor.rs:971-1072) in GMAC/s on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|small] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|small] [--dump-outputs DIR] [--full]
 
 A "step" is one full product z = x (*) y of the workload with x, y already resident in HBM
 (synthetic splitmix64 inputs, SURVEY §8d).  N > 1: one process per GPU (torchrun / RANK env);
@@ -12,8 +12,14 @@ timed region => "strong" scaling of one product.
 
 Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (the product kernel
 against the gfx950 FP64 FMA peak — the product is compute-bound, SURVEY §8d — with the
-algorithmic-HBM figure beside it) and `cpu_baseline` (the oracle = scalar restatement of the
-reference loop nest, timed on this box's host cores on a bounded sample; N = 1 only).
+algorithmic-HBM figure beside it; both from the HIP events of the timed steps).
+
+A plain run does only that: set up, warm up, time the steps, write --dump-outputs.  `--full` adds
+everything that costs runs of its own: `cpu_baseline` (the oracle = scalar restatement of the
+reference loop nest, timed on the host cores on a bounded sample) and the oracle parity sample
+it doubles as, the shader clock during and after the timed loop, and the `e2e` seconds (N = 1
+only); for N > 1, the exchange self-test before the timed region and the single-GPU comparison
+after it.
 """
 import argparse
 import ctypes
@@ -463,10 +469,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end seconds of the NeurIPS'23 programs (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU baselines and oracle parity, "
+                         "shader clock, end-to-end seconds (N = 1); exchange self-test and single-GPU comparison (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and oracle parity")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end seconds of the NeurIPS'23 programs (N = 1 only)")
     ap.add_argument("--conv-mode", type=int, default=0, help="0 auto, 1 reference-order kernel, 2 tiled kernel")
-    ap.add_argument("--no-clock", action="store_true", help="do not sample the shader clock under load (rocm-smi)")
+    ap.add_argument("--no-clock", action="store_true", help="with --full: do not sample the shader clock (sysfs, rocm-smi)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the product of the last timed step to DIR/z.npy (float64; a fixed sample above 64 MB)")
     args = ap.parse_args()
@@ -474,10 +483,11 @@ def main():
         ap.error("--steps must be at least 1")
 
     # (before anything initialises the GPU: see start_clock_helper / ensure_oracle — nothing below spawns a process)
-    have_oracle = ensure_oracle() if int(os.environ.get("RANK", "0")) == 0 else os.path.exists(os.path.join(ROOT, "oracle", "liborc.so"))
-    clock_helper = None
-    if not args.no_clock and int(os.environ.get("WORLD_SIZE", "1")) == 1:
-        clock_helper = start_clock_helper()
+    have_oracle, clock_helper = False, None
+    if args.full:
+        have_oracle = ensure_oracle() if int(os.environ.get("RANK", "0")) == 0 else os.path.exists(os.path.join(ROOT, "oracle", "liborc.so"))
+        if not args.no_clock and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+            clock_helper = start_clock_helper()
 
     import torch
     import torch.distributed as dist
@@ -549,10 +559,10 @@ def main():
             exchange = "torch"
             exchange_note = (err or "another rank could not create the C-ABI communicator") + "; torch.distributed exchange used"
 
-    # every rank proves the exchange (both sharded entries, even and uneven splits, bit for bit against its own full
-    # product) before anything is timed; a mismatch aborts the job non-zero
+    # --full: every rank proves the exchange (both sharded entries, even and uneven splits, bit for bit against its own
+    # full product) before anything is timed; a mismatch aborts the job non-zero
     selftest = None
-    if exchange == "abi":
+    if exchange == "abi" and args.full:
         selftest = "ok" if L.gft_dist_selftest() == 0 else (L.gft_last_error() or b"failed").decode()
         if selftest != "ok":
             print(json.dumps({"error": "gft_dist_selftest failed", "rank": rank, "detail": selftest}), flush=True)
@@ -632,6 +642,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,  # false: headline only (CPU baselines, clock, e2e and the parity checks need --full)
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "strong",
@@ -675,7 +686,7 @@ def main():
         },
     }
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         clk = sclk_under_load(lambda: step(False), clock_helper)
         if clk:
             out["roofline"].update(clk)
@@ -689,7 +700,9 @@ def main():
             clock_helper.stdin.close()  # never told to sample: let it go
         except Exception:  # noqa: BLE001
             pass
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not have_oracle:
+    if not args.full:
+        out["cpu_baseline"] = None  # (timed with --full)
+    elif rank == 0 and world == 1 and not args.no_cpu_baseline and not have_oracle:
         out["cpu_baseline"] = None
         out["cpu_baseline_note"] = "oracle/liborc.so is missing and could not be built before GPU initialisation; CPU legs skipped"
     elif rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -741,7 +754,7 @@ def main():
             out["rccl_comm_count_per_rank"] = counts
             if exchange_note:
                 out["exchange_note"] = exchange_note
-    if rank == 0 and world == 1 and not args.no_e2e and args.workload == "c2":
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and args.workload == "c2":
         out["e2e"] = e2e_seconds(oracle_available=have_oracle)
         if out["e2e"].pop("parity_failed"):
             out["parity_failed"] = True

@@ -66,6 +66,37 @@ def test_smoke_builds_the_oracle_before_it_initialises_the_gpu():
     assert "subprocess" not in after and "os.system" not in after and "_oracle_cls" not in after
 
 
+def test_plain_run_does_only_the_headline():
+    """Everything beside the timed steps that costs time of its own (oracle build, clock sampler, CPU baselines and parity,
+    e2e seconds, the N > 1 self-test and single-GPU comparison) sits under a branch on `args.full` in main()."""
+    tree = ast.parse(_bench_source())
+    main = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    extras = {"ensure_oracle", "start_clock_helper", "sclk_under_load", "cpu_baseline", "cpu_baseline_all_cores", "e2e_seconds",
+              "gft_dist_selftest", "gpu_conv_slabs"}
+    found = set()
+
+    def mentions_full(expr):
+        return any(isinstance(n, ast.Attribute) and n.attr == "full" for n in ast.walk(expr))
+
+    def visit(node, guarded):
+        if isinstance(node, ast.Call):
+            f = node.func
+            name = f.attr if isinstance(f, ast.Attribute) else getattr(f, "id", None)
+            if name in extras:
+                assert guarded, f"{name}() runs without --full (line {node.lineno})"
+                found.add(name)
+        if isinstance(node, ast.If) and mentions_full(node.test):
+            visit(node.test, guarded)
+            for child in node.body + node.orelse:
+                visit(child, True)
+            return
+        for child in ast.iter_child_nodes(node):
+            visit(child, guarded)
+
+    visit(main, False)
+    assert found == extras, extras - found
+
+
 def test_e2e_rows_carry_a_parity_verdict():
     src = _bench_source()
     body = src[src.index("def e2e_seconds("):src.index("_CLOCK_HELPER")]

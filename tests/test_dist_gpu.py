@@ -24,15 +24,16 @@ def test_sharded_product_two_ranks_one_gpu(world):
 @pytest.mark.gpu
 def test_bench_n2_control_flow_dry_run_on_one_gpu():
     """bench.py's own N > 1 control flow (rendezvous, agreement all-reduces, sharded step, max-over-ranks timing, the
-    per-rank gather, rank 0's single JSON line) executed BEFORE the driver's 8-GPU run does it for the first time: two
-    ranks on one device, gloo rendezvous, torch.distributed exchange (RCCL refuses two ranks on one device).  No scaling
+    per-rank gather, rank 0's single JSON line, and with --full the single-GPU comparison) executed BEFORE the driver's
+    8-GPU run does it for the first time: two ranks on one device, gloo rendezvous, torch.distributed exchange (RCCL
+    refuses two ranks on one device).  No scaling
     number is taken from this — the line must say that the exchange was not the library's own."""
     import json
 
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", GFT_BENCH_BACKEND="gloo", GFT_BENCH_EXCHANGE="torch")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29611", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--workload", "small", "--no-clock"]
+           "--workload", "small", "--full", "--no-clock"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]

@@ -73,7 +73,7 @@ print(json.dumps({k: v for k, v in agg.items() if k not in ("_note", "workload")
 PY
 cd "$ROOT"
 cp "$OUT/summary/pmc_k_conv_tiled_c4.json" "$OUT/summary/pmc_k_conv_tiled_c2.json" profiles/r06/ 2>/dev/null  # (bench.py reads the committed files: make this run's visible to the two bench lines below)
-python3 bench.py --steps 20 --warmup 3 > "$OUT/summary/bench_c2_n1.json" 2> "$OUT/bench_c2.err"
+python3 bench.py --steps 20 --warmup 3 --full > "$OUT/summary/bench_c2_n1.json" 2> "$OUT/bench_c2.err"
 python3 bench.py --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-clock > "$OUT/summary/bench_c4_n1.json" 2> "$OUT/bench_c4.err"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/microbench_fp64.hip -o /tmp/microbench_fp64 2> "$OUT/mb.err" && /tmp/microbench_fp64 > "$OUT/summary/microbench_fp64.txt" 2>&1
 python3 tools/bench_interval.py > "$OUT/summary/interval_product.txt" 2> "$OUT/iv.err"
