@@ -20,6 +20,7 @@ import os
 # This is the HOST's choice: libgftaylor itself never touches the environment.
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
+from . import series  # noqa: F401  (batched series on device tensors; loads the library on first use)
 from .taylor import USIZE_MAX, TaylorError, bind  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -33,6 +33,7 @@
 #include "gft_host.hpp"
 #include "gft_fmt.hpp"
 #include "gft_interop.hpp"
+#include "gft_series.hpp"
 
 using namespace gft;
 static const size_t UMAX = SIZE_MAX;
@@ -213,6 +214,8 @@ struct Runtime {
     static constexpr int IO_EVENTS = 16;
     hipEvent_t io_events[IO_EVENTS] = {};  // the device interop's stream joins (interop_event), created on first use
     int io_next = 0;
+    int series_force = 0;  // gft_set_option("series_form"): 0 = by the thresholds, 1 / 2 = form A (where the rows fit) / form B
+    int series_last = 0;   // the form the last gft_series_* call took (gft_series_last_form)
     int conv_mode = 0;
     static constexpr int pairs_first = 1;  // small plain f64 products ask the row-pair form before the tiled kernel ("pairs_first", GFT_PAIRS_FIRST)
     double pairs_first_max = 1.0e7, pairs_first_max_rank2 = 2.0e8;  // ... up to this many multiply-adds (rank >= 3 / rank 2)
@@ -1423,6 +1426,7 @@ int gft_set_option(const char* name, double value) {
     else if (n == "tiled_tile") tiled_set_lane_tile((int)value);
     else if (n == "host_max_elems") R.host_max_elems = value < 0 ? Runtime::HOST_MAX_ELEMS_DEFAULT : (size_t)value;  // < 0: default
     else if (n == "host_max_macs") R.host_max_macs = value < 0 ? Runtime::HOST_MAX_MACS_DEFAULT : value;
+    else if (n == "series_form") R.series_force = (value == 1 || value == 2) ? (int)value : 0;  // test / measurement knob (gft_series.hpp)
     else if (n == "dist_min_macs") dist_set_min_macs(value);
     else if (n == "dist_event_slot") dist_set_event_slot(value);
     else return -1;
@@ -1863,6 +1867,8 @@ static int to_device(const gft_poly& p, double* dst, const int64_t* strides, voi
 }
 
 }  // namespace
+
+#include "gft_api_series.inc"  // gft_series_mul / div / exp / log: batched series on caller-owned device tensors
 
 // ------------------------------------------------------------------------------------------
 // C ABI — handle API, generated for both element types

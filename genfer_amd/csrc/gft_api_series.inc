@@ -1,0 +1,158 @@
+// ------------------------------------------------------------------------------------------
+// batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log
+// (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
+// pointer check and stream joins it shares)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct SeriesArg {  // one operand of a call: rows of `len` elements (unit stride), batch strides in elements
+    const char* what;
+    const double* p;
+    size_t len;
+    size_t st[32];
+    size_t span;  // elements from p to one past its last element
+};
+
+static SeriesArg series_arg(const char* fn, const char* what, const double* p, const int64_t* bs, size_t len, const size_t* batch, size_t nbatch) {
+    SeriesArg a;
+    a.what = what;
+    a.p = p;
+    a.len = len;
+    size_t cs = len;  // NULL: contiguous rows of the operand's own length
+    a.span = len;
+    for (size_t i = nbatch; i-- > 0;) {
+        if (bs && bs[i] < 0)
+            throw Error(std::string(fn) + ": negative strides are not supported (" + what + ", batch axis " + std::to_string(i) + ")");
+        a.st[i] = bs ? (size_t)bs[i] : cs;
+        cs *= batch[i];
+        a.span += (batch[i] - 1) * a.st[i];
+    }
+    return a;
+}
+
+static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_t* batch, size_t nbatch) {
+    if (a.p != b.p || a.len != b.len) return false;
+    for (size_t i = 0; i < nbatch; ++i)
+        if (batch[i] > 1 && a.st[i] != b.st[i]) return false;
+    return true;
+}
+
+// `y`: the second operand (mul, div) or the seeds (exp, log; may be null)
+static int series_call(int op, const char* fn, const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
+                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV;
+    const std::string f(fn);
+    if (n == 0) throw Error(f + ": n == 0 (the result has no coefficients)");
+    if (n > gft::SERIES_MAX_N)
+        throw Error(f + ": n = " + std::to_string(n) + " exceeds the limit of " + std::to_string(gft::SERIES_MAX_N) + " coefficients per series of this version");
+    if (nx == 0 || (binary && ny == 0)) throw Error(f + ": an operand has no coefficients");
+    if (nx > n) throw Error(f + ": nx = " + std::to_string(nx) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
+    if (binary && ny > n) throw Error(f + ": ny = " + std::to_string(ny) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
+    if (nbatch > 32) throw Error(f + ": more than 32 batch axes");
+    if (nbatch && !batch) throw Error(f + ": the batch shape is a null pointer");
+    size_t items = 1;
+    for (size_t i = 0; i < nbatch; ++i) {
+        if (batch[i] == 0) return 0;  // an empty batch: nothing to do
+        items *= batch[i];
+        if (items >= ((size_t)1 << 31)) throw Error(f + ": more than 2^31 - 1 series in one call");
+    }
+    SeriesArg ax = series_arg(fn, "x", x, xbs, nx, batch, nbatch);
+    SeriesArg ay = series_arg(fn, binary ? "y" : "the seeds", y, ybs, binary ? ny : 1, batch, nbatch);
+    SeriesArg ar = series_arg(fn, "the result", res, rbs, n, batch, nbatch);
+    // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
+    {
+        struct Ax {
+            size_t ext, st;
+        } axes[33];
+        int k = 0;
+        for (size_t i = 0; i < nbatch; ++i) {
+            if (batch[i] <= 1) continue;
+            if (ar.st[i] == 0) throw Error(f + ": the result has a zero stride (batch axis " + std::to_string(i) + "): its series overlap");
+            axes[k++] = Ax{batch[i], ar.st[i]};
+        }
+        if (n > 1) axes[k++] = Ax{n, 1};
+        std::sort(axes, axes + k, [](const Ax& u, const Ax& v) { return u.st < v.st; });
+        for (int i = 1; i < k; ++i)
+            if (axes[i].st / axes[i - 1].ext < axes[i - 1].st)
+                throw Error(f + ": the result's series overlap each other (its strides do not separate the rows)");
+    }
+    check_device_ptr(x, (f + ": x").c_str());
+    if (binary || y) check_device_ptr(y, (f + (binary ? ": y" : ": the seeds")).c_str());
+    check_device_ptr(res, (f + ": the result").c_str());
+    // the result may be an input itself (the same view: every row is read before it is written); any other overlap is refused.
+    // Judged by address ranges, so two interleaved views of one buffer count as overlapping.
+    bool inplace = false;
+    auto overlap = [&](const SeriesArg& a, bool same_ok) {
+        if (a.p + a.span <= ar.p || ar.p + ar.span <= a.p) return;
+        if (same_ok && series_same_view(a, ar, batch, nbatch)) {
+            inplace = true;
+            return;
+        }
+        throw Error(f + ": the result partially overlaps " + a.what + " (it may alias an operand only as the same view)");
+    };
+    overlap(ax, true);
+    if (binary) overlap(ay, true);
+    else if (y) overlap(ay, false);
+    // collapse the batch: unit axes go, axes contiguous with their inner neighbour on every operand merge
+    gft::SeriesBatch g;
+    g.nd = 0;
+    g.items = (unsigned)items;
+    g.inplace = inplace;
+    const bool seeds = !binary && y;
+    for (size_t i = 0; i < nbatch; ++i) {
+        if (batch[i] == 1) continue;
+        const size_t e = batch[i], sx = ax.st[i], sy = binary ? ay.st[i] : 0, ss = seeds ? ay.st[i] : 0, sr = ar.st[i];
+        if (g.nd > 0) {
+            const int p = g.nd - 1;
+            // (merged extents stay below 2^31: items does)
+            if (g.xs[p] == sx * e && g.ys[p] == sy * e && g.ss[p] == ss * e && g.rs[p] == sr * e) {
+                g.ext[p] *= (unsigned)e;
+                g.xs[p] = sx;
+                g.ys[p] = sy;
+                g.ss[p] = ss;
+                g.rs[p] = sr;
+                continue;
+            }
+        }
+        if (g.nd == gft::IMAXD - 1)
+            throw Error(f + ": the batch has more than " + std::to_string(gft::IMAXD - 1) + " non-contiguous axes");
+        g.ext[g.nd] = (unsigned)e;
+        g.xs[g.nd] = sx;
+        g.ys[g.nd] = sy;
+        g.ss[g.nd] = ss;
+        g.rs[g.nd] = sr;
+        ++g.nd;
+    }
+    const int form = gft::series_plan(op, g.items, (unsigned)n, R.series_force);
+    const size_t wsn = gft::series_workspace(op, form, g.items, (unsigned)nx, (unsigned)n);
+    Rc<Buf> ws;
+    if (wsn) ws = alloc_doubles(wsn);  // (returned to the pool on exit: later launches follow these on the one stream)
+    const hipStream_t cs = (hipStream_t)stream;
+    join_caller_in(cs);
+    gft::series_launch(R.stream, op, form, x, (unsigned)nx, y, (unsigned)ny, res, (unsigned)n, g, wsn ? ws->p : nullptr);
+    join_caller_out(cs);
+    R.series_last = form;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+int gft_series_mul(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_MUL, "series_mul", x, xbs, nx, y, ybs, ny, res, rbs, n, batch, nbatch, stream); });
+}
+int gft_series_div(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_DIV, "series_div", x, xbs, nx, y, ybs, ny, res, rbs, n, batch, nbatch, stream); });
+}
+int gft_series_exp(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_EXP, "series_exp", x, xbs, nx, seed, sbs, 1, res, rbs, n, batch, nbatch, stream); });
+}
+int gft_series_log(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_LOG, "series_log", x, xbs, nx, seed, sbs, 1, res, rbs, n, batch, nbatch, stream); });
+}
+int gft_series_last_form(void) { return R.series_last; }
+}

@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "gft_kernels.hpp"
+#include "gft_series.hpp"
 #include <cstring>
 #include <type_traits>
 #include <map>
@@ -478,9 +479,9 @@ __global__ void __launch_bounds__(1024) k_div_2d_rows64(const double* __restrict
 // the three element-wise launches the row recursion of div_rec spent per row.
 constexpr int DIV1D_EPT = 4;  // outputs per thread: n <= 4096 in one workgroup
 template <class E>
-__global__ void __launch_bounds__(1024) k_div_1d(const double* __restrict__ xs, size_t xp, unsigned nx,
-                                                 const double* __restrict__ ys, size_t yp, unsigned ny, double* res, size_t rp,
-                                                 unsigned n, int fused) {
+__device__ __forceinline__ void div_1d_body(const double* __restrict__ xs, size_t xp, unsigned nx,
+                                            const double* __restrict__ ys, size_t yp, unsigned ny, double* res, size_t rp,
+                                            unsigned n, int fused) {
     typedef typename E::V V;
     extern __shared__ double d1_lds[];  // [plane][n] quotient mirror, [plane][ny] divisor row
     double* rl = d1_lds;
@@ -530,14 +531,27 @@ __global__ void __launch_bounds__(1024) k_div_1d(const double* __restrict__ xs, 
         }
     }
 }
+template <class E>
+__global__ void __launch_bounds__(1024) k_div_1d(const double* __restrict__ xs, size_t xp, unsigned nx,
+                                                 const double* __restrict__ ys, size_t yp, unsigned ny, double* res, size_t rp,
+                                                 unsigned n, int fused) {
+    div_1d_body<E>(xs, xp, nx, ys, yp, ny, res, rp, n, fused);
+}
+// the same division for item blockIdx.x of a batch (gft_series.hpp); all loads of a row precede its stores, so `res` may be x or y
+template <class E>
+__global__ void __launch_bounds__(1024) k_div_1d_batch(const double* xs, unsigned nx, const double* ys, unsigned ny, double* res,
+                                                       unsigned n, SeriesBatch g) {
+    const SeriesOff o = series_offsets(g, blockIdx.x);
+    div_1d_body<E>(xs + o.x, 0, nx, ys + o.y, 0, ny, res + o.r, 0, n, 0);
+}
 // Rows of at most 1024 coefficients: ONE wave, DIV1D_WSEG = 4, 8 or 16 coefficients per lane (k = 64 e + lane).  The quotient coefficient of
 // the step reaches all lanes by v_readlane instead of an LDS round trip plus a workgroup barrier — 0.06 us a step on
 // the slab kernel's divider against 0.44 us here before (a lone workgroup runs at the idle clock; every instruction and
 // every barrier of the chain is paid in full) — and the divisor row comes from LDS at a per-lane sliding address.
 template <class E, int DIV1D_WSEG>
-__global__ void __launch_bounds__(64) k_div_1d_wave(const double* __restrict__ xs, size_t xp, unsigned nx,
-                                                    const double* __restrict__ ys, size_t yp, unsigned ny, double* res, size_t rp,
-                                                    unsigned n, int fused) {
+__device__ __forceinline__ void div_1d_wave_body(const double* __restrict__ xs, size_t xp, unsigned nx,
+                                                 const double* __restrict__ ys, size_t yp, unsigned ny, double* res, size_t rp,
+                                                 unsigned n, int fused) {
     typedef typename E::V V;
     extern __shared__ double d1_lds[];  // [plane][64 zeros | 64 * DIV1D_WSEG of the divisor row, zero beyond ny]
     constexpr unsigned CAP = 64 * (DIV1D_WSEG + 1);
@@ -623,6 +637,18 @@ __global__ void __launch_bounds__(64) k_div_1d_wave(const double* __restrict__ x
         if (k < n) E::st(res, rp, k, mine[e]);
     }
 }
+template <class E, int DIV1D_WSEG>
+__global__ void __launch_bounds__(64) k_div_1d_wave(const double* __restrict__ xs, size_t xp, unsigned nx,
+                                                    const double* __restrict__ ys, size_t yp, unsigned ny, double* res, size_t rp,
+                                                    unsigned n, int fused) {
+    div_1d_wave_body<E, DIV1D_WSEG>(xs, xp, nx, ys, yp, ny, res, rp, n, fused);
+}
+template <class E, int DIV1D_WSEG>
+__global__ void __launch_bounds__(64) k_div_1d_wave_batch(const double* xs, unsigned nx, const double* ys, unsigned ny, double* res,
+                                                          unsigned n, SeriesBatch g) {
+    const SeriesOff o = series_offsets(g, blockIdx.x);
+    div_1d_wave_body<E, DIV1D_WSEG>(xs + o.x, 0, nx, ys + o.y, 0, ny, res + o.r, 0, n, 0);
+}
 // serial fallback for n > 4096
 template <class E>
 __global__ void k_div_1d_serial(const double* xs, size_t xp, unsigned nx, const double* ys, size_t yp, unsigned ny,
@@ -663,6 +689,23 @@ bool K<E>::div_1d(hipStream_t st, const double* xs, size_t x_plane, unsigned nx,
     GFT_LAUNCH(k_div_1d<E>, dim3(1), dim3(threads), (size_t)E::W * ((size_t)n + std::min(ny, n)) * sizeof(double), st, xs, x_plane, nx, ys,
                        y_plane, ny, res, r_plane, n, fused);
     return true;
+}
+// gft_series.hpp: form B of the batched division — one wave (n <= 1024) or one workgroup per item, the kernels above
+void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
+                     const SeriesBatch& g) {
+    typedef EF64 E;
+    if (n <= 1024) {
+#define GFT_D1WB(SEG) \
+    GFT_LAUNCH((k_div_1d_wave_batch<E, SEG>), dim3(g.items), dim3(64), (size_t)E::W * 64 * (SEG + 1) * sizeof(double), st, x, nx, y, ny, res, n, g)
+        if (n <= 256) GFT_D1WB(4);
+        else if (n <= 512) GFT_D1WB(8);
+        else GFT_D1WB(16);
+#undef GFT_D1WB
+        return;
+    }
+    const unsigned threads = std::min<unsigned>(1024, (n + 63) / 64 * 64);
+    GFT_LAUNCH(k_div_1d_batch<E>, dim3(g.items), dim3(threads), (size_t)E::W * ((size_t)n + std::min(ny, n)) * sizeof(double), st, x, nx, y,
+               ny, res, n, g);
 }
 template bool K<EF64>::div_1d(hipStream_t, const double*, size_t, unsigned, const double*, size_t, unsigned, double*, size_t, unsigned, int);
 template bool K<EIv>::div_1d(hipStream_t, const double*, size_t, unsigned, const double*, size_t, unsigned, double*, size_t, unsigned, int);

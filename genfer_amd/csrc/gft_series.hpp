@@ -1,0 +1,67 @@
+// Batched univariate series on caller-owned device tensors (gft_series_mul / div / exp / log): B independent truncated power
+// series per call, the last axis of every operand is the series, the leading axes are the batch.  Per item the results are
+// the reference's GENERAL algorithms in its operation order (mul_1d mt:972-982, div mt:1162-1192 at one axis, exp_1d
+// mt:1271-1283, log_1d mt:1319-1333), multiply and add rounded separately.  None of the data-dependent shortcuts of the
+// operator wrappers is taken (Mul: zero / one / constant / linear, mt:1020-1070; Div: one / constant, mt:1204-1213): a batch
+// cannot branch per item on the host, and the result of an item must not depend on what else is in the batch.
+//
+// The host side (gft_api_series.inc) validates, collapses the batch axes into a SeriesBatch and joins the streams; this
+// file's planner picks a form and gft_series.hip (div form B: gft_div2d.hip) launches it on the library's stream.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "gft_interop.hpp"  // IMAXD, interop_copy
+
+namespace gft {
+
+enum SeriesOp { SERIES_MUL = 0, SERIES_DIV = 1, SERIES_EXP = 2, SERIES_LOG = 3 };
+// A: one lane is one series, rows staged in LDS.  B: one wave / workgroup is one series (mul, div); for exp / log the
+// lane-per-series loop of form A over a transposed global workspace.
+enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
+
+constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
+
+// The collapsed batch: item (i_0, ..., i_{nd-1}), row-major over ext, has its rows at x + sum i_a * xs[a] (elements), and
+// likewise y (mul / div), the seeds (exp / log; one double per item) and the result.  Stride 0 repeats a row.
+struct SeriesBatch {
+    int nd = 0;
+    unsigned items = 1;  // prod ext, < 2^31
+    int inplace = 0;     // the result is one of the operands (the same view): a row is written by the workgroup that read it
+    unsigned ext[IMAXD];
+    size_t xs[IMAXD], ys[IMAXD], ss[IMAXD], rs[IMAXD];
+};
+
+// The form a call takes.  force: 0 = by the thresholds, SERIES_FORM_A = form A whenever the rows fit its LDS budget,
+// SERIES_FORM_B = never form A (gft_set_option("series_form")).
+int series_plan(int op, unsigned items, unsigned n, int force);
+// doubles of device workspace the call needs (form B of exp / log: the transposed operand and result), else 0
+size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n);
+// Launches the call on `st`.  `y`: the second operand of mul / div; for exp / log the seeds or nullptr (seeds formed on the
+// device by the HIP device library's exp / log).  `ws`: series_workspace() doubles.
+void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
+                   unsigned n, const SeriesBatch& g, double* ws);
+// form B of div: k_div_1d_wave / k_div_1d with blockIdx.x as the item (gft_div2d.hip)
+void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
+                     const SeriesBatch& g);
+
+// the element offsets of item `it` (kernels of gft_series.hip and gft_div2d.hip)
+struct SeriesOff {
+    size_t x, y, s, r;
+};
+__device__ inline SeriesOff series_offsets(const SeriesBatch& g, unsigned it) {
+    SeriesOff o{0, 0, 0, 0};
+    unsigned q = it;
+    for (int a = g.nd - 1; a >= 0; --a) {
+        const unsigned e = g.ext[a], nq = q / e, k = q - nq * e;
+        q = nq;
+        o.x += (size_t)k * g.xs[a];
+        o.y += (size_t)k * g.ys[a];
+        o.s += (size_t)k * g.ss[a];
+        o.r += (size_t)k * g.rs[a];
+    }
+    return o;
+}
+
+}  // namespace gft

@@ -1,0 +1,221 @@
+// Device side of the batched series (gft_series.hip plans and launches these): the per-lane recurrences, form A's LDS
+// staging and the kernels, as templates over the element functor (gft_elem.hpp) so that an interval twin is an instantiation.
+// tests/series_isa_check.hip instantiates the form-A mul and div kernels from this file alone.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "gft_elem.hpp"
+#include "gft_series.hpp"
+
+namespace gft {
+
+template <class E>
+struct RowLds {  // lane's row in a wave's LDS array: [plane][64 * pitch]
+    double* p;
+    size_t plane;
+    __device__ typename E::V ld(unsigned i) const { return E::ld(p, plane, i); }
+    __device__ void st(unsigned i, typename E::V v) const { E::st(p, plane, i, v); }
+};
+template <class E>
+struct ColWs {  // item's column of a transposed workspace: [plane][n][items]
+    double* p;
+    size_t plane, items;
+    __device__ typename E::V ld(unsigned i) const { return E::ld(p, plane, (size_t)i * items); }
+    __device__ void st(unsigned i, typename E::V v) const { E::st(p, plane, (size_t)i * items, v); }
+};
+
+// ---- the recurrences, one series per lane (the loops of k_exp_1d / k_log_1d / k_div_1d_serial / k_conv_* reference order) ----
+// z[k] = 0 + sum_{j = lo .. hi-1} x[j] * y[k-j], ascending j (mul_1d, mt:972-982).  k runs downwards and z[k] overwrites y[k]:
+// the outputs still to come read y[0 .. k-1] only.
+template <class E, class AX, class AY>
+__device__ inline void rec_mul(const AX x, const AY y, unsigned nx, unsigned ny, unsigned n) {
+    typedef typename E::V V;
+    for (unsigned k = n; k-- > 0;) {
+        const unsigned lo = k + 1 > ny ? k + 1 - ny : 0, hi = k + 1 < nx ? k + 1 : nx;
+        V sum = E::zero();
+#pragma unroll 4
+        for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(x.ld(j), y.ld(k - j)));
+        y.st(k, sum);
+    }
+}
+// r[k] = (-(0 + sum_{j = lo .. k-1} r[j] * y[k-j]) + x[k]) / y[0] (div, mt:1162-1192 at one axis); r holds x on entry.
+template <class E, class AY, class AR>
+__device__ inline void rec_div(const AY y, const AR r, unsigned nx, unsigned ny, unsigned n) {
+    typedef typename E::V V;
+    const V y0 = y.ld(0);
+    for (unsigned k = 0; k < n; ++k) {
+        const unsigned lo = k + 1 > ny ? k + 1 - ny : 0;
+        V sum = E::zero();
+#pragma unroll 4
+        for (unsigned j = lo; j < k; ++j) sum = E::add(sum, E::mul(r.ld(j), y.ld(k - j)));
+        V c = E::neg(sum);
+        if (k < nx) c = E::add(c, r.ld(k));
+        r.st(k, E::div(c, y0));
+    }
+}
+// exp_1d, mt:1271-1283
+template <class E, class AX, class AR>
+__device__ inline void rec_exp(const AX x, const AR r, unsigned nx, unsigned n, typename E::V seed) {
+    typedef typename E::V V;
+    r.st(0, seed);
+    for (unsigned k = 1; k < n; ++k) {
+        const unsigned hi = nx < k + 1 ? nx : k + 1;
+        V sum = E::zero();
+#pragma unroll 4
+        for (unsigned j = 1; j < hi; ++j) sum = E::add(sum, E::mul(E::mul(x.ld(j), E::from_u32(j)), r.ld(k - j)));
+        r.st(k, E::div(sum, E::from_u32(k)));
+    }
+}
+// log_1d, mt:1319-1333.  A one-coefficient operand has no higher orders: they are written as +0 (the reference stores none).
+template <class E, class AX, class AR>
+__device__ inline void rec_log(const AX x, const AR r, unsigned nx, unsigned n, typename E::V seed) {
+    typedef typename E::V V;
+    const V x0 = x.ld(0);
+    r.st(0, seed);
+    for (unsigned k = 1; k < n; ++k) {
+        if (nx == 1) {
+            r.st(k, E::zero());
+            continue;
+        }
+        unsigned lo = k + 1 > nx ? k + 1 - nx : 0;
+        if (lo < 1) lo = 1;
+        V sum = E::zero();
+#pragma unroll 4
+        for (unsigned j = lo; j < k; ++j) sum = E::add(sum, E::mul(E::mul(x.ld(k - j), r.ld(j)), E::from_u32(j)));
+        const V xk = k < nx ? x.ld(k) : E::zero();
+        const V num = E::sub(E::mul(xk, E::from_u32(k)), sum);
+        r.st(k, E::div(E::div(num, x0), E::from_u32(k)));
+    }
+}
+
+// ---- form A staging ---------------------------------------------------------------------------------------------------------
+// The wave's 64 rows of `len` elements between global memory (row l at base + off_l, planes gp apart) and LDS (row l at
+// l * pitch, planes lp apart).  A group of 2^lg lanes walks one row, 64 >> lg rows per pass; every lane runs the same number
+// of passes (the row offset of pass t comes from its owner lane by a shuffle, which all lanes execute).
+template <class E, bool IN>
+__device__ inline void stage_rows(double* lds, size_t lp, unsigned pitch, double* gptr, size_t gp, size_t my_off, unsigned len,
+                                  unsigned lg, unsigned item0, unsigned items, unsigned lane) {
+    const unsigned G = 1u << lg, per = 64u >> lg, sub = lane >> lg, i0 = lane & (G - 1);
+    for (unsigned t = 0; t < G; ++t) {
+        const unsigned l = t * per + sub;
+        const size_t off = (size_t)__shfl((unsigned long long)my_off, (int)l, 64);
+        if (item0 + l >= items) continue;
+        for (unsigned i = i0; i < len; i += G) {
+#pragma unroll
+            for (int w = 0; w < E::W; ++w) {
+                if (IN) lds[w * lp + l * pitch + i] = gptr[w * gp + off + i];
+                else gptr[w * gp + off + i] = lds[w * lp + l * pitch + i];
+            }
+        }
+    }
+}
+
+struct FormA {  // what every form-A kernel derives from its thread index
+    unsigned lane, item0, it;
+    size_t lp;       // LDS plane stride: 64 * pitch
+    double *a0, *a1;  // the wave's two arrays
+};
+template <class E>
+__device__ inline FormA form_a(double* lds, unsigned pitch, unsigned items) {
+    FormA f;
+    const unsigned wave = threadIdx.x >> 6;
+    f.lane = threadIdx.x & 63;
+    f.lp = (size_t)64 * pitch;
+    f.a0 = lds + (size_t)wave * 2 * E::W * f.lp;
+    f.a1 = f.a0 + E::W * f.lp;
+    f.item0 = (blockIdx.x * (blockDim.x >> 6) + wave) * 64;
+    f.it = f.item0 + f.lane < items ? f.item0 + f.lane : items - 1;  // a lane past the batch: valid addresses, an unstaged row, nothing stored
+    return f;
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void k_series_mul_a(const double* x, size_t xp, unsigned nx, const double* y, size_t yp, unsigned ny,
+                                                      double* res, size_t rp, unsigned n, unsigned pitch, unsigned lg, SeriesBatch g) {
+    extern __shared__ double sa_lds[];
+    const FormA f = form_a<E>(sa_lds, pitch, g.items);
+    const SeriesOff o = series_offsets(g, f.it);
+    stage_rows<E, true>(f.a0, f.lp, pitch, const_cast<double*>(x), xp, o.x, nx, lg, f.item0, g.items, f.lane);
+    stage_rows<E, true>(f.a1, f.lp, pitch, const_cast<double*>(y), yp, o.y, ny, lg, f.item0, g.items, f.lane);
+    __syncthreads();
+    rec_mul<E>(RowLds<E>{f.a0 + f.lane * pitch, f.lp}, RowLds<E>{f.a1 + f.lane * pitch, f.lp}, nx, ny, n);
+    __syncthreads();
+    stage_rows<E, false>(f.a1, f.lp, pitch, res, rp, o.r, n, lg, f.item0, g.items, f.lane);
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void k_series_div_a(const double* x, size_t xp, unsigned nx, const double* y, size_t yp, unsigned ny,
+                                                      double* res, size_t rp, unsigned n, unsigned pitch, unsigned lg, SeriesBatch g) {
+    extern __shared__ double sa_lds[];
+    const FormA f = form_a<E>(sa_lds, pitch, g.items);
+    const SeriesOff o = series_offsets(g, f.it);
+    stage_rows<E, true>(f.a0, f.lp, pitch, const_cast<double*>(y), yp, o.y, ny, lg, f.item0, g.items, f.lane);
+    stage_rows<E, true>(f.a1, f.lp, pitch, const_cast<double*>(x), xp, o.x, nx, lg, f.item0, g.items, f.lane);
+    __syncthreads();
+    rec_div<E>(RowLds<E>{f.a0 + f.lane * pitch, f.lp}, RowLds<E>{f.a1 + f.lane * pitch, f.lp}, nx, ny, n);
+    __syncthreads();
+    stage_rows<E, false>(f.a1, f.lp, pitch, res, rp, o.r, n, lg, f.item0, g.items, f.lane);
+}
+
+// exp (LOG == false) / log: `seed` holds exp(x[0]) / ln(x[0]) per item, or is null: formed here by the device library
+template <class E, bool LOG>
+__global__ __launch_bounds__(256) void k_series_explog_a(const double* x, size_t xp, unsigned nx, const double* seed, size_t sp,
+                                                         double* res, size_t rp, unsigned n, unsigned pitch, unsigned lg, SeriesBatch g) {
+    extern __shared__ double sa_lds[];
+    const FormA f = form_a<E>(sa_lds, pitch, g.items);
+    const SeriesOff o = series_offsets(g, f.it);
+    stage_rows<E, true>(f.a0, f.lp, pitch, const_cast<double*>(x), xp, o.x, nx, lg, f.item0, g.items, f.lane);
+    __syncthreads();
+    const RowLds<E> xr{f.a0 + f.lane * pitch, f.lp}, rr{f.a1 + f.lane * pitch, f.lp};
+    const typename E::V sd = seed ? E::ld(seed, sp, o.s) : (LOG ? E::log(xr.ld(0)) : E::exp(xr.ld(0)));
+    if (LOG) rec_log<E>(xr, rr, nx, n, sd);
+    else rec_exp<E>(xr, rr, nx, n, sd);
+    __syncthreads();
+    stage_rows<E, false>(f.a1, f.lp, pitch, res, rp, o.r, n, lg, f.item0, g.items, f.lane);
+}
+
+// ---- form B ---------------------------------------------------------------------------------------------------------------
+// mul: blockIdx.x is the item, blockIdx.y a share of its outputs.  A thread owns the outputs k1 = t and k2 = n - 1 - t, together
+// n + 1 terms whatever t, each sum formed from +0 in ascending j over the stored operands only (the bounds of mul_1d).  Within a
+// wave j runs in step, so x[j] is one LDS address for the wave and y[k - j] consecutive across lanes.  A series may be shared
+// by several workgroups only when `res` is neither x nor y (g.inplace == 0): each stages the whole row pair before it stores.
+template <class E>
+__global__ __launch_bounds__(256) void k_series_mul_b(const double* x, size_t xp, unsigned nx, const double* y, size_t yp, unsigned ny,
+                                                      double* res, size_t rp, unsigned n, SeriesBatch g) {
+    typedef typename E::V V;
+    extern __shared__ double sb_lds[];  // [plane][nx] | [plane][ny]
+    double* xl = sb_lds;
+    double* yl = sb_lds + (size_t)E::W * nx;
+    const SeriesOff o = series_offsets(g, blockIdx.x);
+    for (unsigned i = threadIdx.x; i < nx; i += blockDim.x) E::st(xl, nx, i, E::ld(x + o.x, xp, i));
+    for (unsigned i = threadIdx.x; i < ny; i += blockDim.x) E::st(yl, ny, i, E::ld(y + o.y, yp, i));
+    __syncthreads();  // (every global load of this workgroup is done)
+    const unsigned half = (n + 1) / 2;
+    for (unsigned t = blockIdx.y * blockDim.x + threadIdx.x; t < half; t += gridDim.y * blockDim.x) {
+        const unsigned ks[2] = {t, n - 1 - t};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned k = ks[h];
+            if (h == 1 && k == ks[0]) break;  // the middle output of an odd n
+            const unsigned lo = k + 1 > ny ? k + 1 - ny : 0, hi = k + 1 < nx ? k + 1 : nx;
+            V sum = E::zero();
+#pragma unroll 4
+            for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(E::ld(xl, nx, j), E::ld(yl, ny, k - j)));
+            E::st(res + o.r, rp, k, sum);
+        }
+    }
+}
+
+// exp / log over the transposed workspace: xT [nx][items], rT [n][items], one lane per item
+template <class E, bool LOG>
+__global__ __launch_bounds__(64) void k_series_explog_ws(double* xT, unsigned nx, const double* seed, size_t sp, double* rT, unsigned n,
+                                                         SeriesBatch g) {
+    const unsigned it = blockIdx.x * 64 + threadIdx.x;
+    if (it >= g.items) return;
+    const size_t items = g.items;
+    const ColWs<E> xc{xT + it, (size_t)nx * items, items}, rc{rT + it, (size_t)n * items, items};
+    const typename E::V sd = seed ? E::ld(seed, sp, series_offsets(g, it).s) : (LOG ? E::log(xc.ld(0)) : E::exp(xc.ld(0)));
+    if (LOG) rec_log<E>(xc, rc, nx, n, sd);
+    else rec_exp<E>(xc, rc, nx, n, sd);
+}
+
+}  // namespace gft

@@ -116,7 +116,7 @@ int gft_set_conv_mode(int mode);
  * size, 2 whenever it applies, negative: the default), "conv_rb_pairs_cap" (bytes of row sums that form may hold at a time;
  * default 2 GiB), "conv_rb_pairs_lanes" (its slab ranges on two lanes: 0 never, 1 always, negative: the default rule),
  * "tiled_tile" (3..6 force the tiled product's lane tile 8x8 .. 1x64; 0: the planner's choice), "dist_min_macs" (smallest
- * general product gft_mul shards over the GPUs of gft_dist_init), "dist_event_slot".
+ * general product gft_mul shards over the GPUs of gft_dist_init), "dist_event_slot", "series_form" (gft_series_last_form).
  * TEST KNOBS: "debug_fail_next_launch" (1: the next kernel launch requests 1 MB of LDS and fails — on the launch thread; the
  * failure is reported by the next gft_synchronize / value inspection), "trace_lq_report". */
 int gft_set_option(const char* name, double value);
@@ -139,6 +139,43 @@ double gft_conv_macs(const size_t* xshape, const size_t* yshape, const size_t* r
  * {lo0,hi0,lo1,hi1} (folded: low group + mirrored high group).  Pure integer logic; needs no GPU.
  * Returns 1 if every rank's two groups have equal sizes (all-gather friendly), 0 otherwise. */
 int gft_plan_slabs(size_t n0, int world, int rank, size_t out[4]);
+
+/* ---- batched univariate series on caller-owned device tensors ------------------------------
+ * B independent truncated power series per call.  The last axis of every operand is the series (coefficient k of t^k at
+ * index k, UNIT stride), the `nbatch` leading axes of extents `batch` are the batch.  Item b of an operand is the
+ * TaylorPoly<F64> of one variable with stored coefficients x[b, :nx] and degrees_p1 = (n); nx, ny <= n (a shorter operand
+ * is compact: its high orders are implicit zeros, mt:13-19); the result has n coefficients per item, n <= 4096 in this
+ * version.  `xbs` / `ybs` / `sbs` / `rbs` are the element strides of the batch axes (NULL = contiguous rows of the
+ * operand's own length nx / ny / 1 / n).  Any non-negative stride on an input, 0 included (one series against the whole
+ * batch); the result's rows must not overlap each other (no zero stride on an axis longer than 1) and the result may share
+ * memory with an input only as the SAME view (in place) — any other overlap, judged by address ranges, is refused.  An
+ * empty batch is a no-op.
+ * Per item the result is the reference's GENERAL algorithm in its operation order, multiply and add rounded separately.
+ * NONE of the data-dependent shortcuts of the operator wrappers is taken (Mul: zero / one / constant / linear operand,
+ * mt:1020-1070; Div: divisor one / constant, mt:1204-1213): a batch cannot branch per item on the host, and the result of
+ * an item never depends on what else is in the batch.  Coefficients the reference would leave unstored (beyond nx + ny - 1
+ * of a product, beyond the first of exp / log of a one-coefficient operand) are written as +0.0.
+ * exp / log: `seed` holds exp(x[b, 0]) / ln(x[b, 0]) per item (batch strides `sbs`); with the platform libm's values the
+ * whole result carries the reference's bits.  seed == NULL forms the seeds on the device with the HIP device library's
+ * exp / log, a few ulps from the host libm's (the other coefficients of log do not depend on the seed).
+ * Stream contract: gft_from_device's — ordered after everything issued so far on `stream` and on the library's stream,
+ * before everything issued later on either; the call does not wait.  0 on success, -1 with gft_last_error() otherwise. */
+int gft_series_mul(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
+                   double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,
+                   void* stream);                                       /* mul_1d                 mt:972-982   */
+int gft_series_div(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
+                   double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,
+                   void* stream);                                       /* div (one axis)         mt:1162-1192 */
+int gft_series_exp(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs,
+                   double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,
+                   void* stream);                                       /* exp_1d                 mt:1271-1283 */
+int gft_series_log(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs,
+                   double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,
+                   void* stream);                                       /* log_1d                 mt:1319-1333 */
+/* The form the last gft_series_* call took: 1 = one lane per series (rows in LDS), 2 = one wave / workgroup per series (exp /
+ * log: the lane-per-series loop over a transposed workspace), 0 = none yet.  gft_set_option("series_form", 1 | 2) asks for a
+ * form (1 holds only where the rows fit the LDS budget; 0 = the library's thresholds).  Test / measurement aid. */
+int gft_series_last_form(void);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI, collectives internal to the library --------
  * The reference is single-process; a host that wants one large product spread over the GPUs of a node starts one
