@@ -1,5 +1,5 @@
 // ------------------------------------------------------------------------------------------
-// batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log
+// batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -37,10 +37,10 @@ static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_
     return true;
 }
 
-// `y`: the second operand (mul, div) or the seeds (exp, log; may be null)
+// `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; may be null); pow has neither, and `e`
 static int series_call(int op, const char* fn, const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
-                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
-    const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV;
+                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0) {
+    const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE;
     const std::string f(fn);
     if (n == 0) throw Error(f + ": n == 0 (the result has no coefficients)");
     if (n > gft::SERIES_MAX_N)
@@ -56,8 +56,9 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         items *= batch[i];
         if (items >= ((size_t)1 << 31)) throw Error(f + ": more than 2^31 - 1 series in one call");
     }
-    SeriesArg ax = series_arg(fn, "x", x, xbs, nx, batch, nbatch);
-    SeriesArg ay = series_arg(fn, binary ? "y" : "the seeds", y, ybs, binary ? ny : 1, batch, nbatch);
+    const bool comp = op == gft::SERIES_COMPOSE;
+    SeriesArg ax = series_arg(fn, comp ? "f" : "x", x, xbs, nx, batch, nbatch);
+    SeriesArg ay = series_arg(fn, comp ? "g" : (binary ? "y" : "the seeds"), y, ybs, binary ? ny : 1, batch, nbatch);
     SeriesArg ar = series_arg(fn, "the result", res, rbs, n, batch, nbatch);
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
@@ -76,8 +77,8 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
             if (axes[i].st / axes[i - 1].ext < axes[i - 1].st)
                 throw Error(f + ": the result's series overlap each other (its strides do not separate the rows)");
     }
-    check_device_ptr(x, (f + ": x").c_str());
-    if (binary || y) check_device_ptr(y, (f + (binary ? ": y" : ": the seeds")).c_str());
+    check_device_ptr(x, (f + ": " + ax.what).c_str());
+    if (binary || y) check_device_ptr(y, (f + ": " + ay.what).c_str());
     check_device_ptr(res, (f + ": the result").c_str());
     // the result may be an input itself (the same view: every row is read before it is written); any other overlap is refused.
     // Judged by address ranges, so two interleaved views of one buffer count as overlapping.
@@ -123,15 +124,17 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         g.rs[g.nd] = sr;
         ++g.nd;
     }
-    const int form = gft::series_plan(op, g.items, (unsigned)n, R.series_force);
+    const int form = op == gft::SERIES_POW ? gft::SERIES_NONE : gft::series_plan(op, g.items, (unsigned)n, R.series_force);
     const size_t wsn = gft::series_workspace(op, form, g.items, (unsigned)nx, (unsigned)n);
     Rc<Buf> ws;
     if (wsn) ws = alloc_doubles(wsn);  // (returned to the pool on exit: later launches follow these on the one stream)
     const hipStream_t cs = (hipStream_t)stream;
     join_caller_in(cs);
-    gft::series_launch(R.stream, op, form, x, (unsigned)nx, y, (unsigned)ny, res, (unsigned)n, g, wsn ? ws->p : nullptr);
+    int ran = form;
+    if (op == gft::SERIES_POW) ran = gft::series_pow(R.stream, x, (unsigned)nx, e, res, (unsigned)n, g, ws->p, R.series_force);
+    else gft::series_launch(R.stream, op, form, x, (unsigned)nx, y, (unsigned)ny, res, (unsigned)n, g, wsn ? ws->p : nullptr);
     join_caller_out(cs);
-    R.series_last = form;
+    R.series_last = ran;
     return 0;
 }
 
@@ -153,6 +156,14 @@ int gft_series_exp(const double* x, const int64_t* xbs, size_t nx, const double*
 int gft_series_log(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs, double* res,
                    const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
     return guard_int([&] { return series_call(gft::SERIES_LOG, "series_log", x, xbs, nx, seed, sbs, 1, res, rbs, n, batch, nbatch, stream); });
+}
+int gft_series_compose(const double* f, const int64_t* fbs, size_t nf, const double* g, const int64_t* gbs, size_t ng, double* res,
+                       const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_COMPOSE, "series_compose", f, fbs, nf, g, gbs, ng, res, rbs, n, batch, nbatch, stream); });
+}
+int gft_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
+                   const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_POW, "series_pow", x, xbs, nx, nullptr, nullptr, 1, res, rbs, n, batch, nbatch, stream, e); });
 }
 int gft_series_last_form(void) { return R.series_last; }
 }

@@ -1,4 +1,4 @@
-// Batched univariate series kernels (gft_series.hpp): mul, div, exp, log of B independent truncated power series, in the
+// Batched univariate series kernels (gft_series.hpp): mul, div, exp, log, compose, pow of B independent truncated power series, in the
 // reference's operation order per item, multiply and add rounded separately (-ffp-contract=off).  gfx950 only.
 //
 // Form A — one lane is one series.  A wave owns 64 consecutive items.  Their rows are loaded along the series axis
@@ -14,6 +14,11 @@
 // the x address is wave-uniform and the y addresses are consecutive across lanes.  For exp / log, form B is form A's lane-per-series loop over a transposed global workspace
 // ([n][B]: lane = item, so a wave's accesses coalesce); the transposes are interop copies with swapped strides.  That is the
 // slow corner (B = 1 runs at the speed of the one-lane k_exp_1d / k_log_1d).
+//
+// compose (res = f(g), Horner) keeps the result row resident across its nf - 1 steps.  Form A: three arrays per wave (f, g, the
+// result; a step runs in place from the top output down).  Form B: one workgroup per series for the whole loop, two result rows
+// and g in LDS, every step mul form B's balanced product, steps separated by an LDS-only barrier.  pow has no kernel of its
+// own: series_pow plans a sequence of mul launches on workspace rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +39,8 @@ namespace {
 // waves * pitch <= 80: 4 waves up to pitch 19 (n <= 19), 2 waves up to pitch 39 (n <= 39), 1 wave up to pitch 79 (n <= 79).
 // Above 64 KB a kernel needs hipFuncAttributeMaxDynamicSharedMemorySize; if the runtime refuses it the budget is 64 KB
 // (waves * pitch <= 64, n <= 63).
+// compose holds three arrays, 1.5 KB * pitch a wave, so waves * pitch <= 53 (160 / 3): 4 waves up to pitch 13 (n <= 13), 2 waves up
+// to pitch 25 (n <= 25), 1 wave up to pitch 53 (n <= 53, the largest n compose takes in form A); with 64 KB, 128 / 3: n <= 41.
 constexpr unsigned SA_BUDGET_KB = 80;
 constexpr unsigned SA_BUDGET_KB_PLAIN = 64;
 // Form A needs enough items to fill waves: below this many items mul and div take form B, where a whole workgroup works on
@@ -48,17 +55,19 @@ unsigned g_budget_kb = 0;  // 0: not asked yet
 typedef EF64 E;
 
 // largest odd pitch >= n, and the waves per workgroup the budget allows for it (0: the rows do not fit form A)
-unsigned form_a_waves(unsigned n, unsigned budget_kb) {
+// (`arrays` of 64 * pitch doubles per wave: arrays * pitch / 2 KB)
+unsigned form_a_waves(unsigned n, unsigned budget_kb, unsigned arrays = 2) {
     const unsigned pitch = n | 1;
-    if (pitch * E::W > budget_kb) return 0;
-    const unsigned w = budget_kb / (pitch * E::W);
+    if (arrays * pitch * E::W > 2 * budget_kb) return 0;
+    const unsigned w = 2 * budget_kb / (arrays * pitch * E::W);
     return w >= 4 ? 4 : (w >= 2 ? 2 : 1);
 }
+unsigned op_arrays(int op) { return op == SERIES_COMPOSE ? 3 : 2; }
 
 unsigned budget_kb() {
     if (g_budget_kb) return g_budget_kb;
     const void* ks[] = {(const void*)k_series_mul_a<E>, (const void*)k_series_div_a<E>, (const void*)k_series_explog_a<E, false>,
-                        (const void*)k_series_explog_a<E, true>};
+                        (const void*)k_series_explog_a<E, true>, (const void*)k_series_compose_a<E>};
     g_budget_kb = SA_BUDGET_KB;
     for (const void* k : ks)
         if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SA_BUDGET_KB * 1024) != hipSuccess) {
@@ -69,10 +78,37 @@ unsigned budget_kb() {
     return g_budget_kb;
 }
 
+// compose form B wants up to 96 KB (two result rows and g at n = 4096); where the runtime grants only 64 KB, g stays in global memory
+int g_compose_b_big = -1;  // -1: not asked yet
+bool compose_b_big() {
+    if (g_compose_b_big < 0) {
+        g_compose_b_big = hipFuncSetAttribute((const void*)k_series_compose_b<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              3 * E::W * SERIES_MAX_N * sizeof(double)) == hipSuccess;
+        if (!g_compose_b_big) (void)hipGetLastError();
+    }
+    return g_compose_b_big != 0;
+}
+
+// the batch of `g` over workspace rows: C-contiguous rows xp / yp / rp doubles apart (0: one row for every item; rp == 0 keeps
+// the result's own strides)
+SeriesBatch ws_batch(const SeriesBatch& g, size_t xp, size_t yp, size_t rp) {
+    SeriesBatch w = g;
+    w.inplace = 0;
+    size_t cs = 1;
+    for (int a = g.nd - 1; a >= 0; --a) {
+        w.xs[a] = cs * xp;
+        w.ys[a] = cs * yp;
+        w.ss[a] = 0;
+        if (rp) w.rs[a] = cs * rp;
+        cs *= g.ext[a];
+    }
+    return w;
+}
+
 }  // namespace
 
 int series_plan(int op, unsigned items, unsigned n, int force) {
-    const bool fits = form_a_waves(n, budget_kb()) != 0;
+    const bool fits = form_a_waves(n, budget_kb(), op_arrays(op)) != 0;
     if (!fits || force == SERIES_FORM_B) return SERIES_FORM_B;
     if (force == SERIES_FORM_A) return SERIES_FORM_A;
     if (op == SERIES_EXP || op == SERIES_LOG) return SERIES_FORM_A;  // form B of these is the slow corner whatever the batch
@@ -80,6 +116,7 @@ int series_plan(int op, unsigned items, unsigned n, int force) {
 }
 
 size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n) {
+    if (op == SERIES_POW) return (size_t)E::W * (3 * (size_t)items * n + 1);
     if (form != SERIES_FORM_B || (op != SERIES_EXP && op != SERIES_LOG)) return 0;
     return (size_t)E::W * items * ((size_t)nx + n);
 }
@@ -89,7 +126,8 @@ void series_launch(hipStream_t st, int op, int form, const double* x, unsigned n
     if (g.items == 0) return;
     if (form == SERIES_FORM_A) {
         const unsigned pitch = n | 1;
-        unsigned waves = form_a_waves(n, budget_kb());
+        const unsigned arrays = op_arrays(op);
+        unsigned waves = form_a_waves(n, budget_kb(), arrays);
         if (waves == 0) throw std::runtime_error("series: rows of " + std::to_string(n) + " coefficients do not fit form A");
         const unsigned wave_items = (g.items + 63) / 64;
         waves = std::min(waves, wave_items);
@@ -97,10 +135,11 @@ void series_launch(hipStream_t st, int op, int form, const double* x, unsigned n
         unsigned lg = 0;  // lanes per row while staging: the smallest power of two >= n, at most 64
         while (lg < 6 && (1u << lg) < n) ++lg;
         const dim3 grid((wave_items + waves - 1) / waves), block(64 * waves);
-        const size_t lds = (size_t)waves * 2 * E::W * 64 * pitch * sizeof(double);
+        const size_t lds = (size_t)waves * arrays * E::W * 64 * pitch * sizeof(double);
         switch (op) {
             case SERIES_MUL: GFT_LAUNCH(k_series_mul_a<E>, grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, pitch, lg, g); break;
             case SERIES_DIV: GFT_LAUNCH(k_series_div_a<E>, grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, pitch, lg, g); break;
+            case SERIES_COMPOSE: GFT_LAUNCH(k_series_compose_a<E>, grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, pitch, lg, g); break;
             case SERIES_EXP: GFT_LAUNCH((k_series_explog_a<E, false>), grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, res, (size_t)0, n, pitch, lg, g); break;
             default: GFT_LAUNCH((k_series_explog_a<E, true>), grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, res, (size_t)0, n, pitch, lg, g); break;
         }
@@ -115,6 +154,15 @@ void series_launch(hipStream_t st, int op, int form, const double* x, unsigned n
         const unsigned shares = g.inplace ? 1u : (half + threads - 1) / threads;
         GFT_LAUNCH(k_series_mul_b<E>, dim3(g.items, shares), dim3(threads), (size_t)E::W * ((size_t)nx + ny) * sizeof(double), st, x, (size_t)0, nx,
                    y, (size_t)0, ny, res, (size_t)0, n, g);
+        return;
+    }
+    if (op == SERIES_COMPOSE) {
+        const unsigned threads = std::min(256u, ((n + 1) / 2 + 63) / 64 * 64);
+        const size_t rows = (size_t)2 * E::W * n * sizeof(double), all = rows + (size_t)E::W * ny * sizeof(double);
+        if (all <= 64 * 1024 || compose_b_big())
+            GFT_LAUNCH((k_series_compose_b<E, true>), dim3(g.items), dim3(threads), all, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, g);
+        else
+            GFT_LAUNCH((k_series_compose_b<E, false>), dim3(g.items), dim3(threads), rows, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, g);
         return;
     }
     if (op == SERIES_DIV) {
@@ -146,6 +194,68 @@ void series_launch(hipStream_t st, int op, int form, const double* x, unsigned n
     if (op == SERIES_EXP) GFT_LAUNCH((k_series_explog_ws<E, false>), grid, block, 0, st, xT, nx, y, (size_t)0, rT, n, g);
     else GFT_LAUNCH((k_series_explog_ws<E, true>), grid, block, 0, st, xT, nx, y, (size_t)0, rT, n, g);
     interop_copy(st, rT, res, out);
+}
+
+int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws,
+               int force) {
+    if (g.items == 0) return SERIES_NONE;
+    if (e == 0) {
+        GFT_LAUNCH(k_series_unit_rows<E>, dim3(g.items), dim3(std::min(256u, (n + 63) / 64 * 64)), 0, st, res, (size_t)0, n, g);
+        return SERIES_NONE;
+    }
+    const size_t rows = (size_t)E::W * g.items * n;
+    double* spare[2] = {ws + rows, ws + 2 * rows};
+    int nspare = 2;
+    double* unit = ws + 3 * rows;
+    SeriesBatch one_row;
+    one_row.nd = 0;
+    one_row.items = 1;
+    GFT_LAUNCH(k_series_unit_rows<E>, dim3(1), dim3(64), 0, st, unit, (size_t)0, 1u, one_row);
+    // the operand, read once through its strides: base = x as rows of nx
+    double* base = ws;
+    unsigned lb = nx;
+    {
+        CopyGeom in;
+        size_t cs = 1;
+        in.nd = g.nd + 1;
+        for (int a = g.nd - 1; a >= 0; --a) {
+            in.ext[a] = g.ext[a];
+            in.ss[a] = g.xs[a];
+            in.ds[a] = cs * nx;
+            cs *= g.ext[a];
+        }
+        in.ext[g.nd] = nx;
+        in.ss[g.nd] = in.ds[g.nd] = 1;
+        interop_copy(st, x, base, in);
+    }
+    double* acc = unit;  // res of mt:441: [1.0] for every item until the first product
+    unsigned la = 1;
+    int form = SERIES_NONE;
+    auto product = [&](const double* a, unsigned na, size_t ap, const double* b, unsigned nb, double* out, unsigned len, bool last) {
+        form = series_plan(SERIES_MUL, g.items, len, force);
+        series_launch(st, SERIES_MUL, form, a, na, b, nb, out, len, ws_batch(g, ap, nb, last ? 0 : len), nullptr);
+    };
+    while (e > 0) {
+        if (e & 1) {
+            const bool last = (e >> 1) == 0;
+            const unsigned len = std::min(la + lb - 1, n);
+            double* out = last ? res : spare[--nspare];
+            product(acc, la, acc == unit ? 0 : la, base, lb, out, last ? n : len, last);
+            if (acc != unit) spare[nspare++] = acc;
+            acc = out;
+            la = len;
+        }
+        e >>= 1;
+        if (e > 0) {
+            const unsigned len = std::min(2 * lb - 1, n);
+            double* out = spare[--nspare];
+            product(base, lb, lb, base, lb, out, len, false);
+            spare[nspare++] = base;
+            base = out;
+            lb = len;
+        }
+    }
+    return form;
 }
 
 }  // namespace gft

@@ -1,9 +1,12 @@
-// Batched univariate series on caller-owned device tensors (gft_series_mul / div / exp / log): B independent truncated power
+// Batched univariate series on caller-owned device tensors (gft_series_mul / div / exp / log / compose / pow): B independent truncated power
 // series per call, the last axis of every operand is the series, the leading axes are the batch.  Per item the results are
 // the reference's GENERAL algorithms in its operation order (mul_1d mt:972-982, div mt:1162-1192 at one axis, exp_1d
 // mt:1271-1283, log_1d mt:1319-1333), multiply and add rounded separately.  None of the data-dependent shortcuts of the
 // operator wrappers is taken (Mul: zero / one / constant / linear, mt:1020-1070; Div: one / constant, mt:1204-1213): a batch
 // cannot branch per item on the host, and the result of an item must not depend on what else is in the batch.
+// compose is subst_var's Horner loop (mt:574-578) and pow the square-and-multiply of mt:441-450, both over that general product at
+// the compact lengths min(la + lb - 1, n) of sum_shape (mt:150-170).  compose costs about nf * n^2 / 2 multiply-adds per item, all
+// of them on one workgroup at most.
 //
 // The host side (gft_api_series.inc) validates, collapses the batch axes into a SeriesBatch and joins the streams; this
 // file's planner picks a form and gft_series.hip (div form B: gft_div2d.hip) launches it on the library's stream.
@@ -16,9 +19,9 @@
 
 namespace gft {
 
-enum SeriesOp { SERIES_MUL = 0, SERIES_DIV = 1, SERIES_EXP = 2, SERIES_LOG = 3 };
-// A: one lane is one series, rows staged in LDS.  B: one wave / workgroup is one series (mul, div); for exp / log the
-// lane-per-series loop of form A over a transposed global workspace.
+enum SeriesOp { SERIES_MUL = 0, SERIES_DIV = 1, SERIES_EXP = 2, SERIES_LOG = 3, SERIES_COMPOSE = 4, SERIES_POW = 5 };
+// A: one lane is one series, rows staged in LDS.  B: one wave / workgroup is one series (mul, div, compose); for exp / log the
+// lane-per-series loop of form A over a transposed global workspace.  pow is a sequence of mul launches, each planned by itself.
 enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
 
 constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
@@ -36,12 +39,18 @@ struct SeriesBatch {
 // The form a call takes.  force: 0 = by the thresholds, SERIES_FORM_A = form A whenever the rows fit its LDS budget,
 // SERIES_FORM_B = never form A (gft_set_option("series_form")).
 int series_plan(int op, unsigned items, unsigned n, int force);
-// doubles of device workspace the call needs (form B of exp / log: the transposed operand and result), else 0
+// doubles of device workspace the call needs (form B of exp / log: the transposed operand and result; pow: the base, two results
+// taking turns and the factor [1.0]), else 0
 size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n);
-// Launches the call on `st`.  `y`: the second operand of mul / div; for exp / log the seeds or nullptr (seeds formed on the
-// device by the HIP device library's exp / log).  `ws`: series_workspace() doubles.
+// Launches the call on `st`.  `y`: the second operand of mul / div / compose (x is f, y is g); for exp / log the seeds or nullptr
+// (seeds formed on the device by the HIP device library's exp / log).  `ws`: series_workspace() doubles.  Not for SERIES_POW.
 void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
                    unsigned n, const SeriesBatch& g, double* ws);
+// x^e on `st`: x is copied once into the workspace, every product but the last is a mul launch on workspace rows of the compact
+// length, the last one writes the n coefficients through the result's strides.  `force` as for series_plan; returns the form of
+// the last product (SERIES_NONE for e == 0, which only writes [1, 0, ...]).
+int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws,
+               int force);
 // form B of div: k_div_1d_wave / k_div_1d with blockIdx.x as the item (gft_div2d.hip)
 void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
                      const SeriesBatch& g);

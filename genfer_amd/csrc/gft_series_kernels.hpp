@@ -1,6 +1,7 @@
 // Device side of the batched series (gft_series.hip plans and launches these): the per-lane recurrences, form A's LDS
 // staging and the kernels, as templates over the element functor (gft_elem.hpp) so that an interval twin is an instantiation.
-// tests/series_isa_check.hip instantiates the form-A mul and div kernels from this file alone.
+// tests/series_isa_check.hip instantiates the form-A mul and div kernels from this file alone, tests/series_compose_isa_check.hip
+// the two compose kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +37,19 @@ __device__ inline void rec_mul(const AX x, const AY y, unsigned nx, unsigned ny,
 #pragma unroll 4
         for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(x.ld(j), y.ld(k - j)));
         y.st(k, sum);
+    }
+}
+// One Horner step of compose in place: r <- r * g truncated at L <= lr + ng - 1, r holding lr coefficients on entry (the same sums as
+// rec_mul with x = r; here z[k] overwrites x[k], which the outputs still to come, reading r[0 .. k-1], do not need).
+template <class E, class AR, class AG>
+__device__ inline void rec_horner_step(const AR r, const AG g, unsigned lr, unsigned ng, unsigned L) {
+    typedef typename E::V V;
+    for (unsigned k = L; k-- > 0;) {
+        const unsigned lo = k + 1 > ng ? k + 1 - ng : 0, hi = k + 1 < lr ? k + 1 : lr;
+        V sum = E::zero();
+#pragma unroll 4
+        for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(r.ld(j), g.ld(k - j)));
+        r.st(k, sum);
     }
 }
 // r[k] = (-(0 + sum_{j = lo .. k-1} r[j] * y[k-j]) + x[k]) / y[0] (div, mt:1162-1192 at one axis); r holds x on entry.
@@ -113,15 +127,15 @@ __device__ inline void stage_rows(double* lds, size_t lp, unsigned pitch, double
 struct FormA {  // what every form-A kernel derives from its thread index
     unsigned lane, item0, it;
     size_t lp;       // LDS plane stride: 64 * pitch
-    double *a0, *a1;  // the wave's two arrays
+    double *a0, *a1;  // the wave's first two arrays (compose has a third behind them)
 };
 template <class E>
-__device__ inline FormA form_a(double* lds, unsigned pitch, unsigned items) {
+__device__ inline FormA form_a(double* lds, unsigned pitch, unsigned items, unsigned arrays = 2) {
     FormA f;
     const unsigned wave = threadIdx.x >> 6;
     f.lane = threadIdx.x & 63;
     f.lp = (size_t)64 * pitch;
-    f.a0 = lds + (size_t)wave * 2 * E::W * f.lp;
+    f.a0 = lds + (size_t)wave * arrays * E::W * f.lp;
     f.a1 = f.a0 + E::W * f.lp;
     f.item0 = (blockIdx.x * (blockDim.x >> 6) + wave) * 64;
     f.it = f.item0 + f.lane < items ? f.item0 + f.lane : items - 1;  // a lane past the batch: valid addresses, an unstaged row, nothing stored
@@ -173,6 +187,32 @@ __global__ __launch_bounds__(256) void k_series_explog_a(const double* x, size_t
     stage_rows<E, false>(f.a1, f.lp, pitch, res, rp, o.r, n, lg, f.item0, g.items, f.lane);
 }
 
+// compose, res = f(g) by Horner (subst_var's general path, mt:574-578, with mul_1d at every step): three arrays per wave, f, g and
+// the result row, whose compact length lr grows by ng - 1 a step up to n (sum_shape, mt:150-170) -- the same in every lane.
+template <class E>
+__global__ __launch_bounds__(256) void k_series_compose_a(const double* f, size_t fp, unsigned nf, const double* g, size_t gp, unsigned ng,
+                                                          double* res, size_t rp, unsigned n, unsigned pitch, unsigned lg, SeriesBatch b) {
+    extern __shared__ double sa_lds[];
+    const FormA a = form_a<E>(sa_lds, pitch, b.items, 3);
+    double* a2 = a.a1 + E::W * a.lp;
+    const SeriesOff o = series_offsets(b, a.it);
+    stage_rows<E, true>(a.a0, a.lp, pitch, const_cast<double*>(f), fp, o.x, nf, lg, a.item0, b.items, a.lane);
+    stage_rows<E, true>(a.a1, a.lp, pitch, const_cast<double*>(g), gp, o.y, ng, lg, a.item0, b.items, a.lane);
+    __syncthreads();
+    const RowLds<E> fr{a.a0 + a.lane * pitch, a.lp}, gr{a.a1 + a.lane * pitch, a.lp}, rr{a2 + a.lane * pitch, a.lp};
+    unsigned lr = 1;
+    rr.st(0, E::add(E::zero(), fr.ld(nf - 1)));
+    for (unsigned i = nf - 1; i-- > 0;) {
+        const unsigned L = lr + ng - 1 < n ? lr + ng - 1 : n;
+        rec_horner_step<E>(rr, gr, lr, ng, L);
+        rr.st(0, E::add(rr.ld(0), fr.ld(i)));
+        lr = L;
+    }
+    for (unsigned k = lr; k < n; ++k) rr.st(k, E::zero());
+    __syncthreads();
+    stage_rows<E, false>(a2, a.lp, pitch, res, rp, o.r, n, lg, a.item0, b.items, a.lane);
+}
+
 // ---- form B ---------------------------------------------------------------------------------------------------------------
 // mul: blockIdx.x is the item, blockIdx.y a share of its outputs.  A thread owns the outputs k1 = t and k2 = n - 1 - t, together
 // n + 1 terms whatever t, each sum formed from +0 in ascending j over the stored operands only (the bounds of mul_1d).  Within a
@@ -203,6 +243,66 @@ __global__ __launch_bounds__(256) void k_series_mul_b(const double* x, size_t xp
             E::st(res + o.r, rp, k, sum);
         }
     }
+}
+
+// compose: blockIdx.x is the item, and the whole Horner loop runs in this one workgroup (the steps are a dependency chain).  Two
+// result rows in LDS take turns (a step reads one and writes the other) and g sits behind them (GLDS) or stays in global memory
+// (the 64 KB fallback for long rows).  Every step is mul form B's truncated product at the compact length L: a thread owns the
+// outputs t and L - 1 - t, and the owner of output 0 adds f[i], its only global load of the step.  Between steps the threads meet
+// through LDS alone.  A result in place is safe: this workgroup has read all of f and g before its first store.
+template <class E, bool GLDS>
+__global__ __launch_bounds__(256) void k_series_compose_b(const double* f, size_t fp, unsigned nf, const double* g, size_t gp, unsigned ng,
+                                                          double* res, size_t rp, unsigned n, SeriesBatch b) {
+    typedef typename E::V V;
+    extern __shared__ double sb_lds[];  // [plane][n] | [plane][n] | [plane][ng]
+    double* r0 = sb_lds;
+    double* r1 = sb_lds + (size_t)E::W * n;
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    const double* fg = f + o.x;
+    const double* gsrc = g + o.y;
+    size_t gplane = gp;
+    if (GLDS) {
+        double* gl = sb_lds + (size_t)2 * E::W * n;
+        for (unsigned i = threadIdx.x; i < ng; i += blockDim.x) E::st(gl, ng, i, E::ld(g + o.y, gp, i));
+        gsrc = gl;
+        gplane = ng;
+    }
+    if (threadIdx.x == 0) E::st(r0, n, 0, E::add(E::zero(), E::ld(fg, fp, nf - 1)));
+    __syncthreads();
+    unsigned lr = 1;
+    for (unsigned i = nf - 1; i-- > 0;) {
+        const unsigned L = lr + ng - 1 < n ? lr + ng - 1 : n, half = (L + 1) / 2;
+        for (unsigned t = threadIdx.x; t < half; t += blockDim.x) {
+            V fi = E::zero();
+            if (t == 0) fi = E::ld(fg, fp, i);  // in flight during the sums below
+            const unsigned ks[2] = {t, L - 1 - t};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const unsigned k = ks[h];
+                if (h == 1 && k == ks[0]) break;  // the middle output of an odd L
+                const unsigned lo = k + 1 > ng ? k + 1 - ng : 0, hi = k + 1 < lr ? k + 1 : lr;
+                V sum = E::zero();
+#pragma unroll 4
+                for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(E::ld(r0, n, j), E::ld(gsrc, gplane, k - j)));
+                if (k == 0) sum = E::add(sum, fi);
+                E::st(r1, n, k, sum);
+            }
+        }
+        lds_barrier();
+        double* sw = r0;
+        r0 = r1;
+        r1 = sw;
+        lr = L;
+    }
+    __syncthreads();  // (every global load of this workgroup is done: the result may be f or g)
+    for (unsigned k = threadIdx.x; k < n; k += blockDim.x) E::st(res + o.r, rp, k, k < lr ? E::ld(r0, n, k) : E::zero());
+}
+
+// the rows [1, 0, ..., 0] of pow: its first factor (one row: items == 1) and the whole result of e == 0
+template <class E>
+__global__ __launch_bounds__(256) void k_series_unit_rows(double* res, size_t rp, unsigned n, SeriesBatch b) {
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    for (unsigned k = threadIdx.x; k < n; k += blockDim.x) E::st(res + o.r, rp, k, k == 0 ? E::one() : E::zero());
 }
 
 // exp / log over the transposed workspace: xT [nx][items], rT [n][items], one lane per item

@@ -1,4 +1,4 @@
-"""Batched univariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log`` (``gft_series_*``).
+"""Batched univariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` (``gft_series_*``).
 
 The last axis of every tensor is the series (coefficient ``k`` of ``t^k`` at index ``k``, unit stride), the leading axes are
 batch axes and broadcast by torch's rules (``expand``, no copy: one series against a whole batch has batch stride 0).
@@ -11,6 +11,11 @@ never depends on what else is in the batch.  The call is ordered on torch's curr
     >>> z = series.mul(x, y)             # x, y: [B, n] float64 on the GPU
     >>> q = series.div(x, y[0])          # every row by one series
     >>> e = series.exp(x, seed=torch.exp(x[..., 0]))
+    >>> h = series.compose(f, g)         # f(g(t)) per item: Horner over f's coefficients, one launch
+    >>> p = series.pow(x, 5)             # square-and-multiply over mul
+
+``compose`` costs about ``nf * n**2 / 2`` multiply-adds per item and a series never leaves its one workgroup (the Horner steps
+are a dependency chain), so a few long series are slow by construction; no cap is imposed.
 """
 from __future__ import annotations
 
@@ -30,12 +35,14 @@ def _lib():
 
         L = lib()
         i64, sz, vp = C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.c_void_p
-        for name in ("gft_series_mul", "gft_series_div"):
+        for name in ("gft_series_mul", "gft_series_div", "gft_series_compose"):
             f = getattr(L, name)
             f.restype, f.argtypes = C.c_int, [vp, i64, C.c_size_t, vp, i64, C.c_size_t, vp, i64, C.c_size_t, sz, C.c_size_t, vp]
         for name in ("gft_series_exp", "gft_series_log"):
             f = getattr(L, name)
             f.restype, f.argtypes = C.c_int, [vp, i64, C.c_size_t, vp, i64, vp, i64, C.c_size_t, sz, C.c_size_t, vp]
+        L.gft_series_pow.restype = C.c_int
+        L.gft_series_pow.argtypes = [vp, i64, C.c_size_t, C.c_uint32, vp, i64, C.c_size_t, sz, C.c_size_t, vp]
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
@@ -77,12 +84,12 @@ def _i64(seq):
     return (C.c_int64 * max(len(seq), 1))(*seq)
 
 
-def _run(what, fn_name, x, second, n, out, second_is_seed):
+def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), e=None):
     import torch
 
-    _check(torch, x, f"{what}: x")
+    _check(torch, x, f"{what}: {names[0]}")
     if second is not None:
-        _check(torch, second, f"{what}: {'seed' if second_is_seed else 'y'}", series_axis=not second_is_seed)
+        _check(torch, second, f"{what}: {'seed' if second_is_seed else names[1]}", series_axis=not second_is_seed)
     if out is not None:
         _check(torch, out, f"{what}: out")
     lens = (x.shape[-1],) if second_is_seed or second is None else (x.shape[-1], second.shape[-1])
@@ -111,7 +118,10 @@ def _run(what, fn_name, x, second, n, out, second_is_seed):
     bsz = (C.c_size_t * max(nb, 1))(*batch)
     stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     fn = getattr(L, fn_name)
-    if second_is_seed:
+    if e is not None:
+        rc = fn(C.c_void_p(xe.data_ptr()), _i64(xe.stride()[:nb]), xe.shape[-1], e, C.c_void_p(out.data_ptr()), _i64(out.stride()[:nb]),
+                n, bsz, nb, stream)
+    elif second_is_seed:
         if second is None:
             sp, sbs = None, None
         else:
@@ -148,6 +158,32 @@ def log(x, n=None, seed=None, out=None):
     """``log(x[b])`` to order ``n`` (default ``nx``).  ``seed``: ``ln(x[b, 0])`` per item; ``None``: formed on the device (only
     coefficient 0 depends on it)."""
     return _run("series.log", "gft_series_log", x, seed, n, out, True)
+
+
+def compose(f, g, n=None, out=None):
+    """``f[b](g[b])`` truncated at order ``n`` (default ``max(nf, ng)``): Horner over the coefficients of ``f`` with the general
+    product at every step, ``res = res * g + f[i]`` for ``i = nf-2 .. 0`` from ``res = [0.0 + f[nf-1]]`` — ``subst_var``'s general
+    path without its zero / linear shortcuts, the row resident in LDS across the steps.  About ``nf * n**2 / 2`` multiply-adds per
+    item, on one workgroup at most."""
+    return _run("series.compose", "gft_series_compose", f, g, n, out, False, names=("f", "g"))
+
+
+def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
+    """``x[b] ** e`` truncated at order ``n`` (default ``nx``) for an integer ``0 <= e < 2**32``: the reference's
+    square-and-multiply over ``mul`` at compact lengths.  ``e = 0`` gives ``[1, 0, ...]``."""
+    import operator
+
+    if isinstance(e, bool):
+        raise TypeError("series.pow: e must be a non-negative integer, got a bool")
+    try:
+        ei = operator.index(e)
+    except TypeError:
+        raise TypeError(f"series.pow: e must be a non-negative integer, got {e!r} (a non-integral exponent is not a series power)") from None
+    if ei < 0:
+        raise TaylorError(f"series.pow: e = {ei} is negative (use series.div for reciprocals)")
+    if ei >= 2**32:
+        raise TaylorError(f"series.pow: e = {ei} does not fit the 32 bits of the exponent")
+    return _run("series.pow", "gft_series_pow", x, None, n, out, True, e=ei)
 
 
 FORMS = {0: None, 1: "A", 2: "B"}

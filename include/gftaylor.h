@@ -172,8 +172,23 @@ int gft_series_exp(const double* x, const int64_t* xbs, size_t nx, const double*
 int gft_series_log(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs,
                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,
                    void* stream);                                       /* log_1d                 mt:1319-1333 */
+/* compose: res[b] = f[b](g[b]) truncated at order n, f in the place of x and g in the place of y (nf, ng <= n).  Per item it is
+ * subst_var's general Horner path (mt:574-578) with the general product mul_1d at every step and none of the shortcuts of
+ * subst_var (zero / linear substitution, mt:547-568) or of Mul: res = [0.0 + f[nf-1]]; for i = nf-2 .. 0: res = res * g
+ * truncated at the compact length min(len(res) + ng - 1, n) (sum_shape, mt:150-170), res[0] = res[0] + f[i]; the result is res
+ * extended with +0.0 to n.  The whole loop of a series runs in one kernel with the row resident in LDS.  Cost: about
+ * nf * n^2 / 2 multiply-adds per item, on one workgroup at most (no cap is imposed; nf = n = 4096 is 3.4e10 of them for one series).
+ * pow: res[b] = x[b]^e by the reference's square-and-multiply (mt:441-450) over the same product and compact lengths
+ * min(la + lb - 1, n): res = [1.0], base = x; while e > 0: if e & 1 then res = res * base; e >>= 1; if e > 0 then
+ * base = base * base.  e == 0 gives [1, 0, ...]; e == 1 runs the loop (0.0 + 1.0 * x[k]: it differs from the reference's clone in
+ * the sign of a zero).  A sequence of the batched mul launches on pool workspace inside the one stream-ordered call. */
+int gft_series_compose(const double* f, const int64_t* fbs, size_t nf, const double* g, const int64_t* gbs, size_t ng,
+                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,
+                       void* stream);                                   /* subst_var (Horner)     mt:540-580   */
+int gft_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
+                   const size_t* batch, size_t nbatch, void* stream);   /* pow                    mt:433-451   */
 /* The form the last gft_series_* call took: 1 = one lane per series (rows in LDS), 2 = one wave / workgroup per series (exp /
- * log: the lane-per-series loop over a transposed workspace), 0 = none yet.  gft_set_option("series_form", 1 | 2) asks for a
+ * log: the lane-per-series loop over a transposed workspace; pow: the form of its last product), 0 = none yet.  gft_set_option("series_form", 1 | 2) asks for a
  * form (1 holds only where the rows fit the LDS budget; 0 = the library's thresholds).  Test / measurement aid. */
 int gft_series_last_form(void);
 

@@ -8,7 +8,13 @@ For each operation and each (B, n) it times, between two events on torch's curre
 and prints one JSON line per case: both times, their ratio, the algorithmic GB/s (8 * B * (nx + ny + n) bytes) and GMAC/s of
 the batched call, and which form ran.  --form A|B asks for a form (dispatch thresholds are set from such sweeps).
 
+--ops compose,pow: a shape is BxN or BxNxM with nf = ng = M (default M = N) for compose; pow raises to --pow-e.  compose has a
+third leg, (c) the chain of nf - 1 series.mul calls each followed by an add into coefficient 0 on the same tensors (what a
+caller could do before compose existed), reported as chain_ms and chain_over_batched.  Multiply-adds are counted at the compact
+lengths the definition uses.
+
     python tools/bench_series.py > profiles/r07/series_batch.json
+    python tools/bench_series.py --ops compose,pow --shapes 4096x16,4096x64,65536x32,1024x256,64x1024x64,1x4096x16
 """
 import argparse
 import json
@@ -22,17 +28,49 @@ if ROOT not in sys.path:
 
 SHAPES = "4096x16,4096x64,65536x32,1024x256,64x1024,1x4096"
 OPS = "mul,div,exp,log"
+KNOWN_OPS = ("mul", "div", "exp", "log", "compose", "pow")
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--ops", default=OPS, help=f"comma-separated operations (default {OPS})")
-    ap.add_argument("--shapes", default=SHAPES, help=f"comma-separated BxN cases (default {SHAPES})")
+    ap.add_argument("--ops", default=OPS, help=f"comma-separated operations out of {','.join(KNOWN_OPS)} (default {OPS})")
+    ap.add_argument("--shapes", default=SHAPES, help=f"comma-separated BxN cases, BxNxM for compose with nf = ng = M (default {SHAPES})")
+    ap.add_argument("--pow-e", type=int, default=5, help="the exponent of pow (default 5)")
     ap.add_argument("--form", choices=["auto", "A", "B"], default="auto", help="ask the library for a form (default: its thresholds)")
     ap.add_argument("--loop-rows", type=int, default=256, help="rows the per-row loop is timed on (scaled to B)")
     ap.add_argument("--budget-ms", type=float, default=300.0, help="time each leg repeats for, roughly")
     ap.add_argument("--no-loop", action="store_true", help="skip leg (b)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    for op in args.ops.split(","):
+        if op not in KNOWN_OPS:
+            ap.error(f"unknown operation '{op}'")
+    return args
+
+
+def compose_macs(nf, ng, n):
+    """multiply-adds of one item at the compact lengths of the Horner steps"""
+    macs, lr = 0, 1
+    for _ in range(nf - 1):
+        L = min(lr + ng - 1, n)
+        macs += sum(min(k + 1, lr) - max(0, k + 1 - ng) for k in range(L))
+        lr = L
+    return macs
+
+
+def pow_macs(nx, e, n):
+    macs, la, lb = 0, 1, nx
+    prod = lambda a, b, L: sum(min(k + 1, a) - max(0, k + 1 - b) for k in range(L))  # noqa: E731
+    while e > 0:
+        if e & 1:
+            L = min(la + lb - 1, n)
+            macs += prod(la, lb, L)
+            la = L
+        e >>= 1
+        if e > 0:
+            L = min(2 * lb - 1, n)
+            macs += prod(lb, lb, L)
+            lb = L
+    return macs
 
 
 def timed(torch, fn, budget_ms):
@@ -70,7 +108,9 @@ def main(argv=None):
     gen = torch.Generator(device="cpu").manual_seed(7)
     results = []
     for shape in args.shapes.split(","):
-        B, n = (int(t) for t in shape.lower().split("x"))
+        dims = [int(t) for t in shape.lower().split("x")]
+        B, n = dims[0], dims[1]
+        m = dims[2] if len(dims) > 2 else n  # nf = ng of compose
         # bounded results at every order: a dominant constant term in the divisor, a small argument for exp
         x = (0.5 + torch.rand((B, n), dtype=torch.float64, generator=gen) / n).to(dev)
         y = (0.5 + torch.rand((B, n), dtype=torch.float64, generator=gen) / n).to(dev)
@@ -81,9 +121,16 @@ def main(argv=None):
             if op in ("exp", "log"):
                 seed = torch.tensor([getattr(math, op)(v) for v in x[:, 0].cpu().tolist()], dtype=torch.float64).to(dev)
 
+            fc, gc = x[:, :m], y[:, :m]  # compose: f and g as views of the same tensors
+            step = torch.empty((B, n), dtype=torch.float64, device=dev)
+
             def batched():
                 if op in ("mul", "div"):
                     getattr(series, op)(x, y, out=out)
+                elif op == "compose":
+                    series.compose(fc, gc, n=n, out=out)
+                elif op == "pow":
+                    series.pow(x, args.pow_e, out=out)
                 else:
                     getattr(series, op)(x, seed=seed, out=out)
 
@@ -98,26 +145,54 @@ def main(argv=None):
                         r = p * TP.from_torch(y[b])
                     elif op == "div":
                         r = p / TP.from_torch(y[b])
+                    elif op == "compose":
+                        r = TP.from_torch(fc[b], degrees_p1=(n,)).subst_var(0, TP.from_torch(gc[b], degrees_p1=(n,)))
+                        out[b].zero_()
+                        r.to_torch(out=out[b, :r.coeffs_shape()[0]])
+                        continue
+                    elif op == "pow":
+                        r = p.pow(args.pow_e)
                     else:
                         r = p.exp() if op == "exp" else p.log()
                     r.to_torch(out=out[b])
 
+            def chain():  # compose before compose: nf - 1 products at full length, each followed by an add into coefficient 0
+                a, b = step, out
+                if (m - 1) % 2 == 0:
+                    a, b = b, a  # the last product lands in `out`
+                a.zero_()
+                a[:, 0] = fc[:, m - 1]
+                for i in range(m - 2, -1, -1):
+                    series.mul(a, gc, n=n, out=b)
+                    b[:, 0] += fc[:, i]
+                    a, b = b, a
+
             rec = {"op": op, "B": B, "n": n, "form": form, "batched_ms": round(t_batch, 6), "batched_reps": reps_a}
             macs = B * n * (n + 1) / 2.0
             nbytes = 8.0 * B * (n + (n if op in ("mul", "div") else 0) + n)
+            if op == "compose":
+                rec["nf"] = rec["ng"] = m
+                macs, nbytes = float(B * compose_macs(m, m, n)), 8.0 * B * (2 * m + n)
+            elif op == "pow":
+                rec["e"] = args.pow_e
+                macs = float(B * pow_macs(n, args.pow_e, n))
             rec["algorithmic_GBps"] = round(nbytes / (t_batch * 1e-3) / 1e9, 3)
             rec["GMACps"] = round(macs / (t_batch * 1e-3) / 1e9, 3)
             if not args.no_loop:
                 t_loop, reps_b = timed(torch, loop, args.budget_ms)
                 t_loop *= B / rows
                 rec.update({"loop_ms": round(t_loop, 6), "loop_rows": rows, "loop_reps": reps_b, "loop_over_batched": round(t_loop / t_batch, 3)})
+            if op == "compose" and m > 1:
+                t_chain, reps_c = timed(torch, chain, args.budget_ms)
+                rec.update({"chain_ms": round(t_chain, 6), "chain_reps": reps_c, "chain_over_batched": round(t_chain / t_batch, 3)})
             results.append(rec)
             print(json.dumps(rec), flush=True)
     series.set_form(None)
     props = torch.cuda.get_device_properties(0)
     print(json.dumps({"summary": True, "device": props.name, "asked_form": args.form, "cases": len(results),
                       "min_ratio_B_ge_256": min([r["loop_over_batched"] for r in results if r["B"] >= 256 and "loop_over_batched" in r], default=None),
-                      "min_ratio_B_lt_256": min([r["loop_over_batched"] for r in results if r["B"] < 256 and "loop_over_batched" in r], default=None)}))
+                      "min_ratio_B_lt_256": min([r["loop_over_batched"] for r in results if r["B"] < 256 and "loop_over_batched" in r], default=None),
+                      "min_chain_over_batched": min([r["chain_over_batched"] for r in results if "chain_over_batched" in r], default=None)}))
 
 
 if __name__ == "__main__":
