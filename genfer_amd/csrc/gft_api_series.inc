@@ -1,5 +1,6 @@
 // ------------------------------------------------------------------------------------------
-// batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow
+// batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow, and their
+// Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -10,16 +11,23 @@ struct SeriesArg {  // one operand of a call: rows of `len` elements (unit strid
     const double* p;
     size_t len;
     size_t st[32];
-    size_t span;  // elements from p to one past its last element
+    size_t plane;  // w == 2: elements from the lo plane to the hi plane (0 on an operand: a point interval), else 0
+    size_t span;   // elements from p to one past its last element (of the hi plane)
 };
 
-static SeriesArg series_arg(const char* fn, const char* what, const double* p, const int64_t* bs, size_t len, const size_t* batch, size_t nbatch) {
+// `bs`: nbatch strides, for w == 2 preceded by the plane stride
+static SeriesArg series_arg(const char* fn, const char* what, const double* p, const int64_t* bs, size_t len, const size_t* batch, size_t nbatch,
+                            int w) {
     SeriesArg a;
     a.what = what;
     a.p = p;
     a.len = len;
-    size_t cs = len;  // NULL: contiguous rows of the operand's own length
+    size_t cs = len;  // NULL: contiguous rows of the operand's own length (the planes back to back)
     a.span = len;
+    if (w == 2 && bs) {
+        if (bs[0] < 0) throw Error(std::string(fn) + ": negative strides are not supported (" + what + ", the plane axis)");
+        ++bs;
+    }
     for (size_t i = nbatch; i-- > 0;) {
         if (bs && bs[i] < 0)
             throw Error(std::string(fn) + ": negative strides are not supported (" + what + ", batch axis " + std::to_string(i) + ")");
@@ -27,11 +35,13 @@ static SeriesArg series_arg(const char* fn, const char* what, const double* p, c
         cs *= batch[i];
         a.span += (batch[i] - 1) * a.st[i];
     }
+    a.plane = w == 2 ? (bs ? (size_t)bs[-1] : cs) : 0;
+    a.span += a.plane;
     return a;
 }
 
 static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_t* batch, size_t nbatch) {
-    if (a.p != b.p || a.len != b.len) return false;
+    if (a.p != b.p || a.len != b.len || a.plane != b.plane) return false;
     for (size_t i = 0; i < nbatch; ++i)
         if (batch[i] > 1 && a.st[i] != b.st[i]) return false;
     return true;
@@ -39,12 +49,12 @@ static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_
 
 // `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; may be null); pow has neither, and `e`
 static int series_call(int op, const char* fn, const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
-                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0) {
+                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int w = 1) {
     const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE;
     const std::string f(fn);
     if (n == 0) throw Error(f + ": n == 0 (the result has no coefficients)");
-    if (n > gft::SERIES_MAX_N)
-        throw Error(f + ": n = " + std::to_string(n) + " exceeds the limit of " + std::to_string(gft::SERIES_MAX_N) + " coefficients per series of this version");
+    if (n > gft::series_max_n(w))
+        throw Error(f + ": n = " + std::to_string(n) + " exceeds the limit of " + std::to_string(gft::series_max_n(w)) + " coefficients per series of this version");
     if (nx == 0 || (binary && ny == 0)) throw Error(f + ": an operand has no coefficients");
     if (nx > n) throw Error(f + ": nx = " + std::to_string(nx) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
     if (binary && ny > n) throw Error(f + ": ny = " + std::to_string(ny) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
@@ -57,15 +67,19 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         if (items >= ((size_t)1 << 31)) throw Error(f + ": more than 2^31 - 1 series in one call");
     }
     const bool comp = op == gft::SERIES_COMPOSE;
-    SeriesArg ax = series_arg(fn, comp ? "f" : "x", x, xbs, nx, batch, nbatch);
-    SeriesArg ay = series_arg(fn, comp ? "g" : (binary ? "y" : "the seeds"), y, ybs, binary ? ny : 1, batch, nbatch);
-    SeriesArg ar = series_arg(fn, "the result", res, rbs, n, batch, nbatch);
+    SeriesArg ax = series_arg(fn, comp ? "f" : "x", x, xbs, nx, batch, nbatch, w);
+    SeriesArg ay = series_arg(fn, comp ? "g" : (binary ? "y" : "the seeds"), y, ybs, binary ? ny : 1, batch, nbatch, w);
+    SeriesArg ar = series_arg(fn, "the result", res, rbs, n, batch, nbatch, w);
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
         struct Ax {
             size_t ext, st;
-        } axes[33];
+        } axes[34];
         int k = 0;
+        if (w == 2) {  // the two planes are one more axis of the result
+            if (ar.plane == 0) throw Error(f + ": the result has a zero plane stride: its lower and upper bounds overlap");
+            axes[k++] = Ax{2, ar.plane};
+        }
         for (size_t i = 0; i < nbatch; ++i) {
             if (batch[i] <= 1) continue;
             if (ar.st[i] == 0) throw Error(f + ": the result has a zero stride (batch axis " + std::to_string(i) + "): its series overlap");
@@ -115,8 +129,9 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
                 continue;
             }
         }
-        if (g.nd == gft::IMAXD - 1)
-            throw Error(f + ": the batch has more than " + std::to_string(gft::IMAXD - 1) + " non-contiguous axes");
+        // (the workspace copies add the series axis, and for intervals the plane axis, to these)
+        if (g.nd == gft::IMAXD - w)
+            throw Error(f + ": the batch has more than " + std::to_string(gft::IMAXD - w) + " non-contiguous axes");
         g.ext[g.nd] = (unsigned)e;
         g.xs[g.nd] = sx;
         g.ys[g.nd] = sy;
@@ -124,15 +139,21 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         g.rs[g.nd] = sr;
         ++g.nd;
     }
-    const int form = op == gft::SERIES_POW ? gft::SERIES_NONE : gft::series_plan(op, g.items, (unsigned)n, R.series_force);
-    const size_t wsn = gft::series_workspace(op, form, g.items, (unsigned)nx, (unsigned)n);
+    gft::SeriesPlanes pl;
+    pl.w = w;
+    pl.x = ax.plane;
+    pl.y = binary ? ay.plane : 0;
+    pl.s = seeds ? ay.plane : 0;
+    pl.r = ar.plane;
+    const int form = op == gft::SERIES_POW ? gft::SERIES_NONE : gft::series_plan(op, g.items, (unsigned)n, R.series_force, w);
+    const size_t wsn = gft::series_workspace(op, form, g.items, (unsigned)nx, (unsigned)n, w);
     Rc<Buf> ws;
     if (wsn) ws = alloc_doubles(wsn);  // (returned to the pool on exit: later launches follow these on the one stream)
     const hipStream_t cs = (hipStream_t)stream;
     join_caller_in(cs);
     int ran = form;
-    if (op == gft::SERIES_POW) ran = gft::series_pow(R.stream, x, (unsigned)nx, e, res, (unsigned)n, g, ws->p, R.series_force);
-    else gft::series_launch(R.stream, op, form, x, (unsigned)nx, y, (unsigned)ny, res, (unsigned)n, g, wsn ? ws->p : nullptr);
+    if (op == gft::SERIES_POW) ran = gft::series_pow(R.stream, x, (unsigned)nx, e, res, (unsigned)n, g, ws->p, R.series_force, pl);
+    else gft::series_launch(R.stream, op, form, x, (unsigned)nx, y, (unsigned)ny, res, (unsigned)n, g, wsn ? ws->p : nullptr, pl);
     join_caller_out(cs);
     R.series_last = ran;
     return 0;
@@ -164,6 +185,31 @@ int gft_series_compose(const double* f, const int64_t* fbs, size_t nf, const dou
 int gft_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
                    const size_t* batch, size_t nbatch, void* stream) {
     return guard_int([&] { return series_call(gft::SERIES_POW, "series_pow", x, xbs, nx, nullptr, nullptr, 1, res, rbs, n, batch, nbatch, stream, e); });
+}
+// Interval<F64>: the same calls on (lo, hi) planes; every stride array has nbatch + 1 entries, the plane stride first
+int gfti_series_mul(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_MUL, "interval series_mul", x, xbs, nx, y, ybs, ny, res, rbs, n, batch, nbatch, stream, 0, 2); });
+}
+int gfti_series_div(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_DIV, "interval series_div", x, xbs, nx, y, ybs, ny, res, rbs, n, batch, nbatch, stream, 0, 2); });
+}
+int gfti_series_exp(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_EXP, "interval series_exp", x, xbs, nx, seed, sbs, 1, res, rbs, n, batch, nbatch, stream, 0, 2); });
+}
+int gfti_series_log(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs, double* res,
+                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_LOG, "interval series_log", x, xbs, nx, seed, sbs, 1, res, rbs, n, batch, nbatch, stream, 0, 2); });
+}
+int gfti_series_compose(const double* f, const int64_t* fbs, size_t nf, const double* g, const int64_t* gbs, size_t ng, double* res,
+                       const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_COMPOSE, "interval series_compose", f, fbs, nf, g, gbs, ng, res, rbs, n, batch, nbatch, stream, 0, 2); });
+}
+int gfti_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
+                   const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_POW, "interval series_pow", x, xbs, nx, nullptr, nullptr, 1, res, rbs, n, batch, nbatch, stream, e, 2); });
 }
 int gft_series_last_form(void) { return R.series_last; }
 }

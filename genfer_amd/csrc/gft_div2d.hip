@@ -539,10 +539,10 @@ __global__ void __launch_bounds__(1024) k_div_1d(const double* __restrict__ xs, 
 }
 // the same division for item blockIdx.x of a batch (gft_series.hpp); all loads of a row precede its stores, so `res` may be x or y
 template <class E>
-__global__ void __launch_bounds__(1024) k_div_1d_batch(const double* xs, unsigned nx, const double* ys, unsigned ny, double* res,
-                                                       unsigned n, SeriesBatch g) {
+__global__ void __launch_bounds__(1024) k_div_1d_batch(const double* xs, size_t xp, unsigned nx, const double* ys, size_t yp, unsigned ny,
+                                                       double* res, size_t rp, unsigned n, SeriesBatch g) {
     const SeriesOff o = series_offsets(g, blockIdx.x);
-    div_1d_body<E>(xs + o.x, 0, nx, ys + o.y, 0, ny, res + o.r, 0, n, 0);
+    div_1d_body<E>(xs + o.x, xp, nx, ys + o.y, yp, ny, res + o.r, rp, n, 0);
 }
 // Rows of at most 1024 coefficients: ONE wave, DIV1D_WSEG = 4, 8 or 16 coefficients per lane (k = 64 e + lane).  The quotient coefficient of
 // the step reaches all lanes by v_readlane instead of an LDS round trip plus a workgroup barrier — 0.06 us a step on
@@ -644,10 +644,10 @@ __global__ void __launch_bounds__(64) k_div_1d_wave(const double* __restrict__ x
     div_1d_wave_body<E, DIV1D_WSEG>(xs, xp, nx, ys, yp, ny, res, rp, n, fused);
 }
 template <class E, int DIV1D_WSEG>
-__global__ void __launch_bounds__(64) k_div_1d_wave_batch(const double* xs, unsigned nx, const double* ys, unsigned ny, double* res,
-                                                          unsigned n, SeriesBatch g) {
+__global__ void __launch_bounds__(64) k_div_1d_wave_batch(const double* xs, size_t xp, unsigned nx, const double* ys, size_t yp, unsigned ny,
+                                                          double* res, size_t rp, unsigned n, SeriesBatch g) {
     const SeriesOff o = series_offsets(g, blockIdx.x);
-    div_1d_wave_body<E, DIV1D_WSEG>(xs + o.x, 0, nx, ys + o.y, 0, ny, res + o.r, 0, n, 0);
+    div_1d_wave_body<E, DIV1D_WSEG>(xs + o.x, xp, nx, ys + o.y, yp, ny, res + o.r, rp, n, 0);
 }
 // serial fallback for n > 4096
 template <class E>
@@ -691,12 +691,13 @@ bool K<E>::div_1d(hipStream_t st, const double* xs, size_t x_plane, unsigned nx,
     return true;
 }
 // gft_series.hpp: form B of the batched division — one wave (n <= 1024) or one workgroup per item, the kernels above
-void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
-                     const SeriesBatch& g) {
-    typedef EF64 E;
+template <class E>
+static void div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
+                     const SeriesBatch& g, const SeriesPlanes& pl) {
     if (n <= 1024) {
-#define GFT_D1WB(SEG) \
-    GFT_LAUNCH((k_div_1d_wave_batch<E, SEG>), dim3(g.items), dim3(64), (size_t)E::W * 64 * (SEG + 1) * sizeof(double), st, x, nx, y, ny, res, n, g)
+#define GFT_D1WB(SEG)                                                                                                                 \
+    GFT_LAUNCH((k_div_1d_wave_batch<E, SEG>), dim3(g.items), dim3(64), (size_t)E::W * 64 * (SEG + 1) * sizeof(double), st, x, pl.x, nx, y, \
+               pl.y, ny, res, pl.r, n, g)
         if (n <= 256) GFT_D1WB(4);
         else if (n <= 512) GFT_D1WB(8);
         else GFT_D1WB(16);
@@ -704,8 +705,13 @@ void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double*
         return;
     }
     const unsigned threads = std::min<unsigned>(1024, (n + 63) / 64 * 64);
-    GFT_LAUNCH(k_div_1d_batch<E>, dim3(g.items), dim3(threads), (size_t)E::W * ((size_t)n + std::min(ny, n)) * sizeof(double), st, x, nx, y,
-               ny, res, n, g);
+    GFT_LAUNCH(k_div_1d_batch<E>, dim3(g.items), dim3(threads), (size_t)E::W * ((size_t)n + std::min(ny, n)) * sizeof(double), st, x, pl.x,
+               nx, y, pl.y, ny, res, pl.r, n, g);
+}
+void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
+                     const SeriesBatch& g, const SeriesPlanes& pl) {
+    if (pl.w == 2) div_rows<EIv>(st, x, nx, y, ny, res, n, g, pl);
+    else div_rows<EF64>(st, x, nx, y, ny, res, n, g, pl);
 }
 template bool K<EF64>::div_1d(hipStream_t, const double*, size_t, unsigned, const double*, size_t, unsigned, double*, size_t, unsigned, int);
 template bool K<EIv>::div_1d(hipStream_t, const double*, size_t, unsigned, const double*, size_t, unsigned, double*, size_t, unsigned, int);

@@ -19,6 +19,9 @@
 // result; a step runs in place from the top output down).  Form B: one workgroup per series for the whole loop, two result rows
 // and g in LDS, every step mul form B's balanced product, steps separated by an LDS-only barrier.  pow has no kernel of its
 // own: series_pow plans a sequence of mul launches on workspace rows.
+//
+// Every function below is a template over the element functor: EF64 serves gft_series_*, EIv (Interval<F64>, the planes lo and hi
+// a plane stride apart on every operand) gfti_series_*.  The entry points of gft_series.hpp pick the instantiation by the width.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +44,10 @@ namespace {
 // (waves * pitch <= 64, n <= 63).
 // compose holds three arrays, 1.5 KB * pitch a wave, so waves * pitch <= 53 (160 / 3): 4 waves up to pitch 13 (n <= 13), 2 waves up
 // to pitch 25 (n <= 25), 1 wave up to pitch 53 (n <= 53, the largest n compose takes in form A); with 64 KB, 128 / 3: n <= 41.
+// Interval<F64> (E::W = 2 planes per array: 2 KB * pitch a wave for two arrays): waves * pitch <= 40, so 4 waves up to pitch 9
+// (n <= 9), 2 waves up to pitch 19 (n <= 19), 1 wave up to pitch 39 (n <= 39); with 64 KB, waves * pitch <= 32: n <= 31.
+// Interval compose, 3 KB * pitch a wave: waves * pitch <= 26 (160 / 6), so 4 waves up to pitch 5 (n <= 5), 2 waves up to pitch 13
+// (n <= 13), 1 wave up to pitch 25 (n <= 25); with 64 KB, 128 / 6: pitch <= 21, n <= 21.
 constexpr unsigned SA_BUDGET_KB = 80;
 constexpr unsigned SA_BUDGET_KB_PLAIN = 64;
 // Form A needs enough items to fill waves: below this many items mul and div take form B, where a whole workgroup works on
@@ -48,14 +55,23 @@ constexpr unsigned SA_BUDGET_KB_PLAIN = 64;
 // (tools/bench_series.py --form A | B, profiles/r07/series_forms.txt; ms per call, the per-call floor is 0.037) says it is too
 // low for the longer rows: (256, 16) A 0.037 B 0.037, (1024, 16) 0.038 / 0.037, (256, 48) 0.080 / 0.036, (1024, 48) 0.080 / 0.037,
 // (4096, 64) 0.097 / 0.037 (div 0.100 / 0.046).  Form B was not timed above 4096 items, so the value stands.
+// The interval kernels keep it: the two forms were not timed against each other for intervals.
 constexpr unsigned SA_MIN_ITEMS = 256;
 
-unsigned g_budget_kb = 0;  // 0: not asked yet
-
-typedef EF64 E;
+// what the runtime granted, asked once per element type (the EIv kernels are functions of their own)
+template <class E>
+struct Granted {
+    static unsigned budget_kb;  // 0: not asked yet
+    static int compose_b_big;   // -1: not asked yet
+};
+template <class E>
+unsigned Granted<E>::budget_kb = 0;
+template <class E>
+int Granted<E>::compose_b_big = -1;
 
 // largest odd pitch >= n, and the waves per workgroup the budget allows for it (0: the rows do not fit form A)
-// (`arrays` of 64 * pitch doubles per wave: arrays * pitch / 2 KB)
+// (`arrays` of E::W planes of 64 * pitch doubles per wave: arrays * E::W * pitch / 2 KB)
+template <class E>
 unsigned form_a_waves(unsigned n, unsigned budget_kb, unsigned arrays = 2) {
     const unsigned pitch = n | 1;
     if (arrays * pitch * E::W > 2 * budget_kb) return 0;
@@ -64,29 +80,33 @@ unsigned form_a_waves(unsigned n, unsigned budget_kb, unsigned arrays = 2) {
 }
 unsigned op_arrays(int op) { return op == SERIES_COMPOSE ? 3 : 2; }
 
+template <class E>
 unsigned budget_kb() {
-    if (g_budget_kb) return g_budget_kb;
+    unsigned& kb = Granted<E>::budget_kb;
+    if (kb) return kb;
     const void* ks[] = {(const void*)k_series_mul_a<E>, (const void*)k_series_div_a<E>, (const void*)k_series_explog_a<E, false>,
                         (const void*)k_series_explog_a<E, true>, (const void*)k_series_compose_a<E>};
-    g_budget_kb = SA_BUDGET_KB;
+    kb = SA_BUDGET_KB;
     for (const void* k : ks)
         if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SA_BUDGET_KB * 1024) != hipSuccess) {
             (void)hipGetLastError();  // no stale error for the caller's next HIP call
-            g_budget_kb = SA_BUDGET_KB_PLAIN;
+            kb = SA_BUDGET_KB_PLAIN;
             break;
         }
-    return g_budget_kb;
+    return kb;
 }
 
-// compose form B wants up to 96 KB (two result rows and g at n = 4096); where the runtime grants only 64 KB, g stays in global memory
-int g_compose_b_big = -1;  // -1: not asked yet
+// compose form B wants up to 96 KB (two result rows and g at n = 4096, or their two planes each at n = 2048); where the runtime
+// grants only 64 KB, g stays in global memory
+template <class E>
 bool compose_b_big() {
-    if (g_compose_b_big < 0) {
-        g_compose_b_big = hipFuncSetAttribute((const void*)k_series_compose_b<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              3 * E::W * SERIES_MAX_N * sizeof(double)) == hipSuccess;
-        if (!g_compose_b_big) (void)hipGetLastError();
+    int& big = Granted<E>::compose_b_big;
+    if (big < 0) {
+        big = hipFuncSetAttribute((const void*)k_series_compose_b<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  3 * E::W * series_max_n(E::W) * sizeof(double)) == hipSuccess;
+        if (!big) (void)hipGetLastError();
     }
-    return g_compose_b_big != 0;
+    return big != 0;
 }
 
 // the batch of `g` over workspace rows: C-contiguous rows xp / yp / rp doubles apart (0: one row for every item; rp == 0 keeps
@@ -105,29 +125,51 @@ SeriesBatch ws_batch(const SeriesBatch& g, size_t xp, size_t yp, size_t rp) {
     return w;
 }
 
-}  // namespace
+// a copy between the caller's rows (batch strides `bs`, planes `plane` apart) and a workspace [E::W][...] whose planes are `wplane`
+// apart, item stride `wi` and coefficient stride `wc`; `in`: towards the workspace
+template <class E>
+void ws_copy(hipStream_t st, const double* src, double* dst, const SeriesBatch& g, const size_t* bs, size_t plane, unsigned len,
+             size_t wplane, size_t wi, size_t wc, bool in) {
+    CopyGeom c;
+    int k = 0;
+    if (E::W > 1) {
+        c.ext[k] = E::W;
+        c.ss[k] = in ? plane : wplane;
+        c.ds[k] = in ? wplane : plane;
+        ++k;
+    }
+    size_t cs = wi;
+    for (int a = g.nd - 1; a >= 0; --a) {
+        c.ext[k + a] = g.ext[a];
+        c.ss[k + a] = in ? bs[a] : cs;
+        c.ds[k + a] = in ? cs : bs[a];
+        cs *= g.ext[a];
+    }
+    k += g.nd;
+    c.ext[k] = len;
+    c.ss[k] = in ? 1 : wc;
+    c.ds[k] = in ? wc : 1;
+    c.nd = k + 1;
+    interop_copy(st, src, dst, c);
+}
 
-int series_plan(int op, unsigned items, unsigned n, int force) {
-    const bool fits = form_a_waves(n, budget_kb(), op_arrays(op)) != 0;
+template <class E>
+int plan(int op, unsigned items, unsigned n, int force) {
+    const bool fits = form_a_waves<E>(n, budget_kb<E>(), op_arrays(op)) != 0;
     if (!fits || force == SERIES_FORM_B) return SERIES_FORM_B;
     if (force == SERIES_FORM_A) return SERIES_FORM_A;
     if (op == SERIES_EXP || op == SERIES_LOG) return SERIES_FORM_A;  // form B of these is the slow corner whatever the batch
     return items >= SA_MIN_ITEMS ? SERIES_FORM_A : SERIES_FORM_B;
 }
 
-size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n) {
-    if (op == SERIES_POW) return (size_t)E::W * (3 * (size_t)items * n + 1);
-    if (form != SERIES_FORM_B || (op != SERIES_EXP && op != SERIES_LOG)) return 0;
-    return (size_t)E::W * items * ((size_t)nx + n);
-}
-
-void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
-                   unsigned n, const SeriesBatch& g, double* ws) {
+template <class E>
+void launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
+            const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
     if (g.items == 0) return;
     if (form == SERIES_FORM_A) {
         const unsigned pitch = n | 1;
         const unsigned arrays = op_arrays(op);
-        unsigned waves = form_a_waves(n, budget_kb(), arrays);
+        unsigned waves = form_a_waves<E>(n, budget_kb<E>(), arrays);
         if (waves == 0) throw std::runtime_error("series: rows of " + std::to_string(n) + " coefficients do not fit form A");
         const unsigned wave_items = (g.items + 63) / 64;
         waves = std::min(waves, wave_items);
@@ -137,11 +179,11 @@ void series_launch(hipStream_t st, int op, int form, const double* x, unsigned n
         const dim3 grid((wave_items + waves - 1) / waves), block(64 * waves);
         const size_t lds = (size_t)waves * arrays * E::W * 64 * pitch * sizeof(double);
         switch (op) {
-            case SERIES_MUL: GFT_LAUNCH(k_series_mul_a<E>, grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, pitch, lg, g); break;
-            case SERIES_DIV: GFT_LAUNCH(k_series_div_a<E>, grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, pitch, lg, g); break;
-            case SERIES_COMPOSE: GFT_LAUNCH(k_series_compose_a<E>, grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, pitch, lg, g); break;
-            case SERIES_EXP: GFT_LAUNCH((k_series_explog_a<E, false>), grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, res, (size_t)0, n, pitch, lg, g); break;
-            default: GFT_LAUNCH((k_series_explog_a<E, true>), grid, block, lds, st, x, (size_t)0, nx, y, (size_t)0, res, (size_t)0, n, pitch, lg, g); break;
+            case SERIES_MUL: GFT_LAUNCH(k_series_mul_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
+            case SERIES_DIV: GFT_LAUNCH(k_series_div_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
+            case SERIES_COMPOSE: GFT_LAUNCH(k_series_compose_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
+            case SERIES_EXP: GFT_LAUNCH((k_series_explog_a<E, false>), grid, block, lds, st, x, pl.x, nx, y, pl.s, res, pl.r, n, pitch, lg, g); break;
+            default: GFT_LAUNCH((k_series_explog_a<E, true>), grid, block, lds, st, x, pl.x, nx, y, pl.s, res, pl.r, n, pitch, lg, g); break;
         }
         return;
     }
@@ -152,88 +194,67 @@ void series_launch(hipStream_t st, int op, int form, const double* x, unsigned n
         const bool spread = !g.inplace && g.items < SA_MIN_ITEMS;
         const unsigned threads = spread ? 64u : std::min(256u, (half + 63) / 64 * 64);
         const unsigned shares = g.inplace ? 1u : (half + threads - 1) / threads;
-        GFT_LAUNCH(k_series_mul_b<E>, dim3(g.items, shares), dim3(threads), (size_t)E::W * ((size_t)nx + ny) * sizeof(double), st, x, (size_t)0, nx,
-                   y, (size_t)0, ny, res, (size_t)0, n, g);
+        GFT_LAUNCH(k_series_mul_b<E>, dim3(g.items, shares), dim3(threads), (size_t)E::W * ((size_t)nx + ny) * sizeof(double), st, x, pl.x, nx,
+                   y, pl.y, ny, res, pl.r, n, g);
         return;
     }
     if (op == SERIES_COMPOSE) {
         const unsigned threads = std::min(256u, ((n + 1) / 2 + 63) / 64 * 64);
         const size_t rows = (size_t)2 * E::W * n * sizeof(double), all = rows + (size_t)E::W * ny * sizeof(double);
-        if (all <= 64 * 1024 || compose_b_big())
-            GFT_LAUNCH((k_series_compose_b<E, true>), dim3(g.items), dim3(threads), all, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, g);
+        if (all <= 64 * 1024 || compose_b_big<E>())
+            GFT_LAUNCH((k_series_compose_b<E, true>), dim3(g.items), dim3(threads), all, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
         else
-            GFT_LAUNCH((k_series_compose_b<E, false>), dim3(g.items), dim3(threads), rows, st, x, (size_t)0, nx, y, (size_t)0, ny, res, (size_t)0, n, g);
+            GFT_LAUNCH((k_series_compose_b<E, false>), dim3(g.items), dim3(threads), rows, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
         return;
     }
     if (op == SERIES_DIV) {
-        series_div_rows(st, x, nx, y, ny, res, n, g);
+        series_div_rows(st, x, nx, y, ny, res, n, g, pl);
         return;
     }
-    // exp / log: x -> xT, the lane-per-item loop, rT -> res
+    // exp / log: x -> xT [plane][nx][items], the lane-per-item loop, rT [plane][n][items] -> res
     double* xT = ws;
     double* rT = ws + (size_t)E::W * ((size_t)g.items * nx);
-    CopyGeom in, out;
-    size_t cs = 1;  // C stride of the batch axis inside an [..][items] workspace
-    in.nd = out.nd = g.nd + 1;
-    for (int a = g.nd - 1; a >= 0; --a) {
-        in.ext[a] = out.ext[a] = g.ext[a];
-        in.ss[a] = g.xs[a];
-        in.ds[a] = cs;
-        out.ss[a] = cs;
-        out.ds[a] = g.rs[a];
-        cs *= g.ext[a];
-    }
-    in.ext[g.nd] = nx;
-    in.ss[g.nd] = 1;
-    in.ds[g.nd] = g.items;
-    out.ext[g.nd] = n;
-    out.ss[g.nd] = g.items;
-    out.ds[g.nd] = 1;
-    interop_copy(st, x, xT, in);
+    ws_copy<E>(st, x, xT, g, g.xs, pl.x, nx, (size_t)nx * g.items, 1, g.items, true);
     const dim3 grid((g.items + 63) / 64), block(64);
-    if (op == SERIES_EXP) GFT_LAUNCH((k_series_explog_ws<E, false>), grid, block, 0, st, xT, nx, y, (size_t)0, rT, n, g);
-    else GFT_LAUNCH((k_series_explog_ws<E, true>), grid, block, 0, st, xT, nx, y, (size_t)0, rT, n, g);
-    interop_copy(st, rT, res, out);
+    if (op == SERIES_EXP) GFT_LAUNCH((k_series_explog_ws<E, false>), grid, block, 0, st, xT, nx, y, pl.s, rT, n, g);
+    else GFT_LAUNCH((k_series_explog_ws<E, true>), grid, block, 0, st, xT, nx, y, pl.s, rT, n, g);
+    ws_copy<E>(st, rT, res, g, g.rs, pl.r, n, (size_t)n * g.items, 1, g.items, false);
 }
 
-int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws,
-               int force) {
+template <class E>
+int pow_seq(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws, int force,
+            const SeriesPlanes& pl) {
     if (g.items == 0) return SERIES_NONE;
     if (e == 0) {
-        GFT_LAUNCH(k_series_unit_rows<E>, dim3(g.items), dim3(std::min(256u, (n + 63) / 64 * 64)), 0, st, res, (size_t)0, n, g);
+        GFT_LAUNCH(k_series_unit_rows<E>, dim3(g.items), dim3(std::min(256u, (n + 63) / 64 * 64)), 0, st, res, pl.r, n, g);
         return SERIES_NONE;
     }
-    const size_t rows = (size_t)E::W * g.items * n;
+    // three workspace arrays of E::W planes, each plane items * n doubles whatever the compact length of the rows in it
+    const size_t wp = (size_t)g.items * n, rows = (size_t)E::W * wp;
     double* spare[2] = {ws + rows, ws + 2 * rows};
     int nspare = 2;
-    double* unit = ws + 3 * rows;
+    double* unit = ws + 3 * rows;  // E::W doubles: the planes of the one coefficient are neighbours
     SeriesBatch one_row;
     one_row.nd = 0;
     one_row.items = 1;
-    GFT_LAUNCH(k_series_unit_rows<E>, dim3(1), dim3(64), 0, st, unit, (size_t)0, 1u, one_row);
+    GFT_LAUNCH(k_series_unit_rows<E>, dim3(1), dim3(64), 0, st, unit, (size_t)(E::W - 1), 1u, one_row);
     // the operand, read once through its strides: base = x as rows of nx
     double* base = ws;
     unsigned lb = nx;
-    {
-        CopyGeom in;
-        size_t cs = 1;
-        in.nd = g.nd + 1;
-        for (int a = g.nd - 1; a >= 0; --a) {
-            in.ext[a] = g.ext[a];
-            in.ss[a] = g.xs[a];
-            in.ds[a] = cs * nx;
-            cs *= g.ext[a];
-        }
-        in.ext[g.nd] = nx;
-        in.ss[g.nd] = in.ds[g.nd] = 1;
-        interop_copy(st, x, base, in);
-    }
+    ws_copy<E>(st, x, base, g, g.xs, pl.x, nx, wp, nx, 1, true);
     double* acc = unit;  // res of mt:441: [1.0] for every item until the first product
     unsigned la = 1;
     int form = SERIES_NONE;
     auto product = [&](const double* a, unsigned na, size_t ap, const double* b, unsigned nb, double* out, unsigned len, bool last) {
-        form = series_plan(SERIES_MUL, g.items, len, force);
-        series_launch(st, SERIES_MUL, form, a, na, b, nb, out, len, ws_batch(g, ap, nb, last ? 0 : len), nullptr);
+        form = plan<E>(SERIES_MUL, g.items, len, force);
+        SeriesPlanes wpl;
+        wpl.w = E::W;
+        if (E::W > 1) {  // (one plane: the strides stay 0)
+            wpl.x = a == unit ? 1 : wp;
+            wpl.y = wp;
+            wpl.r = last ? pl.r : wp;
+        }
+        launch<E>(st, SERIES_MUL, form, a, na, b, nb, out, len, ws_batch(g, ap, nb, last ? 0 : len), nullptr, wpl);
     };
     while (e > 0) {
         if (e & 1) {
@@ -256,6 +277,29 @@ int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double*
         }
     }
     return form;
+}
+
+}  // namespace
+
+int series_plan(int op, unsigned items, unsigned n, int force, int w) {
+    return w == 2 ? plan<EIv>(op, items, n, force) : plan<EF64>(op, items, n, force);
+}
+
+size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n, int w) {
+    if (op == SERIES_POW) return (size_t)w * (3 * (size_t)items * n + 1);
+    if (form != SERIES_FORM_B || (op != SERIES_EXP && op != SERIES_LOG)) return 0;
+    return (size_t)w * items * ((size_t)nx + n);
+}
+
+void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
+                   unsigned n, const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
+    if (pl.w == 2) launch<EIv>(st, op, form, x, nx, y, ny, res, n, g, ws, pl);
+    else launch<EF64>(st, op, form, x, nx, y, ny, res, n, g, ws, pl);
+}
+
+int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws,
+               int force, const SeriesPlanes& pl) {
+    return pl.w == 2 ? pow_seq<EIv>(st, x, nx, e, res, n, g, ws, force, pl) : pow_seq<EF64>(st, x, nx, e, res, n, g, ws, force, pl);
 }
 
 }  // namespace gft

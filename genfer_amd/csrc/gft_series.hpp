@@ -25,6 +25,16 @@ enum SeriesOp { SERIES_MUL = 0, SERIES_DIV = 1, SERIES_EXP = 2, SERIES_LOG = 3, 
 enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
 
 constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
+// Interval<F64> series (gfti_series_*): two planes per row, so the same LDS footprints are reached at half the order
+constexpr unsigned SERIES_MAX_N_IV = 2048;
+inline unsigned series_max_n(int w) { return w == 2 ? SERIES_MAX_N_IV : SERIES_MAX_N; }
+
+// The element of a call: w = 1 is F64 (one plane, the strides below unused), w = 2 is Interval<F64>, stored as the planes
+// (lo, hi) x / y / s / r elements apart (operands, seeds, result; 0 on an operand: a point interval read twice).
+struct SeriesPlanes {
+    int w = 1;
+    size_t x = 0, y = 0, s = 0, r = 0;
+};
 
 // The collapsed batch: item (i_0, ..., i_{nd-1}), row-major over ext, has its rows at x + sum i_a * xs[a] (elements), and
 // likewise y (mul / div), the seeds (exp / log; one double per item) and the result.  Stride 0 repeats a row.
@@ -38,22 +48,22 @@ struct SeriesBatch {
 
 // The form a call takes.  force: 0 = by the thresholds, SERIES_FORM_A = form A whenever the rows fit its LDS budget,
 // SERIES_FORM_B = never form A (gft_set_option("series_form")).
-int series_plan(int op, unsigned items, unsigned n, int force);
+int series_plan(int op, unsigned items, unsigned n, int force, int w = 1);
 // doubles of device workspace the call needs (form B of exp / log: the transposed operand and result; pow: the base, two results
-// taking turns and the factor [1.0]), else 0
-size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n);
+// taking turns and the factor [1.0]; each of w planes), else 0
+size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n, int w = 1);
 // Launches the call on `st`.  `y`: the second operand of mul / div / compose (x is f, y is g); for exp / log the seeds or nullptr
 // (seeds formed on the device by the HIP device library's exp / log).  `ws`: series_workspace() doubles.  Not for SERIES_POW.
 void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
-                   unsigned n, const SeriesBatch& g, double* ws);
+                   unsigned n, const SeriesBatch& g, double* ws, const SeriesPlanes& pl = SeriesPlanes());
 // x^e on `st`: x is copied once into the workspace, every product but the last is a mul launch on workspace rows of the compact
 // length, the last one writes the n coefficients through the result's strides.  `force` as for series_plan; returns the form of
 // the last product (SERIES_NONE for e == 0, which only writes [1, 0, ...]).
 int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws,
-               int force);
+               int force, const SeriesPlanes& pl = SeriesPlanes());
 // form B of div: k_div_1d_wave / k_div_1d with blockIdx.x as the item (gft_div2d.hip)
 void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
-                     const SeriesBatch& g);
+                     const SeriesBatch& g, const SeriesPlanes& pl = SeriesPlanes());
 
 // the element offsets of item `it` (kernels of gft_series.hip and gft_div2d.hip)
 struct SeriesOff {

@@ -1,0 +1,63 @@
+"""Batched univariate series on interval device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow``
+(``gfti_series_*``), the ``Interval<F64>`` half of ``genfer_amd.series``.
+
+An interval tensor is float64 and stacked ``[2, B..., n]`` = (lo, hi) along its first axis, as ``IntervalTaylorPoly.from_torch``
+takes it.  The last axis is the series (unit stride), the axes between are batch axes and broadcast by torch's rules.  The
+plane axis may have any non-negative stride on an operand, 0 included: ``x.expand(2, ...)`` is a batch of point intervals, no
+copy.  The result's two planes are distinct memory.  Seeds of ``exp`` / ``log`` are ``[2, B...]``.  Item ``b`` is the
+``TaylorPoly<Interval<F64>>`` of one variable with coefficients ``[x[0, b, k], x[1, b, k]]`` and truncation order ``n <= 2048``
+(two planes reach at 2048 the footprints float64 rows reach at 4096).  Per item the results are the reference's *general*
+algorithms over its interval arithmetic (round to nearest, one ulp outwards), every bound with the oracle's bits, and none of
+the operators' shortcuts.  The call is ordered on torch's current stream and does not wait.
+
+    >>> from genfer_amd import interval_series as ivs
+    >>> z = ivs.mul(x, y)                          # x, y: [2, B, n] float64 on the GPU
+    >>> q = ivs.div(p.expand(2, B, n), y)          # p: [B, n] point values
+    >>> e = ivs.exp(x, seed=s)                     # s: [2, B], the interval exp of coefficient 0
+    >>> h = ivs.compose(f, g)
+    >>> p = ivs.pow(x, 5)
+"""
+from __future__ import annotations
+
+from .series import FORMS, _exponent, _run, last_form, set_form  # noqa: F401  (one library, one form option, one last form)
+
+MAX_N = 2048  # gft_series.hpp SERIES_MAX_N_IV
+
+
+def _iv(what, name, x, second, n, out, second_is_seed, **kw):
+    return _run(f"interval_series.{what}", f"gfti_series_{name}", x, second, n, out, second_is_seed, planes=1, max_n=MAX_N, **kw)
+
+
+def mul(x, y, n=None, out=None):
+    """``z[b] = x[b] * y[b]`` truncated at order ``n`` (default ``max(nx, ny)``): the general product ``mul_1d`` over intervals."""
+    return _iv("mul", "mul", x, y, n, out, False)
+
+
+def div(x, y, n=None, out=None):
+    """``r[b] = x[b] / y[b]`` to order ``n`` (default ``max(nx, ny)``): the general division recurrence over intervals."""
+    return _iv("div", "div", x, y, n, out, False)
+
+
+def exp(x, n=None, seed=None, out=None):
+    """``exp(x[b])`` to order ``n`` (default ``nx``).  ``seed``: the interval ``exp`` of coefficient 0 per item, ``[2, B...]``; with
+    the host libm's values widened as the reference widens them the result carries its bits.  ``None``: formed on the device."""
+    return _iv("exp", "exp", x, seed, n, out, True)
+
+
+def log(x, n=None, seed=None, out=None):
+    """``log(x[b])`` to order ``n`` (default ``nx``).  ``seed``: the interval ``ln`` of coefficient 0 per item, ``[2, B...]``;
+    ``None``: formed on the device (only coefficient 0 depends on it)."""
+    return _iv("log", "log", x, seed, n, out, True)
+
+
+def compose(f, g, n=None, out=None):
+    """``f[b](g[b])`` truncated at order ``n`` (default ``max(nf, ng)``): Horner over the coefficients of ``f`` with the general
+    interval product at every step, as ``series.compose``.  About ``nf * n**2 / 2`` interval multiply-adds per item, on one
+    workgroup at most."""
+    return _iv("compose", "compose", f, g, n, out, False, names=("f", "g"))
+
+
+def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
+    """``x[b] ** e`` truncated at order ``n`` (default ``nx``) for an integer ``0 <= e < 2**32``: the reference's
+    square-and-multiply over ``mul`` at compact lengths.  ``e = 0`` gives ``[[1, 1], [0, 0], ...]``."""
+    return _iv("pow", "pow", x, None, n, out, True, e=_exponent("interval_series.pow", e, div="interval_series.div"))

@@ -339,6 +339,27 @@ void gfti_shape(const gft_poly* p, size_t* out);
 void gfti_degrees_p1(const gft_poly* p, size_t* out);
 int gfti_to_host(const gft_poly* p, double* out);
 int gfti_to_device(const gft_poly* p, double* dst, const int64_t* strides, void* stream);
+/* Batched series over Interval<F64>: gft_series_* on tensors [2, B..., n] = (lo, hi).  The argument lists are those of
+ * gft_series_*, but every stride array (xbs / ybs / sbs / rbs) has nbatch + 1 entries: the FIRST is the lo -> hi plane stride in
+ * elements (gfti_from_device's convention), the batch strides follow.  NULL = C-contiguous rows with the two planes back to
+ * back.  The plane stride of an operand or of the seeds may be 0 (a point interval: x.expand(2, ...)); the result's must
+ * separate its planes (the planes count as one more axis of "the rows do not overlap"), the overlap test covers both planes
+ * of every operand, and "the same view" of an in-place result includes the plane stride.  Seeds are [2, B...].  n <= 2048:
+ * with two planes the LDS footprints of gft_series_* at 4096 are reached there.  Per item the results are the reference's
+ * general algorithms over Interval<F64> (interval.rs), each bound with the oracle's bits; gft_series_last_form and the
+ * "series_form" option serve both families. */
+int gfti_series_mul(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_div(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_exp(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_log(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_compose(const double* f, const int64_t* fbs, size_t nf, const double* g, const int64_t* gbs, size_t ng,
+                        double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
+                    const size_t* batch, size_t nbatch, void* stream);
 size_t gfti_len_of(const gft_poly* p, size_t v);
 int gfti_is_constant(const gft_poly* p);
 int gfti_is_zero(const gft_poly* p);

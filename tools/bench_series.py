@@ -13,6 +13,9 @@ third leg, (c) the chain of nf - 1 series.mul calls each followed by an add into
 caller could do before compose existed), reported as chain_ms and chain_over_batched.  Multiply-adds are counted at the compact
 lengths the definition uses.
 
+--interval: the same on interval tensors [2, B, n] (genfer_amd.interval_series against the IntervalTaylorPoly per-row loop), n
+capped at 2048; bytes and multiply-adds count interval elements (16 bytes, one interval multiply-add).
+
     python tools/bench_series.py > profiles/r07/series_batch.json
     python tools/bench_series.py --ops compose,pow --shapes 4096x16,4096x64,65536x32,1024x256,64x1024x64,1x4096x16
 """
@@ -40,6 +43,7 @@ def parse_args(argv=None):
     ap.add_argument("--loop-rows", type=int, default=256, help="rows the per-row loop is timed on (scaled to B)")
     ap.add_argument("--budget-ms", type=float, default=300.0, help="time each leg repeats for, roughly")
     ap.add_argument("--no-loop", action="store_true", help="skip leg (b)")
+    ap.add_argument("--interval", action="store_true", help="interval tensors [2, B, n]: interval_series against the IntervalTaylorPoly loop (n <= 2048)")
     args = ap.parse_args(argv)
     for op in args.ops.split(","):
         if op not in KNOWN_OPS:
@@ -102,7 +106,12 @@ def main(argv=None):
     from genfer_amd import series
 
     genfer_amd.init(0)
-    TP = genfer_amd.TaylorPoly
+    iv = args.interval
+    if iv:
+        from genfer_amd import interval_series as series  # noqa: F811  (the same six functions on [2, B, n])
+    TP = genfer_amd.IntervalTaylorPoly if iv else genfer_amd.TaylorPoly
+    W = 2 if iv else 1
+    item = (lambda t, b: t[:, b]) if iv else (lambda t, b: t[b])  # row b of a batch, with its planes
     dev = torch.device("cuda", 0)
     series.set_form(None if args.form == "auto" else args.form)
     gen = torch.Generator(device="cpu").manual_seed(7)
@@ -110,19 +119,25 @@ def main(argv=None):
     for shape in args.shapes.split(","):
         dims = [int(t) for t in shape.lower().split("x")]
         B, n = dims[0], dims[1]
-        m = dims[2] if len(dims) > 2 else n  # nf = ng of compose
+        if iv:
+            n = min(n, 2048)
+        m = min(dims[2], n) if len(dims) > 2 else n  # nf = ng of compose
         # bounded results at every order: a dominant constant term in the divisor, a small argument for exp
         x = (0.5 + torch.rand((B, n), dtype=torch.float64, generator=gen) / n).to(dev)
         y = (0.5 + torch.rand((B, n), dtype=torch.float64, generator=gen) / n).to(dev)
         y[:, 0] += 2.0
-        out = torch.empty((B, n), dtype=torch.float64, device=dev)
+        if iv:  # [2, B, n]: lower bounds as above, about 2^-30 relative width
+            x = torch.stack([x, x * (1.0 + 2.0**-30)])
+            y = torch.stack([y, y * (1.0 + 2.0**-30)])
+        out = torch.empty((B, n) if not iv else (2, B, n), dtype=torch.float64, device=dev)
         for op in args.ops.split(","):
             seed = None
             if op in ("exp", "log"):
-                seed = torch.tensor([getattr(math, op)(v) for v in x[:, 0].cpu().tolist()], dtype=torch.float64).to(dev)
+                seed = torch.tensor([getattr(math, op)(v) for v in x[..., 0].reshape(-1).cpu().tolist()], dtype=torch.float64)
+                seed = seed.reshape(x.shape[:-1]).to(dev)  # (intervals: the bounds' own exp / log, unwidened -- timing only)
 
-            fc, gc = x[:, :m], y[:, :m]  # compose: f and g as views of the same tensors
-            step = torch.empty((B, n), dtype=torch.float64, device=dev)
+            fc, gc = x[..., :m], y[..., :m]  # compose: f and g as views of the same tensors
+            step = torch.empty_like(out)
 
             def batched():
                 if op in ("mul", "div"):
@@ -140,39 +155,39 @@ def main(argv=None):
 
             def loop():
                 for b in range(rows):
-                    p = TP.from_torch(x[b])
+                    p = TP.from_torch(item(x, b))
                     if op == "mul":
-                        r = p * TP.from_torch(y[b])
+                        r = p * TP.from_torch(item(y, b))
                     elif op == "div":
-                        r = p / TP.from_torch(y[b])
+                        r = p / TP.from_torch(item(y, b))
                     elif op == "compose":
-                        r = TP.from_torch(fc[b], degrees_p1=(n,)).subst_var(0, TP.from_torch(gc[b], degrees_p1=(n,)))
-                        out[b].zero_()
-                        r.to_torch(out=out[b, :r.coeffs_shape()[0]])
+                        r = TP.from_torch(item(fc, b), degrees_p1=(n,)).subst_var(0, TP.from_torch(item(gc, b), degrees_p1=(n,)))
+                        item(out, b).zero_()
+                        r.to_torch(out=item(out, b)[..., :r.coeffs_shape()[0]])
                         continue
                     elif op == "pow":
                         r = p.pow(args.pow_e)
                     else:
                         r = p.exp() if op == "exp" else p.log()
-                    r.to_torch(out=out[b])
+                    r.to_torch(out=item(out, b))
 
             def chain():  # compose before compose: nf - 1 products at full length, each followed by an add into coefficient 0
                 a, b = step, out
                 if (m - 1) % 2 == 0:
                     a, b = b, a  # the last product lands in `out`
                 a.zero_()
-                a[:, 0] = fc[:, m - 1]
+                a[..., 0] = fc[..., m - 1]
                 for i in range(m - 2, -1, -1):
                     series.mul(a, gc, n=n, out=b)
-                    b[:, 0] += fc[:, i]
+                    b[..., 0] += fc[..., i]  # (intervals: unwidened, the cost of the add is what is timed)
                     a, b = b, a
 
-            rec = {"op": op, "B": B, "n": n, "form": form, "batched_ms": round(t_batch, 6), "batched_reps": reps_a}
+            rec = {"op": op, "B": B, "n": n, "form": form, **({"interval": True} if iv else {}), "batched_ms": round(t_batch, 6), "batched_reps": reps_a}
             macs = B * n * (n + 1) / 2.0
-            nbytes = 8.0 * B * (n + (n if op in ("mul", "div") else 0) + n)
+            nbytes = 8.0 * W * B * (n + (n if op in ("mul", "div") else 0) + n)
             if op == "compose":
                 rec["nf"] = rec["ng"] = m
-                macs, nbytes = float(B * compose_macs(m, m, n)), 8.0 * B * (2 * m + n)
+                macs, nbytes = float(B * compose_macs(m, m, n)), 8.0 * W * B * (2 * m + n)
             elif op == "pow":
                 rec["e"] = args.pow_e
                 macs = float(B * pow_macs(n, args.pow_e, n))
@@ -189,7 +204,7 @@ def main(argv=None):
             print(json.dumps(rec), flush=True)
     series.set_form(None)
     props = torch.cuda.get_device_properties(0)
-    print(json.dumps({"summary": True, "device": props.name, "asked_form": args.form, "cases": len(results),
+    print(json.dumps({"summary": True, "device": props.name, "asked_form": args.form, "interval": iv, "cases": len(results),
                       "min_ratio_B_ge_256": min([r["loop_over_batched"] for r in results if r["B"] >= 256 and "loop_over_batched" in r], default=None),
                       "min_ratio_B_lt_256": min([r["loop_over_batched"] for r in results if r["B"] < 256 and "loop_over_batched" in r], default=None),
                       "min_chain_over_batched": min([r["chain_over_batched"] for r in results if "chain_over_batched" in r], default=None)}))
