@@ -183,6 +183,7 @@ struct Runtime {
     int device = -1;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
+    size_t stats_peeled = 0;                // tiled products that took the peel (gft_conv_tiled.hip conv_tiled_peel)
     size_t stats_side[4] = {0, 0, 0, 0};    // {-, -, recordings that rode along with another launch of their kind, lazy observations fused}
     size_t stats_nz = 0;                    // linearity scans answered by a "no exact zero" proof
     size_t stats_sum = 0;                   // Adds that evaluated a recorded Add of two chains in their own launch (K<E>::chain_nest)
@@ -1367,7 +1368,7 @@ void gft_op_stats(size_t out[8]) {
 }
 size_t gft_op_stats_ex(size_t* out, size_t cap) {
     const size_t v[18] = {(size_t)gft::g_launches, R.stats_ex[0], R.stats_ex[1], R.stats_ex[2], (size_t)gft::g_launches_in_place,
-                          R.stats_shallow[0], R.stats_shallow[1], R.stats_side[0], R.stats_side[1], R.stats_side[2], R.stats_side[3], R.stats_nz, R.stats_sum,
+                          R.stats_shallow[0], R.stats_shallow[1], R.stats_peeled, R.stats_side[1], R.stats_side[2], R.stats_side[3], R.stats_nz, R.stats_sum,
                           g_dag_stats[0], g_dag_stats[1], g_dag_stats[2], g_dag_stats[3], g_dag_stats[4]};
     for (size_t i = 0; i < 18 && i < cap; ++i) out[i] = v[i];
     return 18;
@@ -1424,6 +1425,7 @@ int gft_set_option(const char* name, double value) {
     else if (n == "conv_rb_pairs_lanes") staged_set_rb_pairs_lanes(value);
     else if (n == "shallow_pair_min") shallow_set_pair_min(value == -1.0 ? 4096.0 : value);
     else if (n == "tiled_tile") tiled_set_lane_tile((int)value);
+    else if (n == "tiled_peel") tiled_set_peel((int)value);
     else if (n == "host_max_elems") R.host_max_elems = value < 0 ? Runtime::HOST_MAX_ELEMS_DEFAULT : (size_t)value;  // < 0: default
     else if (n == "host_max_macs") R.host_max_macs = value < 0 ? Runtime::HOST_MAX_MACS_DEFAULT : value;
     else if (n == "series_form") R.series_force = (value == 1 || value == 2) ? (int)value : 0;  // test / measurement knob (gft_series.hpp)

@@ -18,7 +18,11 @@
 //                       replaces one of the T1 ring slots (T0 rows, prefetched global->VGPR during the step, written
 //                       to LDS after it); a new row starts with a full window load
 //   triangular waste    none along k2 (the diagonal 8x8 chunk is a 36-FMA triangle); (n+8)/(n+1) per
-//                       lane axis from masked lanes in diagonal tiles
+//                       lane axis from masked lanes in diagonal tiles — unless the product is PEELED (rank 3,
+//                       full extents, 8x8 lane tile): the main launch then stops every tile's step range at the
+//                       tile's first row (TiledArgs::cut, no masked lane left) and the 28-pair leftover triangle
+//                       of every tile runs as two small rank-4 products whose batch axis is the tile index
+//                       (conv_tiled_peel below)
 //   load balance        stream-K: the linearised (tile, ju, j0, j1) step space is cut into equal
 //                       contiguous ranges, one per resident workgroup (2 per CU).  Tiles covered by a
 //                       single range are written straight to z; split tiles go through partial slabs
@@ -64,6 +68,11 @@ struct TiledArgs {
     unsigned slab_lo, slab_hi;
     int accumulate;
     unsigned xcd_remap;              // 1: remap blockIdx so that each XCD owns a contiguous chunk of ranges
+    unsigned cut;                    // bit 0 / 1: the step range of a tile on lane axis 0 / 1 ends at the tile's first row
+                                     // (j <= T a instead of j <= T a + T - 1): the aligned part of a peeled product
+    unsigned lim1;                   // peel instantiation: lane k1 takes window rows d1 <= 8 (k1 / 8) only
+    size_t zsU, zs0, zs1, zoff;      // output strides of (u, k0, k1) and base offset, in doubles (dense unless peeled;
+                                     // read by the peel instantiation and by k_conv_reduce)
     const double* xp;
     const double* yp;
     double* z;
@@ -85,7 +94,15 @@ typedef const double __attribute__((address_space(4))) * cptr_t;
 #ifndef GFT_TILED_DEFAULT_VARIANT
 #define GFT_TILED_DEFAULT_VARIANT 7
 #endif
-// VAR bits: 1 = software-pipelined fast path for full inner extents; diagnostics (wrong results, timing
+#ifndef GFT_TILED_PEEL_DEFAULT
+#define GFT_TILED_PEEL_DEFAULT -1  // "tiled_peel": -1 auto (by size), 0 never, 1 wherever the structure allows
+#endif
+// auto mode peels products whose two lane axes are at least PEEL_MIN_EXTENT long and whose inner axis at least
+// PEEL_MIN_INNER: the range the sweep covers (profiles/r07/tiled_peel_sweep.txt); a short inner axis leaves the same fixed
+// cost (one pack, two more main launches, two more reduces) against a fraction of the work
+constexpr unsigned PEEL_MIN_EXTENT = 112, PEEL_MIN_INNER = 64;
+// VAR bits: 1 = software-pipelined fast path for full inner extents; 128 = peel instantiation (per-lane row limit on
+// axis 1 and strided output, for the leftover products of a peeled product); diagnostics (wrong results, timing
 // only, built with -DGFT_TILED_DIAG): 16 = no LDS reads in the chunk loop, 32 = no scalar x loads,
 // 64 = no window maintenance / barriers.
 
@@ -295,10 +312,12 @@ __host__ __device__ inline TileGeom tile_geom(const TiledArgs& A, unsigned tsh, 
     unsigned k0max = (T0 * a + T0 - 1 < A.z0 - 1) ? T0 * a + T0 - 1 : A.z0 - 1;
     g.j0lo = (T0 * a + 1 > A.y0) ? (T0 * a + 1 - A.y0) : 0;
     unsigned j0hi = (k0max + 1 < A.x0) ? (k0max + 1) : A.x0;
+    if ((A.cut & 1u) && T0 * a + 1 < j0hi) j0hi = T0 * a + 1;
     g.n_j0 = j0hi > g.j0lo ? j0hi - g.j0lo : 0;
     unsigned k1max = (T1 * b + T1 - 1 < A.z1 - 1) ? T1 * b + T1 - 1 : A.z1 - 1;
     g.j1lo = (T1 * b + 1 > A.y1) ? (T1 * b + 1 - A.y1) : 0;
     unsigned j1hi = (k1max + 1 < A.x1) ? (k1max + 1) : A.x1;
+    if ((A.cut & 2u) && T1 * b + 1 < j1hi) j1hi = T1 * b + 1;
     g.n_j1 = j1hi > g.j1lo ? j1hi - g.j1lo : 0;
     return g;
 }
@@ -318,6 +337,7 @@ __global__ void __launch_bounds__(NW * 64, 4)  // 4 waves per SIMD = 16 waves pe
 k_conv_tiled(TiledArgs A) {
     constexpr bool FAST = (VAR & 1) != 0;
     constexpr bool NO_WINDOW = (VAR & 64) != 0;
+    constexpr bool PEEL = (VAR & 128) != 0;
     extern __shared__ double lds[];
     // an operand holds inf/NaN: the reference-order kernel (launched next, guarded the other way) owns z
     if (A.guard && *A.guard == A.guard_epoch) return;
@@ -359,6 +379,9 @@ k_conv_tiled(TiledArgs A) {
         bool lane_in = k0 < A.z0 && k1 < A.z1;
         if (A.slab_axis == 1) lane_in = lane_in && k0 >= A.slab_lo && k0 < A.slab_hi;
         else if (A.slab_axis == 2) lane_in = lane_in && k1 >= A.slab_lo && k1 < A.slab_hi;
+        // (peel: the window rows this lane may take end at its own tile's first row — the leftover product along axis 1)
+        unsigned y1lim = A.y1;
+        if (PEEL && A.lim1 && (k1 & ~7u) + 1u < y1lim) y1lim = (k1 & ~7u) + 1u;
 
         double acc1[8], acc2[8];
 #pragma unroll
@@ -416,7 +439,7 @@ k_conv_tiled(TiledArgs A) {
                 if (do_pf && pf_row) pf = *reinterpret_cast<const double2*>(pf_src);
 
                 // ---- compute this step -------------------------------------------------------------
-                if (valid0 && (unsigned)d1 < A.y1) {  // j1 <= k1 and k1 - j1 < y1
+                if (valid0 && (unsigned)d1 < (PEEL ? y1lim : A.y1)) {  // j1 <= k1 and k1 - j1 < y1
                     const double* yrow = lds_lane + (size_t)((unsigned)d1 & T1m) * A.P1;
                     if constexpr (FAST && (VAR & 8)) {  // pipelined path for compact operands
                         if (has1) block_fast_gen<VAR>(acc1, c1, xr, yrow, A.nxc, A.nyc);
@@ -459,6 +482,7 @@ k_conv_tiled(TiledArgs A) {
         if (seg.dest < 0) {
             if (lane_in) {
                 double* zrow = A.z + (((size_t)u * A.z0 + k0) * A.z1 + k1) * A.zI;
+                if constexpr (PEEL) zrow = A.z + A.zoff + (size_t)u * A.zsU + (size_t)k0 * A.zs0 + (size_t)k1 * A.zs1;
                 if (has1) {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) {
@@ -508,7 +532,7 @@ __global__ void __launch_bounds__(256) k_conv_reduce(TiledArgs A, unsigned n_red
     double v[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = 0.0;
-    double* zrow = A.z + (((size_t)rt.u * A.z0 + k0) * A.z1 + k1) * A.zI;
+    double* zrow = A.z + A.zoff + (size_t)rt.u * A.zsU + (size_t)k0 * A.zs0 + (size_t)k1 * A.zs1;
     if (lane_in) {
         if (q == 0 && A.accumulate) {
 #pragma unroll
@@ -594,6 +618,46 @@ __global__ void __launch_bounds__(256) k_prep_operands(const double* __restrict_
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicMax(flag, epoch);
 }
 
+// Operands of the two leftover products of a peeled n0 x n1 x nI product (conv_tiled_peel), gathered into the packed
+// layout (rows of n8 doubles) in one launch:
+//   w0[v][a][r1][.]  = x[8a+1+v][r1][.]   window operand of L0, (7, n0/8, n1) rows
+//   s1[ju][j1c][.]   = y[j1c][ju][.]      scalar operand of L1, (7, n0) rows
+//   w1[v][b][r][.]   = x[r][8b+1+v][.]    window operand of L1, (7, n1/8, n0) rows
+// No scan: the main product's k_prep_operands has seen all of x and y.
+__global__ void __launch_bounds__(256) k_pack_peel(const double* __restrict__ x, const double* __restrict__ y,
+                                                   double* __restrict__ w0, double* __restrict__ s1, double* __restrict__ w1,
+                                                   unsigned n0, unsigned n1, unsigned nI, unsigned n8) {
+    const size_t t0 = (size_t)7 * (n0 / 8) * n1 * n8, ts = (size_t)7 * n0 * n8, t1 = (size_t)7 * (n1 / 8) * n0 * n8;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < t0 + ts + t1; i += (size_t)gridDim.x * blockDim.x) {
+        const double* src;
+        double* dst;
+        size_t row;
+        unsigned col;
+        if (i < t0) {
+            row = i / n8;
+            col = (unsigned)(i - row * n8);
+            const unsigned r1 = (unsigned)(row % n1), va = (unsigned)(row / n1), a = va % (n0 / 8), v = va / (n0 / 8);
+            src = x + ((size_t)(8 * a + 1 + v) * n1 + r1) * nI;
+            dst = w0 + i;
+        } else if (i < t0 + ts) {
+            const size_t k = i - t0;
+            row = k / n8;
+            col = (unsigned)(k - row * n8);
+            const unsigned j1c = (unsigned)(row % n0), ju = (unsigned)(row / n0);
+            src = y + ((size_t)j1c * n1 + ju) * nI;
+            dst = s1 + k;
+        } else {
+            const size_t k = i - t0 - ts;
+            row = k / n8;
+            col = (unsigned)(k - row * n8);
+            const unsigned r = (unsigned)(row % n0), vb = (unsigned)(row / n0), b = vb % (n1 / 8), v = vb / (n1 / 8);
+            src = x + ((size_t)r * n1 + 8 * b + 1 + v) * nI;
+            dst = w1 + k;
+        }
+        *dst = col < nI ? src[col] : 0.0;
+    }
+}
+
 // ---- inner-axis splitting (rank 2, or an inner axis longer than 128) ---------------------------------------------
 // A row of length n is viewed as P = ceil(n / B) pieces of B: x~[p][r] = x[pB + r] (zero padded).  The product of
 // the (.., Px, B) and (.., Py, B) tensors with an UNtruncated last axis (2B - 1 <= 127 coefficients) contains
@@ -632,7 +696,7 @@ __global__ void __launch_bounds__(256) k_fold_rows(const double* __restrict__ zt
 // ---- host-side plan ------------------------------------------------------------------------------------
 
 struct PlanKey {
-    unsigned v[18];
+    unsigned v[19];
     bool operator<(const PlanKey& o) const { return std::memcmp(v, o.v, sizeof(v)) < 0; }
 };
 
@@ -688,12 +752,55 @@ int num_cus() {
 
 static void assign_blocks(TiledArgs& T, unsigned NW);
 
+// What distinguishes the three plans of a peeled product from a plain one (all zero: plain).
+struct PeelSpec {
+    unsigned role = 0;                      // 0 plain, 1 the aligned main part M, 2 / 3 the leftover products L0 / L1
+    unsigned cut = 0, lim1 = 0;             // TiledArgs::cut, TiledArgs::lim1
+    size_t zsU = 0, zs0 = 0, zs1 = 0, zoff = 0;  // output strides (role 2 / 3; dense otherwise)
+};
+
+unsigned long long& plan_generation() {  // bumped whenever the plan cache is emptied (cached Plan copies are stale then)
+    static unsigned long long g = 0;
+    return g;
+}
+
 int& tiled_force_tsh() {  // A/B and test knob (GFT_TILED_TSH / "tiled_tile"): 3..6 forces the lane tile 8x8 .. 1x64
     static int v = 0;
     return v;
 }
 
-bool build_plan(const ConvArgs& a, Plan& P, hipStream_t st) {
+// Lane tile: the shape whose lanes are busiest.  A lane (k0, k1) works in step (j0, j1) iff j <= k and k - j < y's
+// extent on both axes; the steps a tile runs are the union over its lanes, so a tile straddling the diagonal (or a
+// short axis) carries masked lanes.  Useful / issued lane-steps factorises over the two axes.
+unsigned pick_lane_tile(const TiledArgs& T) {
+    auto axis_eff = [](unsigned T, unsigned nx, unsigned ny, unsigned nz) {
+        double useful = 0, issued = 0;
+        for (unsigned t = 0; t * T < nz; ++t) {
+            const unsigned kmax = std::min(T * t + T - 1, nz - 1);
+            const unsigned jlo = T * t + 1 > ny ? T * t + 1 - ny : 0, jhi = std::min(kmax + 1, nx);
+            if (jhi > jlo) issued += (double)(jhi - jlo) * T;
+            for (unsigned k = T * t; k <= kmax; ++k) {
+                const unsigned lo = k + 1 > ny ? k + 1 - ny : 0, hi = std::min(k + 1, nx);
+                if (hi > lo) useful += hi - lo;
+            }
+        }
+        return issued > 0 ? useful / issued : 0.0;
+    };
+    const int force = tiled_force_tsh();
+    if (force >= 3 && force <= 6) return (unsigned)force;
+    double best = -1.0;
+    unsigned best_tsh = 3;
+    for (unsigned tsh = 3; tsh <= 6; ++tsh) {
+        const double e = axis_eff(64u >> tsh, T.x0, T.y0, T.z0) * axis_eff(1u << tsh, T.x1, T.y1, T.z1);
+        if (e > best * 1.02) {  // ties (and near ties) go to the squarer tile: fewer window reloads per step
+            best = e;
+            best_tsh = tsh;
+        }
+    }
+    return best_tsh;
+}
+
+bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) {
     TiledArgs& T = P.base;
     std::memset(&T, 0, sizeof(T));
     // canonical form z[u][k0][k1][k2]: u is wave-uniform, (k0, k1) are the lane axes, k2 the register axis
@@ -731,34 +838,15 @@ bool build_plan(const ConvArgs& a, Plan& P, hipStream_t st) {
     // front padding + pitch: odd (8-byte slots, bijective mod 16/32 for ds_read_b64/read2_b64) or, for the
     // ds_read_b128 variant, even with P1/2 odd (16-byte slots bijective mod 16 for the b128 lane groups)
     T.P1 = (a.variant & 2) ? T.ny8 + YPAD + 2 : T.ny8 + YPAD + 1;
-    // Lane tile: the shape whose lanes are busiest.  A lane (k0, k1) works in step (j0, j1) iff j <= k and k - j < y's
-    // extent on both axes; the steps a tile runs are the union over its lanes, so a tile straddling the diagonal (or a
-    // short axis) carries masked lanes.  Useful / issued lane-steps factorises over the two axes.
-    {
-        auto axis_eff = [](unsigned T, unsigned nx, unsigned ny, unsigned nz) {
-            double useful = 0, issued = 0;
-            for (unsigned t = 0; t * T < nz; ++t) {
-                const unsigned kmax = std::min(T * t + T - 1, nz - 1);
-                const unsigned jlo = T * t + 1 > ny ? T * t + 1 - ny : 0, jhi = std::min(kmax + 1, nx);
-                if (jhi > jlo) issued += (double)(jhi - jlo) * T;
-                for (unsigned k = T * t; k <= kmax; ++k) {
-                    const unsigned lo = k + 1 > ny ? k + 1 - ny : 0, hi = std::min(k + 1, nx);
-                    if (hi > lo) useful += hi - lo;
-                }
-            }
-            return issued > 0 ? useful / issued : 0.0;
-        };
-        const int force = tiled_force_tsh();
-        double best = -1.0;
-        unsigned best_tsh = 3;
-        for (unsigned tsh = 3; tsh <= 6; ++tsh) {
-            const double e = axis_eff(64u >> tsh, T.x0, T.y0, T.z0) * axis_eff(1u << tsh, T.x1, T.y1, T.z1);
-            if (e > best * 1.02) {  // ties (and near ties) go to the squarer tile: fewer window reloads per step
-                best = e;
-                best_tsh = tsh;
-            }
-        }
-        T.tsh = (force >= 3 && force <= 6) ? (unsigned)force : best_tsh;
+    T.tsh = pick_lane_tile(T);
+    // peeled products: the aligned part ends every tile's step range at the tile's first row; the leftover products
+    // add into z through their own strides (everything else: dense)
+    T.cut = ps.cut;
+    T.lim1 = ps.lim1;
+    if (ps.role >= 2) {
+        T.zsU = ps.zsU; T.zs0 = ps.zs0; T.zs1 = ps.zs1; T.zoff = ps.zoff;
+    } else {
+        T.zsU = (size_t)T.z0 * T.z1 * T.zI; T.zs0 = (size_t)T.z1 * T.zI; T.zs1 = T.zI; T.zoff = 0;
     }
     const unsigned TT0 = 64u >> T.tsh, TT1 = 1u << T.tsh;
     T.slab_lo = a.slab_lo;
@@ -890,6 +978,7 @@ bool build_plan(const ConvArgs& a, Plan& P, hipStream_t st) {
             for (auto& kv : plan_cache())
                 if (kv.second.d_tables) (void)hipFree(kv.second.d_tables);
             plan_cache().clear();
+            plan_generation()++;
             A.head = 0;
         }
         base = A.dev + A.head;
@@ -999,21 +1088,19 @@ void tiled_fold_rows_f64(hipStream_t st, const double* zt, double* z, size_t row
 
 void tiled_set_lane_tile(int tsh) { tiled_force_tsh() = tsh; }
 
-bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a_in, void* ws,
-                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded) {
-    ConvArgs a = a_in;
-    if (a.variant < 0) a.variant = GFT_TILED_DEFAULT_VARIANT;
-    if (a.nd >= 2 && a.nd <= 4) {  // the pipelined fast path (bits 1|2) needs x and y to span every chunk of z's inner axis
-        unsigned nb = (a.zs[a.nd - 1] + 7) / 8;
-        if ((a.xs[a.nd - 1] + 7) / 8 < nb || (a.ys[a.nd - 1] + 7) / 8 < nb) {
-            static const bool compact_fast = true;
-            if (compact_fast && (a.variant & 3) == 3) a.variant = (a.variant & ~0xff) | (a.variant & 7) | 8;  // pipelined path for compact operands
-            else a.variant &= ~3;
-        }
-    }
+namespace {
+
+int& tiled_peel_mode() {  // "tiled_peel": -1 auto, 0 never, 1 wherever the structural conditions hold
+    static int v = GFT_TILED_PEEL_DEFAULT;
+    return v;
+}
+
+// The plan of (problem, peel role) from the cache, built on a miss.  The pointer is good until the cache is next emptied
+// (plan_generation()); nullptr: the tiled kernel does not support the shape.
+const Plan* cached_plan(const ConvArgs& a, const PeelSpec& ps, hipStream_t st) {
     PlanKey key;
     std::memset(&key, 0, sizeof(key));
-    if (a.nd < 2 || a.nd > 4) return false;
+    if (a.nd < 2 || a.nd > 4) return nullptr;
     key.v[0] = (unsigned)a.nd | ((unsigned)a.slab_axis << 8) | ((unsigned)tiled_force_tsh() << 16);
     for (int i = 0; i < a.nd; ++i) {
         key.v[1 + i] = a.xs[i];
@@ -1025,6 +1112,7 @@ bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z,
     key.v[15] = (unsigned)a.accumulate;
     key.v[16] = (unsigned)(a.j0_min | (a.j0_excl << 8) | (a.j0_desc << 16));
     key.v[17] = (unsigned)a.variant;
+    key.v[18] = ps.role | (ps.cut << 4) | (ps.lim1 << 8);  // (the leftover products' output strides follow from role and shapes)
     auto& cache = plan_cache();
     auto it = cache.find(key);
     if (it == cache.end()) {
@@ -1034,12 +1122,227 @@ bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z,
             for (auto& kv : cache)
                 if (kv.second.d_tables) (void)hipFree(kv.second.d_tables);
             cache.clear();
+            plan_generation()++;
             arena().head = 0;
         }
-        if (!build_plan(a, P, st)) return false;  // may itself reset the cache when the table arena wraps
+        if (!build_plan(a, ps, P, st)) return nullptr;  // may itself reset the cache when the table arena wraps
         it = cache.emplace(key, P).first;
     }
-    const Plan& P = it->second;
+    return &it->second;
+}
+
+// the main kernel of plan P on the filled-in arguments T, then the fixed-order reduce of its split tiles
+bool launch_plan(hipStream_t st, const Plan& P, const TiledArgs& T, int variant) {
+    hipError_t e = hipSuccess;
+    constexpr int DEF = GFT_TILED_DEFAULT_VARIANT;
+    if (variant & 128) {  // leftover products of a peeled product
+        switch (P.NW) {
+            case 1: e = launch_main<1, 131>(st, P, T); break;
+            case 2: e = launch_main<2, 131>(st, P, T); break;
+            case 4: e = launch_main<4, 131>(st, P, T); break;
+            default: e = launch_main<8, 131>(st, P, T); break;
+        }
+    } else if (variant & 8) {  // compact operands, pipelined
+        switch (P.NW) {
+            case 1: e = launch_main<1, 11>(st, P, T); break;
+            case 2: e = launch_main<2, 11>(st, P, T); break;
+            case 4: e = launch_main<4, 11>(st, P, T); break;
+            default: e = launch_main<8, 11>(st, P, T); break;
+        }
+    } else if (P.NW == 8) {
+        switch (variant) {
+            case 0: case 4: e = launch_main<8, 0>(st, P, T); break;
+            case 1: e = launch_main<8, 1>(st, P, T); break;
+            case 3: e = launch_main<8, 3>(st, P, T); break;
+            case 7: e = launch_main<8, 3>(st, P, T); break;  // 3 + XCD-contiguous ranges (runtime flag)
+#ifdef GFT_TILED_DIAG
+            case 17: e = launch_main<8, 17>(st, P, T); break;
+            case 33: e = launch_main<8, 33>(st, P, T); break;
+            case 49: e = launch_main<8, 49>(st, P, T); break;
+            case 65: e = launch_main<8, 65>(st, P, T); break;
+            case 113: e = launch_main<8, 113>(st, P, T); break;
+#endif
+            default: return false;
+        }
+    } else {
+        if (variant != 0 && variant != 4 && variant != DEF && variant != (DEF & 3)) return false;
+        if (variant & 1) {
+            switch (P.NW) {
+                case 1: e = launch_main<1, (DEF & 3)>(st, P, T); break;
+                case 2: e = launch_main<2, (DEF & 3)>(st, P, T); break;
+                default: e = launch_main<4, (DEF & 3)>(st, P, T); break;
+            }
+        } else {
+            switch (P.NW) {
+                case 1: e = launch_main<1, 0>(st, P, T); break;
+                case 2: e = launch_main<2, 0>(st, P, T); break;
+                default: e = launch_main<4, 0>(st, P, T); break;
+            }
+        }
+    }
+    if (e != hipSuccess) return false;
+    if (P.n_red) {
+        GFT_LAUNCH(k_conv_reduce, dim3(P.n_red, T.nb), dim3(256), 0, st, T, P.n_red);
+    }
+    return true;
+}
+
+// Does the product take the peel?  Structural conditions: rank 3, the whole slab range, operands as large as the result
+// on every axis, both lane axes whole 8-row tiles (at least two), the pipelined full-extent kernel on the 8x8 lane
+// tile.  Auto mode adds the size threshold: the leftover products' batch axis (n / 8 tiles) must fill the eight lanes
+// of its lane-tile axis, and the two extra launches and their partial slabs must be worth the masks they remove
+// (PEEL_MIN_EXTENT, PEEL_MIN_INNER: profiles/r07/tiled_peel_sweep.txt).
+bool peel_applies(const ConvArgs& a) {
+    const int mode = tiled_peel_mode();
+    if (mode == 0) return false;
+    if (a.nd != 3 || a.slab_axis != 0 || a.slab_lo != 0 || a.slab_hi != a.zs[0]) return false;
+    if (a.j0_min || a.j0_excl || a.j0_desc) return false;
+    for (int i = 0; i < 3; ++i)
+        if (a.xs[i] != a.zs[i] || a.ys[i] != a.zs[i]) return false;
+    const unsigned n0 = a.zs[0], n1 = a.zs[1];
+    if (n0 % 8 || n1 % 8 || n0 < 16 || n1 < 16 || a.zs[2] > 128) return false;
+    if ((a.variant & ~4) != 3) return false;
+    TiledArgs T;
+    std::memset(&T, 0, sizeof(T));
+    T.x0 = T.y0 = T.z0 = n0;
+    T.x1 = T.y1 = T.z1 = n1;
+    if (pick_lane_tile(T) != 3) return false;
+    return mode == 1 || (n0 >= PEEL_MIN_EXTENT && n1 >= PEEL_MIN_EXTENT && a.zs[2] >= PEEL_MIN_INNER);
+}
+
+// A peeled product  z (+)= x (*) y  of full n0 x n1 x nI operands on the 8x8 lane tile.  With a = k0 / 8, b = k1 / 8 a
+// term pair (j0, k0) of axis 0 is ALIGNED if j0 <= 8a and a LEFTOVER if 8a < j0 <= k0 (the 28-pair triangle of tile a),
+// likewise on axis 1, and the term set aligned x aligned  u  leftover0 x all1  u  aligned0 x leftover1 is computed as
+//   M    the plain kernel with every tile's step range cut to j0 <= 8a, j1 <= 8b: no masked lane;
+//   L0   rank 4 (u = m, k0c = a, k1c = k1, k2):  z[8a+1+m][k1] += sum_{ju <= m} y[ju][j1] x[8a+1+m-ju][k1-j1] — the
+//        scalar operand is y's first seven slabs as they stand, the window operand the gathered slabs of x; u is the
+//        wave-uniform axis (no masks), the tile index a a pure batch axis;
+//   L1   rank 4 (u = m, k0c = b, k1c = k0, k2):  z[k0][8b+1+m] += sum_{ju <= m, j} y[j][ju] x[k0-j][8b+1+m-ju] with the
+//        aligned restriction k0 - j <= 8 (k0 / 8) as a per-lane limit on the window row (TiledArgs::lim1).
+// One stream, fixed order (pack, M and its reduce, L0 and its reduce, L1 and its reduce): deterministic.  All three carry
+// the same guard, so a product flagged non-finite is left to the caller's guarded reference-order launch as a whole.
+// Workspace: [partial slabs, shared by the three][packed x][packed y][L0 window][L1 scalar + slack][L1 window].
+// Returns 1 done (or, for a query, sized), 0 a launch failed, -1 the peel cannot be planned or does not fit the workspace
+// it was given — nothing has been launched and the caller takes the plain plan.
+int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, void* ws, size_t ws_bytes,
+                     size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded) {
+    const unsigned n0 = a.zs[0], n1 = a.zs[1], nI = a.zs[2];
+    ConvArgs l0, l1;
+    std::memset(&l0, 0, sizeof(l0));
+    l0.nd = 4;
+    l0.slab_lo = 0;
+    l0.slab_hi = 7;
+    l0.accumulate = 1;
+    l0.variant = a.variant | 128;
+    l1 = l0;
+    const unsigned s0x[4] = {7, 1, n1, nI}, s0y[4] = {7, n0 / 8, n1, nI}, s1x[4] = {7, 1, n0, nI}, s1y[4] = {7, n1 / 8, n0, nI};
+    for (int i = 0; i < 4; ++i) {
+        l0.xs[i] = s0x[i]; l0.ys[i] = l0.zs[i] = s0y[i];
+        l1.xs[i] = s1x[i]; l1.ys[i] = l1.zs[i] = s1y[i];
+    }
+    PeelSpec pm, p0, p1;
+    pm.role = 1; pm.cut = 3;
+    p0.role = 2; p0.zsU = (size_t)n1 * nI; p0.zs0 = 8 * p0.zsU; p0.zs1 = nI; p0.zoff = p0.zsU;
+    p1.role = 3; p1.lim1 = 1; p1.zsU = nI; p1.zs0 = 8 * (size_t)nI; p1.zs1 = (size_t)n1 * nI; p1.zoff = nI;
+    Plan PM, P0, P1;  // copies: building one plan may empty the cache the others came from (then once more, from an empty arena)
+    for (int attempt = 0;; ++attempt) {
+        const unsigned long long gen = plan_generation();
+        const Plan* q = cached_plan(a, pm, st);
+        if (!q) return -1;
+        PM = *q;
+        if (!(q = cached_plan(l0, p0, st))) return -1;
+        P0 = *q;
+        if (!(q = cached_plan(l1, p1, st))) return -1;
+        P1 = *q;
+        if (gen == plan_generation()) break;
+        if (attempt) return -1;
+    }
+    const TiledArgs& B = PM.base;
+    if (B.tsh != 3) return -1;
+    const size_t rows = (size_t)n0 * n1, n8 = B.nx8;
+    const size_t slots = std::max(PM.n_slots, std::max(P0.n_slots, P1.n_slots));
+    const size_t b_slots = slots * B.nb * 512 * sizeof(double);
+    const bool inplace = a.operands_slack && n8 == nI && !((uintptr_t)y & 15) && !((uintptr_t)x & 7);
+    const bool pack_y = !inplace && (n8 != nI || ((uintptr_t)y & 15));
+    const size_t b_xp = (rows * n8 + 8) * sizeof(double), b_yp = rows * n8 * sizeof(double);
+    const size_t e_w0 = (size_t)7 * (n0 / 8) * n1 * n8, e_s1 = (size_t)7 * n0 * n8, e_w1 = (size_t)7 * (n1 / 8) * n0 * n8;
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_xp = al(b_slots), o_yp = o_xp + al(b_xp), o_w0 = o_yp + al(b_yp), o_s1 = o_w0 + al(e_w0 * sizeof(double)),
+                 o_w1 = o_s1 + al((e_s1 + 8) * sizeof(double)), need = o_w1 + al(e_w1 * sizeof(double)) + 256;
+    if (ws && ws_bytes < need) return -1;  // (sized by a query that could not plan the peel)
+    if (ws_needed) *ws_needed = need;
+    if (guarded) *guarded = !inplace;
+    if (!ws) return 1;  // query
+
+    char* wb = (char*)ws;
+    double *xp = (double*)(wb + o_xp), *yp = (double*)(wb + o_yp), *w0 = (double*)(wb + o_w0), *s1 = (double*)(wb + o_s1),
+           *w1 = (double*)(wb + o_w1);
+    TiledArgs T = B;
+    T.ws = (double*)wb;
+    if (inplace) {
+        T.xp = x;
+        T.yp = y;
+        T.guard = nullptr;
+        T.guard_epoch = 0;
+    } else {
+        const size_t tot = rows * n8 + (pack_y ? rows * n8 : rows * nI);
+        GFT_LAUNCH(k_prep_operands, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, x, xp, rows, nI,
+                   (unsigned)n8, y, pack_y ? yp : nullptr, rows, nI, (unsigned)n8, nf_flag, nf_epoch);
+        T.xp = xp;
+        T.yp = pack_y ? yp : y;
+        T.guard = nf_flag;
+        T.guard_epoch = nf_epoch;
+    }
+    {
+        const size_t tot = e_w0 + e_s1 + e_w1;
+        GFT_LAUNCH(k_pack_peel, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 4096)), dim3(256), 0, st, x, y, w0, s1, w1, n0, n1,
+                   nI, (unsigned)n8);
+    }
+    T.z = z;
+    T.xcd_remap = ((a.variant & 4) && (PM.n_wg % 8 == 0)) ? 1u : 0u;
+    if (!launch_plan(st, PM, T, a.variant)) return 0;
+    TiledArgs T0 = P0.base, T1 = P1.base;
+    T0.ws = T1.ws = T.ws;
+    T0.z = T1.z = z;
+    T0.guard = T1.guard = T.guard;
+    T0.guard_epoch = T1.guard_epoch = T.guard_epoch;
+    T0.xp = T.yp;  // y's first seven slabs, in the layout the main launch reads them in (the eighth is the slack)
+    T0.yp = w0;
+    T1.xp = s1;
+    T1.yp = w1;
+    T0.xcd_remap = ((a.variant & 4) && (P0.n_wg % 8 == 0)) ? 1u : 0u;
+    T1.xcd_remap = ((a.variant & 4) && (P1.n_wg % 8 == 0)) ? 1u : 0u;
+    return launch_plan(st, P0, T0, l0.variant) && launch_plan(st, P1, T1, l1.variant) ? 1 : 0;
+}
+
+}  // namespace
+
+void tiled_set_peel(int mode) { tiled_peel_mode() = mode < 0 ? -1 : (mode ? 1 : 0); }
+
+bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a_in, void* ws,
+                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded, bool* peeled) {
+    ConvArgs a = a_in;
+    if (a.variant < 0) a.variant = GFT_TILED_DEFAULT_VARIANT;
+    if (a.nd >= 2 && a.nd <= 4) {  // the pipelined fast path (bits 1|2) needs x and y to span every chunk of z's inner axis
+        unsigned nb = (a.zs[a.nd - 1] + 7) / 8;
+        if ((a.xs[a.nd - 1] + 7) / 8 < nb || (a.ys[a.nd - 1] + 7) / 8 < nb) {
+            static const bool compact_fast = true;
+            if (compact_fast && (a.variant & 3) == 3) a.variant = (a.variant & ~0xff) | (a.variant & 7) | 8;  // pipelined path for compact operands
+            else a.variant &= ~3;
+        }
+    }
+    if (peeled) *peeled = false;
+    if (peel_applies(a)) {
+        const int r = conv_tiled_peel(st, x, y, z, a, ws, ws_bytes, ws_needed, nf_flag, nf_epoch, guarded);
+        if (r >= 0) {
+            if (peeled) *peeled = r == 1;
+            return r == 1;
+        }
+        // (the peel could not be planned: the plain plan below, for the query and for the launch alike)
+    }
+    const Plan* pp = cached_plan(a, PeelSpec(), st);
+    if (!pp) return false;
+    const Plan& P = *pp;
     const TiledArgs& B = P.base;
     // workspace: [partial slabs][packed x][packed y]
     size_t b_slots = (size_t)P.n_slots * B.nb * 512 * sizeof(double);
@@ -1088,52 +1391,7 @@ bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z,
     }
     T.z = z;
     T.xcd_remap = ((a.variant & 4) && (P.n_wg % 8 == 0)) ? 1u : 0u;
-    hipError_t e = hipSuccess;
-    constexpr int DEF = GFT_TILED_DEFAULT_VARIANT;
-    int variant = a.variant;
-    if (variant & 8) {  // compact operands, pipelined
-        switch (P.NW) {
-            case 1: e = launch_main<1, 11>(st, P, T); break;
-            case 2: e = launch_main<2, 11>(st, P, T); break;
-            case 4: e = launch_main<4, 11>(st, P, T); break;
-            default: e = launch_main<8, 11>(st, P, T); break;
-        }
-    } else if (P.NW == 8) {
-        switch (variant) {
-            case 0: case 4: e = launch_main<8, 0>(st, P, T); break;
-            case 1: e = launch_main<8, 1>(st, P, T); break;
-            case 3: e = launch_main<8, 3>(st, P, T); break;
-            case 7: e = launch_main<8, 3>(st, P, T); break;  // 3 + XCD-contiguous ranges (runtime flag)
-#ifdef GFT_TILED_DIAG
-            case 17: e = launch_main<8, 17>(st, P, T); break;
-            case 33: e = launch_main<8, 33>(st, P, T); break;
-            case 49: e = launch_main<8, 49>(st, P, T); break;
-            case 65: e = launch_main<8, 65>(st, P, T); break;
-            case 113: e = launch_main<8, 113>(st, P, T); break;
-#endif
-            default: return false;
-        }
-    } else {
-        if (variant != 0 && variant != 4 && variant != DEF && variant != (DEF & 3)) return false;
-        if (variant & 1) {
-            switch (P.NW) {
-                case 1: e = launch_main<1, (DEF & 3)>(st, P, T); break;
-                case 2: e = launch_main<2, (DEF & 3)>(st, P, T); break;
-                default: e = launch_main<4, (DEF & 3)>(st, P, T); break;
-            }
-        } else {
-            switch (P.NW) {
-                case 1: e = launch_main<1, 0>(st, P, T); break;
-                case 2: e = launch_main<2, 0>(st, P, T); break;
-                default: e = launch_main<4, 0>(st, P, T); break;
-            }
-        }
-    }
-    if (e != hipSuccess) return false;
-    if (P.n_red) {
-        GFT_LAUNCH(k_conv_reduce, dim3(P.n_red, T.nb), dim3(256), 0, st, T, P.n_red);
-    }
-    return true;
+    return launch_plan(st, P, T, a.variant);
 }
 
 }  // namespace gft

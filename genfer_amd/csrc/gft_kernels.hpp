@@ -439,8 +439,11 @@ enum SumMode { SUM_SEQ = 0, SUM_UNROLL8 = 1, SUM_WAVE = 2 };
 // does not produce) and the caller's guarded reference-order launch computes z instead — no host round trip.
 // `guarded` (optional): set to false when the launch read its operands in place — no zero padding, hence no verdict and
 // no guarded fallback launch needed (ConvArgs::operands_slack; round 4) — true otherwise.
+// `peeled` (optional): set to true when the product ran as the aligned main part plus the two leftover products of its
+// diagonal lane triangles (rank 3, full extents; "tiled_peel", tiled_set_peel).
 bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, void* ws,
-                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded = nullptr);
+                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded = nullptr,
+                    bool* peeled = nullptr);
 
 // Inner-axis splitting helpers for the tiled kernel (see gft_conv_tiled.hip): zero-pad rows to `plen`, and the
 // overlap-add that folds the (Pz, 2B-1) pieces of every row back into a row of zI coefficients.
@@ -455,6 +458,7 @@ size_t staged_scratch_bytes();  // bytes the grow-only kernel workspaces of gft_
 void staged_release_scratch();  // frees the register-blocked interval product's row-flag scratch (gft_shutdown)
 void dwf_release_orders();  // frees the row wavefront's cached claim-order tables (gft_shutdown)
 void tiled_set_lane_tile(int tsh);  // 0 = planner's choice, 3..6 = force T1 = 1 << tsh lanes along k1 (tests, A/B)
+void tiled_set_peel(int mode);      // -1 = by size (default), 0 = never, 1 = wherever the structural conditions hold (tests, A/B)
 void tiled_pad_rows_f64(hipStream_t st, const double* in, double* out, size_t rows, unsigned len, unsigned P, unsigned B);
 void tiled_fold_rows_f64(hipStream_t st, const double* zt, double* z, size_t rows, size_t row_lo, size_t row_hi, unsigned Pz,
                          unsigned B, unsigned zI, int accumulate, const unsigned* guard, unsigned epoch);

@@ -176,8 +176,10 @@
                 unsigned* flag = R.d_flag + 2;
                 bool guarded = true;
                 if (!split) {
-                    if (!conv_tiled_f64(R.stream, tx, ty, tz, ash, R.conv_ws, R.conv_ws_bytes, &need, flag, R.nf_epoch, &guarded))
+                    bool peeled = false;
+                    if (!conv_tiled_f64(R.stream, tx, ty, tz, ash, R.conv_ws, R.conv_ws_bytes, &need, flag, R.nf_epoch, &guarded, &peeled))
                         throw Error("tiled convolution launch failed");
+                    if (peeled) R.stats_peeled++;
                 } else {
                     const ConvArgs& a = ash;  // the (possibly shifted) problem; the guarded fallback below uses the original
                     const double* xsrc = tx;

@@ -115,7 +115,9 @@ int gft_set_conv_mode(int mode);
  * register-blocked rows kernel; negative: never), "conv_rb_pairs" (the reference-order product as row-pair sums: 0 never, 1 by
  * size, 2 whenever it applies, negative: the default), "conv_rb_pairs_cap" (bytes of row sums that form may hold at a time;
  * default 2 GiB), "conv_rb_pairs_lanes" (its slab ranges on two lanes: 0 never, 1 always, negative: the default rule),
- * "tiled_tile" (3..6 force the tiled product's lane tile 8x8 .. 1x64; 0: the planner's choice), "dist_min_macs" (smallest
+ * "tiled_tile" (3..6 force the tiled product's lane tile 8x8 .. 1x64; 0: the planner's choice), "tiled_peel" (the peel of
+ * the diagonal lane triangles of rank-3 products of full operands: -1 by size, 0 never, 1 wherever the structure allows;
+ * gft_op_stats_ex slot 7 counts the peeled products), "dist_min_macs" (smallest
  * general product gft_mul shards over the GPUs of gft_dist_init), "dist_event_slot", "series_form" (gft_series_last_form).
  * TEST KNOBS: "debug_fail_next_launch" (1: the next kernel launch requests 1 MB of LDS and fails — on the launch thread; the
  * failure is reported by the next gft_synchronize / value inspection), "trace_lq_report". */
