@@ -244,6 +244,30 @@ struct Runtime {
     int conv_variant = -1;
     void* conv_ws = nullptr;
     size_t conv_ws_bytes = 0;
+    // The tiled product's workspace holds at least `need` bytes.  Grown geometrically (supports, and with them the
+    // workspaces, grow statement by statement); a refused geometric request is retried with the exact size.
+    void ensure_conv_ws(size_t need) {
+        if (need <= conv_ws_bytes) return;
+        size_t want = std::max<size_t>(std::max(need, std::min<size_t>(2 * conv_ws_bytes, (size_t)1 << 32)), (size_t)8 << 20);
+        if (conv_ws) HIP_OK(hipFree(conv_ws));
+        conv_ws = nullptr;
+        conv_ws_bytes = 0;
+        if (hipMalloc(&conv_ws, want) != hipSuccess) {
+            (void)hipGetLastError();
+            want = need;
+            HIP_OK(hipMalloc(&conv_ws, want));
+        }
+        conv_ws_bytes = want;
+    }
+    // Opens the next tiled product's non-finite verdict: a fresh nf_epoch (the flag word is cleared when the stamp wraps
+    // around) and the word, d_flag[2], that the packing / scan kernels raise to it.
+    unsigned* next_nf_epoch() {
+        if (++nf_epoch == 0) {
+            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(d_flag + 2), 0, 1, stream));
+            nf_epoch = 1;
+        }
+        return d_flag + 2;
+    }
     // size-threshold dispatch: an operation whose operands are all host-resident runs on the host
     // tier (gft_host.hpp) if its result has at most host_max_elems elements (and, for a general product, at most
     // host_max_macs multiply-adds); 0 = everything on the device.  Crossovers measured with tools/xover_host.py.

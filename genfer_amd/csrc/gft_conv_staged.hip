@@ -1275,7 +1275,6 @@ static PairLanes& pair_lanes() {
 template <class E>
 static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const double* y, size_t yp, double* z, size_t zp, const ConvArgs& a,
                          bool pairs_only = false, double pairs_max_macs = 1e300) {
-    static const int on = 1;
     const int nd = a.nd;
     if (nd < 2 || nd > 4) return false;
     if (a.accumulate || a.j0_min || a.j0_excl || a.j0_desc || !a.inner_from_zero || a.guard) return false;
@@ -1339,10 +1338,8 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
         g.pitch = E::W * g.n8 + 2;
         // 16 waves per CU (the kernel holds <= 128 VGPRs): two workgroups of 8 where two tiles fit the LDS, else one of 16
         g.NW = (size_t)64 * g.pitch * sizeof(double) * 2 + 1024 <= 160 * 1024 ? 8u : 16u;
-        static const unsigned nw_env = (unsigned)(0);
-        if (nw_env) g.NW = nw_env;
-        static const unsigned xch_env = 8;  // x rows per phase-1 workgroup (sweep in profiles/r04/interval_pairs_sweep.txt: 4 .. 12 equal, 32 loses 10 % to the last round of workgroups)
-        g.xch = xch_env;
+        constexpr unsigned PAIR_XCH = 8;  // x rows per phase-1 workgroup (sweep in profiles/r04/interval_pairs_sweep.txt: 4 .. 12 equal, 32 loses 10 % to the last round of workgroups)
+        g.xch = PAIR_XCH;
         // (small products: fewer x rows per workgroup until there are ~1000 workgroups — half of the (tile, chunk) grid is
         // outside the triangle)
         while (g.xch > 1 && (unsigned long long)g.yU * g.tiles0 * g.tiles1 * ((xrows + g.xch - 1) / g.xch) < 2048ull) g.xch /= 2;
@@ -1468,7 +1465,7 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
                     if (hipFuncSetAttribute((const void*)k_pair_sums<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) (void)hipGetLastError();
                     attr = true;
                 }
-                static const unsigned cw_env = (unsigned)(64);
+                constexpr unsigned COLLECT_W = 64;  // threads (output columns) per k_pair_collect workgroup
                 // (checked for every range BEFORE the first launch: a false return promises that nothing was launched)
                 std::vector<PairArgs> gs;
                 std::vector<dim3> grids;
@@ -1545,7 +1542,7 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
                         if (E::W == 1 && n2 >= 64 && n2 % 2 == 0 && !((uintptr_t)z & 15))  // (shorter rows: too few threads per row — 32^3 0.104 -> 0.113 ms; 80^3 7.7 -> 7.1)
                             GFT_LAUNCH(k_pair_collect2_f64, dim3((unsigned)rows[i], (n2 / 2 + 63) / 64), dim3(64), 0, ls, (const double*)wp, z, q);
                         else
-                            GFT_LAUNCH(k_pair_collect<E>, dim3((unsigned)rows[i], (n2 + cw_env - 1) / cw_env), dim3(cw_env), 0, ls, (const double*)wp, z, zp, q);
+                            GFT_LAUNCH(k_pair_collect<E>, dim3((unsigned)rows[i], (n2 + COLLECT_W - 1) / COLLECT_W), dim3(COLLECT_W), 0, ls, (const double*)wp, z, zp, q);
                     }
                     if (use_lanes) {  // join: the product's stream waits for both lanes
                         hipEvent_t e0 = L.join[0], e1 = L.join[1];
@@ -1566,7 +1563,7 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
     if constexpr (!E::HAS_POS) {
         return false;  // (f64: the row-pair form only)
     } else {
-    if (!on || rb_min_macs < 0.0 || macs < rb_min_macs || n2 < 64) return false;  // (rows shorter than 64: the row-pair form only)
+    if (rb_min_macs < 0.0 || macs < rb_min_macs || n2 < 64) return false;  // (rows shorter than 64: the row-pair form only)
     RbArgs g;
     std::memset(&g, 0, sizeof(g));
     g.no = nd - 1;
@@ -1574,14 +1571,13 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
     g.ntiles = (n2 + 15) / 16;
     g.n2 = n2;
     g.nx2 = nx2;
-    static const unsigned rg_env = (unsigned)(0);
     g.ntw = (g.ntiles + 1) / 2;
     // groups cut the longest chain of a workgroup (what bounds mid sizes) but leave one workgroup per CU with nothing to
     // overlap its staging with; two groups once the workgroups outnumber the CUs ~6 times (128^3: 257 ms with 2, 299 with 4;
     // 96^3: 77 with 2, 68 with 4)
     unsigned long long nblk = g.n_pg;
     for (int ax = 0; ax < P; ++ax) nblk *= ax == 0 ? (a.slab_hi - a.slab_lo) : a.zs[ax];
-    const unsigned want = rg_env ? rg_env : (nblk >= 1536 ? 2u : 4u);
+    const unsigned want = nblk >= 1536 ? 2u : 4u;
     g.tb = std::max(1u, std::min(want, 16u / g.ntw));
     auto lds_of = [&](unsigned tb) {
         return ((size_t)tb * 2 * n2 + 16 + (size_t)(tb + RB_ROWS - 1) * (2 * nx2 + 2) + (2 * tb + RB_ROWS + 8 + 7) / 8 + (size_t)(tb - 1) * g.ntw * 512) *
@@ -1654,7 +1650,6 @@ bool conv_staged(hipStream_t st, const double* x, size_t xp, const double* y, si
     // S = 2 (planes of the last two axes) while the planes are small enough for >= 4 workgroups per CU;
     // larger planes would leave one fat workgroup per CU with a triangular load => rows (S = 1) instead,
     // unless the rows are too short to fill a wave.
-    static const int force_s = 0;
     auto fits = [&](int s, size_t budget) {
         unsigned sxa = s == 2 ? a.xs[nd - 2] : 1, sya = s == 2 ? a.ys[nd - 2] : 1;
         size_t xcap = (size_t)sxa * a.xs[nd - 1], ycap = (size_t)sya * (s == 2 ? a.zs[nd - 1] : a.ys[nd - 1]);
@@ -1663,9 +1658,7 @@ bool conv_staged(hipStream_t st, const double* x, size_t xp, const double* y, si
     for (int i = 0; i < nd; ++i)
         if (a.xs[i] > a.zs[i] || a.ys[i] > a.zs[i]) return false;  // operands are pre-truncated; be safe
     int S = 0;
-    if (force_s == 1 || force_s == 2) {
-        if (force_s <= nd && fits(force_s, LDS_MAX)) S = force_s;
-    } else if (nd >= 2 && fits(2, 40 * 1024)) S = 2;
+    if (nd >= 2 && fits(2, 40 * 1024)) S = 2;
     else if (a.zs[nd - 1] >= 32 && fits(1, LDS_MAX)) S = 1;
     else if (nd >= 2 && fits(2, LDS_MAX)) S = 2;
     else if (fits(1, LDS_MAX)) S = 1;
@@ -1712,9 +1705,9 @@ bool conv_staged(hipStream_t st, const double* x, size_t xp, const double* y, si
     chunks = (span + threads - 1) / threads;
     g.chunks = (unsigned)chunks;
     // row groups (see the kernel): as many as the batch has rows and the block has room for
-    static const unsigned rw_cap = (unsigned)(1024);
+    constexpr unsigned RW_CAP = 1024;
     if (S == 1 && a.inner_from_zero && g.batch > 1) {
-        unsigned rw = std::min<unsigned>(std::min<unsigned>(g.batch, 1024u / threads), rw_cap);
+        unsigned rw = std::min<unsigned>(std::min<unsigned>(g.batch, 1024u / threads), RW_CAP);
         // Row groups shorten the serial chain of ONE block (a recurrence step has a handful of blocks and nothing else to
         // run); a product with thousands of blocks is better served by more, smaller blocks per CU — their staging,
         // summing and adding phases interleave instead of 16 waves idling through them together (interval 128^3:

@@ -24,14 +24,17 @@
 //                       of every tile runs as two small rank-4 products whose batch axis is the tile index
 //                       (conv_tiled_peel below)
 //   load balance        stream-K: the linearised (tile, ju, j0, j1) step space is cut into equal
-//                       contiguous ranges, one per resident workgroup (2 per CU).  Tiles covered by a
+//                       contiguous ranges, 1, 2, 4 or 8 per resident workgroup slot (as many as leave a
+//                       range >= ~190 steps; fewer for small products, cut_ranges below).  Tiles covered by a
 //                       single range are written straight to z; split tiles go through partial slabs
 //                       in a workspace and a fixed-order reduce kernel => deterministic results.
 //
 // Numerics: explicit fma (one rounding per MAC) and a different summation order than the
-// reference => 1e-10 relative parity, not bit-exact (the reference-order kernel in
-// gft_kernels.hip is the bit-exact path).  Operands must be finite (zero padding times inf would
-// create NaNs the reference does not produce); the caller checks and falls back otherwise.
+// reference => 1e-10 relative parity, not bit-exact (the reference-order kernels — the LDS-staged and row-pair
+// forms in gft_conv_staged.hip, k_conv_naive in gft_kernels.hip — are the bit-exact path).  Zero padding times
+// inf / NaN would create NaNs the reference does not produce: k_prep_operands takes the non-finite verdict on the
+// device while it packs (a stamp in the guard word), the tiled kernels then leave z alone and the caller's guarded
+// reference-order launch computes it; operands read in place have no padding and need no verdict (operand_layout).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -695,6 +698,35 @@ __global__ void __launch_bounds__(256) k_fold_rows(const double* __restrict__ zt
 
 // ---- host-side plan ------------------------------------------------------------------------------------
 
+// ConvArgs::variant (gft_set_conv_variant; -1 = GFT_TILED_DEFAULT_VARIANT) is a bit set.  It is decoded ONCE, at the top
+// of conv_tiled_f64, and everything below reads the fields.
+struct Variant {
+    bool fast;       // 1: software-pipelined fast path for full inner extents
+    bool b128;       // 2: ds_read_b128 window loads (even LDS row pitch with P1/2 odd)
+    bool xcd;        // 4: XCD-contiguous ranges (the run-time flag TiledArgs::xcd_remap, no instantiation of its own)
+    bool compact;    // 8: the pipelined path for compact operands (VAR 11); set by the decoder from the shapes
+    bool peel;       // 128: leftover products of a peeled product (VAR 131); set by conv_tiled_peel
+    unsigned other;  // 16, 32, 64: timing-only diagnostics (-DGFT_TILED_DIAG, see the VAR bits above); the rest: nothing
+};
+static_assert((GFT_TILED_DEFAULT_VARIANT & 3) == 3, "only the pipelined b128 kernel (VAR 3) is instantiated for every NW");
+// `compact_operands`: x or y spans fewer chunks than z's inner axis, but the fast path (1 | 2) needs both to span every one
+Variant decode_variant(int variant, bool compact_operands) {
+    if (variant < 0) variant = GFT_TILED_DEFAULT_VARIANT;
+    Variant V = {bool(variant & 1), bool(variant & 2), bool(variant & 4), bool(variant & 8), bool(variant & 128),
+                 unsigned(variant & ~(1 | 2 | 4 | 8 | 128))};
+    if (compact_operands && V.fast && V.b128) V = {true, true, V.xcd, true, false, 0};  // pipelined path for compact operands
+    else if (compact_operands) V.fast = V.b128 = false;
+    return V;
+}
+// The VAR of k_conv_tiled that a decoded variant selects on NW waves, or a value that launch_plan does not know.  VAR 131,
+// 11, 3 and 0 exist for every NW; the pipelined kernel without b128 (VAR 1) and the diagnostics for NW = 8 only.
+int pick_var(const Variant& V, unsigned NW) {
+    if (V.peel) return 131;
+    if (V.compact) return 11;
+    if (V.fast == V.b128 && !V.other) return V.fast ? 3 : 0;
+    return (NW == 8 && V.fast && !V.b128 && !V.xcd) ? 1 + (int)V.other : -1;
+}
+
 struct PlanKey {
     unsigned v[19];
     bool operator<(const PlanKey& o) const { return std::memcmp(v, o.v, sizeof(v)) < 0; }
@@ -738,6 +770,22 @@ std::map<PlanKey, Plan>& plan_cache() {
     return c;
 }
 
+unsigned long long& plan_generation() {  // bumped whenever the plan cache is emptied (cached Plan copies are stale then)
+    static unsigned long long g = 0;
+    return g;
+}
+
+// Drops every cached plan and rewinds the table arena (plans are cheap to rebuild): when the arena wraps, every cached
+// plan's slice may be overwritten from then on; and when the cache reaches its bound.
+void reset_plan_cache(hipStream_t st) {
+    (void)hipStreamSynchronize(st);  // pending uploads still read the host mirror
+    for (auto& kv : plan_cache())
+        if (kv.second.d_tables) (void)hipFree(kv.second.d_tables);
+    plan_cache().clear();
+    plan_generation()++;
+    arena().head = 0;
+}
+
 int num_cus() {
     static int n = 0;
     if (!n) {
@@ -750,19 +798,12 @@ int num_cus() {
     return n;
 }
 
-static void assign_blocks(TiledArgs& T, unsigned NW);
-
 // What distinguishes the three plans of a peeled product from a plain one (all zero: plain).
 struct PeelSpec {
     unsigned role = 0;                      // 0 plain, 1 the aligned main part M, 2 / 3 the leftover products L0 / L1
     unsigned cut = 0, lim1 = 0;             // TiledArgs::cut, TiledArgs::lim1
     size_t zsU = 0, zs0 = 0, zs1 = 0, zoff = 0;  // output strides (role 2 / 3; dense otherwise)
 };
-
-unsigned long long& plan_generation() {  // bumped whenever the plan cache is emptied (cached Plan copies are stale then)
-    static unsigned long long g = 0;
-    return g;
-}
 
 int& tiled_force_tsh() {  // A/B and test knob (GFT_TILED_TSH / "tiled_tile"): 3..6 forces the lane tile 8x8 .. 1x64
     static int v = 0;
@@ -800,11 +841,55 @@ unsigned pick_lane_tile(const TiledArgs& T) {
     return best_tsh;
 }
 
-bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) {
+// Which output blocks each wave of a workgroup accumulates (at most two: 16 accumulator VGPR pairs each).
+// Block c costs one 8x8x8 chunk product per (x chunk, y chunk) pair that lands in it, i.e. c + 1 for full
+// operands.  The classic pairing (c, nb-1-c) gives every ACTIVE wave the same load, but when nb < 2*NW the
+// active waves sit unevenly on the CU's four SIMDs (wave w runs on SIMD w % 4): nb = 10 keeps two busy waves on
+// SIMD 0 and one on the others, and the whole CU waits for SIMD 0 — measured 62% of the nb = 16 rate.
+// Longest-processing-time assignment over SIMDs instead, then over the waves of the SIMD.
+void assign_blocks(TiledArgs& T, unsigned NW) {
+    for (int w = 0; w < 8; ++w) T.blk1[w] = T.blk2[w] = 0xff;
+    // (classic pairs are only balanced when every block c costs c + 1: compact operands — the piece-split products'
+    // untruncated inner axis costs min(c + 1, nxc, nyc, nb - c) — always take the LPT assignment)
+    const bool full = T.nxc >= T.nb && T.nyc >= T.nb;
+    if (full && (2 * NW == T.nb || NW < 4)) {
+        for (unsigned w = 0; w < NW; ++w) {
+            unsigned c1 = w, c2 = T.nb - 1 - w;
+            if (c1 < T.nb && c1 <= c2) T.blk1[w] = (unsigned char)c1;
+            if (c2 < T.nb && c2 > c1) T.blk2[w] = (unsigned char)c2;
+        }
+        return;
+    }
+    auto cost = [&](unsigned c) {
+        unsigned n = 0;
+        for (unsigned xc = 0; xc <= c && xc < T.nxc; ++xc)
+            if (c - xc < T.nyc) n++;
+        return n;
+    };
+    unsigned simd_load[4] = {0, 0, 0, 0}, wave_load[8] = {0}, wave_cnt[8] = {0};
+    for (unsigned i = 0; i < T.nb; ++i) {
+        unsigned c = T.nb - 1 - i;  // heaviest first
+        int best = -1;
+        for (unsigned w = 0; w < NW; ++w) {
+            if (wave_cnt[w] >= 2) continue;
+            if (best < 0) { best = (int)w; continue; }
+            unsigned sb = simd_load[best % 4], sw = simd_load[w % 4];
+            if (sw < sb || (sw == sb && wave_load[w] < wave_load[best])) best = (int)w;
+        }
+        if (wave_cnt[best] == 0) T.blk1[best] = (unsigned char)c;
+        else T.blk2[best] = (unsigned char)c;
+        wave_cnt[best]++;
+        wave_load[best] += cost(c);
+        simd_load[best % 4] += cost(c);
+    }
+}
+
+// Plan step 1: the canonical form z[u][k0][k1][k2] of the problem — u is wave-uniform, (k0, k1) are the lane axes, k2
+// the register axis — with its chunk counts, LDS pitch, lane tile, output strides and the waves' output blocks.
+// false: the tiled kernel does not take the shape.
+bool canonicalise(const ConvArgs& a, const Variant& V, const PeelSpec& ps, Plan& P) {
     TiledArgs& T = P.base;
     std::memset(&T, 0, sizeof(T));
-    // canonical form z[u][k0][k1][k2]: u is wave-uniform, (k0, k1) are the lane axes, k2 the register axis
-    unsigned slab_axis;  // canonical axis the caller's slab range applies to
     if (a.slab_axis < 0 || a.slab_axis >= a.nd - 1) return false;
     if (a.nd == 2) {  // rows x inner: no k0 axis — the lane tile becomes 1 x 64 rows
         T.xU = T.yU = T.zU = 1;
@@ -812,22 +897,21 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
         T.x1 = a.xs[0]; T.xI = a.xs[1];
         T.y1 = a.ys[0]; T.yI = a.ys[1];
         T.z1 = a.zs[0]; T.zI = a.zs[1];
-        slab_axis = 2;
+        T.slab_axis = 2;
     } else if (a.nd == 3) {
         T.xU = T.yU = T.zU = 1;
         T.x0 = a.xs[0]; T.x1 = a.xs[1]; T.xI = a.xs[2];
         T.y0 = a.ys[0]; T.y1 = a.ys[1]; T.yI = a.ys[2];
         T.z0 = a.zs[0]; T.z1 = a.zs[1]; T.zI = a.zs[2];
-        slab_axis = 1 + (unsigned)a.slab_axis;
+        T.slab_axis = 1 + (unsigned)a.slab_axis;
     } else if (a.nd == 4) {
         T.xU = a.xs[0]; T.x0 = a.xs[1]; T.x1 = a.xs[2]; T.xI = a.xs[3];
         T.yU = a.ys[0]; T.y0 = a.ys[1]; T.y1 = a.ys[2]; T.yI = a.ys[3];
         T.zU = a.zs[0]; T.z0 = a.zs[1]; T.z1 = a.zs[2]; T.zI = a.zs[3];
-        slab_axis = (unsigned)a.slab_axis;
+        T.slab_axis = (unsigned)a.slab_axis;
     } else {
         return false;
     }
-    T.slab_axis = slab_axis;
     if (T.zI > 128 || T.xI > T.zI || T.yI > T.zI) return false;
     if (a.j0_min != 0 || a.j0_excl != 0 || a.j0_desc != 0) return false;  // recurrence steps: reference-order kernel
     T.nx8 = (T.xI + 7) / 8 * 8;
@@ -837,7 +921,7 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
     T.nb = (T.zI + 7) / 8;
     // front padding + pitch: odd (8-byte slots, bijective mod 16/32 for ds_read_b64/read2_b64) or, for the
     // ds_read_b128 variant, even with P1/2 odd (16-byte slots bijective mod 16 for the b128 lane groups)
-    T.P1 = (a.variant & 2) ? T.ny8 + YPAD + 2 : T.ny8 + YPAD + 1;
+    T.P1 = V.b128 ? T.ny8 + YPAD + 2 : T.ny8 + YPAD + 1;
     T.tsh = pick_lane_tile(T);
     // peeled products: the aligned part ends every tile's step range at the tile's first row; the leftover products
     // add into z through their own strides (everything else: dense)
@@ -848,7 +932,6 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
     } else {
         T.zsU = (size_t)T.z0 * T.z1 * T.zI; T.zs0 = (size_t)T.z1 * T.zI; T.zs1 = T.zI; T.zoff = 0;
     }
-    const unsigned TT0 = 64u >> T.tsh, TT1 = 1u << T.tsh;
     T.slab_lo = a.slab_lo;
     T.slab_hi = a.slab_hi;
     T.accumulate = a.accumulate;
@@ -856,20 +939,34 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
     P.NW = npairs <= 1 ? 1 : (npairs <= 2 ? 2 : (npairs <= 4 ? 4 : 8));
     P.lds_bytes = (size_t)64 * T.P1 * sizeof(double);
     assign_blocks(T, P.NW);
+    return true;
+}
 
-    // tiles in (u, a, b) order
+struct PlanTables {  // the host images of a plan's device tables
+    std::vector<TileSeg> segs;
+    std::vector<unsigned> wg_begin;
+    std::vector<RedTile> red;
+    std::vector<unsigned> red_slots;
+    bool slots_consecutive = true;  // every split tile's pieces are consecutive slots: red_slots is not needed
+};
+
+// Plan step 2: the tiles of the slab range in (u, a, b) order, their linearised step space cut into P.n_wg contiguous
+// stream-K ranges (segs, wg_begin), and the reduce list of the tiles that a cut splits (red, red_slots).
+bool cut_ranges(Plan& P, PlanTables& tb) {
+    const TiledArgs& T = P.base;
+    const unsigned TT0 = 64u >> T.tsh, TT1 = 1u << T.tsh;
     struct TileInfo { unsigned u, a, b; unsigned long long steps; };
     std::vector<TileInfo> tiles;
     unsigned u_lo = 0, u_hi = T.zU, a_lo = 0, a_hi = (T.z0 + TT0 - 1) / TT0, b_lo = 0, b_hi = (T.z1 + TT1 - 1) / TT1;
-    if (slab_axis == 0) {
-        u_lo = a.slab_lo;
-        u_hi = a.slab_hi;
-    } else if (slab_axis == 1) {
-        a_lo = a.slab_lo / TT0;
-        a_hi = (a.slab_hi + TT0 - 1) / TT0;
+    if (T.slab_axis == 0) {
+        u_lo = T.slab_lo;
+        u_hi = T.slab_hi;
+    } else if (T.slab_axis == 1) {
+        a_lo = T.slab_lo / TT0;
+        a_hi = (T.slab_hi + TT0 - 1) / TT0;
     } else {
-        b_lo = a.slab_lo / TT1;
-        b_hi = (a.slab_hi + TT1 - 1) / TT1;
+        b_lo = T.slab_lo / TT1;
+        b_hi = (T.slab_hi + TT1 - 1) / TT1;
     }
     unsigned long long S = 0;
     for (unsigned u = u_lo; u < u_hi; ++u)
@@ -889,25 +986,23 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
     // the dispatcher even that out — as many (2, 4, 8) as leave a range >= ~190 steps (128^3: 2312 steps per slot, eight ranges, 27.0 -> 28.7
     // TMAC/s in three alternating runs on one box; 96^3 and 100^3 four, +3 %; 64^3, 81 steps per slot, stays at one: two
     // are neutral, four lose 4 % to the extra partial slabs).
-    static const int wg_mult_env = 0;
     unsigned long long n_wg = (unsigned long long)num_cus() * wg_per_cu;
     const unsigned long long per_slot = S / n_wg;  // steps (one lane tile x one (ju, j0, j1)) per resident slot
     const unsigned long long fit = per_slot / 190;  // ranges of >= ~190 steps
-    n_wg *= wg_mult_env ? (unsigned)wg_mult_env : (fit >= 8 ? 8u : (fit >= 4 ? 4u : (fit >= 2 ? 2u : 1u)));
+    n_wg *= fit >= 8 ? 8u : (fit >= 4 ? 4u : (fit >= 2 ? 2u : 1u));
     // Every range pays a window fill and, if it splits a tile, a 4 KB-per-block partial slab plus its share of the
     // reduction, so small products must not be cut into confetti.  A step costs ~ (chunk pairs + 3) units
     // (pairs = nb(nb+1)/2 8x8x8 chunk products per lane tile, 3 ~ barriers + refill) and the fixed part grows
     // with the row length; ranges get >= ~(64 + 20 nb) units (sweep on MI355X: 24^3 171 -> 50 us,
     // 30^3 91 -> 71 us, 10x10x100 154 -> 92 us per product).
-    static const unsigned long long MIN_UNITS = 64;
+    constexpr unsigned long long MIN_UNITS = 64;
     const unsigned long long step_units = (unsigned long long)T.nb * (T.nb + 1) / 2 + 3;
     const unsigned long long min_steps =
         std::max<unsigned long long>(1, (MIN_UNITS + 20ull * T.nb + step_units / 2) / step_units);
     if (n_wg > S / min_steps) n_wg = std::max<unsigned long long>(1, S / min_steps);
     P.n_wg = (unsigned)n_wg;
 
-    std::vector<TileSeg> segs;
-    std::vector<unsigned> wg_begin(P.n_wg + 1, 0);
+    tb.wg_begin.assign(P.n_wg + 1, 0);
     std::vector<std::vector<unsigned>> tile_slots(tiles.size());
     std::vector<int> tile_direct(tiles.size(), 0);
     unsigned n_slots = 0;
@@ -915,7 +1010,7 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
     unsigned long long tile_start = 0;  // global step index where tile ti starts
     for (unsigned w = 0; w < P.n_wg; ++w) {
         unsigned long long lo = S * w / n_wg, hi = S * (w + 1) / n_wg;
-        wg_begin[w] = (unsigned)segs.size();
+        tb.wg_begin[w] = (unsigned)tb.segs.size();
         unsigned long long pos = lo;
         while (pos < hi) {
             while (pos >= tile_start + tiles[ti].steps) {
@@ -924,63 +1019,45 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
             }
             unsigned long long tend = tile_start + tiles[ti].steps;
             unsigned long long e = hi < tend ? hi : tend;
-            TileSeg sg;
-            sg.u = tiles[ti].u;
-            sg.a = tiles[ti].a;
-            sg.b = tiles[ti].b;
-            sg.step_begin = (unsigned)(pos - tile_start);
-            sg.step_end = (unsigned)(e - tile_start);
+            TileSeg sg = {tiles[ti].u, tiles[ti].a, tiles[ti].b, (unsigned)(pos - tile_start), (unsigned)(e - tile_start), -1};
             if (sg.step_begin == 0 && sg.step_end == tiles[ti].steps) {
-                sg.dest = -1;
                 tile_direct[ti] = 1;
             } else {
                 sg.dest = (int)n_slots;
                 tile_slots[ti].push_back(n_slots);
                 n_slots++;
             }
-            segs.push_back(sg);
+            tb.segs.push_back(sg);
             pos = e;
         }
     }
-    wg_begin[P.n_wg] = (unsigned)segs.size();
-    std::vector<RedTile> red;
-    std::vector<unsigned> red_slots;
-    bool slots_consecutive = true;
+    tb.wg_begin[P.n_wg] = (unsigned)tb.segs.size();
     for (size_t i = 0; i < tiles.size(); ++i) {
         if (tile_direct[i] || tile_slots[i].empty()) continue;
-        RedTile r;
-        r.u = tiles[i].u;
-        r.a = tiles[i].a;
-        r.b = tiles[i].b;
-        r.first = (unsigned)red_slots.size();
-        r.count = (unsigned)tile_slots[i].size();
-        r.slot0 = tile_slots[i][0];
+        RedTile r = {tiles[i].u, tiles[i].a, tiles[i].b, (unsigned)tb.red_slots.size(), (unsigned)tile_slots[i].size(), tile_slots[i][0]};
         for (size_t q = 0; q < tile_slots[i].size(); ++q)
-            if (tile_slots[i][q] != r.slot0 + q) slots_consecutive = false;
-        for (unsigned sl : tile_slots[i]) red_slots.push_back(sl);
-        red.push_back(r);
+            if (tile_slots[i][q] != r.slot0 + q) tb.slots_consecutive = false;
+        for (unsigned sl : tile_slots[i]) tb.red_slots.push_back(sl);
+        tb.red.push_back(r);
     }
-    P.n_red = (unsigned)red.size();
+    P.n_red = (unsigned)tb.red.size();
     P.n_slots = n_slots;
+    return true;
+}
 
-    // All tables of a plan live in one slice of a persistent device arena and are uploaded with ONE stream-ordered
-    // copy from the pinned host mirror of that slice: building a plan for a new shape costs no hipMalloc and no
-    // host synchronisation (Genfer's supports grow statement by statement, so new shapes are the common case).
-    size_t b_segs = segs.size() * sizeof(TileSeg), b_wg = wg_begin.size() * sizeof(unsigned);
-    size_t b_red = red.size() * sizeof(RedTile), b_rs = red_slots.size() * sizeof(unsigned);
+// Plan step 3: all tables of a plan live in one slice of a persistent device arena and are uploaded with ONE
+// stream-ordered copy from the pinned host mirror of that slice: building a plan for a new shape costs no hipMalloc and
+// no host synchronisation (Genfer's supports grow statement by statement, so new shapes are the common case).
+bool upload_tables(Plan& P, const PlanTables& tb, hipStream_t st) {
+    TiledArgs& T = P.base;
+    size_t b_segs = tb.segs.size() * sizeof(TileSeg), b_wg = tb.wg_begin.size() * sizeof(unsigned);
+    size_t b_red = tb.red.size() * sizeof(RedTile), b_rs = tb.red_slots.size() * sizeof(unsigned);
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     size_t total = al(b_segs) + al(b_wg) + al(b_red) + al(b_rs) + 256;
     TableArena& A = arena();
     char *base = nullptr, *hbase = nullptr;
     if (A.ensure() && total <= A.bytes / 4) {
-        if (A.head + total > A.bytes) {  // wrap: every cached plan's slice may be overwritten from now on
-            (void)hipStreamSynchronize(st);   // pending uploads still read the host mirror
-            for (auto& kv : plan_cache())
-                if (kv.second.d_tables) (void)hipFree(kv.second.d_tables);
-            plan_cache().clear();
-            plan_generation()++;
-            A.head = 0;
-        }
+        if (A.head + total > A.bytes) reset_plan_cache(st);  // wrap
         base = A.dev + A.head;
         hbase = A.host + A.head;
         A.head += total;
@@ -998,62 +1075,22 @@ bool build_plan(const ConvArgs& a, const PeelSpec& ps, Plan& P, hipStream_t st) 
         off += al(bytes);
         return d;
     };
-    T.segs = (const TileSeg*)put(segs.data(), b_segs);
-    T.wg_begin = (const unsigned*)put(wg_begin.data(), b_wg);
-    T.red = (const RedTile*)put(red.data(), b_red);
-    T.red_slots = (const unsigned*)put(red_slots.data(), b_rs);
-    if (slots_consecutive) T.red_slots = nullptr;  // k_conv_reduce derives the slots from RedTile::slot0
+    T.segs = (const TileSeg*)put(tb.segs.data(), b_segs);
+    T.wg_begin = (const unsigned*)put(tb.wg_begin.data(), b_wg);
+    T.red = (const RedTile*)put(tb.red.data(), b_red);
+    T.red_slots = (const unsigned*)put(tb.red_slots.data(), b_rs);
+    if (tb.slots_consecutive) T.red_slots = nullptr;  // k_conv_reduce derives the slots from RedTile::slot0
     if (hbase && hipMemcpyAsync(base, hbase, off, hipMemcpyHostToDevice, st) != hipSuccess) return false;
     return true;
 }
 
-// Which output blocks each wave of a workgroup accumulates (at most two: 16 accumulator VGPR pairs each).
-// Block c costs one 8x8x8 chunk product per (x chunk, y chunk) pair that lands in it, i.e. c + 1 for full
-// operands.  The classic pairing (c, nb-1-c) gives every ACTIVE wave the same load, but when nb < 2*NW the
-// active waves sit unevenly on the CU's four SIMDs (wave w runs on SIMD w % 4): nb = 10 keeps two busy waves on
-// SIMD 0 and one on the others, and the whole CU waits for SIMD 0 — measured 62% of the nb = 16 rate.
-// Longest-processing-time assignment over SIMDs instead, then over the waves of the SIMD.
-static void assign_blocks(TiledArgs& T, unsigned NW) {
-    static const int mode = 1;
-    for (int w = 0; w < 8; ++w) T.blk1[w] = T.blk2[w] = 0xff;
-    // (classic pairs are only balanced when every block c costs c + 1: compact operands — the piece-split products'
-    // untruncated inner axis costs min(c + 1, nxc, nyc, nb - c) — always take the LPT assignment)
-    const bool full = T.nxc >= T.nb && T.nyc >= T.nb;
-    if (mode == 0 || (full && (2 * NW == T.nb || NW < 4))) {
-        for (unsigned w = 0; w < NW; ++w) {
-            unsigned c1 = w, c2 = T.nb - 1 - w;
-            if (c1 < T.nb && c1 <= c2) T.blk1[w] = (unsigned char)c1;
-            if (c2 < T.nb && c2 > c1) T.blk2[w] = (unsigned char)c2;
-        }
-        return;
-    }
-    auto cost = [&](unsigned c) {
-        unsigned n = 0;
-        for (unsigned xc = 0; xc <= c && xc < T.nxc; ++xc)
-            if (c - xc < T.nyc) n++;
-        return n;
-    };
-    unsigned simd_load[4] = {0, 0, 0, 0}, wave_load[8] = {0}, wave_cnt[8] = {0};
-    auto simd_of = [&](unsigned w) { return mode == 2 ? (w / 2) % 4 : w % 4; };
-    for (unsigned i = 0; i < T.nb; ++i) {
-        unsigned c = T.nb - 1 - i;  // heaviest first
-        int best = -1;
-        for (unsigned w = 0; w < NW; ++w) {
-            if (wave_cnt[w] >= 2) continue;
-            if (best < 0) { best = (int)w; continue; }
-            unsigned sb = simd_load[simd_of((unsigned)best)], sw = simd_load[simd_of(w)];
-            if (sw < sb || (sw == sb && wave_load[w] < wave_load[best])) best = (int)w;
-        }
-        if (wave_cnt[best] == 0) T.blk1[best] = (unsigned char)c;
-        else T.blk2[best] = (unsigned char)c;
-        wave_cnt[best]++;
-        wave_load[best] += cost(c);
-        simd_load[simd_of((unsigned)best)] += cost(c);
-    }
+bool build_plan(const ConvArgs& a, const Variant& V, const PeelSpec& ps, Plan& P, hipStream_t st) {
+    PlanTables tb;
+    return canonicalise(a, V, ps, P) && cut_ranges(P, tb) && upload_tables(P, tb, st);
 }
 
 template <int NW, int VAR, int TSH>
-hipError_t launch_main_t(hipStream_t st, const Plan& P, const TiledArgs& T) {
+void launch_main_t(hipStream_t st, const Plan& P, const TiledArgs& T) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_tiled<NW, VAR, TSH>),
@@ -1062,11 +1099,20 @@ hipError_t launch_main_t(hipStream_t st, const Plan& P, const TiledArgs& T) {
     }
     // (a failed launch is latched by the launch thread and raised by the next drain: gft_launch.hpp lq_note)
     GFT_LAUNCH((k_conv_tiled<NW, VAR, TSH>), dim3(P.n_wg), dim3(NW * 64), P.lds_bytes, st, T);
-    return hipSuccess;
 }
 template <int NW, int VAR>
-hipError_t launch_main(hipStream_t st, const Plan& P, const TiledArgs& T) {
-    return T.tsh == 3 ? launch_main_t<NW, VAR, 3>(st, P, T) : launch_main_t<NW, VAR, 0>(st, P, T);
+void launch_main_nw(hipStream_t st, const Plan& P, const TiledArgs& T) {  // the 8x8 lane tile or the run-time one
+    if (T.tsh == 3) launch_main_t<NW, VAR, 3>(st, P, T);
+    else launch_main_t<NW, VAR, 0>(st, P, T);
+}
+template <int VAR>
+void launch_main(hipStream_t st, const Plan& P, const TiledArgs& T) {  // the plan's run-time NW as a compile-time one
+    switch (P.NW) {
+        case 1: launch_main_nw<1, VAR>(st, P, T); break;
+        case 2: launch_main_nw<2, VAR>(st, P, T); break;
+        case 4: launch_main_nw<4, VAR>(st, P, T); break;
+        default: launch_main_nw<8, VAR>(st, P, T); break;
+    }
 }
 
 }  // namespace
@@ -1085,7 +1131,6 @@ void tiled_fold_rows_f64(hipStream_t st, const double* zt, double* z, size_t row
                        row_lo, row_hi, Pz, B, zI, accumulate, guard, epoch);
 }
 
-
 void tiled_set_lane_tile(int tsh) { tiled_force_tsh() = tsh; }
 
 namespace {
@@ -1095,9 +1140,9 @@ int& tiled_peel_mode() {  // "tiled_peel": -1 auto, 0 never, 1 wherever the stru
     return v;
 }
 
-// The plan of (problem, peel role) from the cache, built on a miss.  The pointer is good until the cache is next emptied
-// (plan_generation()); nullptr: the tiled kernel does not support the shape.
-const Plan* cached_plan(const ConvArgs& a, const PeelSpec& ps, hipStream_t st) {
+// The plan of (problem, variant, peel role) from the cache, built on a miss.  The pointer is good until the cache is next
+// emptied (plan_generation()); nullptr: the tiled kernel does not support the shape.
+const Plan* cached_plan(const ConvArgs& a, const Variant& V, const PeelSpec& ps, hipStream_t st) {
     PlanKey key;
     std::memset(&key, 0, sizeof(key));
     if (a.nd < 2 || a.nd > 4) return nullptr;
@@ -1111,80 +1156,91 @@ const Plan* cached_plan(const ConvArgs& a, const PeelSpec& ps, hipStream_t st) {
     key.v[14] = a.slab_hi;
     key.v[15] = (unsigned)a.accumulate;
     key.v[16] = (unsigned)(a.j0_min | (a.j0_excl << 8) | (a.j0_desc << 16));
-    key.v[17] = (unsigned)a.variant;
+    key.v[17] = V.b128;  // (all a plan takes from the variant is the LDS pitch)
     key.v[18] = ps.role | (ps.cut << 4) | (ps.lim1 << 8);  // (the leftover products' output strides follow from role and shapes)
     auto& cache = plan_cache();
     auto it = cache.find(key);
     if (it == cache.end()) {
         Plan P;
-        if (cache.size() >= 1024) {  // bounded: drop everything (plans are cheap to rebuild) and reuse the arena
-            (void)hipStreamSynchronize(st);
-            for (auto& kv : cache)
-                if (kv.second.d_tables) (void)hipFree(kv.second.d_tables);
-            cache.clear();
-            plan_generation()++;
-            arena().head = 0;
-        }
-        if (!build_plan(a, ps, P, st)) return nullptr;  // may itself reset the cache when the table arena wraps
+        if (cache.size() >= 1024) reset_plan_cache(st);  // bounded
+        if (!build_plan(a, V, ps, P, st)) return nullptr;  // may itself reset the cache when the table arena wraps
         it = cache.emplace(key, P).first;
     }
     return &it->second;
 }
 
 // the main kernel of plan P on the filled-in arguments T, then the fixed-order reduce of its split tiles
-bool launch_plan(hipStream_t st, const Plan& P, const TiledArgs& T, int variant) {
-    hipError_t e = hipSuccess;
-    constexpr int DEF = GFT_TILED_DEFAULT_VARIANT;
-    if (variant & 128) {  // leftover products of a peeled product
-        switch (P.NW) {
-            case 1: e = launch_main<1, 131>(st, P, T); break;
-            case 2: e = launch_main<2, 131>(st, P, T); break;
-            case 4: e = launch_main<4, 131>(st, P, T); break;
-            default: e = launch_main<8, 131>(st, P, T); break;
-        }
-    } else if (variant & 8) {  // compact operands, pipelined
-        switch (P.NW) {
-            case 1: e = launch_main<1, 11>(st, P, T); break;
-            case 2: e = launch_main<2, 11>(st, P, T); break;
-            case 4: e = launch_main<4, 11>(st, P, T); break;
-            default: e = launch_main<8, 11>(st, P, T); break;
-        }
-    } else if (P.NW == 8) {
-        switch (variant) {
-            case 0: case 4: e = launch_main<8, 0>(st, P, T); break;
-            case 1: e = launch_main<8, 1>(st, P, T); break;
-            case 3: e = launch_main<8, 3>(st, P, T); break;
-            case 7: e = launch_main<8, 3>(st, P, T); break;  // 3 + XCD-contiguous ranges (runtime flag)
+bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V) {
+    T.xcd_remap = (V.xcd && P.n_wg % 8 == 0) ? 1u : 0u;
+    switch (pick_var(V, P.NW)) {
+        case 131: launch_main<131>(st, P, T); break;  // leftover products of a peeled product
+        case 11: launch_main<11>(st, P, T); break;    // compact operands, pipelined
+        case 3: launch_main<3>(st, P, T); break;
+        case 0: launch_main<0>(st, P, T); break;
+        case 1: launch_main_nw<8, 1>(st, P, T); break;
 #ifdef GFT_TILED_DIAG
-            case 17: e = launch_main<8, 17>(st, P, T); break;
-            case 33: e = launch_main<8, 33>(st, P, T); break;
-            case 49: e = launch_main<8, 49>(st, P, T); break;
-            case 65: e = launch_main<8, 65>(st, P, T); break;
-            case 113: e = launch_main<8, 113>(st, P, T); break;
+        case 17: launch_main_nw<8, 17>(st, P, T); break;
+        case 33: launch_main_nw<8, 33>(st, P, T); break;
+        case 49: launch_main_nw<8, 49>(st, P, T); break;
+        case 65: launch_main_nw<8, 65>(st, P, T); break;
+        case 113: launch_main_nw<8, 113>(st, P, T); break;
 #endif
-            default: return false;
-        }
-    } else {
-        if (variant != 0 && variant != 4 && variant != DEF && variant != (DEF & 3)) return false;
-        if (variant & 1) {
-            switch (P.NW) {
-                case 1: e = launch_main<1, (DEF & 3)>(st, P, T); break;
-                case 2: e = launch_main<2, (DEF & 3)>(st, P, T); break;
-                default: e = launch_main<4, (DEF & 3)>(st, P, T); break;
-            }
-        } else {
-            switch (P.NW) {
-                case 1: e = launch_main<1, 0>(st, P, T); break;
-                case 2: e = launch_main<2, 0>(st, P, T); break;
-                default: e = launch_main<4, 0>(st, P, T); break;
-            }
-        }
+        default: return false;
     }
-    if (e != hipSuccess) return false;
     if (P.n_red) {
         GFT_LAUNCH(k_conv_reduce, dim3(P.n_red, T.nb), dim3(256), 0, st, T, P.n_red);
     }
     return true;
+}
+
+// How a product's operands reach the kernel, and the common prefix [partial slabs][packed x][packed y] of its workspace.
+// Operands are read IN PLACE where their own layout is the packed one: rows of whole chunks (nx8 == xI, ny8 == yI), both
+// spanning every chunk of the result's rows (nxc >= nb, nyc >= nb: the compact-operand path multiplies a zero window
+// where a block reaches beyond y's last chunk), y 16-byte aligned (window loads are 16-byte), x 8-byte, and 64 readable
+// bytes after x's last element (operands_slack: the pipelined path requests one chunk beyond the one it uses; the
+// library's own buffers have that slack, a caller's raw pointer may not).  There is then no zero padding anywhere, so
+// inf / NaN operands cannot create NaNs the reference does not produce: no verdict, no guarded fallback launch — ONE
+// launch per product.  (A peeled product meets the shape part of the condition through peel_applies: full operands.)
+// Everything else is packed by k_prep_operands (rows padded to whole chunks plus one chunk of slack after the last row),
+// which also takes the non-finite verdict; y alone stays in place if only x needs it.
+struct Operands {
+    bool inplace, pack_y;
+    size_t o_xp, o_yp, end;  // byte offsets of the packed operands in the workspace, and the end of the common prefix
+};
+// (sized for the packed layout whether or not this call packs: a query and the launches that follow it — the high-rank
+// loop's operand blocks, say — must agree on the workspace whatever their pointers' alignment)
+Operands operand_layout(const TiledArgs& B, size_t n_slots, const double* x, const double* y, int operands_slack) {
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t x_rows = (size_t)B.xU * B.x0 * B.x1, y_rows = (size_t)B.yU * B.y0 * B.y1;
+    Operands o;
+    o.inplace = operands_slack && B.nx8 == B.xI && B.ny8 == B.yI && B.nxc >= B.nb && B.nyc >= B.nb && !((uintptr_t)y & 15) &&
+                !((uintptr_t)x & 7);
+    o.pack_y = !o.inplace && (B.ny8 != B.yI || ((uintptr_t)y & 15));
+    o.o_xp = al(n_slots * B.nb * 512 * sizeof(double));
+    o.o_yp = o.o_xp + al((x_rows * B.nx8 + 8) * sizeof(double));
+    o.end = o.o_yp + al(y_rows * B.ny8 * sizeof(double));
+    return o;
+}
+// Binds x and y to T as the layout says: in place, or packed into the workspace `wb` under the verdict (nf_flag, nf_epoch).
+void bind_operands(hipStream_t st, const Operands& o, const double* x, const double* y, char* wb, unsigned* nf_flag,
+                   unsigned nf_epoch, TiledArgs& T) {
+    T.ws = (double*)wb;
+    if (o.inplace) {
+        T.xp = x;
+        T.yp = y;
+        T.guard = nullptr;
+        T.guard_epoch = 0;
+        return;
+    }
+    const size_t x_rows = (size_t)T.xU * T.x0 * T.x1, y_rows = (size_t)T.yU * T.y0 * T.y1;
+    double *xp = (double*)(wb + o.o_xp), *yp = (double*)(wb + o.o_yp);
+    const size_t tot = x_rows * T.nx8 + (o.pack_y ? y_rows * T.ny8 : y_rows * T.yI);
+    GFT_LAUNCH(k_prep_operands, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, x, xp, x_rows, T.xI,
+               T.nx8, y, o.pack_y ? yp : nullptr, y_rows, T.yI, T.ny8, nf_flag, nf_epoch);
+    T.xp = xp;
+    T.yp = o.pack_y ? yp : y;
+    T.guard = nf_flag;
+    T.guard_epoch = nf_epoch;
 }
 
 // Does the product take the peel?  Structural conditions: rank 3, the whole slab range, operands as large as the result
@@ -1192,7 +1248,7 @@ bool launch_plan(hipStream_t st, const Plan& P, const TiledArgs& T, int variant)
 // tile.  Auto mode adds the size threshold: the leftover products' batch axis (n / 8 tiles) must fill the eight lanes
 // of its lane-tile axis, and the two extra launches and their partial slabs must be worth the masks they remove
 // (PEEL_MIN_EXTENT, PEEL_MIN_INNER: profiles/r07/tiled_peel_sweep.txt).
-bool peel_applies(const ConvArgs& a) {
+bool peel_applies(const ConvArgs& a, const Variant& V) {
     const int mode = tiled_peel_mode();
     if (mode == 0) return false;
     if (a.nd != 3 || a.slab_axis != 0 || a.slab_lo != 0 || a.slab_hi != a.zs[0]) return false;
@@ -1201,7 +1257,7 @@ bool peel_applies(const ConvArgs& a) {
         if (a.xs[i] != a.zs[i] || a.ys[i] != a.zs[i]) return false;
     const unsigned n0 = a.zs[0], n1 = a.zs[1];
     if (n0 % 8 || n1 % 8 || n0 < 16 || n1 < 16 || a.zs[2] > 128) return false;
-    if ((a.variant & ~4) != 3) return false;
+    if (!V.fast || !V.b128 || V.compact || V.peel || V.other) return false;  // (external 3 or 7)
     TiledArgs T;
     std::memset(&T, 0, sizeof(T));
     T.x0 = T.y0 = T.z0 = n0;
@@ -1224,8 +1280,8 @@ bool peel_applies(const ConvArgs& a) {
 // Workspace: [partial slabs, shared by the three][packed x][packed y][L0 window][L1 scalar + slack][L1 window].
 // Returns 1 done (or, for a query, sized), 0 a launch failed, -1 the peel cannot be planned or does not fit the workspace
 // it was given — nothing has been launched and the caller takes the plain plan.
-int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, void* ws, size_t ws_bytes,
-                     size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded) {
+int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, const Variant& V, void* ws,
+                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded) {
     const unsigned n0 = a.zs[0], n1 = a.zs[1], nI = a.zs[2];
     ConvArgs l0, l1;
     std::memset(&l0, 0, sizeof(l0));
@@ -1233,8 +1289,9 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
     l0.slab_lo = 0;
     l0.slab_hi = 7;
     l0.accumulate = 1;
-    l0.variant = a.variant | 128;
     l1 = l0;
+    Variant VL = V;  // the leftover products: the peel instantiation
+    VL.peel = true;
     const unsigned s0x[4] = {7, 1, n1, nI}, s0y[4] = {7, n0 / 8, n1, nI}, s1x[4] = {7, 1, n0, nI}, s1y[4] = {7, n1 / 8, n0, nI};
     for (int i = 0; i < 4; ++i) {
         l0.xs[i] = s0x[i]; l0.ys[i] = l0.zs[i] = s0y[i];
@@ -1247,60 +1304,40 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
     Plan PM, P0, P1;  // copies: building one plan may empty the cache the others came from (then once more, from an empty arena)
     for (int attempt = 0;; ++attempt) {
         const unsigned long long gen = plan_generation();
-        const Plan* q = cached_plan(a, pm, st);
+        const Plan* q = cached_plan(a, V, pm, st);
         if (!q) return -1;
         PM = *q;
-        if (!(q = cached_plan(l0, p0, st))) return -1;
+        if (!(q = cached_plan(l0, VL, p0, st))) return -1;
         P0 = *q;
-        if (!(q = cached_plan(l1, p1, st))) return -1;
+        if (!(q = cached_plan(l1, VL, p1, st))) return -1;
         P1 = *q;
         if (gen == plan_generation()) break;
         if (attempt) return -1;
     }
     const TiledArgs& B = PM.base;
     if (B.tsh != 3) return -1;
-    const size_t rows = (size_t)n0 * n1, n8 = B.nx8;
-    const size_t slots = std::max(PM.n_slots, std::max(P0.n_slots, P1.n_slots));
-    const size_t b_slots = slots * B.nb * 512 * sizeof(double);
-    const bool inplace = a.operands_slack && n8 == nI && !((uintptr_t)y & 15) && !((uintptr_t)x & 7);
-    const bool pack_y = !inplace && (n8 != nI || ((uintptr_t)y & 15));
-    const size_t b_xp = (rows * n8 + 8) * sizeof(double), b_yp = rows * n8 * sizeof(double);
+    const size_t n8 = B.nx8;
+    const Operands o = operand_layout(B, std::max(PM.n_slots, std::max(P0.n_slots, P1.n_slots)), x, y, a.operands_slack);
     const size_t e_w0 = (size_t)7 * (n0 / 8) * n1 * n8, e_s1 = (size_t)7 * n0 * n8, e_w1 = (size_t)7 * (n1 / 8) * n0 * n8;
     auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_xp = al(b_slots), o_yp = o_xp + al(b_xp), o_w0 = o_yp + al(b_yp), o_s1 = o_w0 + al(e_w0 * sizeof(double)),
-                 o_w1 = o_s1 + al((e_s1 + 8) * sizeof(double)), need = o_w1 + al(e_w1 * sizeof(double)) + 256;
+    const size_t o_w0 = o.end, o_s1 = o_w0 + al(e_w0 * sizeof(double)), o_w1 = o_s1 + al((e_s1 + 8) * sizeof(double)),
+                 need = o_w1 + al(e_w1 * sizeof(double)) + 256;
     if (ws && ws_bytes < need) return -1;  // (sized by a query that could not plan the peel)
     if (ws_needed) *ws_needed = need;
-    if (guarded) *guarded = !inplace;
+    if (guarded) *guarded = !o.inplace;
     if (!ws) return 1;  // query
 
     char* wb = (char*)ws;
-    double *xp = (double*)(wb + o_xp), *yp = (double*)(wb + o_yp), *w0 = (double*)(wb + o_w0), *s1 = (double*)(wb + o_s1),
-           *w1 = (double*)(wb + o_w1);
+    double *w0 = (double*)(wb + o_w0), *s1 = (double*)(wb + o_s1), *w1 = (double*)(wb + o_w1);
     TiledArgs T = B;
-    T.ws = (double*)wb;
-    if (inplace) {
-        T.xp = x;
-        T.yp = y;
-        T.guard = nullptr;
-        T.guard_epoch = 0;
-    } else {
-        const size_t tot = rows * n8 + (pack_y ? rows * n8 : rows * nI);
-        GFT_LAUNCH(k_prep_operands, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, x, xp, rows, nI,
-                   (unsigned)n8, y, pack_y ? yp : nullptr, rows, nI, (unsigned)n8, nf_flag, nf_epoch);
-        T.xp = xp;
-        T.yp = pack_y ? yp : y;
-        T.guard = nf_flag;
-        T.guard_epoch = nf_epoch;
-    }
+    bind_operands(st, o, x, y, wb, nf_flag, nf_epoch, T);
     {
         const size_t tot = e_w0 + e_s1 + e_w1;
         GFT_LAUNCH(k_pack_peel, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 4096)), dim3(256), 0, st, x, y, w0, s1, w1, n0, n1,
                    nI, (unsigned)n8);
     }
     T.z = z;
-    T.xcd_remap = ((a.variant & 4) && (PM.n_wg % 8 == 0)) ? 1u : 0u;
-    if (!launch_plan(st, PM, T, a.variant)) return 0;
+    if (!launch_plan(st, PM, T, V)) return 0;
     TiledArgs T0 = P0.base, T1 = P1.base;
     T0.ws = T1.ws = T.ws;
     T0.z = T1.z = z;
@@ -1310,88 +1347,42 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
     T0.yp = w0;
     T1.xp = s1;
     T1.yp = w1;
-    T0.xcd_remap = ((a.variant & 4) && (P0.n_wg % 8 == 0)) ? 1u : 0u;
-    T1.xcd_remap = ((a.variant & 4) && (P1.n_wg % 8 == 0)) ? 1u : 0u;
-    return launch_plan(st, P0, T0, l0.variant) && launch_plan(st, P1, T1, l1.variant) ? 1 : 0;
+    return launch_plan(st, P0, T0, VL) && launch_plan(st, P1, T1, VL) ? 1 : 0;
 }
 
 }  // namespace
 
 void tiled_set_peel(int mode) { tiled_peel_mode() = mode < 0 ? -1 : (mode ? 1 : 0); }
 
-bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a_in, void* ws,
-                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded, bool* peeled) {
-    ConvArgs a = a_in;
-    if (a.variant < 0) a.variant = GFT_TILED_DEFAULT_VARIANT;
-    if (a.nd >= 2 && a.nd <= 4) {  // the pipelined fast path (bits 1|2) needs x and y to span every chunk of z's inner axis
-        unsigned nb = (a.zs[a.nd - 1] + 7) / 8;
-        if ((a.xs[a.nd - 1] + 7) / 8 < nb || (a.ys[a.nd - 1] + 7) / 8 < nb) {
-            static const bool compact_fast = true;
-            if (compact_fast && (a.variant & 3) == 3) a.variant = (a.variant & ~0xff) | (a.variant & 7) | 8;  // pipelined path for compact operands
-            else a.variant &= ~3;
-        }
+bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, void* ws, size_t ws_bytes,
+                    size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded, bool* peeled) {
+    bool compact_operands = false;
+    if (a.nd >= 2 && a.nd <= 4) {
+        const unsigned nb = (a.zs[a.nd - 1] + 7) / 8;
+        compact_operands = (a.xs[a.nd - 1] + 7) / 8 < nb || (a.ys[a.nd - 1] + 7) / 8 < nb;
     }
+    const Variant V = decode_variant(a.variant, compact_operands);
     if (peeled) *peeled = false;
-    if (peel_applies(a)) {
-        const int r = conv_tiled_peel(st, x, y, z, a, ws, ws_bytes, ws_needed, nf_flag, nf_epoch, guarded);
+    if (peel_applies(a, V)) {
+        const int r = conv_tiled_peel(st, x, y, z, a, V, ws, ws_bytes, ws_needed, nf_flag, nf_epoch, guarded);
         if (r >= 0) {
             if (peeled) *peeled = r == 1;
             return r == 1;
         }
         // (the peel could not be planned: the plain plan below, for the query and for the launch alike)
     }
-    const Plan* pp = cached_plan(a, PeelSpec(), st);
-    if (!pp) return false;
-    const Plan& P = *pp;
-    const TiledArgs& B = P.base;
-    // workspace: [partial slabs][packed x][packed y]
-    size_t b_slots = (size_t)P.n_slots * B.nb * 512 * sizeof(double);
-    size_t x_rows = (size_t)B.xU * B.x0 * B.x1, y_rows = (size_t)B.yU * B.y0 * B.y1;
-    // Operands are read in place where their own layout IS the packed one (round 4): rows of whole chunks, y 16-byte
-    // aligned (window loads are 16-byte), and 64 readable bytes after x's last element (the pipelined path requests one
-    // chunk beyond the one it uses; the library's own buffers have that slack, a caller's raw pointer may not), both spanning
-    // every chunk of the result's rows.  There is then no zero padding anywhere, so inf / NaN operands cannot create NaNs the reference does not produce: no verdict,
-    // no guarded fallback launch — ONE launch per product.  Everything else is packed by k_prep_operands (rows padded to
-    // whole chunks plus one chunk of slack after the last row), which also takes the non-finite verdict.
-    static const bool inplace_env = true;
-    // (full inner extents only: the compact-operand path multiplies a zero window where a block reaches beyond y's last chunk —
-    // artificial zeros again, which need the verdict)
-    const bool inplace = inplace_env && a.operands_slack && B.nx8 == B.xI && B.ny8 == B.yI && B.nxc >= B.nb && B.nyc >= B.nb &&
-                         !((uintptr_t)y & 15) && !((uintptr_t)x & 7);
-    if (guarded) *guarded = !inplace;
-    bool pack_y = !inplace && (B.ny8 != B.yI || ((uintptr_t)y & 15));  // window loads are 16-byte
-    // (sized for the packed layout whether or not this call packs: a query and the launches that follow it — the high-rank
-    // loop's operand blocks, say — must agree on the workspace whatever their pointers' alignment)
-    size_t b_xp = (x_rows * B.nx8 + 8) * sizeof(double);
-    size_t b_yp = y_rows * B.ny8 * sizeof(double);
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    size_t need = al(b_slots) + al(b_xp) + al(b_yp) + 256;
+    const Plan* P = cached_plan(a, V, PeelSpec(), st);
+    if (!P) return false;
+    const Operands o = operand_layout(P->base, P->n_slots, x, y, a.operands_slack);
+    const size_t need = o.end + 256;  // workspace: [partial slabs][packed x][packed y]
+    if (guarded) *guarded = !o.inplace;
     if (ws_needed) *ws_needed = need;
     if (!ws) return true;  // query
     if (ws_bytes < need) return false;
-
-    char* wb = (char*)ws;
-    TiledArgs T = B;
-    T.ws = (double*)wb;
-    double* xp = (double*)(wb + al(b_slots));
-    double* yp = (double*)(wb + al(b_slots) + al(b_xp));
-    if (inplace) {
-        T.xp = x;
-        T.yp = y;
-        T.guard = nullptr;
-        T.guard_epoch = 0;
-    } else {
-        size_t tot = x_rows * B.nx8 + (pack_y ? y_rows * B.ny8 : y_rows * B.yI);
-        GFT_LAUNCH(k_prep_operands, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, x,
-                           xp, x_rows, B.xI, B.nx8, y, pack_y ? yp : nullptr, y_rows, B.yI, B.ny8, nf_flag, nf_epoch);
-        T.xp = xp;
-        T.yp = pack_y ? yp : y;
-        T.guard = nf_flag;
-        T.guard_epoch = nf_epoch;
-    }
+    TiledArgs T = P->base;
+    bind_operands(st, o, x, y, (char*)ws, nf_flag, nf_epoch, T);
     T.z = z;
-    T.xcd_remap = ((a.variant & 4) && (P.n_wg % 8 == 0)) ? 1u : 0u;
-    return launch_plan(st, P, T, a.variant);
+    return launch_plan(st, *P, T, V);
 }
 
 }  // namespace gft

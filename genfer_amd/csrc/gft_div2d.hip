@@ -674,8 +674,7 @@ bool K<E>::div_1d(hipStream_t st, const double* xs, size_t x_plane, unsigned nx,
         GFT_LAUNCH(k_div_1d_serial<E>, dim3(1), dim3(64), 0, st, xs, x_plane, nx, ys, y_plane, ny, res, r_plane, n);
         return true;
     }
-    static const bool wave_on = true;
-    if (wave_on && n <= 1024) {
+    if (n <= 1024) {
 #define GFT_D1W(SEG)                                                                                                        \
     GFT_LAUNCH((k_div_1d_wave<E, SEG>), dim3(1), dim3(64), (size_t)E::W * 64 * (SEG + 1) * sizeof(double), st, xs, x_plane, \
                        nx, ys, y_plane, ny, res, r_plane, n, fused)

@@ -808,13 +808,11 @@ __global__ void __launch_bounds__(1024) k_horner_pipe_point(const double* __rest
     horner_pipe_point_line<E>(res0, rp0, a, ap, out, plane, g, wit, blockIdx.x, blockDim.x >> 6, hp_lds);
 }
 // the LDS a loop needs on the POINT pipeline, or 0 if it does not run there (lines > 1024, non-point coefficient boxes, rings
-// beyond 60 KB, GFT_HORNER_PIPE / GFT_HORNER_LEAN = 0)
+// beyond 60 KB)
 template <class E>
 static size_t horner_pipe_point_lds(const HornerLoopArgs& args) {
-    static const bool pipe_on = true;
-    static const bool lean_on = true;
     const unsigned lw = args.fs[args.w];
-    if (!pipe_on || !lean_on || lw > 1024) return 0;
+    if (lw > 1024) return 0;
     const bool point = args.coeff_scalar || args.oc[args.w] == 1;
     if (!point) return 0;
     const unsigned nwv = (lw + 63) / 64;
@@ -853,12 +851,11 @@ void K<E>::horner_linear_loop(hipStream_t st, const double* res0, size_t res0_pl
     if (args.nsteps == 0 || lines == 0) return;
     const unsigned lw = args.fs[args.w];
     // wave pipeline (k_horner_linear_pipe): lines up to 1024 whose boundary rings fit LDS
-    static const bool pipe_on = true;
     if (const size_t lds0 = horner_pipe_point_lds<E>(args)) {
         GFT_LAUNCH((k_horner_pipe_point<E>), dim3(lines), dim3((lw + 63) / 64 * 64), lds0, st, res0, res0_plane, a, a_plane, out, plane, args, wit);
         return;
     }
-    if (pipe_on && lw <= 1024) {
+    if (lw <= 1024) {
         const unsigned nwv = (lw + 63) / 64;
         const bool point = args.coeff_scalar || args.oc[args.w] == 1;
         const size_t lds = (size_t)(nwv - 1 + (point ? 1 : 0)) * E::W * args.nsteps * sizeof(double) + (point ? (size_t)128 * 8 : 0) + 16;
@@ -872,8 +869,8 @@ void K<E>::horner_linear_loop(hipStream_t st, const double* res0, size_t res0_pl
     }
     // one position per thread up to 1024-long lines (measured: two per thread is 10 % slower — the element chains
     // are not interleaved by the compiler, more waves hide the latency better)
-    static const unsigned per_thread = 1;
-    unsigned threads = std::min<unsigned>(1024, ((lw + per_thread - 1) / per_thread + 63) / 64 * 64);
+    constexpr unsigned PER_THREAD = 1;
+    unsigned threads = std::min<unsigned>(1024, ((lw + PER_THREAD - 1) / PER_THREAD + 63) / 64 * 64);
     size_t lds = (size_t)2 * E::W * args.lw_pad * sizeof(double);
     if (lw <= threads)
         GFT_LAUNCH((k_horner_linear_loop<E, 1, 8>), dim3(lines), dim3(threads), lds, st, res0, res0_plane, a, a_plane, out, plane, args, wit);

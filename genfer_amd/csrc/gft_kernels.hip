@@ -172,10 +172,6 @@ static void lq_raise() {
 }
 
 bool lq_enabled() { return g_lq.enabled; }
-int lq_debug() {
-    static const int d = 0;
-    return d;
-}
 void lq_configure(int device, bool enabled) {
     g_lq.drain();
     g_lq.device = device;
@@ -445,12 +441,11 @@ void K<E>::gather(hipStream_t st, const double* src, size_t src_plane, double* o
         return;
     }
     // rows of at least a wave's width that missed the 16-byte path: one wave per row (no per-element index arithmetic)
-    static const bool rows_on = true;
     // (only where bandwidth is the issue: on a 180 x 180 tensor one wave per row is 180 waves walking their rows serially
     // where the per-element kernel has 32 000 threads in flight — mixture --bounds 3.0 -> 3.7 s when it was unconditional)
     // (and only with rows enough to fill the chip: four_populations gathers 1e6 elements in a few dozen rows of tens of
     // thousands — 8 workgroups walking them took 337 us where the per-element kernel takes 19)
-    if (rows_on && a.out.nd >= 2 && a.out.d[a.out.nd - 1] >= 48 && total >= ((size_t)1 << 20) && total / a.out.d[a.out.nd - 1] >= 4096) {
+    if (a.out.nd >= 2 && a.out.d[a.out.nd - 1] >= 48 && total >= ((size_t)1 << 20) && total / a.out.d[a.out.nd - 1] >= 4096) {
         const size_t rows = total / a.out.d[a.out.nd - 1];
         const size_t blocks = std::min<size_t>((rows + 3) / 4, 256 * 16);
         GFT_LAUNCH(k_gather_rows<E>, dim3((unsigned)blocks), dim3(256), 0, st, src, src_plane, out, out_plane, a, rows);
@@ -2153,8 +2148,7 @@ __global__ void __launch_bounds__(256) k_conv_line(const double* __restrict__ F,
 template <class E>
 bool K<E>::conv_line(hipStream_t st, const double* x, size_t x_plane, const double* y, size_t y_plane, double* z, size_t z_plane,
                      const ConvArgs& a) {
-    static const bool on = true;
-    if (!on || a.nd < 2 || a.nd > MAXD || a.accumulate || a.j0_min || a.j0_excl || a.j0_desc || a.guard || !a.inner_from_zero) return false;
+    if (a.nd < 2 || a.nd > MAXD || a.accumulate || a.j0_min || a.j0_excl || a.j0_desc || a.guard || !a.inner_from_zero) return false;
     if (a.slab_lo != 0 || a.slab_hi != a.zs[0]) return false;
     // which operand is the line, and along which axis
     auto line_axis = [&](const unsigned* s) -> int {

@@ -41,7 +41,6 @@ struct LaunchSlot {
     alignas(16) unsigned char payload[LQ_SLOT_BYTES];
 };
 bool lq_enabled();
-int lq_debug();  // GFT_ASYNC_DEBUG bits: 1 = wait for the worker after every queued item, 2 = non-launch tasks run on the calling thread
 void lq_configure(int device, bool enabled);  // gft_init / options
 void lq_shutdown();                           // drains and stops the worker
 void lq_report();                             // GFT_TRACE_LQ=1: prints the two threads' time split since the last report (stderr)
@@ -76,17 +75,10 @@ inline void enqueue(F&& f) {
         fn->~Fn();
     };
     lq_commit();
-    if (lq_debug() & 1) launch_drain();
 }
 // a stream operation that is not a kernel launch (copy, memset, event): queued like a launch
 template <class F>
 inline void enqueue_task(F&& f) {
-    if (lq_debug() & 2) {
-        ++g_stream_ops;
-        launch_drain();
-        f();
-        return;
-    }
     enqueue(std::forward<F>(f));
 }
 
@@ -127,7 +119,6 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, 
         fn->~Fn();
     };
     lq_commit();
-    if (lq_debug() & 1) launch_drain();
 }
 
 }  // namespace gft

@@ -45,25 +45,18 @@
                     // same functor on the host, so the same bits — are formed here.  Up to HTAB_CAP of them travel BY VALUE
                     // with the gather (no table launch, no per-thread running product, no device mirror of a host-resident
                     // subst); longer tables are uploaded.
-                    static const bool htab_on = true;
-                    if (htab_on) {
-                        std::vector<double> pw(lens[v] * W);
-                        typename E::V f = E::one();
-                        const typename E::V mv = E::from(Scalar2{m[0], W == 2 ? m[1] : 0.0});
-                        for (size_t k = 0; k < lens[v]; ++k) {
-                            E::st(pw.data(), lens[v], k, f);
-                            f = E::mul(f, mv);
-                        }
-                        if (lens[v] <= (W == 1 ? HTAB_CAP : HTAB_CAP / 2))
-                            return gather(a, lens, deg, shift, a.shape, OP_MUL_HTAB, nullptr, (int)v, pw.data(), lens[v], nullptr, 0);
-                        Rc<Buf> tabh = alloc_doubles(lens[v] * W);
-                        upload_small(R.stream, tabh->p, pw.data(), lens[v] * W);
-                        return gather(a, lens, deg, shift, a.shape, OP_MUL_TAB, nullptr, (int)v, tabh->p, lens[v], nullptr, 0);
+                    std::vector<double> pw(lens[v] * W);
+                    typename E::V f = E::one();
+                    const typename E::V mv = E::from(Scalar2{m[0], W == 2 ? m[1] : 0.0});
+                    for (size_t k = 0; k < lens[v]; ++k) {
+                        E::st(pw.data(), lens[v], k, f);
+                        f = E::mul(f, mv);
                     }
-                    if (lens[v] <= 256) {
-                        const double mm[2] = {m[0], m[1]};
-                        return gather(a, lens, deg, shift, a.shape, OP_MUL_POW, mm, (int)v, nullptr, 0, nullptr, 0);
-                    }
+                    if (lens[v] <= (W == 1 ? HTAB_CAP : HTAB_CAP / 2))
+                        return gather(a, lens, deg, shift, a.shape, OP_MUL_HTAB, nullptr, (int)v, pw.data(), lens[v], nullptr, 0);
+                    Rc<Buf> tabh = alloc_doubles(lens[v] * W);
+                    upload_small(R.stream, tabh->p, pw.data(), lens[v] * W);
+                    return gather(a, lens, deg, shift, a.shape, OP_MUL_TAB, nullptr, (int)v, tabh->p, lens[v], nullptr, 0);
                 }
                 if (lens[v] <= 256)  // short axis: every thread forms its own m^k (same running product), no table launch
                     return gather(a, lens, deg, shift, a.shape, OP_MUL_POW, nullptr, (int)v, dp<E>(subst) + sst[w], subst.numel, nullptr, 0);
@@ -152,7 +145,6 @@
         constexpr size_t HBLK = 8;
         P ca_h;                       // host-tier copy of the slabs [ca_h_lo, ca_h_hi) of ca along v
         size_t ca_h_lo = 0, ca_h_hi = 0;
-        static const bool host_phase_on = true;
         auto fetch_block = [&](size_t i_top) {
             const size_t lo = i_top + 1 > HBLK ? i_top + 1 - HBLK : 0;
             ca_h = to_host_tier(slab_range(ca, v, lo, i_top + 1, ca.deg, OP_COPY, -1, nullptr, 0, 0));
@@ -227,9 +219,8 @@
                     P ahead;
                     bool queued = false;
                     unsigned* ahead_wit = (proven || slots + (unsigned)i > WIT_SLOTS) ? nullptr : R.d_wit + slots;
-                    static const bool ahead_on = true;
                     bool queued_step = false;
-                    if (ahead_on && !tok.done && R.fuse_horner && lin_known && res.shape.size() == deg.size()) {
+                    if (!tok.done && R.fuse_horner && lin_known && res.shape.size() == deg.size()) {
                         if (i >= 1 && (proven || ahead_wit)) {
                             if (slots == 0 && !proven) HIP_OK(hipMemsetAsync(R.d_wit, 0, sizeof(unsigned) * WIT_SLOTS, R.stream));
                             // a proven loop on an operand the main chain has long passed: RECORDED (its launch needs no guard —
@@ -256,7 +247,7 @@
                         continue;
                     }
                     // (queued and linear: `ahead` is dropped — its launch returned at the guard)
-                    if (!res_nonlinear_seen && host_phase_on && R.host_max_elems && res.numel <= R.host_max_elems && !on_host(ca) &&
+                    if (!res_nonlinear_seen && R.host_max_elems && res.numel <= R.host_max_elems && !on_host(ca) &&
                         prod(ca.shape) / ca.shape[v] * HBLK <= 16 * R.host_max_elems) {
                         res = to_host_tier(res);
                         fetch_block(i);
@@ -325,11 +316,9 @@
                 res = horner_linear_step(res, ca, v, i, c, m, w, deg);
             } else {
                 P nxt;
-                static const int shallow_diag = 0;
-                const bool fuse_wit = !(shallow_diag & 1);
-                if (horner_general_step_fused(res, subst, ca, v, i, deg, (fuse_wit && i > 0 && !proven) ? R.d_wit + slots : nullptr, &nxt)) {
+                if (horner_general_step_fused(res, subst, ca, v, i, deg, (i > 0 && !proven) ? R.d_wit + slots : nullptr, &nxt)) {
                     res = nxt;
-                    witnessed = fuse_wit;  // (the step's kernel raised the witness word itself)
+                    witnessed = true;  // (the step's kernel raised the witness word itself)
                 } else {
                     res = addsub(mul_horner(res, subst), horner_coeff(ca, v, i, deg), false);
                 }

@@ -152,28 +152,12 @@
             }
             if (ok) ok = conv_tiled_f64(R.stream, tx, ty, tz, at, nullptr, 0, &need, nullptr, 0);
             if (ok) {
-                if (need > R.conv_ws_bytes) {  // grow geometrically: supports (and workspaces) grow statement by statement
-                    size_t want = std::max(need, std::min<size_t>(2 * R.conv_ws_bytes, (size_t)1 << 32));
-                    want = std::max<size_t>(want, (size_t)8 << 20);
-                    if (R.conv_ws) HIP_OK(hipFree(R.conv_ws));
-                    R.conv_ws = nullptr;
-                    R.conv_ws_bytes = 0;
-                    if (hipMalloc(&R.conv_ws, want) != hipSuccess) {
-                        (void)hipGetLastError();
-                        want = need;
-                        HIP_OK(hipMalloc(&R.conv_ws, want));
-                    }
-                    R.conv_ws_bytes = want;
-                }
+                R.ensure_conv_ws(need);
                 // Zero padding times inf/NaN would create NaNs the reference does not produce.  The verdict stays
                 // on the device: the packing/scan kernels stamp R.d_flag[2] with this product's epoch if an
                 // operand is not finite; the tiled kernels then leave z alone and the guarded reference-order
                 // launch below computes it (and is a no-op otherwise).  No host round trip.
-                if (++R.nf_epoch == 0) {
-                    HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(R.d_flag + 2), 0, 1, R.stream));
-                    R.nf_epoch = 1;
-                }
-                unsigned* flag = R.d_flag + 2;
+                unsigned* flag = R.next_nf_epoch();
                 bool guarded = true;
                 if (!split) {
                     bool peeled = false;
@@ -255,19 +239,8 @@
         if (R.conv_mode == 0 && macs / lead_pairs < R.tiled_min_macs) return false;
         size_t need = 0;
         if (!conv_tiled_f64(R.stream, tx, ty, tz, sub, nullptr, 0, &need, nullptr, 0)) return false;
-        if (need > R.conv_ws_bytes) {
-            size_t want = std::max<size_t>(std::max(need, std::min<size_t>(2 * R.conv_ws_bytes, (size_t)1 << 32)), (size_t)8 << 20);
-            if (R.conv_ws) HIP_OK(hipFree(R.conv_ws));
-            R.conv_ws = nullptr;
-            R.conv_ws_bytes = 0;
-            HIP_OK(hipMalloc(&R.conv_ws, want));
-            R.conv_ws_bytes = want;
-        }
-        if (++R.nf_epoch == 0) {
-            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(R.d_flag + 2), 0, 1, R.stream));
-            R.nf_epoch = 1;
-        }
-        unsigned* flag = R.d_flag + 2;
+        R.ensure_conv_ws(need);
+        unsigned* flag = R.next_nf_epoch();
         // odometer over the leading output index u (axis 0 restricted to the slab range) and, inside, over j
         unsigned u[MAXD] = {0}, j[MAXD] = {0};
         for (int i = 0; i < extra; ++i) u[i] = i == 0 ? ash.slab_lo : 0;

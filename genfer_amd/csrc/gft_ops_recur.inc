@@ -482,10 +482,7 @@
         if (cache.size() > 4096) cache.clear();
         Rc<Buf> tab = alloc_tier(host, len * W);
         if (host) HK<E>::factor_table(table_op, (unsigned)n, (unsigned)len, nullptr, 0, tab->p, len);
-        else if (len * W <= 1920 && [] {
-                     static const bool on = true;
-                     return on;
-                 }()) {
+        else if (len * W <= 1920) {
             // a data-independent table is a serial chain (a running product): one GPU lane takes 8 us for 200 f64 factors
             // and 90 us for 200 interval ones, a host core well under a microsecond — same functor, same bits; the values
             // travel as kernel arguments (no pinned staging, stream-ordered)

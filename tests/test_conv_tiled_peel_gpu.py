@@ -157,3 +157,29 @@ def test_peel_on_and_off_agree_at_64_cubed():
         after = genfer_amd.op_stats()
         assert after["tiled"] == before["tiled"] + 1 and after["tiled_peeled"] == before["tiled_peeled"] + rise
         assert np.all(np.abs(on - off) <= 1e-10 * np.abs(off)), np.abs((on - off) / off).max()
+
+
+# Every instantiation family of the main kernel: full / compact / peel instantiation x NW = 1, 2, 4, 8 waves x the 8x8 lane
+# tile (lane axes 16 x 16) / the run-time one (rank 2: 1 x 64).  NW follows from the result's inner length: 8 (16 where the
+# operand must be compact: an x of inner length 8 spans the only chunk of a result of 8, so it is not compact there), 32,
+# 64, 128 give 1, 2, 4, 8.  The peel exists on the 8x8 tile only.  Compared with the reference-order kernel as above.
+def _dispatch_cases():
+    for inner in (8, 32, 64, 128):
+        for lanes, tile in (((16, 16), "8x8"), ((40,), "runtime")):
+            yield pytest.param(lanes + (inner,), lanes + (inner,), 0, id=f"full-{tile}-{inner}")
+            zi = max(inner, 16)
+            yield pytest.param(lanes + (8,), lanes + (zi,), 0, id=f"compact-{tile}-{zi}")
+        yield pytest.param((16, 16, inner), (16, 16, inner), 1, id=f"peel-8x8-{inner}")
+
+
+@pytest.mark.parametrize("xs,zs,peel", list(_dispatch_cases()))
+def test_tiled_dispatch_reaches_every_instantiation_family(xs, zs, peel):
+    x, y = rand(xs, 71), rand(zs, 72)
+    n = peeled()
+    want = conv(1, x, y, zs, peel=peel)
+    got = conv(2, x, y, zs, peel=peel)
+    assert peeled() == n + peel
+    assert np.all(np.abs(got - want) <= 1e-10 * np.abs(want)), np.abs((got - want) / want).max()
+    xm, ym = 2 * x - 1, 2 * y - 1  # mixed signs: normwise against |x| (*) |y|
+    bound = conv(1, np.abs(xm), np.abs(ym), zs, peel=peel)
+    assert np.all(np.abs(conv(2, xm, ym, zs, peel=peel) - conv(1, xm, ym, zs, peel=peel)) <= 1e-10 * bound)

@@ -596,7 +596,7 @@ def test_conv_tiled_in_place_operands_vs_oracle(xs, ys, deg, OTP, GTP, tier):
         check(want, got, exact=False)
         if tier == "device":
             assert after["tiled"] - before["tiled"] == 1
-            if xs[-1] == deg[-1] and ys[-1] == deg[-1] and os.environ.get("GFT_TILED_INPLACE") != "0":  # (rows that stop short of the result's are packed)
+            if xs[-1] == deg[-1] and ys[-1] == deg[-1]:  # (rows that stop short of the result's are packed)
                 assert after["launches"] - before["launches"] <= 2, "in-place operands: the main kernel and the reduce, nothing else"
         xi, yi = x.copy(), y.copy()
         xi[tuple(min(2, s - 1) for s in xs)] = np.inf
@@ -966,8 +966,7 @@ def test_full_size_interval_row_pair_ranges_equal_the_staged_kernel(GTPI, shape)
             u, v = got[2.0].view(np.uint64), got[0.0].view(np.uint64)
             same = (u == v) | (np.isnan(got[2.0]) & np.isnan(got[0.0]))
             assert np.all(same), (shape, int((~same).sum()), got[2.0][~same][:4], got[0.0][~same][:4])
-            if os.environ.get("GFT_RB_PAIRS_CAP_MB") is None:  # (the verification matrix also runs this with other caps)
-                assert genfer_amd.pool_stats()["in_use"] < (3 << 30)  # (operands, results and a workspace of at most 2 GiB)
+            assert genfer_amd.pool_stats()["in_use"] < (3 << 30)  # (operands, results and a workspace of at most 2 GiB)
     finally:
         L.gft_set_option(b"host_max_elems", -1.0)
 
