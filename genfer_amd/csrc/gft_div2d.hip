@@ -785,7 +785,7 @@ __device__ inline typename E::V row_product(typename E::V a, typename E::V b, un
 
 template <class E>
 struct DwfCfg {
-    static constexpr unsigned NW = E::W == 1 ? 16 : 8;  // waves per task (the LDS stages of an interval task are twice as large)
+    static constexpr unsigned NW = E::W == 1 ? WF_NW_F64 : WF_NW_INTERVAL;  // waves per task (gft_wavefront_plan.hpp)
 };
 // Quotient rows start out as this bit pattern (a NaN payload no arithmetic produces): a consumer loads a source row with
 // ONE coherent load — requested a batch ahead — and sees from the row itself whether its producer has stored it (every

@@ -58,6 +58,10 @@ struct SegWfArgs {
     size_t qbp;
 };
 
+// Waves of a workgroup of these kernels = source rows of one batch (every wave takes one source row of its task, wave 0 adds the
+// batch's row products in order); the LDS stages of an interval task are twice as large, hence half as many.
+constexpr unsigned WF_NW_F64 = 16, WF_NW_INTERVAL = 8;
+
 enum WfOp { WF_DIV = 0, WF_LOG = 1, WF_EXP = 2 };  // (the kernels' mode / log_mode values)
 enum WfFamily {
     WF_NONE,        // no wavefront for this shape: the caller runs the blocked recurrence

@@ -1407,7 +1407,8 @@ WAVEFRONT_SHAPES = [
 def test_div_row_wavefront_bit_exact(zs, ys, xs, OTP, GTP, OTPI, GTPI, tier):
     """The division as a row wavefront (one launch, every quotient row a task of one wave, dependencies through per-row
     flags) consumes its terms in the reference's order (mt:1162-1192 over mt:984-1012): bit-exact against the oracle,
-    and identical to the slab-by-slab blocked recurrence (`div_wavefront` = 0); finite, non-finite and interval data."""
+    and identical to the slab-by-slab blocked recurrence (`div_wavefront` = 0); finite, non-finite and interval data.
+    (exp's other order on these kernels, `rev` = 1: test_exp_arrival_order_gpu.py.)"""
     import genfer_amd
 
     L = genfer_amd.lib()
