@@ -1,6 +1,6 @@
 // ------------------------------------------------------------------------------------------
-// batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow, and their
-// Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
+// batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow / corr / compose_adj,
+// and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -47,17 +47,32 @@ static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_
     return true;
 }
 
-// `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; may be null); pow has neither, and `e`
+// `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; may be null); pow has neither, and `e`.
+// corr (x is g, y is y, n is m) and compose_adj (x is gh, y is g, n is nf) are the transposed operations: their result is the SHORT
+// side, so nx bounds n and ny, and the rows the planner sizes are the nx long ones.
 static int series_call(int op, const char* fn, const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
                        double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int w = 1) {
-    const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE;
+    const bool corr = op == gft::SERIES_CORR, adj = op == gft::SERIES_COMPOSE_ADJ, transposed = corr || adj;
+    const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE || transposed;
     const std::string f(fn);
-    if (n == 0) throw Error(f + ": n == 0 (the result has no coefficients)");
-    if (n > gft::series_max_n(w))
-        throw Error(f + ": n = " + std::to_string(n) + " exceeds the limit of " + std::to_string(gft::series_max_n(w)) + " coefficients per series of this version");
-    if (nx == 0 || (binary && ny == 0)) throw Error(f + ": an operand has no coefficients");
-    if (nx > n) throw Error(f + ": nx = " + std::to_string(nx) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
-    if (binary && ny > n) throw Error(f + ": ny = " + std::to_string(ny) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
+    if (transposed) {
+        const char* nl = corr ? "ng" : "n";   // the long side (x)
+        const char* ns = corr ? "ny" : "ng";  // the second operand
+        const char* nr = corr ? "m" : "nf";   // the result
+        if (n == 0) throw Error(f + ": " + nr + " == 0 (the result has no coefficients)");
+        if (nx > gft::series_max_n(w))
+            throw Error(f + ": " + nl + " = " + std::to_string(nx) + " exceeds the limit of " + std::to_string(gft::series_max_n(w)) + " coefficients per series of this version");
+        if (nx == 0 || ny == 0) throw Error(f + ": an operand has no coefficients");
+        if (n > nx) throw Error(f + ": " + nr + " = " + std::to_string(n) + " > " + nl + " = " + std::to_string(nx) + " (the result of a transposed operation is its short side)");
+        if (ny > nx) throw Error(f + ": " + ns + " = " + std::to_string(ny) + " > " + nl + " = " + std::to_string(nx) + " (an operand is longer than the truncation order)");
+    } else {
+        if (n == 0) throw Error(f + ": n == 0 (the result has no coefficients)");
+        if (n > gft::series_max_n(w))
+            throw Error(f + ": n = " + std::to_string(n) + " exceeds the limit of " + std::to_string(gft::series_max_n(w)) + " coefficients per series of this version");
+        if (nx == 0 || (binary && ny == 0)) throw Error(f + ": an operand has no coefficients");
+        if (nx > n) throw Error(f + ": nx = " + std::to_string(nx) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
+        if (binary && ny > n) throw Error(f + ": ny = " + std::to_string(ny) + " > n = " + std::to_string(n) + " (an operand is longer than the truncation order)");
+    }
     if (nbatch > 32) throw Error(f + ": more than 32 batch axes");
     if (nbatch && !batch) throw Error(f + ": the batch shape is a null pointer");
     size_t items = 1;
@@ -67,8 +82,8 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         if (items >= ((size_t)1 << 31)) throw Error(f + ": more than 2^31 - 1 series in one call");
     }
     const bool comp = op == gft::SERIES_COMPOSE;
-    SeriesArg ax = series_arg(fn, comp ? "f" : "x", x, xbs, nx, batch, nbatch, w);
-    SeriesArg ay = series_arg(fn, comp ? "g" : (binary ? "y" : "the seeds"), y, ybs, binary ? ny : 1, batch, nbatch, w);
+    SeriesArg ax = series_arg(fn, comp ? "f" : (corr ? "g" : (adj ? "gh" : "x")), x, xbs, nx, batch, nbatch, w);
+    SeriesArg ay = series_arg(fn, comp || adj ? "g" : (binary ? "y" : "the seeds"), y, ybs, binary ? ny : 1, batch, nbatch, w);
     SeriesArg ar = series_arg(fn, "the result", res, rbs, n, batch, nbatch, w);
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
@@ -106,7 +121,8 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         throw Error(f + ": the result partially overlaps " + a.what + " (it may alias an operand only as the same view)");
     };
     overlap(ax, true);
-    if (binary) overlap(ay, true);
+    if (transposed) overlap(ay, false);  // corr's result may be g itself, compose_adj's gh; neither may be the second operand
+    else if (binary) overlap(ay, true);
     else if (y) overlap(ay, false);
     // collapse the batch: unit axes go, axes contiguous with their inner neighbour on every operand merge
     gft::SeriesBatch g;
@@ -145,7 +161,7 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
     pl.y = binary ? ay.plane : 0;
     pl.s = seeds ? ay.plane : 0;
     pl.r = ar.plane;
-    const int form = op == gft::SERIES_POW ? gft::SERIES_NONE : gft::series_plan(op, g.items, (unsigned)n, R.series_force, w);
+    const int form = op == gft::SERIES_POW ? gft::SERIES_NONE : gft::series_plan(op, g.items, (unsigned)(transposed ? nx : n), R.series_force, w);
     const size_t wsn = gft::series_workspace(op, form, g.items, (unsigned)nx, (unsigned)n, w);
     Rc<Buf> ws;
     if (wsn) ws = alloc_doubles(wsn);  // (returned to the pool on exit: later launches follow these on the one stream)
@@ -185,6 +201,14 @@ int gft_series_compose(const double* f, const int64_t* fbs, size_t nf, const dou
 int gft_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
                    const size_t* batch, size_t nbatch, void* stream) {
     return guard_int([&] { return series_call(gft::SERIES_POW, "series_pow", x, xbs, nx, nullptr, nullptr, 1, res, rbs, n, batch, nbatch, stream, e); });
+}
+int gft_series_corr(const double* g, const int64_t* gbs, size_t ng, const double* y, const int64_t* ybs, size_t ny, double* res,
+                    const int64_t* rbs, size_t m, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_CORR, "series_corr", g, gbs, ng, y, ybs, ny, res, rbs, m, batch, nbatch, stream); });
+}
+int gft_series_compose_adj(const double* gh, const int64_t* hbs, size_t n, const double* g, const int64_t* gbs, size_t ng, double* res,
+                           const int64_t* rbs, size_t nf, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series_call(gft::SERIES_COMPOSE_ADJ, "series_compose_adj", gh, hbs, n, g, gbs, ng, res, rbs, nf, batch, nbatch, stream); });
 }
 // Interval<F64>: the same calls on (lo, hi) planes; every stride array has nbatch + 1 entries, the plane stride first
 int gfti_series_mul(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny, double* res,

@@ -20,6 +20,10 @@
 // and g in LDS, every step mul form B's balanced product, steps separated by an LDS-only barrier.  pow has no kernel of its
 // own: series_pow plans a sequence of mul launches on workspace rows.
 //
+// corr (the transposed product, the adjoint of mul; f64 only) has mul's two forms with the roles turned round: form A's outputs
+// overwrite g's row from the bottom up, form B's wave walks the offset k - i downwards in lock step.  compose_adj (the transposed
+// Horner loop) is compose form B run backwards; it has no form A.
+//
 // Every function below is a template over the element functor: EF64 serves gft_series_*, EIv (Interval<F64>, the planes lo and hi
 // a plane stride apart on every operand) gfti_series_*.  The entry points of gft_series.hpp pick the instantiation by the width.
 #include <hip/hip_runtime.h>
@@ -63,11 +67,14 @@ template <class E>
 struct Granted {
     static unsigned budget_kb;  // 0: not asked yet
     static int compose_b_big;   // -1: not asked yet
+    static int compose_adj_big;
 };
 template <class E>
 unsigned Granted<E>::budget_kb = 0;
 template <class E>
 int Granted<E>::compose_b_big = -1;
+template <class E>
+int Granted<E>::compose_adj_big = -1;
 
 // largest odd pitch >= n, and the waves per workgroup the budget allows for it (0: the rows do not fit form A)
 // (`arrays` of E::W planes of 64 * pitch doubles per wave: arrays * E::W * pitch / 2 KB)
@@ -85,7 +92,7 @@ unsigned budget_kb() {
     unsigned& kb = Granted<E>::budget_kb;
     if (kb) return kb;
     const void* ks[] = {(const void*)k_series_mul_a<E>, (const void*)k_series_div_a<E>, (const void*)k_series_explog_a<E, false>,
-                        (const void*)k_series_explog_a<E, true>, (const void*)k_series_compose_a<E>};
+                        (const void*)k_series_explog_a<E, true>, (const void*)k_series_compose_a<E>, (const void*)k_series_corr_a<E>};
     kb = SA_BUDGET_KB;
     for (const void* k : ks)
         if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SA_BUDGET_KB * 1024) != hipSuccess) {
@@ -103,6 +110,18 @@ bool compose_b_big() {
     int& big = Granted<E>::compose_b_big;
     if (big < 0) {
         big = hipFuncSetAttribute((const void*)k_series_compose_b<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  3 * E::W * series_max_n(E::W) * sizeof(double)) == hipSuccess;
+        if (!big) (void)hipGetLastError();
+    }
+    return big != 0;
+}
+
+// compose_adj's request is the same: two rows of gh and g
+template <class E>
+bool compose_adj_big() {
+    int& big = Granted<E>::compose_adj_big;
+    if (big < 0) {
+        big = hipFuncSetAttribute((const void*)k_series_compose_adj_b<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   3 * E::W * series_max_n(E::W) * sizeof(double)) == hipSuccess;
         if (!big) (void)hipGetLastError();
     }
@@ -155,6 +174,7 @@ void ws_copy(hipStream_t st, const double* src, double* dst, const SeriesBatch& 
 
 template <class E>
 int plan(int op, unsigned items, unsigned n, int force) {
+    if (op == SERIES_COMPOSE_ADJ) return SERIES_FORM_B;  // its one form
     const bool fits = form_a_waves<E>(n, budget_kb<E>(), op_arrays(op)) != 0;
     if (!fits || force == SERIES_FORM_B) return SERIES_FORM_B;
     if (force == SERIES_FORM_A) return SERIES_FORM_A;
@@ -167,21 +187,24 @@ void launch(hipStream_t st, int op, int form, const double* x, unsigned nx, cons
             const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
     if (g.items == 0) return;
     if (form == SERIES_FORM_A) {
-        const unsigned pitch = n | 1;
+        const unsigned rows = op == SERIES_CORR ? nx : n;  // the longest row a lane holds (corr: g, its result is shorter)
+        const unsigned pitch = rows | 1;
         const unsigned arrays = op_arrays(op);
-        unsigned waves = form_a_waves<E>(n, budget_kb<E>(), arrays);
-        if (waves == 0) throw std::runtime_error("series: rows of " + std::to_string(n) + " coefficients do not fit form A");
+        unsigned waves = form_a_waves<E>(rows, budget_kb<E>(), arrays);
+        if (waves == 0) throw std::runtime_error("series: rows of " + std::to_string(rows) + " coefficients do not fit form A");
         const unsigned wave_items = (g.items + 63) / 64;
         waves = std::min(waves, wave_items);
         if (waves == 3) waves = 2;
         unsigned lg = 0;  // lanes per row while staging: the smallest power of two >= n, at most 64
-        while (lg < 6 && (1u << lg) < n) ++lg;
+        while (lg < 6 && (1u << lg) < rows) ++lg;
         const dim3 grid((wave_items + waves - 1) / waves), block(64 * waves);
         const size_t lds = (size_t)waves * arrays * E::W * 64 * pitch * sizeof(double);
         switch (op) {
             case SERIES_MUL: GFT_LAUNCH(k_series_mul_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
             case SERIES_DIV: GFT_LAUNCH(k_series_div_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
             case SERIES_COMPOSE: GFT_LAUNCH(k_series_compose_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
+            case SERIES_CORR: GFT_LAUNCH(k_series_corr_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
+            case SERIES_COMPOSE_ADJ: throw std::runtime_error("series: compose_adj has no form A");
             case SERIES_EXP: GFT_LAUNCH((k_series_explog_a<E, false>), grid, block, lds, st, x, pl.x, nx, y, pl.s, res, pl.r, n, pitch, lg, g); break;
             default: GFT_LAUNCH((k_series_explog_a<E, true>), grid, block, lds, st, x, pl.x, nx, y, pl.s, res, pl.r, n, pitch, lg, g); break;
         }
@@ -196,6 +219,25 @@ void launch(hipStream_t st, int op, int form, const double* x, unsigned nx, cons
         const unsigned shares = g.inplace ? 1u : (half + threads - 1) / threads;
         GFT_LAUNCH(k_series_mul_b<E>, dim3(g.items, shares), dim3(threads), (size_t)E::W * ((size_t)nx + ny) * sizeof(double), st, x, pl.x, nx,
                    y, pl.y, ny, res, pl.r, n, g);
+        return;
+    }
+    if (op == SERIES_CORR) {  // mul's geometry over the m = n outputs
+        const unsigned half = (n + 1) / 2;
+        const bool spread = !g.inplace && g.items < SA_MIN_ITEMS;
+        const unsigned threads = spread ? 64u : std::min(256u, (half + 63) / 64 * 64);
+        const unsigned shares = g.inplace ? 1u : (half + threads - 1) / threads;
+        GFT_LAUNCH(k_series_corr_b<E>, dim3(g.items, shares), dim3(threads), (size_t)E::W * ((size_t)nx + ny) * sizeof(double), st, x, pl.x, nx,
+                   y, pl.y, ny, res, pl.r, n, g);
+        return;
+    }
+    if (op == SERIES_COMPOSE_ADJ) {  // x = gh (nx = the order n), y = g, n = nf outputs
+        const unsigned full = (n - 1) * (ny - 1) + 1, l0 = std::min(full, nx);
+        const unsigned threads = std::min(256u, ((l0 + 1) / 2 + 63) / 64 * 64);
+        const size_t rows = (size_t)2 * E::W * l0 * sizeof(double), all = rows + (size_t)E::W * ny * sizeof(double);
+        if (all <= 64 * 1024 || compose_adj_big<E>())
+            GFT_LAUNCH((k_series_compose_adj_b<E, true>), dim3(g.items), dim3(threads), all, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
+        else
+            GFT_LAUNCH((k_series_compose_adj_b<E, false>), dim3(g.items), dim3(threads), rows, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
         return;
     }
     if (op == SERIES_COMPOSE) {

@@ -19,7 +19,21 @@
 
 namespace gft {
 
-enum SeriesOp { SERIES_MUL = 0, SERIES_DIV = 1, SERIES_EXP = 2, SERIES_LOG = 3, SERIES_COMPOSE = 4, SERIES_POW = 5 };
+enum SeriesOp {
+    SERIES_MUL = 0,
+    SERIES_DIV = 1,
+    SERIES_EXP = 2,
+    SERIES_LOG = 3,
+    SERIES_COMPOSE = 4,
+    SERIES_POW = 5,
+    // The transposed product, the adjoint of mul (f64 only): c[i] = 0 + sum_k g[k] * y[k-i], k DESCENDING from min(ng-1, i+ny-1) to i,
+    // i < m <= ng -- bit for bit mul_1d(flip(g), y) at index ng-1-i.  x is g (nx = ng: the LONG side), y is y (ny <= ng), n is m.
+    SERIES_CORR = 6,
+    // The transposed Horner loop, the gradient of compose with respect to f (f64 only): a_0 = gh[0 .. l_0), out[i] = a_i[0],
+    // a_{i+1} = corr(a_i, g) at the lengths l_i = min(1 + (nf-1-i)(ng-1), n).  x is gh (nx = n), y is g (ny = ng <= n), n is nf <= nx.
+    // One form (B: one workgroup per series for the whole loop).
+    SERIES_COMPOSE_ADJ = 7
+};
 // A: one lane is one series, rows staged in LDS.  B: one wave / workgroup is one series (mul, div, compose); for exp / log the
 // lane-per-series loop of form A over a transposed global workspace.  pow is a sequence of mul launches, each planned by itself.
 enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
@@ -54,6 +68,7 @@ int series_plan(int op, unsigned items, unsigned n, int force, int w = 1);
 size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n, int w = 1);
 // Launches the call on `st`.  `y`: the second operand of mul / div / compose (x is f, y is g); for exp / log the seeds or nullptr
 // (seeds formed on the device by the HIP device library's exp / log).  `ws`: series_workspace() doubles.  Not for SERIES_POW.
+// corr and compose_adj: the result is the SHORT side, n <= nx, and series_plan takes the long side nx (the rows held in LDS).
 void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
                    unsigned n, const SeriesBatch& g, double* ws, const SeriesPlanes& pl = SeriesPlanes());
 // x^e on `st`: x is copied once into the workspace, every product but the last is a mul launch on workspace rows of the compact

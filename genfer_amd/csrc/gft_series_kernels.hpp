@@ -1,7 +1,7 @@
 // Device side of the batched series (gft_series.hip plans and launches these): the per-lane recurrences, form A's LDS
 // staging and the kernels, as templates over the element functor (gft_elem.hpp) so that an interval twin is an instantiation.
 // tests/series_isa_check.hip instantiates the form-A mul and div kernels from this file alone, tests/series_compose_isa_check.hip
-// the two compose kernels.
+// the two compose kernels, tests/series_corr_isa_check.hip the transposed products (corr forms A and B, compose_adj).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,6 +50,20 @@ __device__ inline void rec_horner_step(const AR r, const AG g, unsigned lr, unsi
 #pragma unroll 4
         for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(r.ld(j), g.ld(k - j)));
         r.st(k, sum);
+    }
+}
+// The transposed product, c[i] = 0 + sum_k g[k] * y[k-i] with k DESCENDING from min(ng-1, i+ny-1) to i: the sums of mul_1d on the
+// flipped row, z = flip(g) * y at index ng-1-i in ascending j = ng-1-k, so <mul(x, y), g> = <x, corr(g, y)> term for term.  i runs
+// upwards and c[i] overwrites g[i]: the outputs still to come read g[i+1 ..] only.
+template <class E, class AG, class AY>
+__device__ inline void rec_corr(const AG g, const AY y, unsigned ng, unsigned ny, unsigned m) {
+    typedef typename E::V V;
+    for (unsigned i = 0; i < m; ++i) {
+        const unsigned top = ng - i < ny ? ng - i : ny;  // terms of this output
+        V sum = E::zero();
+#pragma unroll 4
+        for (unsigned d = top; d-- > 0;) sum = E::add(sum, E::mul(g.ld(i + d), y.ld(d)));
+        g.st(i, sum);
     }
 }
 // r[k] = (-(0 + sum_{j = lo .. k-1} r[j] * y[k-j]) + x[k]) / y[0] (div, mt:1162-1192 at one axis); r holds x on entry.
@@ -168,6 +182,21 @@ __global__ __launch_bounds__(256) void k_series_div_a(const double* x, size_t xp
     rec_div<E>(RowLds<E>{f.a0 + f.lane * pitch, f.lp}, RowLds<E>{f.a1 + f.lane * pitch, f.lp}, nx, ny, n);
     __syncthreads();
     stage_rows<E, false>(f.a1, f.lp, pitch, res, rp, o.r, n, lg, f.item0, g.items, f.lane);
+}
+
+// corr, c = the transposed product of g (ng coefficients) and y (ny <= ng), m <= ng outputs: c overwrites g's row from the bottom up
+template <class E>
+__global__ __launch_bounds__(256) void k_series_corr_a(const double* g, size_t gp, unsigned ng, const double* y, size_t yp, unsigned ny,
+                                                       double* res, size_t rp, unsigned m, unsigned pitch, unsigned lg, SeriesBatch b) {
+    extern __shared__ double sa_lds[];
+    const FormA f = form_a<E>(sa_lds, pitch, b.items);
+    const SeriesOff o = series_offsets(b, f.it);
+    stage_rows<E, true>(f.a0, f.lp, pitch, const_cast<double*>(g), gp, o.x, ng, lg, f.item0, b.items, f.lane);
+    stage_rows<E, true>(f.a1, f.lp, pitch, const_cast<double*>(y), yp, o.y, ny, lg, f.item0, b.items, f.lane);
+    __syncthreads();
+    rec_corr<E>(RowLds<E>{f.a0 + f.lane * pitch, f.lp}, RowLds<E>{f.a1 + f.lane * pitch, f.lp}, ng, ny, m);
+    __syncthreads();
+    stage_rows<E, false>(f.a0, f.lp, pitch, res, rp, o.r, m, lg, f.item0, b.items, f.lane);
 }
 
 // exp (LOG == false) / log: `seed` holds exp(x[0]) / ln(x[0]) per item, or is null: formed here by the device library
@@ -296,6 +325,95 @@ __global__ __launch_bounds__(256) void k_series_compose_b(const double* f, size_
     }
     __syncthreads();  // (every global load of this workgroup is done: the result may be f or g)
     for (unsigned k = threadIdx.x; k < n; k += blockDim.x) E::st(res + o.r, rp, k, k < lr ? E::ld(r0, n, k) : E::zero());
+}
+
+// ---- the transposed product in form B -------------------------------------------------------------------------------------------
+// One output of corr over a staged row pair: c[i] = 0 + sum_d g[i+d] * y[d], d = k - i descending.  The wave walks d in lock step
+// from the highest offset any of its outputs [i_lo, i_hi] has, so y[d] is one address for the wave and g[i+d] consecutive across
+// lanes; a lane whose row ends below i + d forms no term and performs no addition (down to d_all every lane has one: no guard).
+// i_lo, i_hi are the same in every lane of the wave.
+template <class E>
+__device__ inline typename E::V corr_sum(const double* gl, size_t gplane, unsigned ng, const double* yl, size_t yplane, unsigned ny,
+                                         unsigned i, unsigned i_lo, unsigned i_hi) {
+    typedef typename E::V V;
+    const unsigned top = ng - i_lo < ny ? ng - i_lo : ny, all = ng - i_hi < ny ? ng - i_hi : ny;  // offsets below: some lane's, every lane's
+    const unsigned d_top = __builtin_amdgcn_readfirstlane(top), d_all = __builtin_amdgcn_readfirstlane(all);
+    V sum = E::zero();
+    unsigned d = d_top;
+    for (; d > d_all; --d)
+        if (i + d - 1 < ng) sum = E::add(sum, E::mul(E::ld(gl, gplane, i + d - 1), E::ld(yl, yplane, d - 1)));
+#pragma unroll 4
+    for (; d > 0; --d) sum = E::add(sum, E::mul(E::ld(gl, gplane, i + d - 1), E::ld(yl, yplane, d - 1)));
+    return sum;
+}
+// The outputs of one wave's turn: thread t owns i = t and i = m - 1 - t (together about the same number of terms whatever t), t
+// counted from the wave's t0 and below `half` = (m + 1) / 2.  fn(i, sum) stores.
+template <class E, class F>
+__device__ inline void corr_pairs(const double* gl, size_t gplane, unsigned ng, const double* yl, size_t yplane, unsigned ny, unsigned m,
+                                  unsigned half, unsigned t0, unsigned lane, F fn) {
+    const unsigned t = t0 + lane, last = t0 + 63 < half ? t0 + 63 : half - 1;
+    if (t >= half) return;
+    fn(t, corr_sum<E>(gl, gplane, ng, yl, yplane, ny, t, t0, last));
+    const unsigned i = m - 1 - t;
+    if (i != t) fn(i, corr_sum<E>(gl, gplane, ng, yl, yplane, ny, i, m - 1 - last, m - 1 - t0));  // (not the middle output of an odd m again)
+}
+
+// corr: blockIdx.x is the item, blockIdx.y a share of its outputs, as in k_series_mul_b.  A series may be shared by several
+// workgroups only when `res` is not g (b.inplace == 0): each stages the whole row pair before it stores.
+template <class E>
+__global__ __launch_bounds__(256) void k_series_corr_b(const double* g, size_t gp, unsigned ng, const double* y, size_t yp, unsigned ny,
+                                                       double* res, size_t rp, unsigned m, SeriesBatch b) {
+    extern __shared__ double sb_lds[];  // [plane][ng] | [plane][ny]
+    double* gl = sb_lds;
+    double* yl = sb_lds + (size_t)E::W * ng;
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    for (unsigned i = threadIdx.x; i < ng; i += blockDim.x) E::st(gl, ng, i, E::ld(g + o.x, gp, i));
+    for (unsigned i = threadIdx.x; i < ny; i += blockDim.x) E::st(yl, ny, i, E::ld(y + o.y, yp, i));
+    __syncthreads();  // (every global load of this workgroup is done)
+    const unsigned half = (m + 1) / 2, lane = threadIdx.x & 63;
+    for (unsigned t0 = blockIdx.y * blockDim.x + (threadIdx.x - lane); t0 < half; t0 += gridDim.y * blockDim.x)
+        corr_pairs<E>(gl, ng, ng, yl, ny, ny, m, half, t0, lane, [&](unsigned i, typename E::V sum) { E::st(res + o.r, rp, i, sum); });
+}
+
+// compose_adj, the transposed Horner loop (the gradient of compose with respect to f): a_0 = gh[0 .. l_0), out[i] = a_i[0],
+// a_{i+1} = corr(a_i, g) at the compact lengths l_i = min(1 + (nf-1-i)(ng-1), n) of the forward loop run backwards.  The mirror of
+// k_series_compose_b: one workgroup per series for the whole loop, two rows in LDS taking turns, g behind them (GLDS) or in global
+// memory (the 64 KB fallback), steps separated by an LDS-only barrier; the owner of output 0 stores out[i+1].  gh and (GLDS) g are
+// read completely before the first store, so the result may be gh itself; it is never g (the host refuses that).
+template <class E, bool GLDS>
+__global__ __launch_bounds__(256) void k_series_compose_adj_b(const double* gh, size_t hp, unsigned n, const double* g, size_t gp, unsigned ng,
+                                                              double* res, size_t rp, unsigned nf, SeriesBatch b) {
+    extern __shared__ double sb_lds[];  // [plane][l0] | [plane][l0] | [plane][ng]
+    const unsigned full = (nf - 1) * (ng - 1) + 1, l0 = full < n ? full : n;
+    double* r0 = sb_lds;
+    double* r1 = sb_lds + (size_t)E::W * l0;
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    const double* gsrc = g + o.y;
+    size_t gplane = gp;
+    if (GLDS) {
+        double* gl = sb_lds + (size_t)2 * E::W * l0;
+        for (unsigned i = threadIdx.x; i < ng; i += blockDim.x) E::st(gl, ng, i, E::ld(g + o.y, gp, i));
+        gsrc = gl;
+        gplane = ng;
+    }
+    for (unsigned i = threadIdx.x; i < l0; i += blockDim.x) E::st(r0, l0, i, E::ld(gh + o.x, hp, i));
+    __syncthreads();  // (every global load of gh is done)
+    if (threadIdx.x == 0) E::st(res + o.r, rp, 0, E::ld(r0, l0, 0));
+    const unsigned lane = threadIdx.x & 63, w0 = threadIdx.x - lane;
+    unsigned li = l0;
+    for (unsigned i = 0; i + 1 < nf; ++i) {
+        const unsigned rest = (nf - 2 - i) * (ng - 1) + 1, ln = rest < n ? rest : n, half = (ln + 1) / 2;  // l_{i+1}
+        for (unsigned t0 = w0; t0 < half; t0 += blockDim.x)
+            corr_pairs<E>(r0, l0, li, gsrc, gplane, ng, ln, half, t0, lane, [&](unsigned p, typename E::V sum) {
+                E::st(r1, l0, p, sum);
+                if (p == 0) E::st(res + o.r, rp, i + 1, sum);
+            });
+        lds_barrier();
+        double* sw = r0;
+        r0 = r1;
+        r1 = sw;
+        li = ln;
+    }
 }
 
 // the rows [1, 0, ..., 0] of pow: its first factor (one row: items == 1) and the whole result of e == 0

@@ -1,4 +1,5 @@
-"""Batched univariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` (``gft_series_*``).
+"""Batched univariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the transposed
+product ``corr`` (``gft_series_*``), the first six differentiable by torch's autograd.
 
 The last axis of every tensor is the series (coefficient ``k`` of ``t^k`` at index ``k``, unit stride), the leading axes are
 batch axes and broadcast by torch's rules (``expand``, no copy: one series against a whole batch has batch stride 0).
@@ -13,6 +14,15 @@ never depends on what else is in the batch.  The call is ordered on torch's curr
     >>> e = series.exp(x, seed=torch.exp(x[..., 0]))
     >>> h = series.compose(f, g)         # f(g(t)) per item: Horner over f's coefficients, one launch
     >>> p = series.pow(x, 5)             # square-and-multiply over mul
+
+Gradients: when grad mode is on and an operand has ``requires_grad=True`` the six operations record a ``grad_fn`` (forward values
+are the same bits either way).  Every backward pass is a short sequence of calls of this module around ``corr``, the adjoint of the
+truncated product, ``<mul(x, y), g> = <x, corr(g, y)>``; ``compose`` adds one kernel, the transposed Horner loop.  First derivatives
+only (``once_differentiable``), float64 only; ``out=`` cannot be combined with an operand that requires grad, and a ``seed`` never
+carries a gradient (it is ``exp(x[..., 0])`` / ``ln(x[..., 0])`` by contract: the gradient flows to ``x``).
+
+    >>> w = torch.rand(8, dtype=torch.float64, device="cuda", requires_grad=True)
+    >>> series.compose(w, g).sum().backward()   # w.grad: one launch of the transposed Horner loop, summed over the batch
 
 ``compose`` costs about ``nf * n**2 / 2`` multiply-adds per item and a series never leaves its one workgroup (the Horner steps
 are a dependency chain), so a few long series are slow by construction; no cap is imposed.
@@ -36,7 +46,7 @@ def _lib():
         L = lib()
         i64, sz, vp = C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.c_void_p
         for pre in ("gft_series_", "gfti_series_"):  # the interval twins (interval_series.py) take the same argument lists
-            for name in ("mul", "div", "compose"):
+            for name in ("mul", "div", "compose") + (("corr", "compose_adj") if pre == "gft_series_" else ()):
                 f = getattr(L, pre + name)
                 f.restype, f.argtypes = C.c_int, [vp, i64, C.c_size_t, vp, i64, C.c_size_t, vp, i64, C.c_size_t, sz, C.c_size_t, vp]
             for name in ("exp", "log"):
@@ -85,14 +95,31 @@ def _order(what, n, *lens, max_n=None):
     return n
 
 
+def _order_short(what, n, ng, ny, names):
+    """corr / compose_adj: the result (``n`` coefficients, default ``ng``) is the short side of a transposed operation"""
+    if n is None:
+        n = ng
+    n = int(n)
+    if n < 1:
+        raise TaylorError(f"{what}: {names[2]} = {n}; the result needs at least one coefficient")
+    if ng > MAX_N:
+        raise TaylorError(f"{what}: {names[0]} has {ng} coefficients, which exceeds the limit of {MAX_N} per series of this version")
+    if n > ng:
+        raise TaylorError(f"{what}: {names[2]} = {n} > {ng}, the coefficients of {names[0]} (the result of a transposed operation is its short side)")
+    if ny > ng:
+        raise TaylorError(f"{what}: {names[1]} has {ny} coefficients, more than the {ng} of {names[0]}")
+    return n
+
+
 def _i64(seq):
     seq = [int(s) for s in seq]
     return (C.c_int64 * max(len(seq), 1))(*seq)
 
 
-def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), e=None, planes=0, max_n=None):
+def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), e=None, planes=0, max_n=None, short=False):
     """One call of either family.  planes = 1: the tensors are interval tensors [2, B..., n] (seeds [2, B...]); the leading
-    axis travels as the first entry of every stride array, which is where the gfti_series_* entry points expect it."""
+    axis travels as the first entry of every stride array, which is where the gfti_series_* entry points expect it.
+    short: a transposed operation (corr, compose_adj), whose result is no longer than its first operand; names[2] names it."""
     import torch
 
     _check(torch, x, f"{what}: {names[0]}", planes=planes)
@@ -101,7 +128,7 @@ def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), e=N
     if out is not None:
         _check(torch, out, f"{what}: out", planes=planes)
     lens = (x.shape[-1],) if second_is_seed or second is None else (x.shape[-1], second.shape[-1])
-    n = _order(what, n, *lens, max_n=max_n)
+    n = _order_short(what, n, *lens, names) if short else _order(what, n, *lens, max_n=max_n)
     for t in (second, out):
         if t is not None and t.device != x.device:
             raise TaylorError(f"{what}: the tensors are on different devices ({x.device}, {t.device})")
@@ -155,23 +182,31 @@ def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), e=N
 
 def mul(x, y, n=None, out=None):
     """``z[b] = x[b] * y[b]`` truncated at order ``n`` (default ``max(nx, ny)``): the general product ``mul_1d``."""
+    if _tracked("series.mul", (x, y), out):
+        return _autograd().Mul.apply(x, y, n)
     return _run("series.mul", "gft_series_mul", x, y, n, out, False)
 
 
 def div(x, y, n=None, out=None):
     """``r[b] = x[b] / y[b]`` to order ``n`` (default ``max(nx, ny)``): the general division recurrence."""
+    if _tracked("series.div", (x, y), out):
+        return _autograd().Div.apply(x, y, n)
     return _run("series.div", "gft_series_div", x, y, n, out, False)
 
 
 def exp(x, n=None, seed=None, out=None):
     """``exp(x[b])`` to order ``n`` (default ``nx``).  ``seed``: ``exp(x[b, 0])`` per item (a tensor of the batch shape); with
     the host libm's values the result carries the reference's bits.  ``None``: formed on the device (a few ulps from libm)."""
+    if _tracked("series.exp", (x,), out, seed):
+        return _autograd().Exp.apply(x, n, seed)
     return _run("series.exp", "gft_series_exp", x, seed, n, out, True)
 
 
 def log(x, n=None, seed=None, out=None):
     """``log(x[b])`` to order ``n`` (default ``nx``).  ``seed``: ``ln(x[b, 0])`` per item; ``None``: formed on the device (only
     coefficient 0 depends on it)."""
+    if _tracked("series.log", (x,), out, seed):
+        return _autograd().Log.apply(x, n, seed)
     return _run("series.log", "gft_series_log", x, seed, n, out, True)
 
 
@@ -180,7 +215,27 @@ def compose(f, g, n=None, out=None):
     product at every step, ``res = res * g + f[i]`` for ``i = nf-2 .. 0`` from ``res = [0.0 + f[nf-1]]`` — ``subst_var``'s general
     path without its zero / linear shortcuts, the row resident in LDS across the steps.  About ``nf * n**2 / 2`` multiply-adds per
     item, on one workgroup at most."""
+    if _tracked("series.compose", (f, g), out):
+        return _autograd().Compose.apply(f, g, n)
     return _run("series.compose", "gft_series_compose", f, g, n, out, False, names=("f", "g"))
+
+
+def corr(g, y, m=None, out=None):
+    """The transposed product, the adjoint of ``mul``: ``<mul(x, y), g> = <x, corr(g, y)>``.  ``g`` has ``ng`` coefficients, ``y``
+    has ``ny <= ng``, the result ``m <= ng`` (default ``ng``)::
+
+        c[b, i] = 0.0 + sum_k g[b, k] * y[b, k - i],   k descending from min(ng - 1, i + ny - 1) to i
+
+    multiply and add rounded separately, only stored coefficients entering a sum: bit for bit ``mul(flip(g), y)`` at index
+    ``ng - 1 - i``.  ``out`` may be ``g`` itself, never ``y``.  Not differentiable itself (the backward passes are built from it)."""
+    return _run("series.corr", "gft_series_corr", g, y, m, out, False, names=("g", "y", "m"), short=True)
+
+
+def _compose_adj(gh, g, nf, out=None):
+    """The transposed Horner loop: the gradient of ``compose(f, g, n)`` with respect to ``f`` (``nf`` coefficients) from the
+    gradient ``gh`` of the composition (``n`` coefficients) -- ``a = gh[:l_0]; out[0] = a[0];`` then ``a = corr(a, g, l_{i+1});
+    out[i + 1] = a[0]`` at the compact lengths ``l_i = min(1 + (nf - 1 - i)(ng - 1), n)``, in one launch."""
+    return _run("series._compose_adj", "gft_series_compose_adj", gh, g, nf, out, False, names=("gh", "g", "nf"), short=True)
 
 
 def _exponent(what, e, div="series.div"):
@@ -203,7 +258,163 @@ def _exponent(what, e, div="series.div"):
 def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     """``x[b] ** e`` truncated at order ``n`` (default ``nx``) for an integer ``0 <= e < 2**32``: the reference's
     square-and-multiply over ``mul`` at compact lengths.  ``e = 0`` gives ``[1, 0, ...]``."""
-    return _run("series.pow", "gft_series_pow", x, None, n, out, True, e=_exponent("series.pow", e))
+    e = _exponent("series.pow", e)
+    if _tracked("series.pow", (x,), out):
+        return _autograd().Pow.apply(x, e, n)
+    return _run("series.pow", "gft_series_pow", x, None, n, out, True, e=e)
+
+
+# ---- autograd ----------------------------------------------------------------------------------------------------------------
+# Every vector-Jacobian product below is a sequence of this module's own calls on detached tensors; `corr` carries the order of
+# its sums, so a gradient's bits are pinned up to the reduction over broadcast batch axes (sum_to_size: torch's order).
+
+
+def _tracked(what, operands, out, seed=None):
+    """Whether the call records a grad_fn: grad mode is on and an operand requires grad.  Refuses what cannot be differentiated."""
+    try:
+        import torch
+    except ImportError:  # the type check of _run reports it
+        return False
+    if not torch.is_grad_enabled():
+        return False
+    if isinstance(seed, torch.Tensor) and seed.requires_grad:
+        raise TaylorError(f"{what}: seed requires grad; the seed is exp(x[..., 0]) / ln(x[..., 0]) by contract and the gradient flows to x "
+                          "(pass seed.detach())")
+    if not any(isinstance(t, torch.Tensor) and t.requires_grad for t in operands):
+        return False
+    if out is not None:
+        raise TaylorError(f"{what}: out= cannot be combined with an operand that requires grad (the functions with out= do not support "
+                          "automatic differentiation)")
+    return True
+
+
+_functions = None
+
+
+def _autograd():
+    """The torch.autograd.Function of every operation (built on first use: this module imports without torch)."""
+    global _functions
+    if _functions is not None:
+        return _functions
+    import types
+
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def unit_stride(g):  # z.sum().backward() hands over an expanded scalar: stride 0 on the series axis
+        return g if g.shape[-1] == 1 or g.stride(-1) == 1 else g.contiguous()
+
+    def one(t):
+        return torch.ones(1, dtype=torch.float64, device=t.device)
+
+    class Mul(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, n):
+            x, y = x.detach(), y.detach()
+            ctx.save_for_backward(x, y)
+            return _run("series.mul", "gft_series_mul", x, y, n, None, False)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gz):
+            x, y = ctx.saved_tensors
+            gz = unit_stride(gz)
+            gx = corr(gz, y, x.shape[-1]).sum_to_size(x.shape) if ctx.needs_input_grad[0] else None
+            gy = corr(gz, x, y.shape[-1]).sum_to_size(y.shape) if ctx.needs_input_grad[1] else None
+            return gx, gy, None
+
+    class Div(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, n):
+            x, y = x.detach(), y.detach()
+            r = _run("series.div", "gft_series_div", x, y, n, None, False)
+            ctx.save_for_backward(r, y)
+            ctx.shapes = (x.shape, y.shape)
+            return r
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gr):
+            r, y = ctx.saved_tensors
+            xs, ys = ctx.shapes
+            n = r.shape[-1]
+            u = corr(unit_stride(gr), div(one(y), y, n), n)  # the gradient of the dividend at full length
+            gx = u[..., :xs[-1]].sum_to_size(xs) if ctx.needs_input_grad[0] else None
+            gy = (-corr(u, r, ys[-1])).sum_to_size(ys) if ctx.needs_input_grad[1] else None
+            return gx, gy, None
+
+    class Exp(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, n, seed):
+            x = x.detach()
+            e = _run("series.exp", "gft_series_exp", x, seed, n, None, True)
+            ctx.save_for_backward(e)
+            ctx.shape = x.shape
+            return e
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, ge):
+            (e,) = ctx.saved_tensors
+            return corr(unit_stride(ge), e, ctx.shape[-1]).sum_to_size(ctx.shape), None, None
+
+    class Log(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, n, seed):
+            x = x.detach()
+            ctx.save_for_backward(x)
+            return _run("series.log", "gft_series_log", x, seed, n, None, True)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gl):
+            (x,) = ctx.saved_tensors
+            n = gl.shape[-1]
+            return corr(unit_stride(gl), div(one(x), x, n), x.shape[-1]).sum_to_size(x.shape), None, None
+
+    class Pow(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, e, n):
+            x = x.detach()
+            ctx.save_for_backward(x)
+            ctx.e = e
+            return _run("series.pow", "gft_series_pow", x, None, n, None, True, e=e)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gp):
+            (x,) = ctx.saved_tensors
+            if ctx.e == 0:
+                return torch.zeros_like(x), None, None
+            n = gp.shape[-1]
+            return (ctx.e * corr(unit_stride(gp), pow(x, ctx.e - 1, n), x.shape[-1])).sum_to_size(x.shape), None, None
+
+    class Compose(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, f, g, n):
+            f, g = f.detach(), g.detach()
+            ctx.save_for_backward(f, g)
+            return _run("series.compose", "gft_series_compose", f, g, n, None, False, names=("f", "g"))
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gh):
+            f, g = ctx.saved_tensors
+            gh = unit_stride(gh)
+            n, nf = gh.shape[-1], f.shape[-1]
+            gf = gg = None
+            if ctx.needs_input_grad[0]:
+                gf = _compose_adj(gh, g, nf).sum_to_size(f.shape)
+            if ctx.needs_input_grad[1]:  # h = f(g): dh = f'(g) * dg
+                if nf > 1:
+                    fp = f[..., 1:] * torch.arange(1, nf, dtype=torch.float64, device=f.device)
+                else:
+                    fp = torch.zeros_like(f)
+                gg = corr(gh, compose(fp, g, n), g.shape[-1]).sum_to_size(g.shape)
+            return gf, gg, None
+
+    _functions = types.SimpleNamespace(Mul=Mul, Div=Div, Exp=Exp, Log=Log, Pow=Pow, Compose=Compose)
+    return _functions
 
 
 FORMS = {0: None, 1: "A", 2: "B"}

@@ -189,6 +189,23 @@ int gft_series_compose(const double* f, const int64_t* fbs, size_t nf, const dou
                        void* stream);                                   /* subst_var (Horner)     mt:540-580   */
 int gft_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
                    const size_t* batch, size_t nbatch, void* stream);   /* pow                    mt:433-451   */
+/* corr: the transposed product, the adjoint of mul in the truncated inner product, <mul(x, y), g> = <x, corr(g, y)> (f64 only; no
+ * gfti_ twin: a gradient of interval bounds is not defined).  g has ng <= 4096 coefficients, y has ny <= ng, the result m <= ng:
+ *   res[i] = 0.0 + sum_k g[k] * y[k - i],   k DESCENDING from min(ng - 1, i + ny - 1) to i,   i = 0 .. m - 1,
+ * multiply and add rounded separately, only stored operands entering a sum.  The descending order makes res[i] bit for bit
+ * mul_1d(flip(g), y) at index ng - 1 - i in the reference's ascending order.  The result may be g itself (the same view, m == ng);
+ * it may NOT overlap y (refused), and any other overlap is refused as for the other operations.
+ * compose_adj: the transposed Horner loop, the gradient of compose(f, g, n) with respect to f.  gh has n coefficients (the gradient
+ * of the composition), g has ng <= n, the result nf <= n.  With l_i = min(1 + (nf - 1 - i)(ng - 1), n), the compact lengths of the
+ * forward loop: a_0 = gh[0 .. l_0); res[i] = a_i[0]; a_{i+1}[p] = 0.0 + sum_k a_i[k] * g[k - p], k DESCENDING from
+ * min(l_i - 1, p + ng - 1) to p, p < l_{i+1} -- every step is corr at the compact lengths.  One kernel, one workgroup per series
+ * (gft_series_last_form() == 2).  The result may be gh itself (the same view, nf == n); it may NOT overlap g (refused). */
+int gft_series_corr(const double* g, const int64_t* gbs, size_t ng, const double* y, const int64_t* ybs, size_t ny,
+                    double* res, const int64_t* rbs, size_t m, const size_t* batch, size_t nbatch,
+                    void* stream);                                      /* mul_1d transposed                   */
+int gft_series_compose_adj(const double* gh, const int64_t* hbs, size_t n, const double* g, const int64_t* gbs, size_t ng,
+                           double* res, const int64_t* rbs, size_t nf, const size_t* batch, size_t nbatch,
+                           void* stream);                               /* subst_var (Horner) transposed       */
 /* The form the last gft_series_* call took: 1 = one lane per series (rows in LDS), 2 = one wave / workgroup per series (exp /
  * log: the lane-per-series loop over a transposed workspace; pow: the form of its last product), 0 = none yet.  gft_set_option("series_form", 1 | 2) asks for a
  * form (1 holds only where the rows fit the LDS budget; 0 = the library's thresholds).  Test / measurement aid. */

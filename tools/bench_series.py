@@ -16,7 +16,14 @@ lengths the definition uses.
 --interval: the same on interval tensors [2, B, n] (genfer_amd.interval_series against the IntervalTaylorPoly per-row loop), n
 capped at 2048; bytes and multiply-adds count interval elements (16 bytes, one interval multiply-add).
 
+--ops corr,backward (f64 only): `corr` times series.corr(g, y) at every shape against series.mul of the same (B, n) in the same
+process and against the three-call emulation torch.flip -> series.mul -> torch.flip (corr_over_mul, flip_over_corr).  `backward`
+times forward + backward of each of the six operations at --backward-shapes (compose with nf = min(n, 64)), and for compose the
+transposed Horner kernel against gf formed by a Python chain of nf - 1 series.corr calls: alone (adj_ms, chain_ms) and inside the
+same forward + backward (fb_chain_ms).
+
     python tools/bench_series.py > profiles/r07/series_batch.json
+    python tools/bench_series.py --ops corr,backward --no-loop > profiles/r10/series_autograd.json
     python tools/bench_series.py --ops compose,pow --shapes 4096x16,4096x64,65536x32,1024x256,64x1024x64,1x4096x16
 """
 import argparse
@@ -31,13 +38,15 @@ if ROOT not in sys.path:
 
 SHAPES = "4096x16,4096x64,65536x32,1024x256,64x1024,1x4096"
 OPS = "mul,div,exp,log"
-KNOWN_OPS = ("mul", "div", "exp", "log", "compose", "pow")
+KNOWN_OPS = ("mul", "div", "exp", "log", "compose", "pow", "corr", "backward")
+BACKWARD_SHAPES = "4096x64,65536x32,1024x256,64x1024"
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ops", default=OPS, help=f"comma-separated operations out of {','.join(KNOWN_OPS)} (default {OPS})")
     ap.add_argument("--shapes", default=SHAPES, help=f"comma-separated BxN cases, BxNxM for compose with nf = ng = M (default {SHAPES})")
+    ap.add_argument("--backward-shapes", default=BACKWARD_SHAPES, help=f"the BxN cases of --ops backward (default {BACKWARD_SHAPES})")
     ap.add_argument("--pow-e", type=int, default=5, help="the exponent of pow (default 5)")
     ap.add_argument("--form", choices=["auto", "A", "B"], default="auto", help="ask the library for a form (default: its thresholds)")
     ap.add_argument("--loop-rows", type=int, default=256, help="rows the per-row loop is timed on (scaled to B)")
@@ -48,6 +57,8 @@ def parse_args(argv=None):
     for op in args.ops.split(","):
         if op not in KNOWN_OPS:
             ap.error(f"unknown operation '{op}'")
+        if op in ("corr", "backward") and args.interval:
+            ap.error(f"'{op}' is f64 only")
     return args
 
 
@@ -98,6 +109,75 @@ def timed(torch, fn, budget_ms):
     return a.elapsed_time(b) / reps, reps
 
 
+def chain_adj(series, torch, gh, g, nf):
+    """compose_adj before it had a kernel: nf - 1 series.corr calls at the compact lengths, coefficient 0 of each collected"""
+    n, ng = gh.shape[-1], g.shape[-1]
+    ls = [min(1 + (nf - 1 - i) * (ng - 1), n) for i in range(nf)]
+    a = gh[..., :ls[0]]
+    out = torch.empty(gh.shape[:-1] + (nf,), dtype=torch.float64, device=gh.device)
+    out[..., 0] = a[..., 0]
+    for i in range(nf - 1):
+        a = series.corr(a, g[..., :min(ng, a.shape[-1])], ls[i + 1])
+        out[..., i + 1] = a[..., 0]
+    return out
+
+
+def bench_corr(torch, series, args, x, y, out, B, n):
+    t_corr, reps = timed(torch, lambda: series.corr(x, y, out=out), args.budget_ms)
+    form = series.last_form()
+    t_mul, _ = timed(torch, lambda: series.mul(x, y, out=out), args.budget_ms)
+    form_mul = series.last_form()
+    t_flip, _ = timed(torch, lambda: torch.flip(series.mul(torch.flip(x, [-1]), y), [-1]), args.budget_ms)
+    return {"op": "corr", "B": B, "n": n, "form": form, "mul_form": form_mul, "corr_ms": round(t_corr, 6), "corr_reps": reps,
+            "mul_ms": round(t_mul, 6), "flip_mul_flip_ms": round(t_flip, 6), "corr_over_mul": round(t_corr / t_mul, 3),
+            "flip_over_corr": round(t_flip / t_corr, 3), "GMACps": round(B * n * (n + 1) / 2.0 / (t_corr * 1e-3) / 1e9, 3)}
+
+
+def bench_backward(torch, series, args, B, n, gen, dev):
+    """forward + backward of each operation, one record a line"""
+    import math
+
+    x = (0.5 + torch.rand((B, n), dtype=torch.float64, generator=gen) / n).to(dev).requires_grad_()
+    y = (0.5 + torch.rand((B, n), dtype=torch.float64, generator=gen) / n).to(dev)
+    y[:, 0] += 2.0
+    y.requires_grad_()
+    gz = torch.rand((B, n), dtype=torch.float64, generator=gen).to(dev)
+    nf = min(n, 64)
+    seeds = {f: torch.tensor([getattr(math, f)(v) for v in x.detach()[:, 0].tolist()], dtype=torch.float64).to(dev) for f in ("exp", "log")}
+    calls = {"mul": lambda: series.mul(x, y), "div": lambda: series.div(x, y), "exp": lambda: series.exp(x, seed=seeds["exp"]),
+             "log": lambda: series.log(x, seed=seeds["log"]), "pow": lambda: series.pow(x, args.pow_e),
+             "compose": lambda: series.compose(x[:, :nf], y)}
+    recs = []
+    for op, call in calls.items():
+        def fb():
+            x.grad = y.grad = None
+            call().backward(gz)
+
+        def fwd():
+            with torch.no_grad():
+                call()
+
+        t_fb, reps = timed(torch, fb, args.budget_ms)
+        t_f, _ = timed(torch, fwd, args.budget_ms)
+        rec = {"op": "backward", "of": op, "B": B, "n": n, "forward_backward_ms": round(t_fb, 6), "reps": reps, "forward_ms": round(t_f, 6),
+               "backward_over_forward": round((t_fb - t_f) / t_f, 3)}
+        if op == "compose":
+            gd, yd = gz, y.detach()
+            t_adj, _ = timed(torch, lambda: series._compose_adj(gd, yd, nf), args.budget_ms)
+            t_chain, _ = timed(torch, lambda: chain_adj(series, torch, gd, yd, nf), args.budget_ms)
+            kernel = series._compose_adj
+            series._compose_adj = lambda gh, g, k: chain_adj(series, torch, gh, g, k)
+            try:
+                t_fbc, _ = timed(torch, fb, args.budget_ms)
+            finally:
+                series._compose_adj = kernel
+            rec.update({"nf": nf, "adj_ms": round(t_adj, 6), "chain_ms": round(t_chain, 6), "chain_over_adj": round(t_chain / t_adj, 3),
+                        "fb_chain_ms": round(t_fbc, 6), "fb_chain_over_fb": round(t_fbc / t_fb, 3)})
+        recs.append(rec)
+        print(json.dumps(rec), flush=True)
+    return recs
+
+
 def main(argv=None):
     args = parse_args(argv)
     import torch
@@ -131,6 +211,12 @@ def main(argv=None):
             y = torch.stack([y, y * (1.0 + 2.0**-30)])
         out = torch.empty((B, n) if not iv else (2, B, n), dtype=torch.float64, device=dev)
         for op in args.ops.split(","):
+            if op == "backward":  # its own shapes, below
+                continue
+            if op == "corr":
+                results.append(bench_corr(torch, series, args, x, y, out, B, n))
+                print(json.dumps(results[-1]), flush=True)
+                continue
             seed = None
             if op in ("exp", "log"):
                 seed = torch.tensor([getattr(math, op)(v) for v in x[..., 0].reshape(-1).cpu().tolist()], dtype=torch.float64)
@@ -202,8 +288,22 @@ def main(argv=None):
                 rec.update({"chain_ms": round(t_chain, 6), "chain_reps": reps_c, "chain_over_batched": round(t_chain / t_batch, 3)})
             results.append(rec)
             print(json.dumps(rec), flush=True)
+    if "backward" in args.ops.split(","):
+        for shape in args.backward_shapes.split(","):
+            B, n = (int(t) for t in shape.lower().split("x"))
+            results += bench_backward(torch, series, args, B, n, gen, dev)
     series.set_form(None)
     props = torch.cuda.get_device_properties(0)
+    corr_recs = [r for r in results if r["op"] == "corr"]
+    adj_recs = [r for r in results if "chain_over_adj" in r]
+    if corr_recs or adj_recs:  # the three comparisons of DESIGN 3.15: met (true) or missed (false), None where not run
+        print(json.dumps({"summary": "autograd",
+                          "max_corr_over_mul": max([r["corr_over_mul"] for r in corr_recs], default=None),
+                          "corr_no_slower_than_1.1x_mul": all(r["corr_over_mul"] <= 1.1 for r in corr_recs) if corr_recs else None,
+                          "min_flip_over_corr": min([r["flip_over_corr"] for r in corr_recs], default=None),
+                          "corr_faster_than_flip_mul_flip": all(r["flip_over_corr"] > 1.0 for r in corr_recs) if corr_recs else None,
+                          "min_chain_over_adj": min([r["chain_over_adj"] for r in adj_recs], default=None),
+                          "compose_adj_no_slower_than_chain": all(r["chain_over_adj"] >= 1.0 for r in adj_recs) if adj_recs else None}))
     print(json.dumps({"summary": True, "device": props.name, "asked_form": args.form, "interval": iv, "cases": len(results),
                       "min_ratio_B_ge_256": min([r["loop_over_batched"] for r in results if r["B"] >= 256 and "loop_over_batched" in r], default=None),
                       "min_ratio_B_lt_256": min([r["loop_over_batched"] for r in results if r["B"] < 256 and "loop_over_batched" in r], default=None),
