@@ -1,6 +1,7 @@
 // ------------------------------------------------------------------------------------------
 // batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow / corr / compose_adj,
 // and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
+// and the bivariate gft_series2_mul / div / exp / log (f64; the same validation with one row stride per operand: series2_call)
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -10,20 +11,24 @@ struct SeriesArg {  // one operand of a call: rows of `len` elements (unit strid
     const char* what;
     const double* p;
     size_t len;
+    size_t rows, rst;  // rank 2 (gft_series2_*): an item is `rows` such rows, `rst` elements apart; else 1 and 0
     size_t st[32];
     size_t plane;  // w == 2: elements from the lo plane to the hi plane (0 on an operand: a point interval), else 0
     size_t span;   // elements from p to one past its last element (of the hi plane)
 };
 
-// `bs`: nbatch strides, for w == 2 preceded by the plane stride
+// `bs`: nbatch strides, for w == 2 preceded by the plane stride.  rank 2: `rows` rows per item, `rst` elements apart.
 static SeriesArg series_arg(const char* fn, const char* what, const double* p, const int64_t* bs, size_t len, const size_t* batch, size_t nbatch,
-                            int w) {
+                            int w, size_t rows = 1, int64_t rst = 0) {
     SeriesArg a;
     a.what = what;
     a.p = p;
     a.len = len;
-    size_t cs = len;  // NULL: contiguous rows of the operand's own length (the planes back to back)
-    a.span = len;
+    if (rst < 0) throw Error(std::string(fn) + ": negative strides are not supported (" + what + ", the row axis)");
+    a.rows = rows;
+    a.rst = rows > 1 ? (size_t)rst : 0;
+    size_t cs = len * rows;  // NULL: contiguous items of the operand's own shape (the planes back to back)
+    a.span = len + (rows - 1) * a.rst;
     if (w == 2 && bs) {
         if (bs[0] < 0) throw Error(std::string(fn) + ": negative strides are not supported (" + what + ", the plane axis)");
         ++bs;
@@ -41,7 +46,7 @@ static SeriesArg series_arg(const char* fn, const char* what, const double* p, c
 }
 
 static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_t* batch, size_t nbatch) {
-    if (a.p != b.p || a.len != b.len || a.plane != b.plane) return false;
+    if (a.p != b.p || a.len != b.len || a.plane != b.plane || a.rows != b.rows || a.rst != b.rst) return false;
     for (size_t i = 0; i < nbatch; ++i)
         if (batch[i] > 1 && a.st[i] != b.st[i]) return false;
     return true;
@@ -50,12 +55,29 @@ static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_
 // `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; may be null); pow has neither, and `e`.
 // corr (x is g, y is y, n is m) and compose_adj (x is gh, y is g, n is nf) are the transposed operations: their result is the SHORT
 // side, so nx bounds n and ny, and the rows the planner sizes are the nx long ones.
+// `d2` (gft_series2_*, f64 only): the call is at rank 2 -- nx, ny, n are the lengths along the series axis (d2->nx1, ny1, n1), an
+// item has d2->nx0 / ny0 / n0 rows d2->xr / yr / rr elements apart, and the limit bounds n0 * n1.
 static int series_call(int op, const char* fn, const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
-                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int w = 1) {
+                       double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int w = 1,
+                       const gft::Series2Dims* d2 = nullptr, const int64_t* rowst = nullptr) {
     const bool corr = op == gft::SERIES_CORR, adj = op == gft::SERIES_COMPOSE_ADJ, transposed = corr || adj;
     const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE || transposed;
     const std::string f(fn);
-    if (transposed) {
+    size_t x0 = 1, y0 = 1, r0 = 1;  // rows per item
+    if (d2) {
+        x0 = d2->nx0, y0 = binary ? d2->ny0 : 1, r0 = d2->n0;
+        if (r0 == 0 || n == 0) throw Error(f + ": n0 * n1 == 0 (the result has no coefficients)");
+        if (r0 > gft::SERIES2_MAX_ELEMS || n > gft::SERIES2_MAX_ELEMS || r0 * n > gft::SERIES2_MAX_ELEMS)
+            throw Error(f + ": n0 * n1 = " + std::to_string(r0) + " * " + std::to_string(n) + " exceeds the limit of " + std::to_string(gft::SERIES2_MAX_ELEMS) +
+                        " coefficients per item of this version");
+        if (x0 == 0 || nx == 0 || (binary && (y0 == 0 || ny == 0))) throw Error(f + ": an operand has no coefficients");
+        if (x0 > r0 || nx > n)
+            throw Error(f + ": x has " + std::to_string(x0) + " x " + std::to_string(nx) + " coefficients, the result " + std::to_string(r0) + " x " + std::to_string(n) +
+                        " (an operand is longer than the truncation order)");
+        if (binary && (y0 > r0 || ny > n))
+            throw Error(f + ": y has " + std::to_string(y0) + " x " + std::to_string(ny) + " coefficients, the result " + std::to_string(r0) + " x " + std::to_string(n) +
+                        " (an operand is longer than the truncation order)");
+    } else if (transposed) {
         const char* nl = corr ? "ng" : "n";   // the long side (x)
         const char* ns = corr ? "ny" : "ng";  // the second operand
         const char* nr = corr ? "m" : "nf";   // the result
@@ -82,14 +104,14 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         if (items >= ((size_t)1 << 31)) throw Error(f + ": more than 2^31 - 1 series in one call");
     }
     const bool comp = op == gft::SERIES_COMPOSE;
-    SeriesArg ax = series_arg(fn, comp ? "f" : (corr ? "g" : (adj ? "gh" : "x")), x, xbs, nx, batch, nbatch, w);
-    SeriesArg ay = series_arg(fn, comp || adj ? "g" : (binary ? "y" : "the seeds"), y, ybs, binary ? ny : 1, batch, nbatch, w);
-    SeriesArg ar = series_arg(fn, "the result", res, rbs, n, batch, nbatch, w);
+    SeriesArg ax = series_arg(fn, comp ? "f" : (corr ? "g" : (adj ? "gh" : "x")), x, xbs, nx, batch, nbatch, w, x0, rowst ? rowst[0] : 0);
+    SeriesArg ay = series_arg(fn, comp || adj ? "g" : (binary ? "y" : "the seeds"), y, ybs, binary ? ny : 1, batch, nbatch, w, y0, rowst && binary ? rowst[1] : 0);
+    SeriesArg ar = series_arg(fn, "the result", res, rbs, n, batch, nbatch, w, r0, rowst ? rowst[2] : 0);
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
         struct Ax {
             size_t ext, st;
-        } axes[34];
+        } axes[35];
         int k = 0;
         if (w == 2) {  // the two planes are one more axis of the result
             if (ar.plane == 0) throw Error(f + ": the result has a zero plane stride: its lower and upper bounds overlap");
@@ -99,6 +121,10 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
             if (batch[i] <= 1) continue;
             if (ar.st[i] == 0) throw Error(f + ": the result has a zero stride (batch axis " + std::to_string(i) + "): its series overlap");
             axes[k++] = Ax{batch[i], ar.st[i]};
+        }
+        if (r0 > 1) {  // rank 2: the rows of an item are one more axis of the result
+            if (ar.rst == 0) throw Error(f + ": the result has a zero row stride: the rows of an item overlap");
+            axes[k++] = Ax{r0, ar.rst};
         }
         if (n > 1) axes[k++] = Ax{n, 1};
         std::sort(axes, axes + k, [](const Ax& u, const Ax& v) { return u.st < v.st; });
@@ -161,6 +187,17 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
     pl.y = binary ? ay.plane : 0;
     pl.s = seeds ? ay.plane : 0;
     pl.r = ar.plane;
+    if (d2) {  // one form; planned before the streams are joined (the planner may refuse)
+        gft::Series2Dims d = *d2;
+        d.xr = ax.rst, d.yr = ay.rst, d.rr = ar.rst;
+        const gft::Series2Plan plan = gft::series2_plan(op, d);
+        const hipStream_t cs = (hipStream_t)stream;
+        join_caller_in(cs);
+        gft::series2_launch(R.stream, op, plan, x, y, res, d, g);
+        join_caller_out(cs);
+        R.series_last = gft::SERIES_FORM_B;
+        return 0;
+    }
     const int form = op == gft::SERIES_POW ? gft::SERIES_NONE : gft::series_plan(op, g.items, (unsigned)(transposed ? nx : n), R.series_force, w);
     const size_t wsn = gft::series_workspace(op, form, g.items, (unsigned)nx, (unsigned)n, w);
     Rc<Buf> ws;
@@ -234,6 +271,36 @@ int gfti_series_compose(const double* f, const int64_t* fbs, size_t nf, const do
 int gfti_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
                    const size_t* batch, size_t nbatch, void* stream) {
     return guard_int([&] { return series_call(gft::SERIES_POW, "interval series_pow", x, xbs, nx, nullptr, nullptr, 1, res, rbs, n, batch, nbatch, stream, e, 2); });
+}
+// rank 2: the last two axes are an item's coefficient array; xrs / yrs / rrs are the row strides
+static int series2_call(int op, const char* fn, const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y,
+                        const int64_t* ybs, int64_t yrs, size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1,
+                        const size_t* batch, size_t nbatch, void* stream) {
+    const size_t cap = gft::SERIES2_MAX_ELEMS + 1;  // (the limits are judged by series_call; this only keeps the narrowing below exact)
+    gft::Series2Dims d;
+    d.nx0 = (unsigned)std::min(nx0, cap), d.nx1 = (unsigned)std::min(nx1, cap), d.ny0 = (unsigned)std::min(ny0, cap), d.ny1 = (unsigned)std::min(ny1, cap);
+    d.n0 = (unsigned)std::min(n0, cap), d.n1 = (unsigned)std::min(n1, cap);
+    d.xr = d.yr = d.rr = 0;
+    const int64_t rowst[3] = {xrs, yrs, rrs};
+    return series_call(op, fn, x, xbs, d.nx1, y, ybs, d.ny1, res, rbs, d.n1, batch, nbatch, stream, 0, 1, &d, rowst);
+}
+int gft_series2_mul(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,
+                    size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                    void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_MUL, "series2_mul", x, xbs, xrs, nx0, nx1, y, ybs, yrs, ny0, ny1, res, rbs, rrs, n0, n1, batch, nbatch, stream); });
+}
+int gft_series2_div(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,
+                    size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                    void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_DIV, "series2_div", x, xbs, xrs, nx0, nx1, y, ybs, yrs, ny0, ny1, res, rbs, rrs, n0, n1, batch, nbatch, stream); });
+}
+int gft_series2_exp(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs, double* res,
+                    const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_EXP, "series2_exp", x, xbs, xrs, nx0, nx1, seed, sbs, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream); });
+}
+int gft_series2_log(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs, double* res,
+                    const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_LOG, "series2_log", x, xbs, xrs, nx0, nx1, seed, sbs, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream); });
 }
 int gft_series_last_form(void) { return R.series_last; }
 }

@@ -80,6 +80,29 @@ int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double*
 void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
                      const SeriesBatch& g, const SeriesPlanes& pl = SeriesPlanes());
 
+// ---- rank 2: batched bivariate series (gft_series2_mul / div / exp / log; f64 only) ---------------------------------------------
+// The last TWO axes of every operand are one item's coefficient array: axis -2 is variable 0 (rows, any non-negative stride), axis
+// -1 variable 1 (unit stride).  Per item the results are the reference's general recursion over axis 0 (mul mt:984-1012, div
+// mt:1162-1192, exp mt:1285-1317, log mt:1335-1386) with the univariate loops above on the rows: a row sum mul_1d(a, b) is formed
+// from 0.0 first and then added, in ascending j, to the row's accumulator.  One form: one workgroup per item for the whole
+// operation, the operands resident in LDS (gft_series2_kernels.hpp); gft_series_last_form() reports SERIES_FORM_B.
+constexpr unsigned SERIES2_MAX_ELEMS = 4096;  // n0 * n1 of the result: two resident arrays are then 64 KB
+struct Series2Dims {
+    unsigned nx0, nx1, ny0, ny1, n0, n1;  // stored shapes of x and y (exp / log: ny* unused) and the result's; nx*, ny* <= n*
+    size_t xr, yr, rr;                    // row strides in elements
+};
+// The geometry of a call: lanes per workgroup, scratch rows of n1 doubles (div / exp / log: the row sums of one chunk of j) and
+// the dynamic LDS in bytes.  Throws std::runtime_error where the runtime grants less LDS than the resident arrays and one
+// scratch row need.
+struct Series2Plan {
+    unsigned threads, srows;
+    size_t lds;
+};
+Series2Plan series2_plan(int op, const Series2Dims& d);
+// Launches SERIES_MUL / DIV / EXP / LOG at rank 2 on `st`.  `y`: the divisor / second factor; for exp / log the seeds or nullptr.
+void series2_launch(hipStream_t st, int op, const Series2Plan& p, const double* x, const double* y, double* res, const Series2Dims& d,
+                    const SeriesBatch& g);
+
 // the element offsets of item `it` (kernels of gft_series.hip and gft_div2d.hip)
 struct SeriesOff {
     size_t x, y, s, r;

@@ -59,15 +59,21 @@ def _lib():
     return _declared
 
 
-def _check(torch, t, what, series_axis=True, planes=0):
+def _placed(t, what):
+    if t.device.type != "cuda":
+        raise TaylorError(f"{what}: the tensor is on {t.device}; it must be in device memory of the library's GPU")
+
+
+def _check(torch, t, what, series_axis=True, planes=0, placement=True):
     """Everything that can be refused without the library: type, dtype, placement, the series axis (and, for an interval
-    tensor, the leading axis of the two planes)."""
+    tensor, the leading axis of the two planes).  placement=False leaves the placement to a later _placed (series2 judges
+    the shapes first)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what}: expected a torch.Tensor, got {type(t).__name__}")
     if t.dtype != torch.float64:
         raise TaylorError(f"{what}: the tensor is {t.dtype}; only torch.float64 is accepted (no implicit conversion)")
-    if t.device.type != "cuda":
-        raise TaylorError(f"{what}: the tensor is on {t.device}; it must be in device memory of the library's GPU")
+    if placement:
+        _placed(t, what)
     if planes and (t.dim() < 1 or t.shape[0] != 2):
         lead = "no axes" if t.dim() < 1 else f"a first axis of {t.shape[0]}"
         raise TaylorError(f"{what}: the tensor has {lead}; an interval tensor is stacked [2, ...] = (lo, hi) along its first axis")

@@ -1,0 +1,162 @@
+"""Batched bivariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log`` (``gft_series2_*``).
+
+The last two axes of every tensor are the coefficient array of one ``TaylorPoly<F64>`` in two variables: axis -2 is variable 0
+(any non-negative stride), axis -1 is variable 1 (unit stride); the leading axes are batch axes and broadcast by torch's rules
+(``expand``, no copy).  An operand of stored shape ``(nx0, nx1)`` smaller than the result's ``(n0, n1)`` is a compact operand.
+Per item the results are the reference's *general* recursion over axis 0 in its operation order, with the univariate loops of
+``genfer_amd.series`` on the rows -- none of the shortcuts the handle operators take, so a result never depends on what else is
+in the batch (``include/gftaylor.h`` states the loops).  One launch per call, one workgroup per item; ``n0 * n1 <= 4096``.  The
+call is ordered on torch's current stream and does not wait.
+
+    >>> from genfer_amd import series2
+    >>> z = series2.mul(x, y)                      # x, y: [B, n0, n1] float64 on the GPU
+    >>> q = series2.div(x, y[0])                   # every item by one series
+    >>> e = series2.exp(x, seed=torch.exp(x[..., 0, 0]))
+
+No autograd in this version: an operand that requires grad is refused while grad mode is on (``detach()`` it, or use
+``torch.no_grad()``).  float64 only; no intervals, no ``compose`` / ``pow`` at rank 2.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from .series import _check, _i64, _placed
+from .taylor import TaylorError
+
+MAX_ELEMS = 4096  # gft_series.hpp SERIES2_MAX_ELEMS: n0 * n1 of the result in this version
+
+_declared = None
+
+
+def _lib():
+    global _declared
+    if _declared is None:
+        from . import lib
+
+        L = lib()
+        i64, sz, vp, i, s = C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.c_void_p, C.c_int64, C.c_size_t
+        for name in ("mul", "div"):
+            f = getattr(L, "gft_series2_" + name)
+            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, vp, i64, i, s, s, sz, s, vp]
+        for name in ("exp", "log"):
+            f = getattr(L, "gft_series2_" + name)
+            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, vp, i64, i, s, s, sz, s, vp]
+        L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
+        _declared = L
+    return _declared
+
+
+def _axes(t, what):
+    """the two series axes of an operand or of ``out`` (type and dtype are judged by series._check)"""
+    if t.dim() < 2:
+        raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate series needs at least 2 (the last two are the coefficient array)")
+    if t.shape[-1] == 0 or t.shape[-2] == 0:
+        raise TaylorError(f"{what}: a series axis is empty (the last two axes are {tuple(t.shape[-2:])})")
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
+
+
+def _orders(what, n, *shapes):
+    if n is None:
+        n = (max(s[0] for s in shapes), max(s[1] for s in shapes))
+    try:
+        n0, n1 = (int(v) for v in n)
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: n must be a pair (n0, n1), got {n!r}") from None
+    if n0 < 1 or n1 < 1:
+        raise TaylorError(f"{what}: n = ({n0}, {n1}); the result needs at least one coefficient on each axis (n == 0 is refused)")
+    if n0 * n1 > MAX_ELEMS:
+        raise TaylorError(f"{what}: n0 * n1 = {n0} * {n1} = {n0 * n1} exceeds the limit of {MAX_ELEMS} coefficients per item of this version")
+    for s in shapes:
+        for a in (0, 1):
+            if s[a] > (n0, n1)[a]:
+                raise TaylorError(f"{what}: an operand has {s[a]} coefficients on axis {a - 2}, more than n{a} = {(n0, n1)[a]} (nx > n)")
+    return n0, n1
+
+
+def _run(what, fn_name, x, second, n, out, second_is_seed):
+    import torch
+
+    # everything that needs no device first: types, shapes, strides, orders, out, grad -- then the placement
+    _check(torch, x, f"{what}: x", series_axis=False, placement=False)
+    _axes(x, f"{what}: x")
+    sname = "seed" if second_is_seed else "y"
+    if second is not None:
+        _check(torch, second, f"{what}: {sname}", series_axis=False, placement=False)
+        if not second_is_seed:
+            _axes(second, f"{what}: y")
+    if out is not None:
+        _check(torch, out, f"{what}: out", series_axis=False, placement=False)
+        _axes(out, f"{what}: out")
+    operands = [x] if second_is_seed or second is None else [x, second]
+    n0, n1 = _orders(what, n, *(tuple(t.shape[-2:]) for t in operands))
+    shapes = [x.shape[:-2]]
+    if second is not None:
+        shapes.append(second.shape if second_is_seed else second.shape[:-2])
+    if out is not None:
+        if tuple(out.shape[-2:]) != (n0, n1):
+            raise TaylorError(f"{what}: out has {tuple(out.shape[-2:])} coefficients per item, the result has n = ({n0}, {n1})")
+        batch = tuple(out.shape[:-2])
+        if tuple(torch.broadcast_shapes(*shapes, batch)) != batch:
+            raise TaylorError(f"{what}: out has batch shape {batch}; the operands broadcast to {tuple(torch.broadcast_shapes(*shapes))}")
+    else:
+        batch = tuple(torch.broadcast_shapes(*shapes))
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, second)):
+        raise TaylorError(f"{what}: an operand requires grad, and this version of series2 has no autograd; pass x.detach() or call under "
+                          "torch.no_grad() (nothing is detached silently)")
+    _placed(x, f"{what}: x")
+    if second is not None:
+        _placed(second, f"{what}: {sname}")
+    if out is not None:
+        _placed(out, f"{what}: out")
+    for t in (second, out):
+        if t is not None and t.device != x.device:
+            raise TaylorError(f"{what}: the tensors are on different devices ({x.device}, {t.device})")
+    if out is None:
+        out = torch.empty(batch + (n0, n1), dtype=torch.float64, device=x.device)
+    L = _lib()
+    dev = int(L.gft_device())
+    if dev >= 0 and x.device.index != dev:
+        raise TaylorError(f"{what}: the tensors are on {x.device}, but the library runs on cuda:{dev}")
+    nb = len(batch)
+    xe = x.expand(batch + tuple(x.shape[-2:]))
+    bsz = (C.c_size_t * max(nb, 1))(*batch)
+    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    fn = getattr(L, fn_name)
+    xa = (C.c_void_p(xe.data_ptr()), _i64(xe.stride()[:nb]), xe.stride(-2), xe.shape[-2], xe.shape[-1])
+    ra = (C.c_void_p(out.data_ptr()), _i64(out.stride()[:nb]), out.stride(-2), n0, n1, bsz, nb, stream)
+    if second_is_seed:
+        if second is None:
+            sa = (None, None)
+        else:
+            se = second.expand(batch)
+            sa = (C.c_void_p(se.data_ptr()), _i64(se.stride()))
+        rc = fn(*xa, *sa, *ra)
+    else:
+        ye = second.expand(batch + tuple(second.shape[-2:]))
+        rc = fn(*xa, C.c_void_p(ye.data_ptr()), _i64(ye.stride()[:nb]), ye.stride(-2), ye.shape[-2], ye.shape[-1], *ra)
+    if rc != 0:
+        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
+    return out
+
+
+def mul(x, y, n=None, out=None):
+    """``z[b] = x[b] * y[b]`` truncated at orders ``n = (n0, n1)`` (default: the larger stored length on each axis)."""
+    return _run("series2.mul", "gft_series2_mul", x, y, n, out, False)
+
+
+def div(x, y, n=None, out=None):
+    """``r[b] = x[b] / y[b]`` to orders ``n = (n0, n1)``: the general division recurrence over the rows."""
+    return _run("series2.div", "gft_series2_div", x, y, n, out, False)
+
+
+def exp(x, n=None, seed=None, out=None):
+    """``exp(x[b])`` to orders ``n``.  ``seed``: ``exp(x[b, 0, 0])`` per item (a tensor of the batch shape); with the host libm's
+    values the result carries the reference's bits.  ``None``: formed on the device (a few ulps from libm)."""
+    return _run("series2.exp", "gft_series2_exp", x, seed, n, out, True)
+
+
+def log(x, n=None, seed=None, out=None):
+    """``log(x[b])`` to orders ``n``.  ``seed``: ``ln(x[b, 0, 0])`` per item; ``None``: formed on the device (only coefficient
+    ``[0, 0]`` depends on it)."""
+    return _run("series2.log", "gft_series2_log", x, seed, n, out, True)

@@ -211,6 +211,43 @@ int gft_series_compose_adj(const double* gh, const int64_t* hbs, size_t n, const
  * form (1 holds only where the rows fit the LDS budget; 0 = the library's thresholds).  Test / measurement aid. */
 int gft_series_last_form(void);
 
+/* ---- batched BIVARIATE series on caller-owned device tensors (f64 only) ----------------------
+ * The last TWO axes of every operand are the coefficient array of one TaylorPoly<F64> in two variables: axis -2 is variable 0
+ * (`nx0` rows, `xrs` elements apart: any non-negative stride), axis -1 is variable 1 (`nx1` coefficients, UNIT stride).  The
+ * `nbatch` leading axes are the batch, with strides `xbs` / `ybs` / `sbs` / `rbs` as for gft_series_* (NULL = contiguous items
+ * of the operand's own shape).  x has stored shape (nx0, nx1), y (ny0, ny1), the result always (n0, n1) with nx*, ny* <= n*,
+ * n0, n1 >= 1 and n0 * n1 <= 4096 in this version.  The result's rows and items must be distinct addresses (its row stride
+ * joins the batch strides in that proof); the result may be an operand itself (the same view), any other overlap is refused by
+ * address range.  Per item the result is the reference's GENERAL recursion over axis 0 in its operation order, multiply and add
+ * rounded separately, only stored coefficients entering a sum, and none of the operator wrappers' zero / one / constant /
+ * linear shortcuts.  With mul1d / div1d / exp1d / log1d the loops of gft_series_* (sums from 0.0):
+ *   mul  z = 0;  for k < n0, j ascending in max(0, k+1-ny0) .. min(k+1, nx0)-1:  z[k] += mul1d(x[j], y[k-j], n1)
+ *        (the row sum is formed from 0.0 FIRST, then added to z[k])
+ *   div  for k < n0:  c = 0;  for j in max(0, k+1-ny0) .. k-1: c += mul1d(r[j], y[k-j], n1);  c = -c;
+ *        if k < nx0: c[:nx1] += x[k];  r[k] = div1d(c, y[0], n1)
+ *   exp  r[0] = exp1d(x[0], n1, seed);  for k >= 1:  c = 0;  for j in 1 .. min(nx0, k+1)-1: c += mul1d(x[j] * (double)j, r[k-j], n1);
+ *        r[k] = c / (double)k          (x[j] * j is rounded before it meets r)
+ *   log  r[0] = log1d(x[0], n1, seed);  for k >= 1:  c = 0;  for j in max(1, k+1-nx0) .. k-1: c += mul1d(x[k-j], r[j] * (double)j, n1);
+ *        c = -c;  if k < nx0: c[:nx1] += (double)k * x[k];  c = div1d(c, x[0], n1);  r[k] = c / (double)k
+ * These are the bits of the reference's *, /, exp() and log() at rank 2 wherever the divisor / the operand of log stores at
+ * least 2 coefficients on both axes; elsewhere (where the reference shortcuts or stores fewer rows) the loops are the
+ * definition and differ from it in signs of zeros only.  `seed`: exp(x[b, 0, 0]) / ln(x[b, 0, 0]) per item, or NULL (formed on
+ * the device), as for gft_series_exp / log.  One kernel per call, one workgroup per item with the operands resident in LDS;
+ * where the runtime grants less LDS than an item needs the call fails and says so.  gft_series_last_form() reports 2 afterwards;
+ * the "series_form" option does not apply.  Stream contract and return values: those of gft_series_*. */
+int gft_series2_mul(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs,
+                    int64_t yrs, size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1,
+                    const size_t* batch, size_t nbatch, void* stream);   /* mul                    mt:984-1012  */
+int gft_series2_div(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs,
+                    int64_t yrs, size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1,
+                    const size_t* batch, size_t nbatch, void* stream);   /* div                    mt:1162-1192 */
+int gft_series2_exp(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs,
+                    double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                    void* stream);                                       /* exp                    mt:1285-1317 */
+int gft_series2_log(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs,
+                    double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                    void* stream);                                       /* log                    mt:1335-1386 */
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI, collectives internal to the library --------
  * The reference is single-process; a host that wants one large product spread over the GPUs of a node starts one
  * process per GPU (each with its own gft_init(device)), lets rank 0 call gft_dist_unique_id, hands the 128 bytes to
