@@ -5,6 +5,8 @@
 // terms are univariate products of rows, mul_1d(a, b)[k1] = 0.0 + sum_{j1} a[j1] * b[k1 - j1] (ascending j1, stored
 // coefficients only), added in ascending j to the accumulator of row k: "independent row sums, ordered additions".
 //   mul            a thread owns whole outputs (k0, k1) and runs both sums; no step depends on another.
+//   compose        the Horner loop over the slices of f along the substituted axis, every step that product at the compact shape
+//                  of the step, the result resident in LDS from step to step (k_series2_compose).
 //   div, exp, log  rows k one after the other.  Pass 1 forms the row sums of a chunk of j in parallel over (j, k1) into an LDS
 //                  scratch of `srows` rows, pass 2 adds them in ascending j into r[k] (which holds the accumulator between
 //                  chunks); then the row's own step: negate and add the dividend, the 1-d division by row 0 of the divisor, the
@@ -39,13 +41,14 @@ __device__ inline void s2_store(double* res, size_t rstride, const double* lds, 
 
 // ---- mul (mt:984-1012) ------------------------------------------------------------------------------------------------------
 // z[k0][k1] = 0 + sum_{j0} (0 + sum_{j1} x[j0][j1] * y[k0-j0][k1-j1]), both ascending over the stored coefficients.
-__device__ inline double s2_mul_out(const double* xl, const double* yl, const Series2Dims& d, unsigned k0, unsigned k1) {
+// x has pitch d.nx1; `yp` is the pitch of y: d.ny1 for a staged y, its row stride where it stays in global memory.
+__device__ inline double s2_mul_out(const double* xl, const double* yl, const Series2Dims& d, size_t yp, unsigned k0, unsigned k1) {
     const unsigned lo0 = k0 + 1 > d.ny0 ? k0 + 1 - d.ny0 : 0, hi0 = k0 + 1 < d.nx0 ? k0 + 1 : d.nx0;
     const unsigned lo1 = k1 + 1 > d.ny1 ? k1 + 1 - d.ny1 : 0, hi1 = k1 + 1 < d.nx1 ? k1 + 1 : d.nx1;
     double z = 0.0;
     for (unsigned j0 = lo0; j0 < hi0; ++j0) {
         const double* xr = xl + j0 * d.nx1;
-        const double* yr = yl + (k0 - j0) * d.ny1 + k1;
+        const double* yr = yl + (k0 - j0) * yp + k1;
         double o = 0.0;
 #pragma unroll 4
         for (unsigned j1 = lo1; j1 < hi1; ++j1) o = o + xr[j1] * yr[-(int)j1];
@@ -72,8 +75,76 @@ __global__ __launch_bounds__(256) void k_series2_mul(const double* x, const doub
             const unsigned i = is[h];
             if (h == 1 && i == is[0]) break;  // the middle output of an odd N
             const unsigned k0 = i / d.n1, k1 = i - k0 * d.n1;
-            res[o.r + (size_t)k0 * d.rr + k1] = s2_mul_out(xl, yl, d, k0, k1);
+            res[o.r + (size_t)k0 * d.rr + k1] = s2_mul_out(xl, yl, d, d.ny1, k0, k1);
         }
+    }
+}
+
+// ---- compose (subst_var's Horner path, mt:569-579) --------------------------------------------------------------------------------
+// res = f(g) with g in the place of variable `var` of f.  The slices of f along that axis are its rows (var 0) or its columns (var 1);
+// with S of them and `len` coefficients each:
+//   res = 0.0 + slice S-1, stored shape (1, len) / (len, 1);  for i = S-2 .. 0:  res = mul(res, g) at the compact shape
+//   L = (min(r0 + ng0 - 1, n0), min(r1 + ng1 - 1, n1)) of sum_shape;  row 0 / column 0 of res += slice i
+// One workgroup runs the whole loop of its item (the steps are a dependency chain).  Two result arrays of n0 * n1 doubles take turns
+// in LDS, the current one compact at pitch r1; g sits compact behind them (GLDS) or stays in global memory at its row stride (the
+// fallback where 2 N + ng0 * ng1 doubles exceed the granted LDS).  Every step is k_series2_mul's pairing on a Series2Dims built for
+// the step: a thread owns the outputs t and L0 * L1 - 1 - t, all bounds the same for every item; up to 512 lanes.  The owner of an output on the
+// added slice loads f's coefficient before its sums and adds it after them -- with GLDS the only global traffic between steps,
+// which meet through LDS alone.  f and g are read completely before the first store: the result may be f or g itself.
+template <bool GLDS>
+__global__ __launch_bounds__(512) void k_series2_compose(const double* f, const double* g, double* res, Series2Dims d, int var, SeriesBatch b) {
+    extern __shared__ double s2_lds[];  // res [n0 * n1] | res [n0 * n1] | (GLDS) g [ng0][ng1]
+    const unsigned N = d.n0 * d.n1, tid = threadIdx.x, nt = blockDim.x;
+    double* cur = s2_lds;
+    double* nxt = s2_lds + N;
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    const double* fg = f + o.x;
+    const double* gs = g + o.y;
+    size_t gp = d.yr;
+    if (GLDS) {
+        double* gl = s2_lds + 2 * N;
+        s2_stage(gl, g + o.y, d.yr, d.ny0, d.ny1);
+        gs = gl;
+        gp = d.ny1;
+    }
+    // slice i of f is fg[i * fslice + c * fstep], c < len
+    const unsigned slices = var == 0 ? d.nx0 : d.nx1, len = var == 0 ? d.nx1 : d.nx0;
+    const size_t fslice = var == 0 ? d.xr : 1, fstep = var == 0 ? 1 : d.xr;
+    for (unsigned c = tid; c < len; c += nt) cur[c] = 0.0 + fg[(slices - 1) * fslice + c * fstep];
+    __syncthreads();
+    unsigned r0 = var == 0 ? 1 : len, r1 = var == 0 ? len : 1;  // the stored shape of res
+    for (unsigned i = slices - 1; i-- > 0;) {
+        Series2Dims s;
+        s.nx0 = r0, s.nx1 = r1, s.ny0 = d.ny0, s.ny1 = d.ny1;
+        s.n0 = r0 + d.ny0 - 1 < d.n0 ? r0 + d.ny0 - 1 : d.n0;
+        s.n1 = r1 + d.ny1 - 1 < d.n1 ? r1 + d.ny1 - 1 : d.n1;
+        const unsigned M = s.n0 * s.n1, half = (M + 1) / 2;
+        const double* fi = fg + i * fslice;
+        for (unsigned t = tid; t < half; t += nt) {
+            const unsigned is[2] = {t, M - 1 - t};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const unsigned idx = is[h];
+                if (h == 1 && idx == is[0]) break;  // the middle output of an odd M
+                const unsigned k0 = idx / s.n1, k1 = idx - k0 * s.n1;
+                const bool added = var == 0 ? (k0 == 0 && k1 < len) : (k1 == 0 && k0 < len);
+                double fv = 0.0;
+                if (added) fv = fi[(var == 0 ? k1 : k0) * fstep];  // in flight during the sums below
+                double z = s2_mul_out(cur, gs, s, gp, k0, k1);
+                if (added) z = z + fv;
+                nxt[idx] = z;
+            }
+        }
+        lds_barrier();
+        double* sw = cur;
+        cur = nxt;
+        nxt = sw;
+        r0 = s.n0, r1 = s.n1;
+    }
+    __syncthreads();  // (every global load of this workgroup is done: the result may be f or g)
+    for (unsigned idx = tid; idx < N; idx += nt) {
+        const unsigned k0 = idx / d.n1, k1 = idx - k0 * d.n1;
+        res[o.r + (size_t)k0 * d.rr + k1] = k0 < r0 && k1 < r1 ? cur[k0 * r1 + k1] : 0.0;
     }
 }
 

@@ -1,4 +1,4 @@
-"""Batched bivariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log`` (``gft_series2_*``).
+"""Batched bivariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` (``gft_series2_*``).
 
 The last two axes of every tensor are the coefficient array of one ``TaylorPoly<F64>`` in two variables: axis -2 is variable 0
 (any non-negative stride), axis -1 is variable 1 (unit stride); the leading axes are batch axes and broadcast by torch's rules
@@ -6,21 +6,24 @@ The last two axes of every tensor are the coefficient array of one ``TaylorPoly<
 Per item the results are the reference's *general* recursion over axis 0 in its operation order, with the univariate loops of
 ``genfer_amd.series`` on the rows -- none of the shortcuts the handle operators take, so a result never depends on what else is
 in the batch (``include/gftaylor.h`` states the loops).  One launch per call, one workgroup per item; ``n0 * n1 <= 4096``.  The
-call is ordered on torch's current stream and does not wait.
+call is ordered on torch's current stream and does not wait.  ``compose`` substitutes a series for one of the two variables
+(``subst_var``'s Horner loop, the whole loop in one launch); ``pow`` is square-and-multiply over ``mul``'s launches inside one call.
 
     >>> from genfer_amd import series2
     >>> z = series2.mul(x, y)                      # x, y: [B, n0, n1] float64 on the GPU
     >>> q = series2.div(x, y[0])                   # every item by one series
     >>> e = series2.exp(x, seed=torch.exp(x[..., 0, 0]))
+    >>> h = series2.compose(f, g, var=1)           # g for variable 1 of f
+    >>> p = series2.pow(x, 5)
 
 No autograd in this version: an operand that requires grad is refused while grad mode is on (``detach()`` it, or use
-``torch.no_grad()``).  float64 only; no intervals, no ``compose`` / ``pow`` at rank 2.
+``torch.no_grad()``).  float64 only; no intervals.
 """
 from __future__ import annotations
 
 import ctypes as C
 
-from .series import _check, _i64, _placed
+from .series import _check, _exponent, _i64, _placed
 from .taylor import TaylorError
 
 MAX_ELEMS = 4096  # gft_series.hpp SERIES2_MAX_ELEMS: n0 * n1 of the result in this version
@@ -41,6 +44,9 @@ def _lib():
         for name in ("exp", "log"):
             f = getattr(L, "gft_series2_" + name)
             f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, vp, i64, i, s, s, sz, s, vp]
+        L.gft_series2_compose.restype = L.gft_series2_pow.restype = C.c_int
+        L.gft_series2_compose.argtypes = [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
+        L.gft_series2_pow.argtypes = [vp, i64, i, s, s, C.c_uint32, vp, i64, i, s, s, sz, s, vp]
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
@@ -74,17 +80,19 @@ def _orders(what, n, *shapes):
     return n0, n1
 
 
-def _run(what, fn_name, x, second, n, out, second_is_seed):
+def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), scalar=None):
+    """``scalar``: compose's ``var`` (passed behind the second operand) or pow's ``e`` (in the place of the seeds)"""
     import torch
 
     # everything that needs no device first: types, shapes, strides, orders, out, grad -- then the placement
-    _check(torch, x, f"{what}: x", series_axis=False, placement=False)
-    _axes(x, f"{what}: x")
-    sname = "seed" if second_is_seed else "y"
+    xname = names[0]
+    _check(torch, x, f"{what}: {xname}", series_axis=False, placement=False)
+    _axes(x, f"{what}: {xname}")
+    sname = "seed" if second_is_seed else names[1]
     if second is not None:
         _check(torch, second, f"{what}: {sname}", series_axis=False, placement=False)
         if not second_is_seed:
-            _axes(second, f"{what}: y")
+            _axes(second, f"{what}: {sname}")
     if out is not None:
         _check(torch, out, f"{what}: out", series_axis=False, placement=False)
         _axes(out, f"{what}: out")
@@ -102,9 +110,9 @@ def _run(what, fn_name, x, second, n, out, second_is_seed):
     else:
         batch = tuple(torch.broadcast_shapes(*shapes))
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, second)):
-        raise TaylorError(f"{what}: an operand requires grad, and this version of series2 has no autograd; pass x.detach() or call under "
+        raise TaylorError(f"{what}: an operand requires grad, and this version of series2 has no autograd; pass {xname}.detach() or call under "
                           "torch.no_grad() (nothing is detached silently)")
-    _placed(x, f"{what}: x")
+    _placed(x, f"{what}: {xname}")
     if second is not None:
         _placed(second, f"{what}: {sname}")
     if out is not None:
@@ -126,7 +134,9 @@ def _run(what, fn_name, x, second, n, out, second_is_seed):
     xa = (C.c_void_p(xe.data_ptr()), _i64(xe.stride()[:nb]), xe.stride(-2), xe.shape[-2], xe.shape[-1])
     ra = (C.c_void_p(out.data_ptr()), _i64(out.stride()[:nb]), out.stride(-2), n0, n1, bsz, nb, stream)
     if second_is_seed:
-        if second is None:
+        if scalar is not None:
+            sa = (C.c_uint32(scalar),)
+        elif second is None:
             sa = (None, None)
         else:
             se = second.expand(batch)
@@ -134,7 +144,8 @@ def _run(what, fn_name, x, second, n, out, second_is_seed):
         rc = fn(*xa, *sa, *ra)
     else:
         ye = second.expand(batch + tuple(second.shape[-2:]))
-        rc = fn(*xa, C.c_void_p(ye.data_ptr()), _i64(ye.stride()[:nb]), ye.stride(-2), ye.shape[-2], ye.shape[-1], *ra)
+        va = () if scalar is None else (C.c_int(scalar),)
+        rc = fn(*xa, C.c_void_p(ye.data_ptr()), _i64(ye.stride()[:nb]), ye.stride(-2), ye.shape[-2], ye.shape[-1], *va, *ra)
     if rc != 0:
         raise TaylorError((L.gft_last_error() or b"unknown error").decode())
     return out
@@ -160,3 +171,21 @@ def log(x, n=None, seed=None, out=None):
     """``log(x[b])`` to orders ``n``.  ``seed``: ``ln(x[b, 0, 0])`` per item; ``None``: formed on the device (only coefficient
     ``[0, 0]`` depends on it)."""
     return _run("series2.log", "gft_series2_log", x, seed, n, out, True)
+
+
+def compose(f, g, var=0, n=None, out=None):
+    """``f[b]`` with ``g[b]`` substituted for variable ``var`` (0: axis -2, 1: axis -1) of ``f``, truncated at ``n = (n0, n1)``
+    (default: the larger stored length on each axis).  ``subst_var``'s general Horner path without its shortcuts: over the slices
+    of ``f`` along the substituted axis, ``res = res * g + slice`` with the general product at the compact shape of every step,
+    from ``res = 0.0 + the last slice``; the result stays in LDS across the steps of the one launch.  Cost: about
+    ``nslices * (n0*n1)**2 / 4`` multiply-adds per item, all on one workgroup; no cap is imposed."""
+    if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
+        raise TaylorError(f"series2.compose: var = {var!r}; the variable of f that g replaces is 0 or 1")
+    return _run("series2.compose", "gft_series2_compose", f, g, n, out, False, names=("f", "g"), scalar=var)
+
+
+def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
+    """``x[b] ** e`` truncated at ``n = (n0, n1)`` (default: the stored shape) for an integer ``0 <= e < 2**32``: the reference's
+    square-and-multiply over ``mul`` at compact shapes.  ``e = 0`` gives the unit item ``[[1, 0, ...], [0, ...], ...]``."""
+    e = _exponent("series2.pow", e, div="series2.div")
+    return _run("series2.pow", "gft_series2_pow", x, None, n, out, True, scalar=e)

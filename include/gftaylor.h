@@ -211,7 +211,7 @@ int gft_series_compose_adj(const double* gh, const int64_t* hbs, size_t n, const
  * form (1 holds only where the rows fit the LDS budget; 0 = the library's thresholds).  Test / measurement aid. */
 int gft_series_last_form(void);
 
-/* ---- batched BIVARIATE series on caller-owned device tensors (f64 only) ----------------------
+/* ---- batched BIVARIATE series on caller-owned device tensors (f64 only): mul / div / exp / log / compose / pow ----
  * The last TWO axes of every operand are the coefficient array of one TaylorPoly<F64> in two variables: axis -2 is variable 0
  * (`nx0` rows, `xrs` elements apart: any non-negative stride), axis -1 is variable 1 (`nx1` coefficients, UNIT stride).  The
  * `nbatch` leading axes are the batch, with strides `xbs` / `ybs` / `sbs` / `rbs` as for gft_series_* (NULL = contiguous items
@@ -247,6 +247,29 @@ int gft_series2_exp(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0
 int gft_series2_log(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs,
                     double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
                     void* stream);                                       /* log                    mt:1335-1386 */
+/* compose: res[b] = f[b] with g[b] substituted for variable `var` (0: the row axis, 1: the unit-stride axis) of f, f in the place
+ * of x (stored shape (nf0, nf1)) and g in the place of y ((ng0, ng1)), truncated at (n0, n1).  With mul2(a, b, L) the loop of
+ * gft_series2_mul on the stored shapes truncated at L, it is subst_var's general Horner path (mt:569-579) with the general product
+ * at every step and none of the shortcuts of subst_var (mt:547-568) or of Mul.  var == 0:
+ *   res = [[0.0 + f[nf0-1][c], c < nf1]]                           (stored shape (1, nf1))
+ *   for i = nf0-2 .. 0:  L = (min(r0 + ng0 - 1, n0), min(r1 + ng1 - 1, n1)), (r0, r1) the stored shape of res (sum_shape);
+ *                        res = mul2(res, g, L);  res[0][c] = res[0][c] + f[i][c], c < nf1
+ * and the result is res extended with +0.0 to (n0, n1).  var == 1 is the same loop over the columns of f: res starts as the column
+ * 0.0 + f[:, nf1-1], stored shape (nf0, 1), and after each product res[r][0] = res[r][0] + f[r][i], r < nf0.  With one slice
+ * (nf0 == 1, resp. nf1 == 1) the result is 0.0 + f padded and g's values are not used.  A var other than 0 or 1 is refused.  One
+ * kernel, one workgroup per item for the whole loop, the result resident in LDS from step to step (g beside it where the granted
+ * LDS holds both, else read from global memory).  Cost: about nslices * (n0 * n1)^2 / 4 multiply-adds per item on that one
+ * workgroup; no cap is imposed.  The result may be f or g itself (the same view).
+ * pow: res[b] = x[b]^e by the reference's square-and-multiply (mt:433-451) without its wasted last squaring, over mul2 at the
+ * compact shapes min(la + lb - 1, n) per axis: res = [[1.0]], base = x; while e > 0: if e & 1 then res = mul2(res, base);
+ * e >>= 1; if e > 0 then base = mul2(base, base).  The result is padded with +0.0; e == 0 gives the unit item, e == 1 runs the
+ * loop (0.0 + 1.0 * x).  A sequence of gft_series2_mul's launches on pool workspace inside the one stream-ordered call. */
+int gft_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t nf0, size_t nf1, const double* g, const int64_t* gbs,
+                        int64_t grs, size_t ng0, size_t ng1, int var, double* res, const int64_t* rbs, int64_t rrs, size_t n0,
+                        size_t n1, const size_t* batch, size_t nbatch, void* stream);   /* subst_var (Horner)     mt:540-580   */
+int gft_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
+                    const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                    void* stream);                                       /* pow                    mt:433-451   */
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI, collectives internal to the library --------
  * The reference is single-process; a host that wants one large product spread over the GPUs of a node starts one
