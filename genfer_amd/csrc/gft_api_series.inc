@@ -1,8 +1,8 @@
 // ------------------------------------------------------------------------------------------
 // batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow / corr / compose_adj,
 // and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
-// and the bivariate gft_series2_mul / div / exp / log / compose / pow (f64; the same validation with one row stride per operand:
-// series2_call)
+// and the bivariate gft_series2_mul / div / exp / log / compose / pow with their Interval<F64> twins gfti_series2_* (the same
+// validation with one row stride per operand: series2_call)
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -56,7 +56,7 @@ static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_
 // `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; may be null); pow has neither, and `e`.
 // corr (x is g, y is y, n is m) and compose_adj (x is gh, y is g, n is nf) are the transposed operations: their result is the SHORT
 // side, so nx bounds n and ny, and the rows the planner sizes are the nx long ones.
-// `d2` (gft_series2_*, f64 only): the call is at rank 2 -- nx, ny, n are the lengths along the series axis (d2->nx1, ny1, n1), an
+// `d2` (gft_series2_*, gfti_series2_*): the call is at rank 2 -- nx, ny, n are the lengths along the series axis (d2->nx1, ny1, n1), an
 // item has d2->nx0 / ny0 / n0 rows d2->xr / yr / rr elements apart, and the limit bounds n0 * n1.  `var`: compose's variable there.
 static int series_call(int op, const char* fn, const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
                        double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int w = 1,
@@ -68,8 +68,9 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
     if (d2) {
         x0 = d2->nx0, y0 = binary ? d2->ny0 : 1, r0 = d2->n0;
         if (r0 == 0 || n == 0) throw Error(f + ": n0 * n1 == 0 (the result has no coefficients)");
-        if (r0 > gft::SERIES2_MAX_ELEMS || n > gft::SERIES2_MAX_ELEMS || r0 * n > gft::SERIES2_MAX_ELEMS)
-            throw Error(f + ": n0 * n1 = " + std::to_string(r0) + " * " + std::to_string(n) + " exceeds the limit of " + std::to_string(gft::SERIES2_MAX_ELEMS) +
+        const size_t most = gft::series2_max_elems(w);
+        if (r0 > most || n > most || r0 * n > most)
+            throw Error(f + ": n0 * n1 = " + std::to_string(r0) + " * " + std::to_string(n) + " exceeds the limit of " + std::to_string(most) +
                         " coefficients per item of this version");
         if (x0 == 0 || nx == 0 || (binary && (y0 == 0 || ny == 0))) throw Error(f + ": an operand has no coefficients");
         if (x0 > r0 || nx > n)
@@ -193,13 +194,13 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
         d.xr = ax.rst, d.yr = ay.rst, d.rr = ar.rst;
         const hipStream_t cs = (hipStream_t)stream;
         if (op == gft::SERIES_POW) {
-            Rc<Buf> ws = alloc_doubles(gft::series2_pow_workspace(g.items, d));  // (returned to the pool on exit, as below)
+            Rc<Buf> ws = alloc_doubles(gft::series2_pow_workspace(g.items, d, w));  // (returned to the pool on exit, as below)
             join_caller_in(cs);
-            gft::series2_pow(R.stream, x, e, res, d, g, ws->p);
+            gft::series2_pow(R.stream, x, e, res, d, g, ws->p, pl);
         } else {
-            const gft::Series2Plan plan = gft::series2_plan(op, d);
+            const gft::Series2Plan plan = gft::series2_plan(op, d, w);
             join_caller_in(cs);
-            gft::series2_launch(R.stream, op, plan, x, y, res, d, g, var);
+            gft::series2_launch(R.stream, op, plan, x, y, res, d, g, var, pl);
         }
         join_caller_out(cs);
         R.series_last = gft::SERIES_FORM_B;
@@ -282,14 +283,14 @@ int gfti_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, 
 // rank 2: the last two axes are an item's coefficient array; xrs / yrs / rrs are the row strides
 static int series2_call(int op, const char* fn, const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y,
                         const int64_t* ybs, int64_t yrs, size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1,
-                        const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int var = 0) {
+                        const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int var = 0, int w = 1) {
     const size_t cap = gft::SERIES2_MAX_ELEMS + 1;  // (the limits are judged by series_call; this only keeps the narrowing below exact)
     gft::Series2Dims d;
     d.nx0 = (unsigned)std::min(nx0, cap), d.nx1 = (unsigned)std::min(nx1, cap), d.ny0 = (unsigned)std::min(ny0, cap), d.ny1 = (unsigned)std::min(ny1, cap);
     d.n0 = (unsigned)std::min(n0, cap), d.n1 = (unsigned)std::min(n1, cap);
     d.xr = d.yr = d.rr = 0;
     const int64_t rowst[3] = {xrs, yrs, rrs};
-    return series_call(op, fn, x, xbs, d.nx1, y, ybs, d.ny1, res, rbs, d.n1, batch, nbatch, stream, e, 1, &d, rowst, var);
+    return series_call(op, fn, x, xbs, d.nx1, y, ybs, d.ny1, res, rbs, d.n1, batch, nbatch, stream, e, w, &d, rowst, var);
 }
 int gft_series2_mul(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,
                     size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
@@ -320,6 +321,37 @@ int gft_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t
 int gft_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res, const int64_t* rbs, int64_t rrs,
                     size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
     return guard_int([&] { return series2_call(gft::SERIES_POW, "series2_pow", x, xbs, xrs, nx0, nx1, nullptr, nullptr, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream, e); });
+}
+// Interval<F64> at rank 2: the same calls on (lo, hi) planes; every batch-stride array has nbatch + 1 entries, the plane stride first
+int gfti_series2_mul(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,
+                     size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                     void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_MUL, "interval series2_mul", x, xbs, xrs, nx0, nx1, y, ybs, yrs, ny0, ny1, res, rbs, rrs, n0, n1, batch, nbatch, stream, 0, 0, 2); });
+}
+int gfti_series2_div(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,
+                     size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                     void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_DIV, "interval series2_div", x, xbs, xrs, nx0, nx1, y, ybs, yrs, ny0, ny1, res, rbs, rrs, n0, n1, batch, nbatch, stream, 0, 0, 2); });
+}
+int gfti_series2_exp(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs, double* res,
+                     const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_EXP, "interval series2_exp", x, xbs, xrs, nx0, nx1, seed, sbs, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream, 0, 0, 2); });
+}
+int gfti_series2_log(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs, double* res,
+                     const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_LOG, "interval series2_log", x, xbs, xrs, nx0, nx1, seed, sbs, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream, 0, 0, 2); });
+}
+int gfti_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t nf0, size_t nf1, const double* g, const int64_t* gbs, int64_t grs,
+                         size_t ng0, size_t ng1, int var, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch,
+                         size_t nbatch, void* stream) {
+    return guard_int([&] {
+        if (var != 0 && var != 1) throw Error("interval series2_compose: var = " + std::to_string(var) + " (the variable of f that g replaces is 0 or 1)");
+        return series2_call(gft::SERIES_COMPOSE, "interval series2_compose", f, fbs, frs, nf0, nf1, g, gbs, grs, ng0, ng1, res, rbs, rrs, n0, n1, batch, nbatch, stream, 0, var, 2);
+    });
+}
+int gfti_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res, const int64_t* rbs, int64_t rrs,
+                     size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_POW, "interval series2_pow", x, xbs, xrs, nx0, nx1, nullptr, nullptr, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream, e, 0, 2); });
 }
 int gft_series_last_form(void) { return R.series_last; }
 }

@@ -80,7 +80,7 @@ int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double*
 void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
                      const SeriesBatch& g, const SeriesPlanes& pl = SeriesPlanes());
 
-// ---- rank 2: batched bivariate series (gft_series2_mul / div / exp / log / compose / pow; f64 only) ------------------------------
+// ---- rank 2: batched bivariate series (gft_series2_* on F64, gfti_series2_* on Interval<F64>: mul / div / exp / log / compose / pow) --
 // The last TWO axes of every operand are one item's coefficient array: axis -2 is variable 0 (rows, any non-negative stride), axis
 // -1 variable 1 (unit stride).  Per item the results are the reference's general recursion over axis 0 (mul mt:984-1012, div
 // mt:1162-1192, exp mt:1285-1317, log mt:1335-1386) with the univariate loops above on the rows: a row sum mul_1d(a, b) is formed
@@ -90,11 +90,14 @@ void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double*
 // mt:441-450, both over that general product at the compact shapes min(la + lb - 1, n) per axis.  compose costs about
 // slices * (n0 * n1)^2 / 4 multiply-adds per item, all of them on one workgroup.
 constexpr unsigned SERIES2_MAX_ELEMS = 4096;  // n0 * n1 of the result: two resident arrays are then 64 KB
+// Interval<F64> items (gfti_series2_*): an LDS element is a 16-byte {lo, hi}, so two resident arrays are the same 64 KB at half that
+constexpr unsigned SERIES2_MAX_ELEMS_IV = 2048;
+inline unsigned series2_max_elems(int w) { return w == 2 ? SERIES2_MAX_ELEMS_IV : SERIES2_MAX_ELEMS; }
 struct Series2Dims {
     unsigned nx0, nx1, ny0, ny1, n0, n1;  // stored shapes of x and y (exp / log / pow: ny* unused) and the result's; nx*, ny* <= n*
     size_t xr, yr, rr;                    // row strides in elements
 };
-// The geometry of a call: lanes per workgroup, scratch rows of n1 doubles (div / exp / log: the row sums of one chunk of j), the
+// The geometry of a call of element width w (1: F64, 2: Interval<F64>): lanes per workgroup, scratch rows of n1 elements (div / exp / log: the row sums of one chunk of j), the
 // dynamic LDS in bytes, and for compose whether g is resident in LDS.  Throws std::runtime_error where the runtime grants less LDS
 // than the resident arrays and one scratch row need.
 struct Series2Plan {
@@ -102,17 +105,20 @@ struct Series2Plan {
     size_t lds;
     bool glds = false;
 };
-Series2Plan series2_plan(int op, const Series2Dims& d);
+Series2Plan series2_plan(int op, const Series2Dims& d, int w = 1);
 // Launches SERIES_MUL / DIV / EXP / LOG / COMPOSE at rank 2 on `st`.  `y`: the divisor / second factor / compose's g (x is f, and
-// `var` the variable of f that g replaces); for exp / log the seeds or nullptr.  Not for SERIES_POW.
+// `var` the variable of f that g replaces); for exp / log the seeds or nullptr.  `pl`: the element width and the plane strides.  Not
+// for SERIES_POW.
 void series2_launch(hipStream_t st, int op, const Series2Plan& p, const double* x, const double* y, double* res, const Series2Dims& d,
-                    const SeriesBatch& g, int var = 0);
-// doubles of device workspace series2_pow needs: the base and two results taking turns, each items * n0 * n1, and the factor [[1.0]]
-size_t series2_pow_workspace(unsigned items, const Series2Dims& d);
+                    const SeriesBatch& g, int var = 0, const SeriesPlanes& pl = SeriesPlanes());
+// doubles of device workspace series2_pow needs: the base and two results taking turns, each items * n0 * n1, and the factor [[1.0]];
+// w planes of that, plane-major
+size_t series2_pow_workspace(unsigned items, const Series2Dims& d, int w = 1);
 // x^e on `st`, series_pow at rank 2: x is copied once into the workspace, every product but the last is a SERIES_MUL launch on
 // compact workspace items, the last one writes all (n0, n1) coefficients through the result's strides.  e == 0 only writes the
 // unit item.
-void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws);
+void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws,
+                 const SeriesPlanes& pl = SeriesPlanes());
 
 // the element offsets of item `it` (kernels of gft_series.hip and gft_div2d.hip)
 struct SeriesOff {

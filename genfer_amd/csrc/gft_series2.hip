@@ -1,5 +1,6 @@
 // Batched bivariate series (gft_series.hpp, "rank 2"): the planner and the launches of gft_series2_mul / div / exp / log / compose,
-// and pow's sequence of mul launches.  The kernels are in gft_series2_kernels.hpp; gfx950 only, f64 only.
+// and pow's sequence of mul launches, for F64 and for Interval<F64> (the element width w of the entry point: SeriesPlanes).  The kernels
+// are in gft_series2_kernels.hpp; gfx950 only.
 //
 // One form: one workgroup per item for the whole operation.
 //   lanes    one wave while the item has at most 64 coefficients, else up to 256 in whole waves: mul counts its output PAIRS (a
@@ -11,6 +12,9 @@
 //            Where the runtime grants only 64 KB an item whose arrays and one scratch row do not fit is refused by name.
 //            compose: two result arrays of n0 * n1 doubles taking turns, at most 64 KB, and g compact behind them where the three
 //            fit the grant of that 80 KB request; otherwise g stays in global memory, so every admissible shape runs on 64 KB.
+// Intervals (w == 2): an LDS element is 16 bytes, so every footprint above is reached at half the coefficients -- the limit is 2048
+// (SERIES2_MAX_ELEMS_IV), two resident arrays are the same 64 KB, and the scratch rows, compose's GLDS decision and the refusal
+// scale with the width.  The LDS requests and what the runtime answered are kept per element type.
 // compose's lanes count mul's output pairs of the full shape, in whole waves up to 512 (measured: S2_COMPOSE_LANES).  pow has no
 // kernel of its own beside the writer of the unit item.
 #include <hip/hip_runtime.h>
@@ -30,13 +34,16 @@ namespace {
 constexpr size_t S2_BUDGET = 80 * 1024, S2_BUDGET_PLAIN = 64 * 1024;
 
 // what the runtime grants the three recurrence kernels and compose with g resident, asked once
-size_t s2_budget() {
-    static size_t granted = 0;
+size_t s2_budget(int w) {
+    static size_t answers[2] = {0, 0};
+    size_t& granted = answers[w == 2];
     if (granted) return granted;
-    const void* ks[] = {(const void*)k_series2_rec<SERIES_DIV>, (const void*)k_series2_rec<SERIES_EXP>, (const void*)k_series2_rec<SERIES_LOG>,
+    const void* kf[] = {(const void*)k_series2_rec<SERIES_DIV>, (const void*)k_series2_rec<SERIES_EXP>, (const void*)k_series2_rec<SERIES_LOG>,
                         (const void*)k_series2_compose<true>};
+    const void* ki[] = {(const void*)k_series2i_rec<EIv, SERIES_DIV>, (const void*)k_series2i_rec<EIv, SERIES_EXP>,
+                        (const void*)k_series2i_rec<EIv, SERIES_LOG>, (const void*)k_series2i_compose<EIv, true>};
     granted = S2_BUDGET;
-    for (const void* k : ks)
+    for (const void* k : (w == 2 ? ki : kf))
         if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_BUDGET) != hipSuccess) {
             (void)hipGetLastError();  // no stale error for the caller's next HIP call
             granted = S2_BUDGET_PLAIN;
@@ -46,11 +53,13 @@ size_t s2_budget() {
 }
 
 // the unit item [[1, 0, ...], [0, ...], ...] of pow: its first factor (one item of one coefficient) and the whole result of e == 0
-__global__ __launch_bounds__(256) void k_series2_unit(double* res, size_t rr, unsigned n0, unsigned n1, SeriesBatch b) {
+// (an interval item: [1,1] and [0,0], both planes `plane` apart)
+template <class E>
+__global__ __launch_bounds__(256) void k_series2_unit(double* res, size_t plane, size_t rr, unsigned n0, unsigned n1, SeriesBatch b) {
     const SeriesOff o = series_offsets(b, blockIdx.x);
     for (unsigned idx = threadIdx.x; idx < n0 * n1; idx += blockDim.x) {
         const unsigned k0 = idx / n1, k1 = idx - k0 * n1;
-        res[o.r + (size_t)k0 * rr + k1] = idx == 0 ? 1.0 : 0.0;
+        E::st(res, plane, o.r + (size_t)k0 * rr + k1, idx == 0 ? E::one() : E::zero());
     }
 }
 
@@ -61,33 +70,34 @@ constexpr unsigned S2_COMPOSE_LANES = 512;
 
 }  // namespace
 
-Series2Plan series2_plan(int op, const Series2Dims& d) {
+Series2Plan series2_plan(int op, const Series2Dims& d, int w) {
     Series2Plan p;
+    const size_t elem = (size_t)w * sizeof(double);  // of an LDS element
     const unsigned N = d.n0 * d.n1;
     if (op == SERIES_MUL) {
         p.threads = s2_threads((N + 1) / 2);
         p.srows = 0;
-        p.lds = ((size_t)d.nx0 * d.nx1 + (size_t)d.ny0 * d.ny1) * sizeof(double);
+        p.lds = ((size_t)d.nx0 * d.nx1 + (size_t)d.ny0 * d.ny1) * elem;
         return p;
     }
     if (op == SERIES_COMPOSE) {
-        const size_t rows = (size_t)2 * N * sizeof(double), all = rows + (size_t)d.ny0 * d.ny1 * sizeof(double);
+        const size_t rows = (size_t)2 * N * elem, all = rows + (size_t)d.ny0 * d.ny1 * elem;
         p.threads = s2_threads((N + 1) / 2, S2_COMPOSE_LANES);
         p.srows = 0;
-        p.glds = all <= S2_BUDGET_PLAIN || all <= s2_budget();
+        p.glds = all <= S2_BUDGET_PLAIN || all <= s2_budget(w);
         p.lds = p.glds ? all : rows;
         return p;
     }
     const unsigned a0 = op == SERIES_DIV ? d.ny0 : d.nx0, a1 = op == SERIES_DIV ? d.ny1 : d.nx1;
-    const size_t resident = ((size_t)a0 * a1 + N) * sizeof(double), row = (size_t)d.n1 * sizeof(double);
+    const size_t resident = ((size_t)a0 * a1 + N) * elem, row = (size_t)d.n1 * elem;
     unsigned terms = std::min(d.n0, a0) - 1;  // of the longest j range (log's starts at 1: one term fewer while k < nx0)
     if (op == SERIES_LOG && d.n0 <= a0) terms = d.n0 >= 2 ? d.n0 - 2 : 0;
     p.threads = s2_threads(N);
     p.srows = 0;
     if (terms) {
-        const size_t budget = s2_budget();
+        const size_t budget = s2_budget(w);
         if (resident + row > budget)
-            throw std::runtime_error("series2: an item of " + std::to_string(d.n0) + " x " + std::to_string(d.n1) + " coefficients needs " +
+            throw std::runtime_error("series2: an item of " + std::to_string(d.n0) + " x " + std::to_string(d.n1) + " coefficients" + (w == 2 ? " of two bounds" : "") + " needs " +
                                      std::to_string(resident + row) + " bytes of LDS (two resident arrays and one scratch row), but the runtime grants " +
                                      std::to_string(budget) + " bytes per workgroup");
         p.srows = (unsigned)std::min<size_t>(terms, (budget - resident) / row);
@@ -97,9 +107,23 @@ Series2Plan series2_plan(int op, const Series2Dims& d) {
 }
 
 void series2_launch(hipStream_t st, int op, const Series2Plan& p, const double* x, const double* y, double* res, const Series2Dims& d,
-                    const SeriesBatch& g, int var) {
+                    const SeriesBatch& g, int var, const SeriesPlanes& pl) {
     if (g.items == 0) return;
     const dim3 grid(g.items), block(p.threads);
+    if (pl.w == 2) {
+        switch (op) {
+            case SERIES_MUL: GFT_LAUNCH(k_series2i_mul<EIv>, grid, block, p.lds, st, x, y, res, d, g, pl); break;
+            case SERIES_DIV: GFT_LAUNCH((k_series2i_rec<EIv, SERIES_DIV>), grid, block, p.lds, st, x, y, res, d, p.srows, g, pl); break;
+            case SERIES_EXP: GFT_LAUNCH((k_series2i_rec<EIv, SERIES_EXP>), grid, block, p.lds, st, x, y, res, d, p.srows, g, pl); break;
+            case SERIES_LOG: GFT_LAUNCH((k_series2i_rec<EIv, SERIES_LOG>), grid, block, p.lds, st, x, y, res, d, p.srows, g, pl); break;
+            case SERIES_COMPOSE:
+                if (p.glds) GFT_LAUNCH((k_series2i_compose<EIv, true>), grid, block, p.lds, st, x, y, res, d, var, g, pl);
+                else GFT_LAUNCH((k_series2i_compose<EIv, false>), grid, block, p.lds, st, x, y, res, d, var, g, pl);
+                break;
+            default: throw std::runtime_error("series2: no such operation at rank 2");
+        }
+        return;
+    }
     switch (op) {
         case SERIES_MUL: GFT_LAUNCH(k_series2_mul, grid, block, p.lds, st, x, y, res, d, g); break;
         case SERIES_DIV: GFT_LAUNCH(k_series2_rec<SERIES_DIV>, grid, block, p.lds, st, x, y, res, d, p.srows, g); break;
@@ -113,37 +137,43 @@ void series2_launch(hipStream_t st, int op, const Series2Plan& p, const double* 
     }
 }
 
-size_t series2_pow_workspace(unsigned items, const Series2Dims& d) { return 3 * (size_t)items * d.n0 * d.n1 + 1; }
+size_t series2_pow_workspace(unsigned items, const Series2Dims& d, int w) { return (size_t)w * (3 * (size_t)items * d.n0 * d.n1 + 1); }
 
-void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws) {
+namespace {
+
+template <class E>
+void s2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
     if (g.items == 0) return;
     const unsigned N = d.n0 * d.n1;
     if (e == 0) {
-        GFT_LAUNCH(k_series2_unit, dim3(g.items), dim3(s2_threads(N)), 0, st, res, d.rr, d.n0, d.n1, g);
+        GFT_LAUNCH(k_series2_unit<E>, dim3(g.items), dim3(s2_threads(N)), 0, st, res, pl.r, d.rr, d.n0, d.n1, g);
         return;
     }
-    // three workspace arrays of items * N doubles each, whatever the compact shape of the items in it
-    const size_t arr = (size_t)g.items * N;
+    // three workspace arrays of items * N elements each, whatever the compact shape of the items in it, and the unit item; plane-major:
+    // the upper bounds of everything in the workspace lie `wp` doubles behind the lower ones
+    const size_t arr = (size_t)g.items * N, wp = 3 * arr + 1;
     double* spare[2] = {ws + arr, ws + 2 * arr};
     int nspare = 2;
     double* unit = ws + 3 * arr;
     SeriesBatch one;
     one.nd = 0;
     one.items = 1;
-    GFT_LAUNCH(k_series2_unit, dim3(1), dim3(64), 0, st, unit, (size_t)1, 1u, 1u, one);
+    GFT_LAUNCH(k_series2_unit<E>, dim3(1), dim3(64), 0, st, unit, wp, (size_t)1, 1u, 1u, one);
     // the operand, read once through its strides: base = x as compact items of (nx0, nx1)
     double* base = ws;
     unsigned lb0 = d.nx0, lb1 = d.nx1;
     {
         CopyGeom c;
+        int k = 0;
+        if (E::W == 2) c.ext[k] = 2, c.ss[k] = pl.x, c.ds[k] = wp, ++k;
         size_t cs = (size_t)lb0 * lb1;
         for (int a = g.nd - 1; a >= 0; --a) {
-            c.ext[a] = g.ext[a];
-            c.ss[a] = g.xs[a];
-            c.ds[a] = cs;
+            c.ext[k + a] = g.ext[a];
+            c.ss[k + a] = g.xs[a];
+            c.ds[k + a] = cs;
             cs *= g.ext[a];
         }
-        int k = g.nd;
+        k += g.nd;
         c.ext[k] = lb0, c.ss[k] = d.xr, c.ds[k] = lb1, ++k;
         c.ext[k] = lb1, c.ss[k] = 1, c.ds[k] = 1, ++k;
         c.nd = k;
@@ -170,7 +200,10 @@ void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const
             if (!last) w.rs[ax] = cs * ri;
             cs *= g.ext[ax];
         }
-        series2_launch(st, SERIES_MUL, series2_plan(SERIES_MUL, m), a, b, out, m, w);
+        SeriesPlanes wpl;
+        wpl.w = E::W;
+        if (E::W == 2) wpl.x = wpl.y = wp, wpl.r = last ? pl.r : wp;
+        series2_launch(st, SERIES_MUL, series2_plan(SERIES_MUL, m, E::W), a, b, out, m, w, 0, wpl);
     };
     while (e > 0) {
         if (e & 1) {
@@ -192,6 +225,14 @@ void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const
             lb0 = l0, lb1 = l1;
         }
     }
+}
+
+}  // namespace
+
+void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws,
+                 const SeriesPlanes& pl) {
+    if (pl.w == 2) s2_pow<EIv>(st, x, e, res, d, g, ws, pl);
+    else s2_pow<EF64>(st, x, e, res, d, g, ws, pl);
 }
 
 }  // namespace gft

@@ -1,4 +1,4 @@
-// Device side of the batched bivariate series (gft_series2.hip plans and launches these; f64 only).  One workgroup is one item
+// Device side of the batched bivariate series (gft_series2.hip plans and launches these).  One workgroup is one item
 // for the whole operation, the operands resident in LDS.  tests/series2_isa_check.hip instantiates the kernels from this file.
 //
 // An item is an [n0, n1] coefficient array, axis 0 the rows.  Every operation is the reference's recursion over axis 0 whose
@@ -12,6 +12,14 @@
 //                  chunks); then the row's own step: negate and add the dividend, the 1-d division by row 0 of the divisor, the
 //                  division by k.  Chunking changes how many row sums are in flight, never the order of an addition.
 // Multiply and add are rounded separately (-ffp-contract=off) and no explicit fma is written.
+//
+// The bodies are templates over the element functor (gft_elem.hpp).  k_series2_mul, k_series2_rec<OP> and k_series2_compose<GLDS> are
+// the EF64 kernels; k_series2i_mul<E>, k_series2i_rec<E, OP> and k_series2i_compose<E, GLDS> run the same bodies on Interval<F64>
+// (E = EIv, tests/series2_interval_isa_check.hip), every step through the functor: E::zero, add, neg, mul, mac, div, from_u32, exp,
+// log, with mac / mulw / addw's wave-uniform shortcut (their ballot sees the active lanes only, so they stand inside the divergent
+// loops).  In global memory an interval array is two planes (lo, hi) a plane stride apart; in LDS an interval is ONE 16-byte
+// element {lo, hi} (S2Iv, the dynamic LDS declared 16-byte aligned): staging interleaves on the write, and the inner loops of mul
+// and compose read one ds_read_b128 per operand.  All LDS sizes below are in elements: 8 bytes for EF64, 16 for EIv.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,51 +29,103 @@
 
 namespace gft {
 
-// rows x cols doubles from global rows `rstride` apart into a compact LDS array
-__device__ inline void s2_stage(double* lds, const double* src, size_t rstride, unsigned rows, unsigned cols) {
+// ---- the LDS element of a functor -------------------------------------------------------------------------------------------------
+struct alignas(16) S2Iv {  // an interval in LDS: one aligned 16-byte element
+    double lo, hi;
+};
+template <class E>
+struct S2L;
+template <>
+struct S2L<EF64> {
+    typedef double T;
+    __device__ static double get(const double* p, int i) { return p[i]; }
+    __device__ static void put(double* p, unsigned i, double v) { p[i] = v; }
+};
+template <>
+struct S2L<EIv> {
+    typedef S2Iv T;
+    __device__ static Iv get(const S2Iv* p, int i) {
+        const S2Iv t = p[i];
+        return Iv{t.lo, t.hi};
+    }
+    __device__ static void put(S2Iv* p, unsigned i, Iv v) { p[i] = S2Iv{v.lo, v.hi}; }
+};
+// a row of an LDS array as rec_exp / rec_log take it
+template <class E>
+struct S2Row {
+    typename S2L<E>::T* p;
+    __device__ typename E::V ld(unsigned i) const { return S2L<E>::get(p, (int)i); }
+    __device__ void st(unsigned i, typename E::V v) const { S2L<E>::put(p, i, v); }
+};
+// the second factor of s2_mul_out: compact in LDS, or in global memory at its row stride (planes `plane` apart)
+template <class E>
+struct S2InLds {
+    const typename S2L<E>::T* p;
+    __device__ S2InLds at(size_t off) const { return S2InLds{p + off}; }
+    __device__ typename E::V ld(int i) const { return S2L<E>::get(p, i); }
+};
+template <class E>
+struct S2InGlobal {
+    const double* p;
+    size_t plane;
+    __device__ S2InGlobal at(size_t off) const { return S2InGlobal{p + off, plane}; }
+    __device__ typename E::V ld(int i) const {
+        if constexpr (E::W == 1) return p[i];
+        else return E::ld(p + i, plane, 0);
+    }
+};
+
+// rows x cols elements from global rows `rstride` apart (planes `plane` apart) into a compact LDS array
+template <class E>
+__device__ inline void s2_stage(typename S2L<E>::T* lds, const double* src, size_t plane, size_t rstride, unsigned rows, unsigned cols) {
     const unsigned total = rows * cols;
     for (unsigned i = threadIdx.x; i < total; i += blockDim.x) {
         const unsigned r = i / cols, c = i - r * cols;
-        lds[i] = src[(size_t)r * rstride + c];
+        S2L<E>::put(lds, i, E::ld(src, plane, (size_t)r * rstride + c));
     }
 }
 // the item's result from its compact LDS array: after a __syncthreads that follows every global load of this workgroup, so the
 // result may be an operand itself
-__device__ inline void s2_store(double* res, size_t rstride, const double* lds, unsigned rows, unsigned cols) {
+template <class E>
+__device__ inline void s2_store(double* res, size_t plane, size_t rstride, const typename S2L<E>::T* lds, unsigned rows, unsigned cols) {
     const unsigned total = rows * cols;
     for (unsigned i = threadIdx.x; i < total; i += blockDim.x) {
         const unsigned r = i / cols, c = i - r * cols;
-        res[(size_t)r * rstride + c] = lds[i];
+        E::st(res, plane, (size_t)r * rstride + c, S2L<E>::get(lds, (int)i));
     }
 }
 
 // ---- mul (mt:984-1012) ------------------------------------------------------------------------------------------------------
 // z[k0][k1] = 0 + sum_{j0} (0 + sum_{j1} x[j0][j1] * y[k0-j0][k1-j1]), both ascending over the stored coefficients.
 // x has pitch d.nx1; `yp` is the pitch of y: d.ny1 for a staged y, its row stride where it stays in global memory.
-__device__ inline double s2_mul_out(const double* xl, const double* yl, const Series2Dims& d, size_t yp, unsigned k0, unsigned k1) {
+template <class E, class YA>
+__device__ inline typename E::V s2_mul_out(const typename S2L<E>::T* xl, const YA yl, const Series2Dims& d, size_t yp, unsigned k0, unsigned k1) {
+    typedef typename E::V V;
     const unsigned lo0 = k0 + 1 > d.ny0 ? k0 + 1 - d.ny0 : 0, hi0 = k0 + 1 < d.nx0 ? k0 + 1 : d.nx0;
     const unsigned lo1 = k1 + 1 > d.ny1 ? k1 + 1 - d.ny1 : 0, hi1 = k1 + 1 < d.nx1 ? k1 + 1 : d.nx1;
-    double z = 0.0;
+    V z = E::zero();
     for (unsigned j0 = lo0; j0 < hi0; ++j0) {
-        const double* xr = xl + j0 * d.nx1;
-        const double* yr = yl + (k0 - j0) * yp + k1;
-        double o = 0.0;
+        const typename S2L<E>::T* xr = xl + j0 * d.nx1;
+        const YA yr = yl.at((k0 - j0) * yp + k1);
+        V o = E::zero();
 #pragma unroll 4
-        for (unsigned j1 = lo1; j1 < hi1; ++j1) o = o + xr[j1] * yr[-(int)j1];
-        z = z + o;
+        for (unsigned j1 = lo1; j1 < hi1; ++j1) o = E::mac(o, S2L<E>::get(xr, (int)j1), yr.ld(-(int)j1));
+        z = E::addw(z, o);
     }
     return z;
 }
 // x and y staged compactly.  Thread t owns the outputs t and N - 1 - t of the row-major item, (k0, k1) and (n0-1-k0, n1-1-k1): a
 // heavy output with a light one, as mul form B pairs k with n - 1 - k.  Lanes of a wave take consecutive k1, so the x address is
 // wave-uniform where the bounds agree and the y addresses are consecutive.
-__global__ __launch_bounds__(256) void k_series2_mul(const double* x, const double* y, double* res, Series2Dims d, SeriesBatch g) {
-    extern __shared__ double s2_lds[];  // [nx0][nx1] | [ny0][ny1]
-    double* xl = s2_lds;
-    double* yl = s2_lds + d.nx0 * d.nx1;
+template <class E>
+__device__ inline void s2_mul_body(typename S2L<E>::T* lds, const double* x, const double* y, double* res, const Series2Dims& d,
+                                   const SeriesBatch& g, const SeriesPlanes& pl) {
+    typedef typename S2L<E>::T T;  // [nx0][nx1] | [ny0][ny1]
+    T* xl = lds;
+    T* yl = lds + d.nx0 * d.nx1;
     const SeriesOff o = series_offsets(g, blockIdx.x);
-    s2_stage(xl, x + o.x, d.xr, d.nx0, d.nx1);
-    s2_stage(yl, y + o.y, d.yr, d.ny0, d.ny1);
+    s2_stage<E>(xl, x + o.x, pl.x, d.xr, d.nx0, d.nx1);
+    s2_stage<E>(yl, y + o.y, pl.y, d.yr, d.ny0, d.ny1);
     __syncthreads();  // (every global load of this workgroup is done: the result may be x or y)
     const unsigned N = d.n0 * d.n1, half = (N + 1) / 2;
     for (unsigned t = threadIdx.x; t < half; t += blockDim.x) {
@@ -75,9 +135,18 @@ __global__ __launch_bounds__(256) void k_series2_mul(const double* x, const doub
             const unsigned i = is[h];
             if (h == 1 && i == is[0]) break;  // the middle output of an odd N
             const unsigned k0 = i / d.n1, k1 = i - k0 * d.n1;
-            res[o.r + (size_t)k0 * d.rr + k1] = s2_mul_out(xl, yl, d, d.ny1, k0, k1);
+            E::st(res, pl.r, o.r + (size_t)k0 * d.rr + k1, s2_mul_out<E>(xl, S2InLds<E>{yl}, d, d.ny1, k0, k1));
         }
     }
+}
+__global__ __launch_bounds__(256) void k_series2_mul(const double* x, const double* y, double* res, Series2Dims d, SeriesBatch g) {
+    extern __shared__ double s2_lds[];
+    s2_mul_body<EF64>(s2_lds, x, y, res, d, g, SeriesPlanes());
+}
+template <class E>
+__global__ __launch_bounds__(256) void k_series2i_mul(const double* x, const double* y, double* res, Series2Dims d, SeriesBatch g, SeriesPlanes pl) {
+    extern __shared__ S2Iv s2_lds_iv[];
+    s2_mul_body<E>(s2_lds_iv, x, y, res, d, g, pl);
 }
 
 // ---- compose (subst_var's Horner path, mt:569-579) --------------------------------------------------------------------------------
@@ -85,32 +154,29 @@ __global__ __launch_bounds__(256) void k_series2_mul(const double* x, const doub
 // with S of them and `len` coefficients each:
 //   res = 0.0 + slice S-1, stored shape (1, len) / (len, 1);  for i = S-2 .. 0:  res = mul(res, g) at the compact shape
 //   L = (min(r0 + ng0 - 1, n0), min(r1 + ng1 - 1, n1)) of sum_shape;  row 0 / column 0 of res += slice i
-// One workgroup runs the whole loop of its item (the steps are a dependency chain).  Two result arrays of n0 * n1 doubles take turns
+// One workgroup runs the whole loop of its item (the steps are a dependency chain).  Two result arrays of n0 * n1 elements take turns
 // in LDS, the current one compact at pitch r1; g sits compact behind them (GLDS) or stays in global memory at its row stride (the
-// fallback where 2 N + ng0 * ng1 doubles exceed the granted LDS).  Every step is k_series2_mul's pairing on a Series2Dims built for
+// fallback where 2 N + ng0 * ng1 elements exceed the granted LDS).  Every step is k_series2_mul's pairing on a Series2Dims built for
 // the step: a thread owns the outputs t and L0 * L1 - 1 - t, all bounds the same for every item; up to 512 lanes.  The owner of an output on the
 // added slice loads f's coefficient before its sums and adds it after them -- with GLDS the only global traffic between steps,
 // which meet through LDS alone.  f and g are read completely before the first store: the result may be f or g itself.
-template <bool GLDS>
-__global__ __launch_bounds__(512) void k_series2_compose(const double* f, const double* g, double* res, Series2Dims d, int var, SeriesBatch b) {
-    extern __shared__ double s2_lds[];  // res [n0 * n1] | res [n0 * n1] | (GLDS) g [ng0][ng1]
+template <class E, bool GLDS>
+__device__ inline void s2_compose_body(typename S2L<E>::T* lds, const double* f, const double* g, double* res, const Series2Dims& d, int var,
+                                       const SeriesBatch& b, const SeriesPlanes& pl) {
+    typedef typename E::V V;
+    typedef typename S2L<E>::T T;  // res [n0 * n1] | res [n0 * n1] | (GLDS) g [ng0][ng1]
     const unsigned N = d.n0 * d.n1, tid = threadIdx.x, nt = blockDim.x;
-    double* cur = s2_lds;
-    double* nxt = s2_lds + N;
+    T* cur = lds;
+    T* nxt = lds + N;
+    T* gl = lds + 2 * N;
     const SeriesOff o = series_offsets(b, blockIdx.x);
     const double* fg = f + o.x;
-    const double* gs = g + o.y;
-    size_t gp = d.yr;
-    if (GLDS) {
-        double* gl = s2_lds + 2 * N;
-        s2_stage(gl, g + o.y, d.yr, d.ny0, d.ny1);
-        gs = gl;
-        gp = d.ny1;
-    }
+    if (GLDS) s2_stage<E>(gl, g + o.y, pl.y, d.yr, d.ny0, d.ny1);
+    const size_t gp = GLDS ? d.ny1 : d.yr;
     // slice i of f is fg[i * fslice + c * fstep], c < len
     const unsigned slices = var == 0 ? d.nx0 : d.nx1, len = var == 0 ? d.nx1 : d.nx0;
     const size_t fslice = var == 0 ? d.xr : 1, fstep = var == 0 ? 1 : d.xr;
-    for (unsigned c = tid; c < len; c += nt) cur[c] = 0.0 + fg[(slices - 1) * fslice + c * fstep];
+    for (unsigned c = tid; c < len; c += nt) S2L<E>::put(cur, c, E::add(E::zero(), E::ld(fg, pl.x, (slices - 1) * fslice + c * fstep)));
     __syncthreads();
     unsigned r0 = var == 0 ? 1 : len, r1 = var == 0 ? len : 1;  // the stored shape of res
     for (unsigned i = slices - 1; i-- > 0;) {
@@ -128,15 +194,17 @@ __global__ __launch_bounds__(512) void k_series2_compose(const double* f, const 
                 if (h == 1 && idx == is[0]) break;  // the middle output of an odd M
                 const unsigned k0 = idx / s.n1, k1 = idx - k0 * s.n1;
                 const bool added = var == 0 ? (k0 == 0 && k1 < len) : (k1 == 0 && k0 < len);
-                double fv = 0.0;
-                if (added) fv = fi[(var == 0 ? k1 : k0) * fstep];  // in flight during the sums below
-                double z = s2_mul_out(cur, gs, s, gp, k0, k1);
-                if (added) z = z + fv;
-                nxt[idx] = z;
+                V fv = E::zero();
+                if (added) fv = E::ld(fi, pl.x, (var == 0 ? k1 : k0) * fstep);  // in flight during the sums below
+                V z;
+                if (GLDS) z = s2_mul_out<E>(cur, S2InLds<E>{gl}, s, gp, k0, k1);
+                else z = s2_mul_out<E>(cur, S2InGlobal<E>{g + o.y, pl.y}, s, gp, k0, k1);
+                if (added) z = E::add(z, fv);
+                S2L<E>::put(nxt, idx, z);
             }
         }
         lds_barrier();
-        double* sw = cur;
+        T* sw = cur;
         cur = nxt;
         nxt = sw;
         r0 = s.n0, r1 = s.n1;
@@ -144,8 +212,19 @@ __global__ __launch_bounds__(512) void k_series2_compose(const double* f, const 
     __syncthreads();  // (every global load of this workgroup is done: the result may be f or g)
     for (unsigned idx = tid; idx < N; idx += nt) {
         const unsigned k0 = idx / d.n1, k1 = idx - k0 * d.n1;
-        res[o.r + (size_t)k0 * d.rr + k1] = k0 < r0 && k1 < r1 ? cur[k0 * r1 + k1] : 0.0;
+        E::st(res, pl.r, o.r + (size_t)k0 * d.rr + k1, k0 < r0 && k1 < r1 ? S2L<E>::get(cur, (int)(k0 * r1 + k1)) : E::zero());
     }
+}
+template <bool GLDS>
+__global__ __launch_bounds__(512) void k_series2_compose(const double* f, const double* g, double* res, Series2Dims d, int var, SeriesBatch b) {
+    extern __shared__ double s2_lds[];
+    s2_compose_body<EF64, GLDS>(s2_lds, f, g, res, d, var, b, SeriesPlanes());
+}
+template <class E, bool GLDS>
+__global__ __launch_bounds__(512) void k_series2i_compose(const double* f, const double* g, double* res, Series2Dims d, int var, SeriesBatch b,
+                                                          SeriesPlanes pl) {
+    extern __shared__ S2Iv s2_lds_iv[];
+    s2_compose_body<E, GLDS>(s2_lds_iv, f, g, res, d, var, b, pl);
 }
 
 // ---- the 1-d division of a row in place (mt:1162-1192 at one axis: rec_div with a full-length dividend) -----------------------
@@ -165,26 +244,28 @@ __device__ inline void s2_step_sync() {
 }
 constexpr unsigned S2_WAVE_EPT = 8;    // rows up to 512 coefficients: one wave, 8 coefficients a lane
 constexpr unsigned S2_BLOCK_EPT = 16;  // longer rows (then the workgroup has 256 lanes): 16 a lane, 4096 at most
-template <bool WAVE>
-__device__ inline void s2_div1d(double* row, const double* yv, unsigned ny1, unsigned n1, unsigned tid, unsigned P) {
-    constexpr unsigned EPT = WAVE ? S2_WAVE_EPT : S2_BLOCK_EPT;
-    double cur[EPT];
+constexpr unsigned S2_BLOCK_EPT_IV = 8;  // intervals: rows of 2048 at most, and an accumulator is two register pairs
+template <class E, bool WAVE>
+__device__ __forceinline__ void s2_div1d(typename S2L<E>::T* row, const typename S2L<E>::T* yv, unsigned ny1, unsigned n1, unsigned tid, unsigned P) {
+    typedef typename E::V V;
+    constexpr unsigned EPT = WAVE ? S2_WAVE_EPT : (E::W == 2 ? S2_BLOCK_EPT_IV : S2_BLOCK_EPT);
+    V cur[EPT];
 #pragma unroll
-    for (unsigned e = 0; e < EPT; ++e) cur[e] = 0.0;
-    const double y0 = yv[0];
+    for (unsigned e = 0; e < EPT; ++e) cur[e] = E::zero();
+    const V y0 = S2L<E>::get(yv, 0);
     for (unsigned j = 0; j < n1; ++j) {
         const unsigned oe = j / P;
         if (tid == j - oe * P) {
 #pragma unroll
             for (unsigned e = 0; e < EPT; ++e)
-                if (e == oe) row[j] = (-cur[e] + row[j]) / y0;
+                if (e == oe) S2L<E>::put(row, j, E::div(E::add(E::neg(cur[e]), S2L<E>::get(row, (int)j)), y0));
         }
         s2_step_sync<WAVE>();
-        const double q = row[j];
+        const V q = S2L<E>::get(row, (int)j);
 #pragma unroll
         for (unsigned e = 0; e < EPT; ++e) {
             const unsigned i = tid + e * P;
-            if (i < n1 && i > j && i - j < ny1) cur[e] = cur[e] + q * yv[i - j];
+            if (i < n1 && i > j && i - j < ny1) cur[e] = E::mac(cur[e], q, S2L<E>::get(yv, (int)(i - j)));
         }
     }
 }
@@ -197,26 +278,29 @@ __device__ inline void s2_div1d(double* row, const double* yv, unsigned ny1, uns
 //   log  r[0] = log_1d(x[0]);  c = sum_{j = max(1,k+1-nx0) .. k-1} mul_1d(x[k-j], r[j] * j);  c = -c;  c[:nx1] += k * x[k] (k < nx0);
 //        r[k] = div_1d(c, x[0]) / k
 // `y`: div's divisor; exp / log: the seeds exp(x[0][0]) / ln(x[0][0]) per item, or null (formed here by the device library).
-template <int OP>
-__global__ __launch_bounds__(256) void k_series2_rec(const double* x, const double* y, double* res, Series2Dims d, unsigned srows,
-                                                     SeriesBatch g) {
+// j and k enter as E::from_u32 (the reference's S::from_u32): with intervals the point [j, j], whose product with a coefficient is
+// the functor's mul, short-circuits included ([1,1] * b is b).
+template <class E, int OP>
+__device__ inline void s2_rec_body(typename S2L<E>::T* lds, const double* x, const double* y, double* res, const Series2Dims& d, unsigned srows,
+                                   const SeriesBatch& g, const SeriesPlanes& pl) {
+    typedef typename E::V V;
+    typedef typename S2L<E>::T T;  // A [a0][a1] | r [n0][n1] | scratch [srows][n1]
     constexpr bool DIV = OP == SERIES_DIV, EXP = OP == SERIES_EXP;
-    extern __shared__ double s2_lds[];  // A [a0][a1] | r [n0][n1] | scratch [srows][n1]
     const unsigned a0 = DIV ? d.ny0 : d.nx0, a1 = DIV ? d.ny1 : d.nx1, n1 = d.n1;
-    double* al = s2_lds;
-    double* rl = al + a0 * a1;
-    double* sl = rl + d.n0 * n1;
+    T* al = lds;
+    T* rl = al + a0 * a1;
+    T* sl = rl + d.n0 * n1;
     const unsigned tid = threadIdx.x, nt = blockDim.x;
     const SeriesOff o = series_offsets(g, blockIdx.x);
-    if (DIV) s2_stage(al, y + o.y, d.yr, a0, a1);
-    else s2_stage(al, x + o.x, d.xr, a0, a1);
+    if (DIV) s2_stage<E>(al, y + o.y, pl.y, d.yr, a0, a1);
+    else s2_stage<E>(al, x + o.x, pl.x, d.xr, a0, a1);
     __syncthreads();
     if (!DIV) {  // row 0: the univariate recurrence, a dependency chain on one lane
         if (tid == 0) {
-            const RowLds<EF64> xr{al, 0}, rr{rl, 0};
-            const double sd = y ? y[o.s] : (EXP ? EF64::exp(al[0]) : EF64::log(al[0]));
-            if (EXP) rec_exp<EF64>(xr, rr, a1, n1, sd);
-            else rec_log<EF64>(xr, rr, a1, n1, sd);
+            const S2Row<E> xr{al}, rr{rl};
+            const V sd = y ? E::ld(y, pl.s, o.s) : (EXP ? E::exp(S2L<E>::get(al, 0)) : E::log(S2L<E>::get(al, 0)));
+            if (EXP) rec_exp<E>(xr, rr, a1, n1, sd);
+            else rec_log<E>(xr, rr, a1, n1, sd);
         }
         lds_barrier();
     }
@@ -230,72 +314,85 @@ __global__ __launch_bounds__(256) void k_series2_rec(const double* x, const doub
             if (!DIV && jlo < 1) jlo = 1;
             jhi = k;
         }
-        double* rk = rl + k * n1;
+        T* rk = rl + k * n1;
         for (unsigned jb = jlo; jb < jhi; jb += srows) {
             const unsigned cnt = jhi - jb < srows ? jhi - jb : srows;
             // pass 1: the row sums of the chunk, one (j, k1) a lane
             for (unsigned idx = tid; idx < cnt * n1; idx += nt) {
                 const unsigned jj = idx / n1, k1 = idx - jj * n1, j = jb + jj;
-                double s = 0.0;
+                V s = E::zero();
                 if (DIV) {  // mul_1d(r[j], y[k-j]): r[j] has n1 coefficients, y[k-j] has ny1
-                    const double* a = rl + j * n1;
-                    const double* b = al + (k - j) * a1 + k1;
+                    const T* a = rl + j * n1;
+                    const T* b = al + (k - j) * a1 + k1;
                     const unsigned lo = k1 + 1 > a1 ? k1 + 1 - a1 : 0;
 #pragma unroll 4
-                    for (unsigned j1 = lo; j1 <= k1; ++j1) s = s + a[j1] * b[-(int)j1];
+                    for (unsigned j1 = lo; j1 <= k1; ++j1) s = E::mac(s, S2L<E>::get(a, (int)j1), S2L<E>::get(b, -(int)j1));
                 } else {
-                    const double fj = (double)j;
+                    const V fj = E::from_u32(j);
                     const unsigned hi = k1 + 1 < a1 ? k1 + 1 : a1;
                     if (EXP) {  // mul_1d(x[j] * j, r[k-j]): x[j] * j is rounded before it meets r
-                        const double* a = al + j * a1;
-                        const double* b = rl + (k - j) * n1 + k1;
+                        const T* a = al + j * a1;
+                        const T* b = rl + (k - j) * n1 + k1;
 #pragma unroll 4
-                        for (unsigned j1 = 0; j1 < hi; ++j1) s = s + (a[j1] * fj) * b[-(int)j1];
+                        for (unsigned j1 = 0; j1 < hi; ++j1) s = E::mac(s, E::mulw(S2L<E>::get(a, (int)j1), fj), S2L<E>::get(b, -(int)j1));
                     } else {  // mul_1d(x[k-j], r[j] * j)
-                        const double* a = al + (k - j) * a1;
-                        const double* b = rl + j * n1 + k1;
+                        const T* a = al + (k - j) * a1;
+                        const T* b = rl + j * n1 + k1;
 #pragma unroll 4
-                        for (unsigned j1 = 0; j1 < hi; ++j1) s = s + a[j1] * (b[-(int)j1] * fj);
+                        for (unsigned j1 = 0; j1 < hi; ++j1) s = E::mac(s, S2L<E>::get(a, (int)j1), E::mulw(S2L<E>::get(b, -(int)j1), fj));
                     }
                 }
-                sl[idx] = s;
+                S2L<E>::put(sl, idx, s);
             }
             lds_barrier();
             // pass 2: the ordered additions; r[k] carries the accumulator from chunk to chunk
             for (unsigned k1 = tid; k1 < n1; k1 += nt) {
-                double c = jb == jlo ? 0.0 : rk[k1];
-                for (unsigned jj = 0; jj < cnt; ++jj) c = c + sl[jj * n1 + k1];
-                rk[k1] = c;
+                V c = jb == jlo ? E::zero() : S2L<E>::get(rk, (int)k1);
+                for (unsigned jj = 0; jj < cnt; ++jj) c = E::addw(c, S2L<E>::get(sl, (int)(jj * n1 + k1)));
+                S2L<E>::put(rk, k1, c);
             }
             lds_barrier();
         }
         // the row's own step (a lane meets the k1 it owned in pass 2)
         for (unsigned k1 = tid; k1 < n1; k1 += nt) {
-            double c = jlo < jhi ? rk[k1] : 0.0;
+            V c = jlo < jhi ? S2L<E>::get(rk, (int)k1) : E::zero();
             if (EXP) {
-                c = c / (double)k;
+                c = E::div(c, E::from_u32(k));
             } else {
-                c = -c;
-                if (k < d.nx0 && k1 < d.nx1) c = c + (DIV ? x[o.x + (size_t)k * d.xr + k1] : (double)k * al[k * a1 + k1]);
+                c = E::neg(c);
+                if (k < d.nx0 && k1 < d.nx1)
+                    c = E::add(c, DIV ? E::ld(x, pl.x, o.x + (size_t)k * d.xr + k1) : E::mul(E::from_u32(k), S2L<E>::get(al, (int)(k * a1 + k1))));
             }
-            rk[k1] = c;
+            S2L<E>::put(rk, k1, c);
         }
         lds_barrier();
         if (!EXP) {
             if (n1 <= 64 * S2_WAVE_EPT) {
-                if (tid < 64) s2_div1d<true>(rk, al, a1, n1, tid, 64);
+                if (tid < 64) s2_div1d<E, true>(rk, al, a1, n1, tid, 64);
             } else {
-                s2_div1d<false>(rk, al, a1, n1, tid, nt);
+                s2_div1d<E, false>(rk, al, a1, n1, tid, nt);
             }
             lds_barrier();
             if (!DIV) {
-                for (unsigned k1 = tid; k1 < n1; k1 += nt) rk[k1] = rk[k1] / (double)k;
+                for (unsigned k1 = tid; k1 < n1; k1 += nt) S2L<E>::put(rk, k1, E::div(S2L<E>::get(rk, (int)k1), E::from_u32(k)));
                 lds_barrier();
             }
         }
     }
     __syncthreads();  // (every global load of this workgroup is done: the result may be an operand)
-    s2_store(res + o.r, d.rr, rl, d.n0, n1);
+    s2_store<E>(res + o.r, pl.r, d.rr, rl, d.n0, n1);
+}
+template <int OP>
+__global__ __launch_bounds__(256) void k_series2_rec(const double* x, const double* y, double* res, Series2Dims d, unsigned srows,
+                                                     SeriesBatch g) {
+    extern __shared__ double s2_lds[];
+    s2_rec_body<EF64, OP>(s2_lds, x, y, res, d, srows, g, SeriesPlanes());
+}
+template <class E, int OP>
+__global__ __launch_bounds__(256) void k_series2i_rec(const double* x, const double* y, double* res, Series2Dims d, unsigned srows, SeriesBatch g,
+                                                      SeriesPlanes pl) {
+    extern __shared__ S2Iv s2_lds_iv[];
+    s2_rec_body<E, OP>(s2_lds_iv, x, y, res, d, srows, g, pl);
 }
 
 }  // namespace gft

@@ -1,0 +1,71 @@
+"""Batched bivariate series on interval device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow``
+(``gfti_series2_*``), the ``Interval<F64>`` half of ``genfer_amd.series2``.
+
+An interval tensor is float64 and stacked ``[2, B..., n0, n1]`` = (lo, hi) along its first axis, as ``IntervalTaylorPoly.from_torch``
+takes it.  The last two axes are the coefficient array of one ``TaylorPoly<Interval<F64>>`` in two variables (axis -2: variable 0,
+any non-negative stride; axis -1: variable 1, unit stride), the axes between are batch axes and broadcast by torch's rules.  The
+plane axis may have any non-negative stride on an operand, 0 included: ``x.expand(2, ...)`` is a batch of point intervals, no
+copy.  The result's two planes are distinct memory.  Seeds of ``exp`` / ``log`` are ``[2, B...]``.  ``n0 * n1 <= 2048``: an
+interval takes 16 bytes of LDS, so the footprints float64 items reach at 4096 are reached there.  Per item the results are the
+recursions of ``genfer_amd.series2`` with every step one operation of the reference's interval arithmetic (round to nearest, one
+ulp outwards, its short-circuits included), every bound with the oracle's bits.  One launch per call (``pow``: a sequence inside
+one call), one workgroup per item; the call is ordered on torch's current stream and does not wait.
+
+    >>> from genfer_amd import interval_series2 as ivs2
+    >>> z = ivs2.mul(x, y)                          # x, y: [2, B, n0, n1] float64 on the GPU
+    >>> q = ivs2.div(p.expand(2, B, n0, n1), y)     # p: [B, n0, n1] point values
+    >>> e = ivs2.exp(x, seed=s)                     # s: [2, B], the interval exp of coefficient [0, 0]
+    >>> h = ivs2.compose(f, g, var=1)
+    >>> p = ivs2.pow(x, 5)
+
+No autograd: an operand that requires grad is refused while grad mode is on, as in ``series2``.
+"""
+from __future__ import annotations
+
+from .series import _exponent
+from .series2 import _run
+from .taylor import TaylorError
+
+MAX_ELEMS = 2048  # gft_series.hpp SERIES2_MAX_ELEMS_IV: n0 * n1 of the result
+
+
+def _iv(what, x, second, n, out, second_is_seed, **kw):
+    return _run(f"interval_series2.{what}", f"gfti_series2_{what}", x, second, n, out, second_is_seed, planes=1, max_elems=MAX_ELEMS, **kw)
+
+
+def mul(x, y, n=None, out=None):
+    """``z[b] = x[b] * y[b]`` truncated at orders ``n = (n0, n1)`` (default: the larger stored length on each axis): the general
+    product over intervals."""
+    return _iv("mul", x, y, n, out, False)
+
+
+def div(x, y, n=None, out=None):
+    """``r[b] = x[b] / y[b]`` to orders ``n = (n0, n1)``: the general division recurrence over the rows, over intervals."""
+    return _iv("div", x, y, n, out, False)
+
+
+def exp(x, n=None, seed=None, out=None):
+    """``exp(x[b])`` to orders ``n``.  ``seed``: the interval ``exp`` of coefficient ``[0, 0]`` per item, ``[2, B...]``; with the host
+    libm's values widened as the reference widens them the result carries its bits.  ``None``: formed on the device."""
+    return _iv("exp", x, seed, n, out, True)
+
+
+def log(x, n=None, seed=None, out=None):
+    """``log(x[b])`` to orders ``n``.  ``seed``: the interval ``ln`` of coefficient ``[0, 0]`` per item, ``[2, B...]``; ``None``:
+    formed on the device (only coefficient ``[0, 0]`` depends on it)."""
+    return _iv("log", x, seed, n, out, True)
+
+
+def compose(f, g, var=0, n=None, out=None):
+    """``f[b]`` with ``g[b]`` substituted for variable ``var`` (0: axis -2, 1: axis -1) of ``f``, truncated at ``n = (n0, n1)``:
+    ``series2.compose``'s Horner loop with the general interval product at every step, the whole loop in one launch."""
+    if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
+        raise TaylorError(f"interval_series2.compose: var = {var!r}; the variable of f that g replaces is 0 or 1")
+    return _iv("compose", f, g, n, out, False, names=("f", "g"), scalar=var)
+
+
+def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
+    """``x[b] ** e`` truncated at ``n = (n0, n1)`` (default: the stored shape) for an integer ``0 <= e < 2**32``: the reference's
+    square-and-multiply over ``mul`` at compact shapes.  ``e = 0`` gives the unit item: ``[1, 1]`` at ``[0, 0]``, ``[0, 0]`` elsewhere."""
+    e = _exponent("interval_series2.pow", e, div="interval_series2.div")
+    return _iv("pow", x, None, n, out, True, scalar=e)

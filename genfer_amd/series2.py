@@ -17,7 +17,7 @@ call is ordered on torch's current stream and does not wait.  ``compose`` substi
     >>> p = series2.pow(x, 5)
 
 No autograd in this version: an operand that requires grad is refused while grad mode is on (``detach()`` it, or use
-``torch.no_grad()``).  float64 only; no intervals.
+``torch.no_grad()``).  float64 only; the ``Interval<F64>`` twins on ``[2, B..., n0, n1]`` tensors are ``genfer_amd.interval_series2``.
 """
 from __future__ import annotations
 
@@ -38,23 +38,28 @@ def _lib():
 
         L = lib()
         i64, sz, vp, i, s = C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.c_void_p, C.c_int64, C.c_size_t
-        for name in ("mul", "div"):
-            f = getattr(L, "gft_series2_" + name)
-            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, vp, i64, i, s, s, sz, s, vp]
-        for name in ("exp", "log"):
-            f = getattr(L, "gft_series2_" + name)
-            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, vp, i64, i, s, s, sz, s, vp]
-        L.gft_series2_compose.restype = L.gft_series2_pow.restype = C.c_int
-        L.gft_series2_compose.argtypes = [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
-        L.gft_series2_pow.argtypes = [vp, i64, i, s, s, C.c_uint32, vp, i64, i, s, s, sz, s, vp]
+        for pre in ("gft_series2_", "gfti_series2_"):  # the interval twins (interval_series2.py) take the same argument lists
+            for name in ("mul", "div"):
+                f = getattr(L, pre + name)
+                f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, vp, i64, i, s, s, sz, s, vp]
+            for name in ("exp", "log"):
+                f = getattr(L, pre + name)
+                f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, vp, i64, i, s, s, sz, s, vp]
+            f = getattr(L, pre + "compose")
+            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
+            f = getattr(L, pre + "pow")
+            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, C.c_uint32, vp, i64, i, s, s, sz, s, vp]
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
 
 
-def _axes(t, what):
+def _axes(t, what, planes=0):
     """the two series axes of an operand or of ``out`` (type and dtype are judged by series._check)"""
-    if t.dim() < 2:
+    if t.dim() < 2 + planes:
+        if planes:
+            raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate interval series needs at least 3 (the first holds the two "
+                              "planes, the last two are the coefficient array)")
         raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate series needs at least 2 (the last two are the coefficient array)")
     if t.shape[-1] == 0 or t.shape[-2] == 0:
         raise TaylorError(f"{what}: a series axis is empty (the last two axes are {tuple(t.shape[-2:])})")
@@ -62,7 +67,8 @@ def _axes(t, what):
         raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
 
 
-def _orders(what, n, *shapes):
+def _orders(what, n, *shapes, max_elems=None):
+    max_elems = MAX_ELEMS if max_elems is None else max_elems
     if n is None:
         n = (max(s[0] for s in shapes), max(s[1] for s in shapes))
     try:
@@ -71,8 +77,8 @@ def _orders(what, n, *shapes):
         raise TypeError(f"{what}: n must be a pair (n0, n1), got {n!r}") from None
     if n0 < 1 or n1 < 1:
         raise TaylorError(f"{what}: n = ({n0}, {n1}); the result needs at least one coefficient on each axis (n == 0 is refused)")
-    if n0 * n1 > MAX_ELEMS:
-        raise TaylorError(f"{what}: n0 * n1 = {n0} * {n1} = {n0 * n1} exceeds the limit of {MAX_ELEMS} coefficients per item of this version")
+    if n0 * n1 > max_elems:
+        raise TaylorError(f"{what}: n0 * n1 = {n0} * {n1} = {n0 * n1} exceeds the limit of {max_elems} coefficients per item of this version")
     for s in shapes:
         for a in (0, 1):
             if s[a] > (n0, n1)[a]:
@@ -80,37 +86,41 @@ def _orders(what, n, *shapes):
     return n0, n1
 
 
-def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), scalar=None):
-    """``scalar``: compose's ``var`` (passed behind the second operand) or pow's ``e`` (in the place of the seeds)"""
+def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), scalar=None, planes=0, max_elems=None):
+    """``scalar``: compose's ``var`` (passed behind the second operand) or pow's ``e`` (in the place of the seeds).  planes = 1:
+    the tensors are interval tensors [2, B..., n0, n1] (seeds [2, B...]); the leading axis travels as the first entry of every
+    batch-stride array, which is where the gfti_series2_* entry points expect it."""
     import torch
 
     # everything that needs no device first: types, shapes, strides, orders, out, grad -- then the placement
     xname = names[0]
-    _check(torch, x, f"{what}: {xname}", series_axis=False, placement=False)
-    _axes(x, f"{what}: {xname}")
+    _check(torch, x, f"{what}: {xname}", series_axis=False, planes=planes, placement=False)
+    _axes(x, f"{what}: {xname}", planes)
     sname = "seed" if second_is_seed else names[1]
     if second is not None:
-        _check(torch, second, f"{what}: {sname}", series_axis=False, placement=False)
+        _check(torch, second, f"{what}: {sname}", series_axis=False, planes=planes, placement=False)
         if not second_is_seed:
-            _axes(second, f"{what}: {sname}")
+            _axes(second, f"{what}: {sname}", planes)
     if out is not None:
-        _check(torch, out, f"{what}: out", series_axis=False, placement=False)
-        _axes(out, f"{what}: out")
+        _check(torch, out, f"{what}: out", series_axis=False, planes=planes, placement=False)
+        _axes(out, f"{what}: out", planes)
     operands = [x] if second_is_seed or second is None else [x, second]
-    n0, n1 = _orders(what, n, *(tuple(t.shape[-2:]) for t in operands))
-    shapes = [x.shape[:-2]]
+    n0, n1 = _orders(what, n, *(tuple(t.shape[-2:]) for t in operands), max_elems=max_elems)
+    lead = (2,) * planes
+    shapes = [x.shape[planes:-2]]
     if second is not None:
-        shapes.append(second.shape if second_is_seed else second.shape[:-2])
+        shapes.append(second.shape[planes:] if second_is_seed else second.shape[planes:-2])
     if out is not None:
         if tuple(out.shape[-2:]) != (n0, n1):
             raise TaylorError(f"{what}: out has {tuple(out.shape[-2:])} coefficients per item, the result has n = ({n0}, {n1})")
-        batch = tuple(out.shape[:-2])
+        batch = tuple(out.shape[planes:-2])
         if tuple(torch.broadcast_shapes(*shapes, batch)) != batch:
             raise TaylorError(f"{what}: out has batch shape {batch}; the operands broadcast to {tuple(torch.broadcast_shapes(*shapes))}")
     else:
         batch = tuple(torch.broadcast_shapes(*shapes))
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, second)):
-        raise TaylorError(f"{what}: an operand requires grad, and this version of series2 has no autograd; pass {xname}.detach() or call under "
+        mod = what.split(".")[0]
+        raise TaylorError(f"{what}: an operand requires grad, and this version of {mod} has no autograd; pass {xname}.detach() or call under "
                           "torch.no_grad() (nothing is detached silently)")
     _placed(x, f"{what}: {xname}")
     if second is not None:
@@ -121,31 +131,37 @@ def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), sca
         if t is not None and t.device != x.device:
             raise TaylorError(f"{what}: the tensors are on different devices ({x.device}, {t.device})")
     if out is None:
-        out = torch.empty(batch + (n0, n1), dtype=torch.float64, device=x.device)
+        out = torch.empty(lead + batch + (n0, n1), dtype=torch.float64, device=x.device)
+    nb = len(batch)
+    if planes:  # torch aligns shapes from the right: the plane axis stays first, missing batch axes go behind it (a view)
+        lift = lambda t, rank: t if t.dim() >= rank else t[(slice(None),) + (None,) * (rank - t.dim())]  # noqa: E731
+        x = lift(x, nb + 3)
+        if second is not None:
+            second = lift(second, nb + (1 if second_is_seed else 3))
     L = _lib()
     dev = int(L.gft_device())
     if dev >= 0 and x.device.index != dev:
         raise TaylorError(f"{what}: the tensors are on {x.device}, but the library runs on cuda:{dev}")
-    nb = len(batch)
-    xe = x.expand(batch + tuple(x.shape[-2:]))
+    ns = nb + planes  # entries of a batch-stride array
+    xe = x.expand(lead + batch + tuple(x.shape[-2:]))
     bsz = (C.c_size_t * max(nb, 1))(*batch)
     stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     fn = getattr(L, fn_name)
-    xa = (C.c_void_p(xe.data_ptr()), _i64(xe.stride()[:nb]), xe.stride(-2), xe.shape[-2], xe.shape[-1])
-    ra = (C.c_void_p(out.data_ptr()), _i64(out.stride()[:nb]), out.stride(-2), n0, n1, bsz, nb, stream)
+    xa = (C.c_void_p(xe.data_ptr()), _i64(xe.stride()[:ns]), xe.stride(-2), xe.shape[-2], xe.shape[-1])
+    ra = (C.c_void_p(out.data_ptr()), _i64(out.stride()[:ns]), out.stride(-2), n0, n1, bsz, nb, stream)
     if second_is_seed:
         if scalar is not None:
             sa = (C.c_uint32(scalar),)
         elif second is None:
             sa = (None, None)
         else:
-            se = second.expand(batch)
+            se = second.expand(lead + batch)
             sa = (C.c_void_p(se.data_ptr()), _i64(se.stride()))
         rc = fn(*xa, *sa, *ra)
     else:
-        ye = second.expand(batch + tuple(second.shape[-2:]))
+        ye = second.expand(lead + batch + tuple(second.shape[-2:]))
         va = () if scalar is None else (C.c_int(scalar),)
-        rc = fn(*xa, C.c_void_p(ye.data_ptr()), _i64(ye.stride()[:nb]), ye.stride(-2), ye.shape[-2], ye.shape[-1], *va, *ra)
+        rc = fn(*xa, C.c_void_p(ye.data_ptr()), _i64(ye.stride()[:ns]), ye.stride(-2), ye.shape[-2], ye.shape[-1], *va, *ra)
     if rc != 0:
         raise TaylorError((L.gft_last_error() or b"unknown error").decode())
     return out

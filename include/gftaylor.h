@@ -439,6 +439,35 @@ int gfti_series_compose(const double* f, const int64_t* fbs, size_t nf, const do
                         double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
 int gfti_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
                     const size_t* batch, size_t nbatch, void* stream);
+/* Batched bivariate series over Interval<F64>: gft_series2_* on tensors [2, B..., n0, n1] = (lo, hi).  The argument lists are those
+ * of gft_series2_* (row strides `xrs` / `yrs` / `rrs` included, one per operand: both planes share it); the stride-array convention
+ * is gfti_series_*'s: every batch-stride array (xbs / ybs / sbs / rbs) has nbatch + 1 entries, the lo -> hi plane stride FIRST, NULL =
+ * C-contiguous items with the two planes back to back.  An operand's or the seeds' plane stride may be 0 (a point interval read
+ * twice); the result's planes are distinct memory, the planes and the rows both join the proof that the result's elements are
+ * distinct addresses, and "the same view" of an in-place result includes the plane stride.  Seeds are [2, B...]; NULL: formed on the
+ * device by the interval exp / log of coefficient [0, 0].  n0 * n1 <= 2048: an interval occupies 16 bytes of LDS, so the footprints of
+ * gft_series2_* at 4096 are reached there.  Per item the results are the loops stated above for gft_series2_mul / div / exp / log /
+ * compose / pow with every step one operation of Interval<F64> (interval.rs: round to nearest, one ulp outwards, with its
+ * short-circuits): sums start from [0,0] (and [0,0] + b is b), j and k enter as the point intervals from_u32(j), from_u32(k),
+ * pow starts from [[[1,1]]].  Each bound carries the oracle's bits under the same rule as for gft_series2_*.  One workgroup per item;
+ * gft_series_last_form() reports 2 afterwards. */
+int gfti_series2_mul(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs,
+                     int64_t yrs, size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1,
+                     const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_div(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs,
+                     int64_t yrs, size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1,
+                     const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_exp(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs,
+                     double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                     void* stream);
+int gfti_series2_log(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs,
+                     double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
+                     void* stream);
+int gfti_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t nf0, size_t nf1, const double* g, const int64_t* gbs,
+                         int64_t grs, size_t ng0, size_t ng1, int var, double* res, const int64_t* rbs, int64_t rrs, size_t n0,
+                         size_t n1, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
+                     const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
 size_t gfti_len_of(const gft_poly* p, size_t v);
 int gfti_is_constant(const gft_poly* p);
 int gfti_is_zero(const gft_poly* p);

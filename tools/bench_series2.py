@@ -13,8 +13,14 @@ loop measured in the same run: at least 10x for B >= 256, no slower than 1.1x fo
 ``subst_var`` in the loop, and also against (c) the Python chain of ``series2.mul`` calls with the slice added after each -- the
 way to compose before the fused kernel -- with its own target, no slower than 1.1x that chain; pow runs at ``--pow-e``.
 
+``--interval``: the same on ``Interval<F64>`` tensors ``[2, B, n0, n1]`` (genfer_amd.interval_series2) against the loop over
+``IntervalTaylorPoly`` handles, every shape with ``n0 * n1`` capped at 2048 (the longer axis is halved until the item fits); the
+chain of leg (c) is ``interval_series2.mul`` plus the slice add (exact where the running result's slice is still [0,0], one
+``torch`` add per bound otherwise: a caller's chain, not the definition).
+
     python tools/bench_series2.py > profiles/r11/series2.json
     python tools/bench_series2.py --ops compose,pow --budget-ms 150 > profiles/r12/series2_compose.json
+    python tools/bench_series2.py --interval --ops mul,div,exp,log,compose,pow --budget-ms 100 > profiles/r13/series2_interval.json
 """
 import argparse
 import json
@@ -39,6 +45,7 @@ def parse_args(argv=None):
     ap.add_argument("--budget-ms", type=float, default=300.0, help="time each leg repeats for, roughly")
     ap.add_argument("--no-loop", action="store_true", help="skip leg (b)")
     ap.add_argument("--pow-e", type=int, default=5, help="the exponent of pow (default 5)")
+    ap.add_argument("--interval", action="store_true", help="Interval<F64> tensors [2, B, n0, n1] (interval_series2), n0 * n1 capped at 2048")
     args = ap.parse_args(argv)
     for op in args.ops.split(","):
         if op not in KNOWN_OPS.split(","):
@@ -87,19 +94,30 @@ def compose_macs(n0, n1, var):
 
 
 def chain_compose(torch, series2, f, g, var, n):
-    """compose as a caller writes it without the fused kernel: one series2.mul per slice and an add into the slice's place"""
+    """compose as a caller writes it without the fused kernel: one series2.mul per slice and an add into the slice's place (with a
+    leading plane axis for interval_series2: the ellipsis takes it)"""
     n0, n1 = n
     if var == 0:
-        res = 0.0 + f[:, -1:, :]
-        for i in range(f.shape[1] - 2, -1, -1):
-            res = series2.mul(res, g, n=(min(res.shape[1] + g.shape[1] - 1, n0), min(res.shape[2] + g.shape[2] - 1, n1)))
-            res[:, 0, :f.shape[2]] += f[:, i, :]
+        res = 0.0 + f[..., -1:, :]
+        for i in range(f.shape[-2] - 2, -1, -1):
+            res = series2.mul(res, g, n=(min(res.shape[-2] + g.shape[-2] - 1, n0), min(res.shape[-1] + g.shape[-1] - 1, n1)))
+            res[..., 0, :f.shape[-1]] += f[..., i, :]
     else:
-        res = 0.0 + f[:, :, -1:]
-        for i in range(f.shape[2] - 2, -1, -1):
-            res = series2.mul(res, g, n=(min(res.shape[1] + g.shape[1] - 1, n0), min(res.shape[2] + g.shape[2] - 1, n1)))
-            res[:, :f.shape[1], 0] += f[:, :, i]
+        res = 0.0 + f[..., :, -1:]
+        for i in range(f.shape[-1] - 2, -1, -1):
+            res = series2.mul(res, g, n=(min(res.shape[-2] + g.shape[-2] - 1, n0), min(res.shape[-1] + g.shape[-1] - 1, n1)))
+            res[..., :f.shape[-2], 0] += f[..., :, i]
     return res
+
+
+def cap_item(n0, n1, most):
+    """halve the longer axis until n0 * n1 <= most"""
+    while n0 * n1 > most:
+        if n0 >= n1:
+            n0 = (n0 + 1) // 2
+        else:
+            n1 = (n1 + 1) // 2
+    return n0, n1
 
 
 def main(argv=None):
@@ -107,24 +125,37 @@ def main(argv=None):
     import torch
 
     import genfer_amd
-    from genfer_amd import series2
+    from genfer_amd import interval_series2, series2
 
     genfer_amd.init(0)
-    TP = genfer_amd.TaylorPoly
+    iv = args.interval
+    TP = genfer_amd.IntervalTaylorPoly if iv else genfer_amd.TaylorPoly
+    if iv:
+        series2 = interval_series2
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device="cpu").manual_seed(7)
     results = []
     for shape in args.shapes.split(","):
         B, n0, n1 = (int(t) for t in shape.lower().split("x"))
+        if iv:
+            n0, n1 = cap_item(n0, n1, interval_series2.MAX_ELEMS)
         # bounded results at every order: a dominant constant term in the divisor, a small argument for exp
         x = (0.5 + torch.rand((B, n0, n1), dtype=torch.float64, generator=gen) / (n0 * n1)).to(dev)
         y = (0.5 + torch.rand((B, n0, n1), dtype=torch.float64, generator=gen) / (n0 * n1)).to(dev)
         y[:, 0, 0] += 2.0
-        out = torch.empty((B, n0, n1), dtype=torch.float64, device=dev)
+        if iv:  # (lo, hi) planes about 2^-20 apart; the loop indexes items behind the plane axis
+            x = torch.stack([x, x * (1.0 + 2.0**-20)])
+            y = torch.stack([y, y * (1.0 + 2.0**-20)])
+        item = (lambda t, b: t[:, b]) if iv else (lambda t, b: t[b])
+        out = torch.empty(((2,) if iv else ()) + (B, n0, n1), dtype=torch.float64, device=dev)
         for op, var in [(o, v) for o in args.ops.split(",") for v in ((0, 1) if o == "compose" else (None,))]:
             seed = None
             if op in ("exp", "log"):
-                seed = torch.tensor([getattr(math, op)(v) for v in x[:, 0, 0].cpu().tolist()], dtype=torch.float64).to(dev)
+                if iv:  # a host's seeds: libm, one ulp outwards
+                    s = torch.tensor([[getattr(math, op)(v) for v in pl] for pl in x[:, :, 0, 0].cpu().tolist()], dtype=torch.float64)
+                    seed = torch.stack([torch.nextafter(s[0], s[0] - 1.0), torch.nextafter(s[1], s[1] + 1.0)]).to(dev)
+                else:
+                    seed = torch.tensor([getattr(math, op)(v) for v in x[:, 0, 0].cpu().tolist()], dtype=torch.float64).to(dev)
 
             def batched():
                 if op in ("mul", "div"):
@@ -141,25 +172,25 @@ def main(argv=None):
 
             def loop():
                 for b in range(items):
-                    p = TP.from_torch(x[b])
+                    p = TP.from_torch(item(x, b))
                     if op == "mul":
-                        r = p * TP.from_torch(y[b])
+                        r = p * TP.from_torch(item(y, b))
                     elif op == "div":
-                        r = p / TP.from_torch(y[b])
+                        r = p / TP.from_torch(item(y, b))
                     elif op == "compose":
-                        r = p.subst_var(var, TP.from_torch(y[b]))
+                        r = p.subst_var(var, TP.from_torch(item(y, b)))
                     elif op == "pow":
                         r = p.pow(args.pow_e)
                     else:
                         r = p.exp() if op == "exp" else p.log()
-                    r.to_torch(out=out[b])
+                    r.to_torch(out=item(out, b))
 
             work = macs(n0, n1)
             if op == "compose":
                 work = compose_macs(n0, n1, var)
             elif op == "pow":  # the dense products of square-and-multiply, each at the full shape at most
                 work *= bin(args.pow_e).count("1") + max(args.pow_e.bit_length() - 1, 0)
-            rec = {"op": op, "B": B, "n0": n0, "n1": n1, "batched_ms": round(t_batch, 6), "batched_reps": reps_a,
+            rec = {**({"element": "interval"} if iv else {}), "op": op, "B": B, "n0": n0, "n1": n1, "batched_ms": round(t_batch, 6), "batched_reps": reps_a,
                    "GMACps": round(B * work / (t_batch * 1e-3) / 1e9, 3)}
             if op == "compose":
                 rec["var"] = var
