@@ -2,7 +2,7 @@
 // batched univariate series on caller-owned device tensors: gft_series_mul / div / exp / log / compose / pow / corr / compose_adj,
 // and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
 // and the bivariate gft_series2_mul / div / exp / log / compose / pow with their Interval<F64> twins gfti_series2_* (the same
-// validation with one row stride per operand: series2_call)
+// validation with one row stride per operand: series2_call), and the f64-only transposed gft_series2_corr / compose_adj
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -65,7 +65,22 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
     const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE || transposed;
     const std::string f(fn);
     size_t x0 = 1, y0 = 1, r0 = 1;  // rows per item
-    if (d2) {
+    if (d2 && transposed) {  // x (g, gh) is the long side on both axes: it carries the limit and bounds y and the result
+        x0 = d2->nx0, y0 = d2->ny0, r0 = d2->n0;
+        const std::string xn = corr ? "g" : "gh", yn = corr ? "y" : "g";
+        if (r0 == 0 || n == 0) throw Error(f + ": the result has no coefficients (an axis of its shape is 0)");
+        const size_t most = gft::series2_max_elems(w);
+        if (x0 > most || nx > most || x0 * nx > most)
+            throw Error(f + ": " + xn + " has " + std::to_string(x0) + " * " + std::to_string(nx) + " coefficients, which exceeds the limit of " +
+                        std::to_string(most) + " coefficients per item of this version");
+        if (x0 == 0 || nx == 0 || y0 == 0 || ny == 0) throw Error(f + ": an operand has no coefficients");
+        if (r0 > x0 || n > nx)
+            throw Error(f + ": the result has " + std::to_string(r0) + " x " + std::to_string(n) + " coefficients, " + xn + " " + std::to_string(x0) + " x " +
+                        std::to_string(nx) + " (the result of a transposed operation is its short side)");
+        if (y0 > x0 || ny > nx)
+            throw Error(f + ": " + yn + " has " + std::to_string(y0) + " x " + std::to_string(ny) + " coefficients, " + xn + " " + std::to_string(x0) + " x " +
+                        std::to_string(nx) + " (an operand is longer than the truncation order)");
+    } else if (d2) {
         x0 = d2->nx0, y0 = binary ? d2->ny0 : 1, r0 = d2->n0;
         if (r0 == 0 || n == 0) throw Error(f + ": n0 * n1 == 0 (the result has no coefficients)");
         const size_t most = gft::series2_max_elems(w);
@@ -321,6 +336,20 @@ int gft_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t
 int gft_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res, const int64_t* rbs, int64_t rrs,
                     size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
     return guard_int([&] { return series2_call(gft::SERIES_POW, "series2_pow", x, xbs, xrs, nx0, nx1, nullptr, nullptr, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream, e); });
+}
+// the transposed operations at rank 2 (f64 only): g / gh is the long side, the result the short one
+int gft_series2_corr(const double* g, const int64_t* gbs, int64_t grs, size_t g0, size_t g1, const double* y, const int64_t* ybs, int64_t yrs,
+                     size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t m0, size_t m1, const size_t* batch, size_t nbatch,
+                     void* stream) {
+    return guard_int([&] { return series2_call(gft::SERIES_CORR, "series2_corr", g, gbs, grs, g0, g1, y, ybs, yrs, ny0, ny1, res, rbs, rrs, m0, m1, batch, nbatch, stream); });
+}
+int gft_series2_compose_adj(const double* gh, const int64_t* hbs, int64_t hrs, size_t n0, size_t n1, const double* g, const int64_t* gbs, int64_t grs,
+                            size_t ng0, size_t ng1, int var, double* res, const int64_t* rbs, int64_t rrs, size_t nf0, size_t nf1, const size_t* batch,
+                            size_t nbatch, void* stream) {
+    return guard_int([&] {
+        if (var != 0 && var != 1) throw Error("series2_compose_adj: var = " + std::to_string(var) + " (the variable of f that g replaces is 0 or 1)");
+        return series2_call(gft::SERIES_COMPOSE_ADJ, "series2_compose_adj", gh, hbs, hrs, n0, n1, g, gbs, grs, ng0, ng1, res, rbs, rrs, nf0, nf1, batch, nbatch, stream, 0, var);
+    });
 }
 // Interval<F64> at rank 2: the same calls on (lo, hi) planes; every batch-stride array has nbatch + 1 entries, the plane stride first
 int gfti_series2_mul(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,

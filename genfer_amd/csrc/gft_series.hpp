@@ -95,6 +95,7 @@ constexpr unsigned SERIES2_MAX_ELEMS_IV = 2048;
 inline unsigned series2_max_elems(int w) { return w == 2 ? SERIES2_MAX_ELEMS_IV : SERIES2_MAX_ELEMS; }
 struct Series2Dims {
     unsigned nx0, nx1, ny0, ny1, n0, n1;  // stored shapes of x and y (exp / log / pow: ny* unused) and the result's; nx*, ny* <= n*
+                                          // (SERIES_CORR / SERIES_COMPOSE_ADJ at rank 2: x is g / gh, the LONG side: ny*, n* <= nx*)
     size_t xr, yr, rr;                    // row strides in elements
 };
 // The geometry of a call of element width w (1: F64, 2: Interval<F64>): lanes per workgroup, scratch rows of n1 elements (div / exp / log: the row sums of one chunk of j), the
@@ -108,7 +109,8 @@ struct Series2Plan {
 Series2Plan series2_plan(int op, const Series2Dims& d, int w = 1);
 // Launches SERIES_MUL / DIV / EXP / LOG / COMPOSE at rank 2 on `st`.  `y`: the divisor / second factor / compose's g (x is f, and
 // `var` the variable of f that g replaces); for exp / log the seeds or nullptr.  `pl`: the element width and the plane strides.  Not
-// for SERIES_POW.
+// for SERIES_POW.  SERIES_CORR and SERIES_COMPOSE_ADJ (w == 1 only): the transposed product and the transposed Horner loop of
+// gft_series2_corr / gft_series2_compose_adj, x the long side (g; gh with y = g and `var`), the result the short one.
 void series2_launch(hipStream_t st, int op, const Series2Plan& p, const double* x, const double* y, double* res, const Series2Dims& d,
                     const SeriesBatch& g, int var = 0, const SeriesPlanes& pl = SeriesPlanes());
 // doubles of device workspace series2_pow needs: the base and two results taking turns, each items * n0 * n1, and the factor [[1.0]];

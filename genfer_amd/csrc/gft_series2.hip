@@ -1,5 +1,5 @@
-// Batched bivariate series (gft_series.hpp, "rank 2"): the planner and the launches of gft_series2_mul / div / exp / log / compose,
-// and pow's sequence of mul launches, for F64 and for Interval<F64> (the element width w of the entry point: SeriesPlanes).  The kernels
+// Batched bivariate series (gft_series.hpp, "rank 2"): the planner and the launches of gft_series2_mul / div / exp / log / compose /
+// corr / compose_adj, and pow's sequence of mul launches, for F64 and (the first five and pow) for Interval<F64> (the element width w of the entry point: SeriesPlanes).  The kernels
 // are in gft_series2_kernels.hpp; gfx950 only.
 //
 // One form: one workgroup per item for the whole operation.
@@ -17,6 +17,9 @@
 // scale with the width.  The LDS requests and what the runtime answered are kept per element type.
 // compose's lanes count mul's output pairs of the full shape, in whole waves up to 512 (measured: S2_COMPOSE_LANES).  pow has no
 // kernel of its own beside the writer of the unit item.
+// The transposed operations (F64 only; x is the LONG side, g resp. gh, and the result the short one): corr has mul's plan with the
+// lanes counted over the output pairs of the result; compose_adj has compose's plan on gh's shape -- two arrays of nx0 * nx1 doubles
+// and g beside them where the grant holds all three -- and its own measured lane count (S2_ADJ_LANES).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,18 +36,20 @@ namespace {
 
 constexpr size_t S2_BUDGET = 80 * 1024, S2_BUDGET_PLAIN = 64 * 1024;
 
-// what the runtime grants the three recurrence kernels and compose with g resident, asked once
+// what the runtime grants the three recurrence kernels and compose / compose_adj with g resident, asked once
 size_t s2_budget(int w) {
     static size_t answers[2] = {0, 0};
     size_t& granted = answers[w == 2];
     if (granted) return granted;
     const void* kf[] = {(const void*)k_series2_rec<SERIES_DIV>, (const void*)k_series2_rec<SERIES_EXP>, (const void*)k_series2_rec<SERIES_LOG>,
-                        (const void*)k_series2_compose<true>};
+                        (const void*)k_series2_compose<true>, (const void*)k_series2_compose_adj<EF64, true>};
     const void* ki[] = {(const void*)k_series2i_rec<EIv, SERIES_DIV>, (const void*)k_series2i_rec<EIv, SERIES_EXP>,
                         (const void*)k_series2i_rec<EIv, SERIES_LOG>, (const void*)k_series2i_compose<EIv, true>};
     granted = S2_BUDGET;
-    for (const void* k : (w == 2 ? ki : kf))
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_BUDGET) != hipSuccess) {
+    const void* const* ks = w == 2 ? ki : kf;
+    const size_t nk = w == 2 ? sizeof(ki) / sizeof(*ki) : sizeof(kf) / sizeof(*kf);
+    for (size_t i = 0; i < nk; ++i)
+        if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_BUDGET) != hipSuccess) {
             (void)hipGetLastError();  // no stale error for the caller's next HIP call
             granted = S2_BUDGET_PLAIN;
             break;
@@ -67,6 +72,9 @@ unsigned s2_threads(unsigned work, unsigned most = 256) { return work <= 64 ? 64
 // compose: two waves a SIMD on the large items.  Measured on (256, 32, 32) / (256, 64, 64) / (64, 32, 128) items: 256 lanes 1.93 / 67.3 /
 // 27.4 ms, 512 lanes 1.23 / 59.0 / 22.0 ms, 1024 lanes 1.23 / 59.9 / 22.5 ms (profiles/r12/series2_compose_lanes.json).
 constexpr unsigned S2_COMPOSE_LANES = 512;
+// compose_adj, as compose: two waves a SIMD.  Measured on 256 items of f = g = n = (32, 32), var 0 / var 1, two builds alternating in
+// one run: 256 lanes 1.87 / 1.86 ms, 512 lanes 1.25 / 1.24 ms (profiles/r14/series2_adj_lanes.json).
+constexpr unsigned S2_ADJ_LANES = 512;
 
 }  // namespace
 
@@ -74,15 +82,17 @@ Series2Plan series2_plan(int op, const Series2Dims& d, int w) {
     Series2Plan p;
     const size_t elem = (size_t)w * sizeof(double);  // of an LDS element
     const unsigned N = d.n0 * d.n1;
-    if (op == SERIES_MUL) {
+    if (op == SERIES_MUL || op == SERIES_CORR) {  // (corr: N counts the result m, and g and y <= g are 64 KB at most as well)
         p.threads = s2_threads((N + 1) / 2);
         p.srows = 0;
         p.lds = ((size_t)d.nx0 * d.nx1 + (size_t)d.ny0 * d.ny1) * elem;
         return p;
     }
-    if (op == SERIES_COMPOSE) {
-        const size_t rows = (size_t)2 * N * elem, all = rows + (size_t)d.ny0 * d.ny1 * elem;
-        p.threads = s2_threads((N + 1) / 2, S2_COMPOSE_LANES);
+    if (op == SERIES_COMPOSE || op == SERIES_COMPOSE_ADJ) {
+        const bool adj = op == SERIES_COMPOSE_ADJ;
+        const unsigned A = adj ? d.nx0 * d.nx1 : N;  // of an array taking turns: the composition's shape (compose_adj: gh's)
+        const size_t rows = (size_t)2 * A * elem, all = rows + (size_t)d.ny0 * d.ny1 * elem;
+        p.threads = s2_threads((A + 1) / 2, adj ? S2_ADJ_LANES : S2_COMPOSE_LANES);
         p.srows = 0;
         p.glds = all <= S2_BUDGET_PLAIN || all <= s2_budget(w);
         p.lds = p.glds ? all : rows;
@@ -126,6 +136,11 @@ void series2_launch(hipStream_t st, int op, const Series2Plan& p, const double* 
     }
     switch (op) {
         case SERIES_MUL: GFT_LAUNCH(k_series2_mul, grid, block, p.lds, st, x, y, res, d, g); break;
+        case SERIES_CORR: GFT_LAUNCH(k_series2_corr<EF64>, grid, block, p.lds, st, x, y, res, d, g); break;
+        case SERIES_COMPOSE_ADJ:
+            if (p.glds) GFT_LAUNCH((k_series2_compose_adj<EF64, true>), grid, block, p.lds, st, x, y, res, d, var, g);
+            else GFT_LAUNCH((k_series2_compose_adj<EF64, false>), grid, block, p.lds, st, x, y, res, d, var, g);
+            break;
         case SERIES_DIV: GFT_LAUNCH(k_series2_rec<SERIES_DIV>, grid, block, p.lds, st, x, y, res, d, p.srows, g); break;
         case SERIES_EXP: GFT_LAUNCH(k_series2_rec<SERIES_EXP>, grid, block, p.lds, st, x, y, res, d, p.srows, g); break;
         case SERIES_LOG: GFT_LAUNCH(k_series2_rec<SERIES_LOG>, grid, block, p.lds, st, x, y, res, d, p.srows, g); break;

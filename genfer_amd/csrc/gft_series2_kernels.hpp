@@ -11,6 +11,10 @@
 //                  scratch of `srows` rows, pass 2 adds them in ascending j into r[k] (which holds the accumulator between
 //                  chunks); then the row's own step: negate and add the dividend, the 1-d division by row 0 of the divisor, the
 //                  division by k.  Chunking changes how many row sums are in flight, never the order of an addition.
+//   corr           mul transposed: both sums descending, so an output is mul's on the flipped array, which is how g is staged
+//                  (k_series2_corr).
+//   compose_adj    compose's loop transposed: every step that corr at the compact shapes of the forward loop run backwards
+//                  (k_series2_compose_adj).  Both F64 only, and templates so that only gft_series2.hip emits them.
 // Multiply and add are rounded separately (-ffp-contract=off) and no explicit fma is written.
 //
 // The bodies are templates over the element functor (gft_elem.hpp).  k_series2_mul, k_series2_rec<OP> and k_series2_compose<GLDS> are
@@ -225,6 +229,108 @@ __global__ __launch_bounds__(512) void k_series2i_compose(const double* f, const
                                                           SeriesPlanes pl) {
     extern __shared__ S2Iv s2_lds_iv[];
     s2_compose_body<E, GLDS>(s2_lds_iv, f, g, res, d, var, b, pl);
+}
+
+// ---- corr, the transposed product (the adjoint of mul; F64 only) -------------------------------------------------------------------
+// c[i0][i1] = 0 + sum_{k0} (0 + sum_{k1} g[k0][k1] * y[k0-i0][k1-i1]), both DESCENDING over the stored coefficients: k0 from
+// min(g0-1, i0+ny0-1) to i0, k1 from min(g1-1, i1+ny1-1) to i1.  With j = g-1-k ascending these are the sums of s2_mul_out on the
+// array flipped along both axes: c[i0][i1] is bit for bit mul(flip(g), y, (g0, g1))[g0-1-i0][g1-1-i1].  So g is staged FLIPPED
+// (element i of the row-major item at g0 * g1 - 1 - i) and an output is s2_mul_out itself, the same inner loops as mul.
+template <class E>
+__device__ inline void s2_stage_flipped(typename S2L<E>::T* lds, const double* src, size_t rstride, unsigned rows, unsigned cols) {
+    const unsigned total = rows * cols;
+    for (unsigned i = threadIdx.x; i < total; i += blockDim.x) {
+        const unsigned r = i / cols, c = i - r * cols;
+        S2L<E>::put(lds, total - 1 - i, E::ld(src, 0, (size_t)r * rstride + c));
+    }
+}
+// The outputs of one step from `fl` = flip(a), a of stored shape (g0, g1): thread t owns the outputs M - 1 - t and t of the
+// row-major (m0, m1) result, in that order -- the light one first, as s2_mul_body runs its pair (here the heavy outputs are the LOW
+// indices: output (0, 0) has every term, the last one a single product).  With m == g this is mul's assignment of outputs to lanes
+// exactly.  fn(idx, i0, i1, sum) stores.
+template <class E, class YA, class F>
+__device__ inline void s2_corr_pairs(const typename S2L<E>::T* fl, unsigned g0, unsigned g1, const YA yl, unsigned ny0, unsigned ny1, size_t yp,
+                                     unsigned m0, unsigned m1, F fn) {
+    Series2Dims s;  // of the product flip(a) * y (s2_mul_out reads the operands' shapes only)
+    s.nx0 = g0, s.nx1 = g1, s.ny0 = ny0, s.ny1 = ny1;
+    const unsigned M = m0 * m1, half = (M + 1) / 2;
+    for (unsigned t = threadIdx.x; t < half; t += blockDim.x) {
+        const unsigned is[2] = {M - 1 - t, t};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned idx = is[h];
+            if (h == 1 && idx == is[0]) break;  // the middle output of an odd M
+            const unsigned i0 = idx / m1, i1 = idx - i0 * m1;
+            fn(idx, i0, i1, s2_mul_out<E>(fl, yl, s, yp, g0 - 1 - i0, g1 - 1 - i1));
+        }
+    }
+}
+// d: x is g (nx0, nx1), y is y (ny0, ny1) <= g, the result (n0, n1) <= g.  g and y staged compactly, every global load before the
+// first store: the result may be g itself (the same view); the host refuses a result that overlaps y.
+template <class E>
+__global__ __launch_bounds__(256) void k_series2_corr(const double* g, const double* y, double* res, Series2Dims d, SeriesBatch b) {
+    extern __shared__ double s2_lds[];  // flip(g) [g0][g1] | [ny0][ny1]
+    double* gl = s2_lds;
+    double* yl = s2_lds + d.nx0 * d.nx1;
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    s2_stage_flipped<E>(gl, g + o.x, d.xr, d.nx0, d.nx1);
+    s2_stage<E>(yl, y + o.y, 0, d.yr, d.ny0, d.ny1);
+    __syncthreads();  // (every global load of this workgroup is done: the result may be g)
+    s2_corr_pairs<E>(gl, d.nx0, d.nx1, S2InLds<E>{yl}, d.ny0, d.ny1, d.ny1, d.n0, d.n1,
+                     [&](unsigned, unsigned i0, unsigned i1, typename E::V sum) { E::st(res, 0, o.r + (size_t)i0 * d.rr + i1, sum); });
+}
+
+// ---- compose_adj, the transposed Horner loop (the gradient of compose with respect to f; F64 only) ------------------------------
+// d: x is gh (nx0, nx1) = the n of the composition, y is g (ny0, ny1) <= n, the result f's stored shape (n0, n1) <= n.  With S slices
+// of f of `len` coefficients (rows for var 0, columns for var 1) and base = (1, len) / (len, 1), the forward loop's compact shapes
+// are L_i = min(base + (S-1-i) * (ng - 1), n) per axis.  a_0 = gh[:L_0]; slice i of the result is the first `len` entries of row 0
+// / column 0 of a_i; a_{i+1} = corr(a_i, g) at the result shape L_{i+1} (s2_corr_pairs at the compact shapes).  The mirror of
+// s2_compose_body: one workgroup runs the whole loop of its item, two arrays of n0 * n1 elements take turns in LDS, the current one
+// compact at pitch L_i[1] and FLIPPED, as corr wants its first operand; g sits compact behind them (GLDS) or stays in global memory
+// at its row stride.  The owner of an output on row 0 / column 0 stores it to the result as well, so the steps meet through LDS
+// alone.  gh is read completely before the first store: the result may be gh itself (the same view); it never overlaps g (the host
+// refuses that).
+template <class E, bool GLDS>
+__global__ __launch_bounds__(512) void k_series2_compose_adj(const double* gh, const double* g, double* res, Series2Dims d, int var, SeriesBatch b) {
+    extern __shared__ double s2_lds[];  // flip(a) [nx0 * nx1] | flip(a) [nx0 * nx1] | (GLDS) g [ng0][ng1]
+    const unsigned N = d.nx0 * d.nx1, tid = threadIdx.x, nt = blockDim.x;
+    double* cur = s2_lds;
+    double* nxt = s2_lds + N;
+    double* gl = s2_lds + 2 * N;
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    double* rg = res + o.r;
+    const unsigned slices = var == 0 ? d.n0 : d.n1, len = var == 0 ? d.n1 : d.n0;
+    const size_t rslice = var == 0 ? d.rr : 1, rstep = var == 0 ? 1 : d.rr;  // slice i of the result is rg[i * rslice + c * rstep], c < len
+    const unsigned b0 = var == 0 ? 1 : len, b1 = var == 0 ? len : 1;
+    auto shape = [&](unsigned i, unsigned& l0, unsigned& l1) {  // L_i
+        const unsigned k = slices - 1 - i, f0 = b0 + k * (d.ny0 - 1), f1 = b1 + k * (d.ny1 - 1);
+        l0 = f0 < d.nx0 ? f0 : d.nx0;
+        l1 = f1 < d.nx1 ? f1 : d.nx1;
+    };
+    unsigned r0, r1;  // the stored shape of a
+    shape(0, r0, r1);
+    if (GLDS && slices > 1) s2_stage<E>(gl, g + o.y, 0, d.yr, d.ny0, d.ny1);
+    s2_stage_flipped<E>(cur, gh + o.x, d.xr, r0, r1);
+    __syncthreads();  // (every global load of gh is done: the result may be gh)
+    for (unsigned c = tid; c < len; c += nt) rg[c * rstep] = cur[r0 * r1 - 1 - (var == 0 ? c : c * r1)];  // a_0[0][c] / a_0[c][0]
+    const size_t gp = GLDS ? d.ny1 : d.yr;
+    for (unsigned i = 1; i < slices; ++i) {
+        unsigned m0, m1;
+        shape(i, m0, m1);
+        double* ri = rg + i * rslice;
+        const unsigned last = m0 * m1 - 1;
+        auto put = [&](unsigned idx, unsigned i0, unsigned i1, double sum) {
+            nxt[last - idx] = sum;
+            if (var == 0 ? (i0 == 0 && i1 < len) : (i1 == 0 && i0 < len)) ri[(var == 0 ? i1 : i0) * rstep] = sum;
+        };
+        if (GLDS) s2_corr_pairs<E>(cur, r0, r1, S2InLds<E>{gl}, d.ny0, d.ny1, gp, m0, m1, put);
+        else s2_corr_pairs<E>(cur, r0, r1, S2InGlobal<E>{g + o.y, 0}, d.ny0, d.ny1, gp, m0, m1, put);
+        lds_barrier();
+        double* sw = cur;
+        cur = nxt;
+        nxt = sw;
+        r0 = m0, r1 = m1;
+    }
 }
 
 // ---- the 1-d division of a row in place (mt:1162-1192 at one axis: rec_div with a full-length dividend) -----------------------

@@ -1,4 +1,5 @@
-"""Batched bivariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` (``gft_series2_*``).
+"""Batched bivariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the transposed
+product ``corr`` (``gft_series2_*``).
 
 The last two axes of every tensor are the coefficient array of one ``TaylorPoly<F64>`` in two variables: axis -2 is variable 0
 (any non-negative stride), axis -1 is variable 1 (unit stride); the leading axes are batch axes and broadcast by torch's rules
@@ -16,8 +17,10 @@ call is ordered on torch's current stream and does not wait.  ``compose`` substi
     >>> h = series2.compose(f, g, var=1)           # g for variable 1 of f
     >>> p = series2.pow(x, 5)
 
-No autograd in this version: an operand that requires grad is refused while grad mode is on (``detach()`` it, or use
-``torch.no_grad()``).  float64 only; the ``Interval<F64>`` twins on ``[2, B..., n0, n1]`` tensors are ``genfer_amd.interval_series2``.
+No autograd in this version of the module: it is the raw layer, and an operand that requires grad is refused while grad mode is on
+(``detach()`` it, or use ``torch.no_grad()``).  The differentiable twins of the six operations are ``genfer_amd.series2_grad``; their
+backward passes are sequences of this module's calls around ``corr`` (the adjoint of ``mul``) and ``_compose_adj`` (the transposed
+Horner loop).  float64 only; the ``Interval<F64>`` twins on ``[2, B..., n0, n1]`` tensors are ``genfer_amd.interval_series2``.
 """
 from __future__ import annotations
 
@@ -49,6 +52,10 @@ def _lib():
             f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
             f = getattr(L, pre + "pow")
             f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, C.c_uint32, vp, i64, i, s, s, sz, s, vp]
+        # the transposed operations (f64 only): mul's and compose's argument lists
+        L.gft_series2_corr.restype, L.gft_series2_corr.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, vp, i64, i, s, s, sz, s, vp]
+        f = L.gft_series2_compose_adj
+        f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
@@ -86,10 +93,35 @@ def _orders(what, n, *shapes, max_elems=None):
     return n0, n1
 
 
-def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), scalar=None, planes=0, max_elems=None):
+def _orders_short(what, n, g, y, names):
+    """corr / _compose_adj: the result (shape ``n``, default ``g``) is the short side of a transposed operation on both axes; the
+    first operand (stored shape ``g``) carries the limit and bounds the second (``y``)"""
+    if n is None:
+        n = g
+    try:
+        n0, n1 = (int(v) for v in n)
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: {names[2]} must be a pair, got {n!r}") from None
+    if n0 < 1 or n1 < 1:
+        raise TaylorError(f"{what}: {names[2]} = ({n0}, {n1}); the result needs at least one coefficient on each axis")
+    if g[0] * g[1] > MAX_ELEMS:
+        raise TaylorError(f"{what}: {names[0]} has {g[0]} * {g[1]} = {g[0] * g[1]} coefficients, which exceeds the limit of {MAX_ELEMS} per item "
+                          "of this version")
+    for a in (0, 1):
+        if (n0, n1)[a] > g[a]:
+            raise TaylorError(f"{what}: {names[2]} = ({n0}, {n1}) exceeds the {tuple(g)} coefficients of {names[0]} on axis {a - 2} (the result of "
+                              "a transposed operation is its short side)")
+    for a in (0, 1):
+        if y[a] > g[a]:
+            raise TaylorError(f"{what}: {names[1]} has {y[a]} coefficients on axis {a - 2}, more than the {g[a]} of {names[0]}")
+    return n0, n1
+
+
+def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), scalar=None, planes=0, max_elems=None, short=False):
     """``scalar``: compose's ``var`` (passed behind the second operand) or pow's ``e`` (in the place of the seeds).  planes = 1:
     the tensors are interval tensors [2, B..., n0, n1] (seeds [2, B...]); the leading axis travels as the first entry of every
-    batch-stride array, which is where the gfti_series2_* entry points expect it."""
+    batch-stride array, which is where the gfti_series2_* entry points expect it.  short: a transposed operation (corr,
+    _compose_adj), whose result is no larger than its first operand; names[2] names it."""
     import torch
 
     # everything that needs no device first: types, shapes, strides, orders, out, grad -- then the placement
@@ -105,7 +137,10 @@ def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), sca
         _check(torch, out, f"{what}: out", series_axis=False, planes=planes, placement=False)
         _axes(out, f"{what}: out", planes)
     operands = [x] if second_is_seed or second is None else [x, second]
-    n0, n1 = _orders(what, n, *(tuple(t.shape[-2:]) for t in operands), max_elems=max_elems)
+    if short:
+        n0, n1 = _orders_short(what, n, *(tuple(t.shape[-2:]) for t in operands), names)
+    else:
+        n0, n1 = _orders(what, n, *(tuple(t.shape[-2:]) for t in operands), max_elems=max_elems)
     lead = (2,) * planes
     shapes = [x.shape[planes:-2]]
     if second is not None:
@@ -198,6 +233,34 @@ def compose(f, g, var=0, n=None, out=None):
     if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
         raise TaylorError(f"series2.compose: var = {var!r}; the variable of f that g replaces is 0 or 1")
     return _run("series2.compose", "gft_series2_compose", f, g, n, out, False, names=("f", "g"), scalar=var)
+
+
+def _var(what, var):
+    if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
+        raise TaylorError(f"{what}: var = {var!r}; the variable of f that g replaces is 0 or 1")
+    return var
+
+
+def corr(g, y, m=None, out=None):
+    """The transposed product, the adjoint of ``mul``: ``<mul(x, y, g.shape), g> = <x, corr(g, y)>``.  ``g`` has stored shape
+    ``(g0, g1)`` with ``g0 * g1 <= 4096``, ``y`` has ``(ny0, ny1) <= (g0, g1)`` per axis, the result ``m = (m0, m1) <= (g0, g1)``
+    per axis (default: ``g``'s stored shape)::
+
+        c[b, i0, i1] = 0.0 + sum_k0 (0.0 + sum_k1 g[b, k0, k1] * y[b, k0 - i0, k1 - i1])
+
+    with ``k0`` descending from ``min(g0 - 1, i0 + ny0 - 1)`` to ``i0`` and ``k1`` from ``min(g1 - 1, i1 + ny1 - 1)`` to ``i1``,
+    multiply and add rounded separately, only stored coefficients entering a sum: bit for bit ``mul(flip(g), y, n=g.shape)`` at
+    index ``[g0 - 1 - i0, g1 - 1 - i1]``, ``flip`` reversing both series axes.  ``out`` may be ``g`` itself, never ``y``."""
+    return _run("series2.corr", "gft_series2_corr", g, y, m, out, False, names=("g", "y", "m"), short=True)
+
+
+def _compose_adj(gh, g, var, nf, out=None):
+    """The transposed Horner loop: the gradient of ``compose(f, g, var, n)`` with respect to ``f`` (stored shape ``nf``) from the
+    gradient ``gh`` of the composition (shape ``n``).  With ``S`` slices of ``f`` of ``len`` coefficients along axis ``var`` and
+    ``L_i = min(base + (S - 1 - i) * (ng - 1), n)`` per axis, ``base = (1, len)`` / ``(len, 1)``: ``a = gh[:L_0]``; slice ``i`` of the
+    result is the first ``len`` entries of row 0 (var 0) / column 0 (var 1) of ``a``; then ``a = corr(a, g, L_{i+1})`` -- in one launch."""
+    _var("series2._compose_adj", var)
+    return _run("series2._compose_adj", "gft_series2_compose_adj", gh, g, nf, out, False, names=("gh", "g", "nf"), scalar=var, short=True)
 
 
 def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)

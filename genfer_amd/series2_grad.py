@@ -1,0 +1,208 @@
+"""Differentiable batched bivariate series: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` with the signatures, the
+operand layout and the forward bits of ``genfer_amd.series2``, recording a ``grad_fn`` for torch's autograd.
+
+``series2`` is the raw layer and refuses an operand that requires grad; this module is its differentiable twin, as
+``interval_series2`` is its interval twin.  With grad mode off, or with no operand that requires grad, a call here IS the call of
+``series2`` (``out=`` included).  Otherwise the forward pass runs the same launch on the detached operands and the backward pass is
+a short sequence of ``series2``'s own calls on detached tensors, around ``series2.corr`` -- the adjoint of the truncated product,
+``<mul(x, y, n), g> = <x, corr(g, y)>`` -- and, for ``compose``, the transposed Horner loop ``series2._compose_adj`` (one launch).
+With ``n`` the shape of the result's series axes, ``one`` the item ``[[1.0]]`` and ``gz`` the incoming gradient (made contiguous
+first when its last stride is not 1, as ``z.sum().backward()`` hands it over):
+
+    mul      gx = corr(gz, y, x.shape[-2:]);  gy = corr(gz, x, y.shape[-2:])
+    div      (r = x / y)  u = corr(gr, div(one, y, n), n);  gx = u[..., :nx0, :nx1];  gy = -corr(u, r, y.shape[-2:])
+    exp      (e = exp(x)) gx = corr(ge, e, x.shape[-2:])
+    log      gx = corr(gl, div(one, x, n), x.shape[-2:])
+    pow      e == 0: zeros;  else gx = e * corr(gp, pow(x, e - 1, n), x.shape[-2:])
+    compose  gf = _compose_adj(gh, g, var, f.shape[-2:]);  gg = corr(gh, compose(fp, g, var, n), g.shape[-2:]), where fp is the
+             derivative of f along axis var: slice i of f times i, shifted down one (zeros of f's shape when f has one slice)
+
+Every gradient is then reduced over the broadcast batch axes with ``sum_to_size`` (torch's order of additions); everything before
+that carries the bits of the calls above.  Only the gradients that are asked for are computed.  First derivatives only
+(``once_differentiable``), float64 only; ``out=`` cannot be combined with an operand that requires grad, and a ``seed`` never
+carries a gradient (it is ``exp(x[..., 0, 0])`` / ``ln(x[..., 0, 0])`` by contract: the gradient flows to ``x``).
+
+    >>> from genfer_amd import series2_grad as s2g
+    >>> w = torch.rand(4, 6, dtype=torch.float64, device="cuda", requires_grad=True)
+    >>> s2g.compose(w, g, var=1).sum().backward()   # w.grad: the transposed Horner loop, summed over the batch of g
+"""
+from __future__ import annotations
+
+from . import series2
+from .series import _exponent, _tracked
+
+_functions = None
+
+
+def _autograd():
+    """The torch.autograd.Function of every operation (built on first use: this module imports without torch)."""
+    global _functions
+    if _functions is not None:
+        return _functions
+    import types
+
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    run = series2._run
+
+    def unit_stride(g):  # z.sum().backward() hands over an expanded scalar: stride 0 on the series axes
+        return g if g.shape[-1] == 1 or g.stride(-1) == 1 else g.contiguous()
+
+    def one(t):
+        return torch.ones((1, 1), dtype=torch.float64, device=t.device)
+
+    class Mul(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, n):
+            x, y = x.detach(), y.detach()
+            ctx.save_for_backward(x, y)
+            return run("series2_grad.mul", "gft_series2_mul", x, y, n, None, False)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gz):
+            x, y = ctx.saved_tensors
+            gz = unit_stride(gz)
+            gx = series2.corr(gz, y, x.shape[-2:]).sum_to_size(x.shape) if ctx.needs_input_grad[0] else None
+            gy = series2.corr(gz, x, y.shape[-2:]).sum_to_size(y.shape) if ctx.needs_input_grad[1] else None
+            return gx, gy, None
+
+    class Div(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, y, n):
+            x, y = x.detach(), y.detach()
+            r = run("series2_grad.div", "gft_series2_div", x, y, n, None, False)
+            ctx.save_for_backward(r, y)
+            ctx.shapes = (x.shape, y.shape)
+            return r
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gr):
+            r, y = ctx.saved_tensors
+            xs, ys = ctx.shapes
+            n = tuple(r.shape[-2:])
+            u = series2.corr(unit_stride(gr), series2.div(one(y), y, n), n)  # the gradient of the dividend at the full shape
+            gx = u[..., :xs[-2], :xs[-1]].sum_to_size(xs) if ctx.needs_input_grad[0] else None
+            gy = (-series2.corr(u, r, ys[-2:])).sum_to_size(ys) if ctx.needs_input_grad[1] else None
+            return gx, gy, None
+
+    class Exp(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, n, seed):
+            x = x.detach()
+            e = run("series2_grad.exp", "gft_series2_exp", x, seed, n, None, True)
+            ctx.save_for_backward(e)
+            ctx.shape = x.shape
+            return e
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, ge):
+            (e,) = ctx.saved_tensors
+            return series2.corr(unit_stride(ge), e, ctx.shape[-2:]).sum_to_size(ctx.shape), None, None
+
+    class Log(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, n, seed):
+            x = x.detach()
+            ctx.save_for_backward(x)
+            return run("series2_grad.log", "gft_series2_log", x, seed, n, None, True)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gl):
+            (x,) = ctx.saved_tensors
+            n = tuple(gl.shape[-2:])
+            return series2.corr(unit_stride(gl), series2.div(one(x), x, n), x.shape[-2:]).sum_to_size(x.shape), None, None
+
+    class Pow(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, e, n):
+            x = x.detach()
+            ctx.save_for_backward(x)
+            ctx.e = e
+            return run("series2_grad.pow", "gft_series2_pow", x, None, n, None, True, scalar=e)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gp):
+            (x,) = ctx.saved_tensors
+            if ctx.e == 0:
+                return torch.zeros_like(x), None, None
+            n = tuple(gp.shape[-2:])
+            return (ctx.e * series2.corr(unit_stride(gp), series2.pow(x, ctx.e - 1, n), x.shape[-2:])).sum_to_size(x.shape), None, None
+
+    class Compose(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, f, g, var, n):
+            f, g = f.detach(), g.detach()
+            ctx.save_for_backward(f, g)
+            ctx.var = var
+            return run("series2_grad.compose", "gft_series2_compose", f, g, n, None, False, names=("f", "g"), scalar=var)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gh):
+            f, g = ctx.saved_tensors
+            var = ctx.var
+            gh = unit_stride(gh)
+            n = tuple(gh.shape[-2:])
+            gf = gg = None
+            if ctx.needs_input_grad[0]:
+                gf = series2._compose_adj(gh, g, var, f.shape[-2:]).sum_to_size(f.shape)
+            if ctx.needs_input_grad[1]:  # h = f(g): dh = (df / dvar)(g) * dg
+                slices = f.shape[var - 2]
+                if slices > 1:
+                    i = torch.arange(1, slices, dtype=torch.float64, device=f.device)
+                    fp = f[..., 1:, :] * i[:, None] if var == 0 else f[..., :, 1:] * i
+                else:
+                    fp = torch.zeros_like(f)
+                gg = series2.corr(gh, series2.compose(fp, g, var, n), g.shape[-2:]).sum_to_size(g.shape)
+            return gf, gg, None, None
+
+    _functions = types.SimpleNamespace(Mul=Mul, Div=Div, Exp=Exp, Log=Log, Pow=Pow, Compose=Compose)
+    return _functions
+
+
+def mul(x, y, n=None, out=None):
+    """``series2.mul``, differentiable in ``x`` and ``y``."""
+    if _tracked("series2_grad.mul", (x, y), out):
+        return _autograd().Mul.apply(x, y, n)
+    return series2.mul(x, y, n, out)
+
+
+def div(x, y, n=None, out=None):
+    """``series2.div``, differentiable in ``x`` and ``y``."""
+    if _tracked("series2_grad.div", (x, y), out):
+        return _autograd().Div.apply(x, y, n)
+    return series2.div(x, y, n, out)
+
+
+def exp(x, n=None, seed=None, out=None):
+    """``series2.exp``, differentiable in ``x`` (never in ``seed``)."""
+    if _tracked("series2_grad.exp", (x,), out, seed):
+        return _autograd().Exp.apply(x, n, seed)
+    return series2.exp(x, n, seed, out)
+
+
+def log(x, n=None, seed=None, out=None):
+    """``series2.log``, differentiable in ``x`` (never in ``seed``)."""
+    if _tracked("series2_grad.log", (x,), out, seed):
+        return _autograd().Log.apply(x, n, seed)
+    return series2.log(x, n, seed, out)
+
+
+def compose(f, g, var=0, n=None, out=None):
+    """``series2.compose``, differentiable in ``f`` (the transposed Horner loop) and ``g``."""
+    if _tracked("series2_grad.compose", (f, g), out):
+        return _autograd().Compose.apply(f, g, series2._var("series2_grad.compose", var), n)
+    return series2.compose(f, g, var, n, out)
+
+
+def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
+    """``series2.pow``, differentiable in ``x``."""
+    if _tracked("series2_grad.pow", (x,), out):
+        return _autograd().Pow.apply(x, _exponent("series2_grad.pow", e, div="series2_grad.div"), n)
+    return series2.pow(x, e, n, out)

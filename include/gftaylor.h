@@ -270,6 +270,32 @@ int gft_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t
 int gft_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
                     const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
                     void* stream);                                       /* pow                    mt:433-451   */
+/* corr at rank 2: the transposed product, the adjoint of gft_series2_mul in the truncated inner product,
+ * <mul2(x, y, (g0, g1)), g> = <x, corr2(g, y)> (f64 only; no gfti_ twin, for the reason given at gft_series_corr: a gradient of
+ * interval bounds is not defined).  g has stored shape (g0, g1) with g0 * g1 <= 4096, y has (ny0, ny1) <= (g0, g1) per axis, the
+ * result (m0, m1) <= (g0, g1) per axis:
+ *   res[i0][i1] = 0.0 + sum over k0 DESCENDING from min(g0-1, i0+ny0-1) to i0 of
+ *                 (0.0 + sum over k1 DESCENDING from min(g1-1, i1+ny1-1) to i1 of g[k0][k1] * y[k0-i0][k1-i1])
+ * multiply and add rounded separately, only stored coefficients entering a sum; the inner row sum is formed from 0.0 FIRST and then
+ * added to the outer one.  That order makes res[i0][i1] bit for bit mul2(flip(g), y, (g0, g1))[g0-1-i0][g1-1-i1], flip reversing both
+ * series axes.  One kernel, one workgroup per item, g and y resident in LDS.  Aliasing: the result may be g itself as the SAME view
+ * (then m == g); it may NOT overlap y, and any partial overlap with g is refused by address range as for the other entries.
+ * compose_adj at rank 2: the transposed Horner loop, the gradient of gft_series2_compose(f, g, var, (n0, n1)) with respect to f.  gh
+ * has shape (n0, n1) (the gradient of the composition), g has (ng0, ng1) <= n, the result f's stored shape (nf0, nf1) <= n; var is 0 or
+ * 1, anything else is refused.  Let S be the number of slices of f and len their length (S = nf0, len = nf1 for var 0, the other way
+ * round for var 1), base = (1, len) for var 0 and (len, 1) for var 1, and L_i[a] = min(base[a] + (S-1-i) * (ng_a - 1), n_a), i < S, the
+ * compact shapes of the forward loop.  Then a_0 = gh[:L_0[0], :L_0[1]]; slice i of the result is the first len entries of row 0
+ * (var 0) or column 0 (var 1) of a_i; a_{i+1} = corr2(a_i, g) at the result shape L_{i+1} -- every step is the sum above at the compact
+ * shapes.  One kernel, one workgroup per item for the whole loop, a resident in LDS (g beside it where the granted LDS holds both,
+ * else read from global memory).  With one slice the result is gh's leading entries and g's values are not read.  The result may be
+ * gh itself as the same view; it may NOT overlap g (refused).
+ * Argument conventions, stream contract, empty-batch behaviour and return values of both: those of gft_series2_mul. */
+int gft_series2_corr(const double* g, const int64_t* gbs, int64_t grs, size_t g0, size_t g1, const double* y, const int64_t* ybs,
+                     int64_t yrs, size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t m0, size_t m1,
+                     const size_t* batch, size_t nbatch, void* stream);  /* mul transposed                      */
+int gft_series2_compose_adj(const double* gh, const int64_t* hbs, int64_t hrs, size_t n0, size_t n1, const double* g, const int64_t* gbs,
+                            int64_t grs, size_t ng0, size_t ng1, int var, double* res, const int64_t* rbs, int64_t rrs, size_t nf0,
+                            size_t nf1, const size_t* batch, size_t nbatch, void* stream);   /* subst_var (Horner) transposed */
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI, collectives internal to the library --------
  * The reference is single-process; a host that wants one large product spread over the GPUs of a node starts one
