@@ -3,6 +3,8 @@
 // and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
 // and the bivariate gft_series2_mul / div / exp / log / compose / pow with their Interval<F64> twins gfti_series2_* (the same
 // validation with one row stride per operand: series2_call), and the f64-only transposed gft_series2_corr / compose_adj
+// and the observation ops gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one with
+// their gfti_ twins (one operand, the result shorter by the order k on one axis; the kernels: gft_series_observe.hip)
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -58,14 +60,40 @@ static bool series_same_view(const SeriesArg& a, const SeriesArg& b, const size_
 // side, so nx bounds n and ny, and the rows the planner sizes are the nx long ones.
 // `d2` (gft_series2_*, gfti_series2_*): the call is at rank 2 -- nx, ny, n are the lengths along the series axis (d2->nx1, ny1, n1), an
 // item has d2->nx0 / ny0 / n0 rows d2->xr / yr / rr elements apart, and the limit bounds n0 * n1.  `var`: compose's variable there.
+// The observation ops (SERIES_DERIVATIVE ...): x is the one operand and the LONG side, `k` the order, `var` the axis at rank 2 (at
+// rank 1 the callers pass 1, the series axis), and the result's shape must be x's with k taken off that axis (evaluate_all_one: one
+// element per item).  The limits bound x's stored shape.
 static int series_call(int op, const char* fn, const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
                        double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream, uint32_t e = 0, int w = 1,
-                       const gft::Series2Dims* d2 = nullptr, const int64_t* rowst = nullptr, int var = 0) {
+                       const gft::Series2Dims* d2 = nullptr, const int64_t* rowst = nullptr, int var = 0, size_t k = 0) {
+    const bool observe = op >= gft::SERIES_DERIVATIVE;
     const bool corr = op == gft::SERIES_CORR, adj = op == gft::SERIES_COMPOSE_ADJ, transposed = corr || adj;
     const bool binary = op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE || transposed;
     const std::string f(fn);
     size_t x0 = 1, y0 = 1, r0 = 1;  // rows per item
-    if (d2 && transposed) {  // x (g, gh) is the long side on both axes: it carries the limit and bounds y and the result
+    if (observe) {
+        x0 = d2 ? d2->nx0 : 1, r0 = d2 ? d2->n0 : 1;
+        if (x0 == 0 || nx == 0) throw Error(f + ": x has no coefficients");
+        if (d2) {
+            const size_t most = gft::series2_max_elems(w);
+            if (x0 > most || nx > most || x0 * nx > most)
+                throw Error(f + ": x has " + std::to_string(x0) + " * " + std::to_string(nx) + " coefficients, which exceeds the limit of " +
+                            std::to_string(most) + " coefficients per item of this version");
+            if (var != 0 && var != 1) throw Error(f + ": var = " + std::to_string(var) + " (the variable the operation acts on is 0 or 1)");
+        } else if (nx > gft::series_max_n(w))
+            throw Error(f + ": nx = " + std::to_string(nx) + " exceeds the limit of " + std::to_string(gft::series_max_n(w)) + " coefficients per series of this version");
+        if (op != gft::SERIES_EVAL_ONE) {
+            const bool rows = d2 && var == 0;
+            const size_t len = rows ? x0 : nx;
+            if (k >= len)
+                throw Error(f + ": k = " + std::to_string(k) + ", but x has " + std::to_string(len) + " stored coefficients" +
+                            (d2 ? " on axis " + std::to_string(var) : std::string()) + " (the order must satisfy 0 <= k < " + std::to_string(len) + ")");
+            const size_t w0 = rows ? x0 - k : x0, w1 = rows ? nx : nx - k;
+            if (r0 != w0 || n != w1)
+                throw Error(f + ": the result has " + (d2 ? std::to_string(r0) + " x " : std::string()) + std::to_string(n) + " coefficients; with k = " +
+                            std::to_string(k) + " it has " + (d2 ? std::to_string(w0) + " x " : std::string()) + std::to_string(w1) + " (x's, less k on the axis)");
+        }
+    } else if (d2 && transposed) {  // x (g, gh) is the long side on both axes: it carries the limit and bounds y and the result
         x0 = d2->nx0, y0 = d2->ny0, r0 = d2->n0;
         const std::string xn = corr ? "g" : "gh", yn = corr ? "y" : "g";
         if (r0 == 0 || n == 0) throw Error(f + ": the result has no coefficients (an axis of its shape is 0)");
@@ -204,6 +232,26 @@ static int series_call(int op, const char* fn, const double* x, const int64_t* x
     pl.y = binary ? ay.plane : 0;
     pl.s = seeds ? ay.plane : 0;
     pl.r = ar.plane;
+    if (observe) {
+        gft::Series2Dims d;
+        d.nx0 = (unsigned)x0, d.nx1 = (unsigned)nx, d.ny0 = d.ny1 = 1, d.n0 = (unsigned)r0, d.n1 = (unsigned)n;
+        d.xr = ax.rst, d.yr = 0, d.rr = ar.rst;
+        // the factors depend on (op, k, len) only: computed once with the reference's rounding (k_factor_table's functor) and kept.
+        // A table is written on the library's stream, where the kernel below runs: its first use is ordered behind it.
+        Rc<Buf> tab;
+        size_t tlen = 0;
+        if (op == gft::SERIES_DERIVATIVE || op == gft::SERIES_COEFF) {
+            tlen = d2 && var == 0 ? r0 : n;
+            const int top = op == gft::SERIES_DERIVATIVE ? TAB_DERIV : TAB_COEFF;
+            tab = w == 2 ? Ops<EIv>::cached_table(top, k, tlen) : Ops<EF64>::cached_table(top, k, tlen);
+        }
+        const hipStream_t cs = (hipStream_t)stream;
+        join_caller_in(cs);
+        gft::series_observe(R.stream, op, x, res, d, var, (unsigned)k, g, pl, tab ? tab->p : nullptr, tlen, d2 != nullptr);
+        join_caller_out(cs);
+        R.series_last = gft::SERIES_NONE;
+        return 0;
+    }
     if (d2) {  // one form; planned before the streams are joined (the planner may refuse)
         gft::Series2Dims d = *d2;
         d.xr = ax.rst, d.yr = ay.rst, d.rr = ar.rst;
@@ -382,5 +430,61 @@ int gfti_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx
                      size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {
     return guard_int([&] { return series2_call(gft::SERIES_POW, "interval series2_pow", x, xbs, xrs, nx0, nx1, nullptr, nullptr, 0, 1, 1, res, rbs, rrs, n0, n1, batch, nbatch, stream, e, 0, 2); });
 }
+// the observation ops: one operand, the order k (at rank 2 behind the variable), the result k shorter on that axis
+#define GFT_SERIES_OBSERVE(PFX, WHAT, W)                                                                                                          \
+    int PFX##series_derivative(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs, size_t n,               \
+                               const size_t* batch, size_t nbatch, void* stream) {                                                                \
+        return guard_int([&] { return series_call(gft::SERIES_DERIVATIVE, WHAT "series_derivative", x, xbs, nx, nullptr, nullptr, 1, res, rbs, n, \
+                                                  batch, nbatch, stream, 0, W, nullptr, nullptr, 1, k); });                                       \
+    }                                                                                                                                             \
+    int PFX##series_taylor_expansion_of_coeff(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs,          \
+                                              size_t n, const size_t* batch, size_t nbatch, void* stream) {                                       \
+        return guard_int([&] { return series_call(gft::SERIES_COEFF, WHAT "series_taylor_expansion_of_coeff", x, xbs, nx, nullptr, nullptr, 1,    \
+                                                  res, rbs, n, batch, nbatch, stream, 0, W, nullptr, nullptr, 1, k); });                          \
+    }                                                                                                                                             \
+    int PFX##series_shift_down(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs, size_t n,               \
+                               const size_t* batch, size_t nbatch, void* stream) {                                                                \
+        return guard_int([&] { return series_call(gft::SERIES_SHIFT_DOWN, WHAT "series_shift_down", x, xbs, nx, nullptr, nullptr, 1, res, rbs, n, \
+                                                  batch, nbatch, stream, 0, W, nullptr, nullptr, 1, k); });                                       \
+    }                                                                                                                                             \
+    int PFX##series_evaluate_all_one(const double* x, const int64_t* xbs, size_t nx, double* res, const int64_t* rbs, const size_t* batch,        \
+                                     size_t nbatch, void* stream) {                                                                               \
+        return guard_int([&] { return series_call(gft::SERIES_EVAL_ONE, WHAT "series_evaluate_all_one", x, xbs, nx, nullptr, nullptr, 1, res,     \
+                                                  rbs, 1, batch, nbatch, stream, 0, W, nullptr, nullptr, 1, 0); });                               \
+    }                                                                                                                                             \
+    int PFX##series2_derivative(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k, double* res,         \
+                                const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {        \
+        return guard_int([&] { return series2_observe(gft::SERIES_DERIVATIVE, WHAT "series2_derivative", x, xbs, xrs, nx0, nx1, var, k, res, rbs, \
+                                                      rrs, n0, n1, batch, nbatch, stream, W); });                                                 \
+    }                                                                                                                                             \
+    int PFX##series2_taylor_expansion_of_coeff(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k,       \
+                                               double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch,           \
+                                               size_t nbatch, void* stream) {                                                                     \
+        return guard_int([&] { return series2_observe(gft::SERIES_COEFF, WHAT "series2_taylor_expansion_of_coeff", x, xbs, xrs, nx0, nx1, var, k, \
+                                                      res, rbs, rrs, n0, n1, batch, nbatch, stream, W); });                                       \
+    }                                                                                                                                             \
+    int PFX##series2_shift_down(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k, double* res,         \
+                                const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {        \
+        return guard_int([&] { return series2_observe(gft::SERIES_SHIFT_DOWN, WHAT "series2_shift_down", x, xbs, xrs, nx0, nx1, var, k, res, rbs, \
+                                                      rrs, n0, n1, batch, nbatch, stream, W); });                                                 \
+    }                                                                                                                                             \
+    int PFX##series2_evaluate_all_one(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, double* res, const int64_t* rbs,  \
+                                      const size_t* batch, size_t nbatch, void* stream) {                                                         \
+        return guard_int([&] { return series2_observe(gft::SERIES_EVAL_ONE, WHAT "series2_evaluate_all_one", x, xbs, xrs, nx0, nx1, 0, 0, res,    \
+                                                      rbs, 0, 1, 1, batch, nbatch, stream, W); });                                                \
+    }
+static int series2_observe(int op, const char* fn, const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k,
+                           double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream, int w) {
+    const size_t cap = gft::SERIES2_MAX_ELEMS + 1;  // (as in series2_call: the limits and the shapes are judged by series_call)
+    gft::Series2Dims d;
+    d.nx0 = (unsigned)std::min(nx0, cap), d.nx1 = (unsigned)std::min(nx1, cap), d.ny0 = d.ny1 = 1;
+    d.n0 = (unsigned)std::min(n0, cap), d.n1 = (unsigned)std::min(n1, cap);
+    d.xr = d.yr = d.rr = 0;
+    const int64_t rowst[3] = {xrs, 0, rrs};
+    return series_call(op, fn, x, xbs, d.nx1, nullptr, nullptr, 1, res, rbs, d.n1, batch, nbatch, stream, 0, w, &d, rowst, var, k);
+}
+GFT_SERIES_OBSERVE(gft_, "", 1)
+GFT_SERIES_OBSERVE(gfti_, "interval ", 2)
+#undef GFT_SERIES_OBSERVE
 int gft_series_last_form(void) { return R.series_last; }
 }

@@ -32,7 +32,13 @@ enum SeriesOp {
     // The transposed Horner loop, the gradient of compose with respect to f (f64 only): a_0 = gh[0 .. l_0), out[i] = a_i[0],
     // a_{i+1} = corr(a_i, g) at the lengths l_i = min(1 + (nf-1-i)(ng-1), n).  x is gh (nx = n), y is g (ny = ng <= n), n is nf <= nx.
     // One form (B: one workgroup per series for the whole loop).
-    SERIES_COMPOSE_ADJ = 7
+    SERIES_COMPOSE_ADJ = 7,
+    // The observation ops (gft_series_observe.hip): one operand, the result shorter by the order k on the axis they act on.
+    // derivative (mt:457-481), taylor_expansion_of_coeff (mt:484-509), shift_down (mt:514-536), evaluate_all_one (mt:583-586).
+    SERIES_DERIVATIVE = 8,
+    SERIES_COEFF = 9,
+    SERIES_SHIFT_DOWN = 10,
+    SERIES_EVAL_ONE = 11
 };
 // A: one lane is one series, rows staged in LDS.  B: one wave / workgroup is one series (mul, div, compose); for exp / log the
 // lane-per-series loop of form A over a transposed global workspace.  pow is a sequence of mul launches, each planned by itself.
@@ -121,6 +127,15 @@ size_t series2_pow_workspace(unsigned items, const Series2Dims& d, int w = 1);
 // unit item.
 void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws,
                  const SeriesPlanes& pl = SeriesPlanes());
+
+// ---- the observation ops at ranks 1 and 2 (gft_series_observe.hip) ----------------------------------------------------------------
+// op is SERIES_DERIVATIVE / SERIES_COEFF / SERIES_SHIFT_DOWN / SERIES_EVAL_ONE.  `d`: the operand's stored shape (nx0, nx1), row
+// stride xr, and the result's (n0, n1), rr (rank 1: nx0 == n0 == 1; evaluate_all_one: n0 == n1 == 1); the axis `var` of the result
+// is `k` shorter than the operand's.  `tab`: the k_factor_table factors of (TAB_DERIV | TAB_COEFF, k, len - k), planes tab_plane
+// apart (the two scalings only).  `rank2`: the call is gft_series2_* -- ndarray's sum_axis folds a unit-stride axis of a rank-2
+// array 8-way and sums everything else in ascending order.  One launch; no workspace.
+void series_observe(hipStream_t st, int op, const double* x, double* res, const Series2Dims& d, int var, unsigned k, const SeriesBatch& g,
+                    const SeriesPlanes& pl, const double* tab, size_t tab_plane, bool rank2);
 
 // the element offsets of item `it` (kernels of gft_series.hip and gft_div2d.hip)
 struct SeriesOff {

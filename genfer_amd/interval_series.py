@@ -1,5 +1,5 @@
-"""Batched univariate series on interval device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow``
-(``gfti_series_*``), the ``Interval<F64>`` half of ``genfer_amd.series``.
+"""Batched univariate series on interval device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the
+observation ops ``derivative``, ``taylor_expansion_of_coeff``, ``shift_down``, ``evaluate_all_one`` (``gfti_series_*``), the ``Interval<F64>`` half of ``genfer_amd.series``.
 
 An interval tensor is float64 and stacked ``[2, B..., n]`` = (lo, hi) along its first axis, as ``IntervalTaylorPoly.from_torch``
 takes it.  The last axis is the series (unit stride), the axes between are batch axes and broadcast by torch's rules.  The
@@ -19,7 +19,7 @@ the operators' shortcuts.  The call is ordered on torch's current stream and doe
 """
 from __future__ import annotations
 
-from .series import FORMS, _exponent, _run, last_form, set_form  # noqa: F401  (one library, one form option, one last form)
+from .series import FORMS, _exponent, _observe, _run, last_form, set_form  # noqa: F401  (one library, one form option, one last form)
 
 MAX_N = 2048  # gft_series.hpp SERIES_MAX_N_IV
 
@@ -61,3 +61,29 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     """``x[b] ** e`` truncated at order ``n`` (default ``nx``) for an integer ``0 <= e < 2**32``: the reference's
     square-and-multiply over ``mul`` at compact lengths.  ``e = 0`` gives ``[[1, 1], [0, 0], ...]``."""
     return _iv("pow", "pow", x, None, n, out, True, e=_exponent("interval_series.pow", e, div="interval_series.div"))
+
+
+# ---- the observation ops: series.derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one over intervals --------
+# (no autograd here: an operand that requires grad is refused while grad mode is on)
+
+
+def derivative(x, k, out=None):
+    """``out[:, b, j] = x[:, b, k + j] * ff_j`` with the reference's interval factors ``ff_j`` (``series.derivative``'s recurrence in
+    interval arithmetic); ``[2, B..., nx - k]``."""
+    return _observe("interval_series.derivative", "derivative", x, k, out, planes=1, limit=MAX_N, raw=True)
+
+
+def taylor_expansion_of_coeff(x, k, out=None):
+    """Coefficient ``k`` untouched, coefficient ``k + j`` times the interval factor ``f_j`` for ``j >= 1``."""
+    return _observe("interval_series.taylor_expansion_of_coeff", "taylor_expansion_of_coeff", x, k, out, planes=1, limit=MAX_N, raw=True)
+
+
+def shift_down(x, k, out=None):
+    """``out[:, b, 0] = x[:, b, k] + S`` with ``S`` the ascending interval sum of coefficients ``0 .. k-1`` from ``[0, 0]`` (all of them
+    when ``nx == k + 1``), the others copies."""
+    return _observe("interval_series.shift_down", "shift_down", x, k, out, planes=1, limit=MAX_N, raw=True)
+
+
+def evaluate_all_one(x, out=None):
+    """The ascending interval sum of every item's coefficients from ``[0, 0]``; ``[2, B...]``."""
+    return _observe("interval_series.evaluate_all_one", "evaluate_all_one", x, None, out, planes=1, limit=MAX_N, raw=True)

@@ -1,5 +1,5 @@
-"""Batched bivariate series on interval device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow``
-(``gfti_series2_*``), the ``Interval<F64>`` half of ``genfer_amd.series2``.
+"""Batched bivariate series on interval device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the
+observation ops ``derivative``, ``taylor_expansion_of_coeff``, ``shift_down``, ``evaluate_all_one`` (``gfti_series2_*``), the ``Interval<F64>`` half of ``genfer_amd.series2``.
 
 An interval tensor is float64 and stacked ``[2, B..., n0, n1]`` = (lo, hi) along its first axis, as ``IntervalTaylorPoly.from_torch``
 takes it.  The last two axes are the coefficient array of one ``TaylorPoly<Interval<F64>>`` in two variables (axis -2: variable 0,
@@ -22,7 +22,7 @@ No autograd: an operand that requires grad is refused while grad mode is on, as 
 """
 from __future__ import annotations
 
-from .series import _exponent
+from .series import _exponent, _observe
 from .series2 import _run
 from .taylor import TaylorError
 
@@ -69,3 +69,27 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     square-and-multiply over ``mul`` at compact shapes.  ``e = 0`` gives the unit item: ``[1, 1]`` at ``[0, 0]``, ``[0, 0]`` elsewhere."""
     e = _exponent("interval_series2.pow", e, div="interval_series2.div")
     return _iv("pow", x, None, n, out, True, scalar=e)
+
+
+# ---- the observation ops: series2's over intervals ----------------------------------------------------------------------------
+
+
+def derivative(x, var, k, out=None):
+    """``series2.derivative`` with the reference's interval factors; the axis of ``var`` is ``k`` shorter."""
+    return _observe("interval_series2.derivative", "derivative", x, k, out, rank=2, var=var, planes=1, limit=MAX_ELEMS, raw=True)
+
+
+def taylor_expansion_of_coeff(x, var, k, out=None):
+    """``series2.taylor_expansion_of_coeff`` over intervals: slice ``k`` untouched, slice ``k + j`` times the interval ``f_j``."""
+    return _observe("interval_series2.taylor_expansion_of_coeff", "taylor_expansion_of_coeff", x, k, out, rank=2, var=var, planes=1,
+                    limit=MAX_ELEMS, raw=True)
+
+
+def shift_down(x, var, k, out=None):
+    """``series2.shift_down`` over intervals: the same orders of summation, every step the reference's interval addition."""
+    return _observe("interval_series2.shift_down", "shift_down", x, k, out, rank=2, var=var, planes=1, limit=MAX_ELEMS, raw=True)
+
+
+def evaluate_all_one(x, out=None):
+    """The row-major interval sum of every item from ``[0, 0]``; ``[2, B...]``."""
+    return _observe("interval_series2.evaluate_all_one", "evaluate_all_one", x, None, out, rank=2, planes=1, limit=MAX_ELEMS, raw=True)

@@ -1,5 +1,6 @@
-"""Batched univariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the transposed
-product ``corr`` (``gft_series_*``), the first six differentiable by torch's autograd.
+"""Batched univariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow``, the transposed
+product ``corr`` and the observation ops ``derivative``, ``taylor_expansion_of_coeff``, ``shift_down``, ``evaluate_all_one``
+(``gft_series_*``), all but ``corr`` differentiable by torch's autograd.
 
 The last axis of every tensor is the series (coefficient ``k`` of ``t^k`` at index ``k``, unit stride), the leading axes are
 batch axes and broadcast by torch's rules (``expand``, no copy: one series against a whole batch has batch stride 0).
@@ -14,6 +15,8 @@ never depends on what else is in the batch.  The call is ordered on torch's curr
     >>> e = series.exp(x, seed=torch.exp(x[..., 0]))
     >>> h = series.compose(f, g)         # f(g(t)) per item: Horner over f's coefficients, one launch
     >>> p = series.pow(x, 5)             # square-and-multiply over mul
+    >>> d = series.derivative(h, 2)      # [B, n - 2]: h[b, 2 + j] times the reference's factor table
+    >>> m = series.evaluate_all_one(h)   # [B]: 0.0 + h[b, 0] + h[b, 1] + ..., the reference's order
 
 Gradients: when grad mode is on and an operand has ``requires_grad=True`` the six operations record a ``grad_fn`` (forward values
 are the same bits either way).  Every backward pass is a short sequence of calls of this module around ``corr``, the adjoint of the
@@ -54,6 +57,11 @@ def _lib():
                 f.restype, f.argtypes = C.c_int, [vp, i64, C.c_size_t, vp, i64, vp, i64, C.c_size_t, sz, C.c_size_t, vp]
             f = getattr(L, pre + "pow")
             f.restype, f.argtypes = C.c_int, [vp, i64, C.c_size_t, C.c_uint32, vp, i64, C.c_size_t, sz, C.c_size_t, vp]
+            for name in ("derivative", "taylor_expansion_of_coeff", "shift_down"):  # the observation ops: x, the order k, the result
+                f = getattr(L, pre + name)
+                f.restype, f.argtypes = C.c_int, [vp, i64, C.c_size_t, C.c_size_t, vp, i64, C.c_size_t, sz, C.c_size_t, vp]
+            f = getattr(L, pre + "evaluate_all_one")
+            f.restype, f.argtypes = C.c_int, [vp, i64, C.c_size_t, vp, i64, sz, C.c_size_t, vp]
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
@@ -270,6 +278,151 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     return _run("series.pow", "gft_series_pow", x, None, n, out, True, e=e)
 
 
+# ---- the observation ops: derivative, taylor_expansion_of_coeff, shift_down, evaluate_all_one --------------------------------
+# One operand, an order k on one axis; the result is k shorter there (include/gftaylor.h states the loops).  _observe serves both
+# ranks and both element types: series2, interval_series and interval_series2 call it with their own names and limits.
+
+
+def _order_k(what, k, length, axis=""):
+    """The order of an observation op: an integer with 0 <= k < the stored length on the axis it acts on."""
+    import operator
+
+    if isinstance(k, bool):
+        raise TypeError(f"{what}: k must be a non-negative integer, got a bool")
+    try:
+        ki = operator.index(k)
+    except TypeError:
+        raise TypeError(f"{what}: k must be a non-negative integer, got {k!r}") from None
+    if not 0 <= ki < length:
+        raise TaylorError(f"{what}: k = {ki}, but x has {length} stored coefficients{axis} (the order must satisfy 0 <= k < {length})")
+    return ki
+
+
+def _observe(what, name, x, k, out, rank=1, var=None, planes=0, limit=None, raw=False):
+    """One call of gft[i]_series[2]_<name>.  k is None: evaluate_all_one (the result has the batch shape).  raw: the module has no
+    autograd and refuses an operand that requires grad.  Everything that needs no device is judged first."""
+    import torch
+
+    ev = k is None
+    if rank == 2:
+        from . import series2 as mod
+
+        def axes(t, w):
+            _check(torch, t, w, series_axis=False, planes=planes, placement=False)
+            mod._axes(t, w, planes)
+    else:
+        mod = None
+
+        def axes(t, w):
+            _check(torch, t, w, planes=planes, placement=False)
+
+    axes(x, f"{what}: x")
+    if out is not None:
+        if ev:
+            _check(torch, out, f"{what}: out", series_axis=False, planes=planes, placement=False)
+        else:
+            axes(out, f"{what}: out")
+    shape = tuple(x.shape[-rank:])
+    count = shape[0] * shape[-1] if rank == 2 else shape[0]
+    if limit is None:
+        limit = MAX_N
+    if count > limit:
+        if rank == 2:
+            raise TaylorError(f"{what}: x has {shape[0]} * {shape[1]} = {count} coefficients, which exceeds the limit of {limit} per item of this version")
+        raise TaylorError(f"{what}: x has {count} coefficients, which exceeds the limit of {limit} per series of this version")
+    axis = -1
+    if rank == 2 and not ev:
+        if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
+            raise TaylorError(f"{what}: var = {var!r}; the variable the operation acts on is 0 (axis -2) or 1 (axis -1)")
+        axis = var - 2
+    if ev:
+        rshape = ()
+    else:
+        k = _order_k(what, k, shape[axis], f" on axis {axis}" if rank == 2 else "")
+        rshape = list(shape)
+        rshape[axis] -= k
+        rshape = tuple(rshape)
+    lead = (2,) * planes
+    xbatch = tuple(x.shape[planes:-rank])
+    if out is not None:
+        nr = len(rshape)
+        if out.dim() < planes + nr or tuple(out.shape[out.dim() - nr:]) != rshape:
+            raise TaylorError(f"{what}: out has shape {tuple(out.shape)}; the result has {rshape if nr else 'no'} coefficients per item"
+                              + (f" (x's {shape}, less k = {k} on the axis)" if nr else " (the batch shape alone)"))
+        batch = tuple(out.shape[planes:out.dim() - nr])
+        try:
+            fits = tuple(torch.broadcast_shapes(xbatch, batch)) == batch
+        except RuntimeError:
+            fits = False
+        if not fits:
+            raise TaylorError(f"{what}: out has batch shape {batch}; the operand has {xbatch}")
+    else:
+        batch = xbatch
+    if raw and torch.is_grad_enabled() and x.requires_grad:
+        raise TaylorError(f"{what}: an operand requires grad, and this version of {what.split('.')[0]} has no autograd; pass x.detach() or call "
+                          "under torch.no_grad() (nothing is detached silently)")
+    _placed(x, f"{what}: x")
+    if out is not None:
+        _placed(out, f"{what}: out")
+        if out.device != x.device:
+            raise TaylorError(f"{what}: the tensors are on different devices ({x.device}, {out.device})")
+    else:
+        out = torch.empty(lead + batch + rshape, dtype=torch.float64, device=x.device)
+    nb = len(batch)
+    if planes and x.dim() < nb + 1 + rank:  # the plane axis stays first, missing batch axes go behind it (a view)
+        x = x[(slice(None),) + (None,) * (nb + 1 + rank - x.dim())]
+    L = mod._lib() if mod else _lib()
+    dev = int(L.gft_device())
+    if dev >= 0 and x.device.index != dev:
+        raise TaylorError(f"{what}: the tensors are on {x.device}, but the library runs on cuda:{dev}")
+    ns = nb + planes
+    xe = x.expand(lead + batch + shape)
+    bsz = (C.c_size_t * max(nb, 1))(*batch)
+    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series2_" if rank == 2 else "series_") + name)
+    xa = (C.c_void_p(xe.data_ptr()), _i64(xe.stride()[:ns])) + ((xe.stride(-2),) if rank == 2 else ()) + shape
+    ra = (C.c_void_p(out.data_ptr()), _i64(out.stride()[:ns]))
+    if ev:
+        rc = fn(*xa, *ra, bsz, nb, stream)
+    else:
+        ka = (C.c_int(var), k) if rank == 2 else (k,)
+        rc = fn(*xa, *ka, *ra, *((out.stride(-2),) if rank == 2 else ()), *rshape, bsz, nb, stream)
+    if rc != 0:
+        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
+    return out
+
+
+def derivative(x, k, out=None):
+    """The ``k``-th derivative's coefficients: ``out[b, j] = x[b, k + j] * ff_j`` for ``j < nx - k``, one rounding each, with the
+    reference's running-product factors ``ff_0 = k!``, ``ff_{j+1} = ff_j * ((k + j + 1) / (j + 1))`` (the quotient rounded first)."""
+    if _tracked("series.derivative", (x,), out):
+        return _autograd().observe("series", 1).Derivative.apply(x, None, k)
+    return _observe("series.derivative", "derivative", x, k, out)
+
+
+def taylor_expansion_of_coeff(x, k, out=None):
+    """The expansion of coefficient ``k``: ``out[b, 0] = x[b, k]`` and ``out[b, j] = x[b, k + j] * f_j`` with ``f_0 = 1``,
+    ``f_j = f_{j-1} * ((k + j) / j)`` -- ``derivative`` without its factor ``k!``."""
+    if _tracked("series.taylor_expansion_of_coeff", (x,), out):
+        return _autograd().observe("series", 1).Coeff.apply(x, None, k)
+    return _observe("series.taylor_expansion_of_coeff", "taylor_expansion_of_coeff", x, k, out)
+
+
+def shift_down(x, k, out=None):
+    """The coefficients moved down by ``k``, those pushed out gathered at 0: ``out[b, 0] = x[b, k] + (0.0 + x[b, 0] + ... +
+    x[b, k - 1])`` (ascending; with ``nx == k + 1`` the ascending sum of all of them) and ``out[b, j] = x[b, k + j]``."""
+    if _tracked("series.shift_down", (x,), out):
+        return _autograd().observe("series", 1).ShiftDown.apply(x, None, k)
+    return _observe("series.shift_down", "shift_down", x, k, out)
+
+
+def evaluate_all_one(x, out=None):
+    """The series at ``t = 1``: ``0.0 + x[b, 0] + x[b, 1] + ...``, one ascending chain per item; the result has the batch shape."""
+    if _tracked("series.evaluate_all_one", (x,), out):
+        return _autograd().observe("series", 1).EvalOne.apply(x)
+    return _observe("series.evaluate_all_one", "evaluate_all_one", x, None, out)
+
+
 # ---- autograd ----------------------------------------------------------------------------------------------------------------
 # Every vector-Jacobian product below is a sequence of this module's own calls on detached tensors; `corr` carries the order of
 # its sums, so a gradient's bits are pinned up to the reduction over broadcast batch axes (sum_to_size: torch's order).
@@ -419,7 +572,76 @@ def _autograd():
                 gg = corr(gh, compose(fp, g, n), g.shape[-1]).sum_to_size(g.shape)
             return gf, gg, None
 
-    _functions = types.SimpleNamespace(Mul=Mul, Div=Div, Exp=Exp, Log=Log, Pow=Pow, Compose=Compose)
+    # The observation ops are linear maps; their adjoints are torch indexing around this module's own calls.  One set of
+    # Functions per (module, rank): series at rank 1, series2_grad at rank 2 (var is None at rank 1).
+    observers = {}
+
+    def observe(module, rank):
+        if (module, rank) in observers:
+            return observers[(module, rank)]
+
+        def axis_of(var):
+            return -1 if rank == 1 else var - 2
+
+        def scaled(name, long_name):
+            class Scaled(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, x, var, k):
+                    x = x.detach()
+                    ctx.var, ctx.shape = var, x.shape
+                    z = _observe(f"{module}.{long_name}", long_name, x, k, None, rank=rank, var=var)
+                    ctx.k = x.shape[axis_of(var)] - z.shape[axis_of(var)]
+                    return z
+
+                @staticmethod
+                @once_differentiable
+                def backward(ctx, gz):  # gx[k + j] = gz[j] * factor_j, the factors the forward op of ones; gx[< k] = +0.0
+                    ax, k = axis_of(ctx.var), ctx.k
+                    ln = ctx.shape[ax]
+                    fac = _observe(f"{module}.{long_name}", long_name, torch.ones(ln, dtype=torch.float64, device=gz.device), k, None)
+                    gx = torch.zeros(ctx.shape, dtype=torch.float64, device=gz.device)
+                    gx.narrow(ax, k, ln - k).copy_(gz * (fac if ax == -1 else fac[:, None]))
+                    return gx, None, None
+
+            Scaled.__name__ = Scaled.__qualname__ = name
+            return Scaled
+
+        class ShiftDown(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, var, k):
+                x = x.detach()
+                ctx.var = var
+                z = _observe(f"{module}.shift_down", "shift_down", x, k, None, rank=rank, var=var)
+                ctx.k = x.shape[axis_of(var)] - z.shape[axis_of(var)]
+                return z
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, gz):  # gx[i] = gz[0] for i <= k, gx[k + j] = gz[j] for j >= 1
+                ax, k = axis_of(ctx.var), ctx.k
+                if k == 0:
+                    return gz, None, None
+                head = gz.narrow(ax, 0, 1)
+                return torch.cat([head.expand(*(k if a == gz.dim() + ax else s for a, s in enumerate(gz.shape))), gz], dim=ax), None, None
+
+        class EvalOne(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x):
+                x = x.detach()
+                ctx.shape = x.shape
+                return _observe(f"{module}.evaluate_all_one", "evaluate_all_one", x, None, None, rank=rank)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, gz):  # gz broadcast over the item
+                return gz[(...,) + (None,) * rank].expand(ctx.shape)
+
+        ns = types.SimpleNamespace(Derivative=scaled("Derivative", "derivative"), Coeff=scaled("Coeff", "taylor_expansion_of_coeff"),
+                                   ShiftDown=ShiftDown, EvalOne=EvalOne)
+        observers[(module, rank)] = ns
+        return ns
+
+    _functions = types.SimpleNamespace(Mul=Mul, Div=Div, Exp=Exp, Log=Log, Pow=Pow, Compose=Compose, observe=observe)
     return _functions
 
 

@@ -1,5 +1,6 @@
 """Batched bivariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the transposed
-product ``corr`` (``gft_series2_*``).
+product ``corr`` and the observation ops ``derivative``, ``taylor_expansion_of_coeff``, ``shift_down``, ``evaluate_all_one``
+(``gft_series2_*``).
 
 The last two axes of every tensor are the coefficient array of one ``TaylorPoly<F64>`` in two variables: axis -2 is variable 0
 (any non-negative stride), axis -1 is variable 1 (unit stride); the leading axes are batch axes and broadcast by torch's rules
@@ -26,7 +27,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from .series import _check, _exponent, _i64, _placed
+from .series import _check, _exponent, _i64, _observe, _placed
 from .taylor import TaylorError
 
 MAX_ELEMS = 4096  # gft_series.hpp SERIES2_MAX_ELEMS: n0 * n1 of the result in this version
@@ -52,6 +53,11 @@ def _lib():
             f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
             f = getattr(L, pre + "pow")
             f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, C.c_uint32, vp, i64, i, s, s, sz, s, vp]
+            for name in ("derivative", "taylor_expansion_of_coeff", "shift_down"):  # the observation ops: x, var, k, the result
+                f = getattr(L, pre + name)
+                f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, C.c_int, s, vp, i64, i, s, s, sz, s, vp]
+            f = getattr(L, pre + "evaluate_all_one")
+            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, sz, s, vp]
         # the transposed operations (f64 only): mul's and compose's argument lists
         L.gft_series2_corr.restype, L.gft_series2_corr.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, vp, i64, i, s, s, sz, s, vp]
         f = L.gft_series2_compose_adj
@@ -268,3 +274,30 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     square-and-multiply over ``mul`` at compact shapes.  ``e = 0`` gives the unit item ``[[1, 0, ...], [0, ...], ...]``."""
     e = _exponent("series2.pow", e, div="series2.div")
     return _run("series2.pow", "gft_series2_pow", x, None, n, out, True, scalar=e)
+
+
+# ---- the observation ops (series._observe at rank 2; include/gftaylor.h states the loops) -------------------------------------
+
+
+def derivative(x, var, k, out=None):
+    """The ``k``-th derivative in variable ``var`` (0: axis -2, 1: axis -1): slice ``j`` of the result is slice ``k + j`` of ``x`` times
+    the reference's factor ``ff_j`` (``series.derivative``), one rounding per coefficient; the axis is ``k`` shorter."""
+    return _observe("series2.derivative", "derivative", x, k, out, rank=2, var=var, limit=MAX_ELEMS, raw=True)
+
+
+def taylor_expansion_of_coeff(x, var, k, out=None):
+    """The expansion of the coefficient of ``var**k``: slice 0 is slice ``k`` of ``x`` untouched, slice ``j >= 1`` is slice ``k + j``
+    times ``f_j`` (``series.taylor_expansion_of_coeff``)."""
+    return _observe("series2.taylor_expansion_of_coeff", "taylor_expansion_of_coeff", x, k, out, rank=2, var=var, limit=MAX_ELEMS, raw=True)
+
+
+def shift_down(x, var, k, out=None):
+    """Variable ``var`` moved down by ``k``: slice 0 of the result is slice ``k`` of ``x`` plus the ordered sum of slices ``0 .. k-1``
+    (all slices when the axis has ``k + 1``), the others are copies.  The order is ndarray's ``sum_axis``: along axis -2 ascending over
+    the rows from 0.0 per column; along axis -1, and along axis -2 of a one-column item, the 8-way unrolled fold."""
+    return _observe("series2.shift_down", "shift_down", x, k, out, rank=2, var=var, limit=MAX_ELEMS, raw=True)
+
+
+def evaluate_all_one(x, out=None):
+    """Every item at ``(1, 1)``: ``0.0 + x[b, 0, 0] + x[b, 0, 1] + ...`` in row-major order, one chain; the batch shape."""
+    return _observe("series2.evaluate_all_one", "evaluate_all_one", x, None, out, rank=2, limit=MAX_ELEMS, raw=True)

@@ -1,4 +1,5 @@
-"""Differentiable batched bivariate series: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` with the signatures, the
+"""Differentiable batched bivariate series: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the observation ops
+``derivative``, ``taylor_expansion_of_coeff``, ``shift_down``, ``evaluate_all_one`` with the signatures, the
 operand layout and the forward bits of ``genfer_amd.series2``, recording a ``grad_fn`` for torch's autograd.
 
 ``series2`` is the raw layer and refuses an operand that requires grad; this module is its differentiable twin, as
@@ -29,6 +30,7 @@ carries a gradient (it is ``exp(x[..., 0, 0])`` / ``ln(x[..., 0, 0])`` by contra
 from __future__ import annotations
 
 from . import series2
+from . import series as _series
 from .series import _exponent, _tracked
 
 _functions = None
@@ -206,3 +208,41 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     if _tracked("series2_grad.pow", (x,), out):
         return _autograd().Pow.apply(x, _exponent("series2_grad.pow", e, div="series2_grad.div"), n)
     return series2.pow(x, e, n, out)
+
+
+# ---- the observation ops: linear maps, their adjoints torch indexing around series2's own calls (series._autograd().observe) ---
+#     derivative, taylor_expansion_of_coeff   gx[k + j] = gz[j] * factor_j along axis var (the factors: the op of ones), gx[< k] = +0.0
+#     shift_down                              gx[i] = gz[0] for i <= k, gx[k + j] = gz[j] for j >= 1, along axis var
+#     evaluate_all_one                        gz broadcast over the item
+
+
+def _observers():
+    return _series._autograd().observe("series2_grad", 2)
+
+
+def derivative(x, var, k, out=None):
+    """``series2.derivative``, differentiable in ``x``."""
+    if _tracked("series2_grad.derivative", (x,), out):
+        return _observers().Derivative.apply(x, var, k)
+    return series2.derivative(x, var, k, out)
+
+
+def taylor_expansion_of_coeff(x, var, k, out=None):
+    """``series2.taylor_expansion_of_coeff``, differentiable in ``x``."""
+    if _tracked("series2_grad.taylor_expansion_of_coeff", (x,), out):
+        return _observers().Coeff.apply(x, var, k)
+    return series2.taylor_expansion_of_coeff(x, var, k, out)
+
+
+def shift_down(x, var, k, out=None):
+    """``series2.shift_down``, differentiable in ``x``."""
+    if _tracked("series2_grad.shift_down", (x,), out):
+        return _observers().ShiftDown.apply(x, var, k)
+    return series2.shift_down(x, var, k, out)
+
+
+def evaluate_all_one(x, out=None):
+    """``series2.evaluate_all_one``, differentiable in ``x``."""
+    if _tracked("series2_grad.evaluate_all_one", (x,), out):
+        return _observers().EvalOne.apply(x)
+    return series2.evaluate_all_one(x, out)

@@ -297,6 +297,46 @@ int gft_series2_compose_adj(const double* gh, const int64_t* hbs, int64_t hrs, s
                             int64_t grs, size_t ng0, size_t ng1, int var, double* res, const int64_t* rbs, int64_t rrs, size_t nf0,
                             size_t nf1, const size_t* batch, size_t nbatch, void* stream);   /* subst_var (Horner) transposed */
 
+/* ---- batched observation ops on caller-owned device tensors: derivative / taylor_expansion_of_coeff / shift_down /
+ * evaluate_all_one at ranks 1 (gft_series_*) and 2 (gft_series2_*), what `observe X = k`, `X -= k` and the mass read-outs are made
+ * of.  One operand x of stored length nx (rank 2: shape (nx0, nx1), rows xrs elements apart) per item; `k` is the order, at rank 2
+ * behind `var`, the axis it acts on (0: axis -2, 1: axis -1).  0 <= k < the stored length on that axis, anything else is refused
+ * before the device is touched.  The result has the operand's shape with k taken off that axis, and (n | n0, n1) must say so.
+ * Batch strides, row strides, NULL stride arrays, empty batches, the stream contract and return values: those of gft_series_mul /
+ * gft_series2_mul; the limits nx <= 4096 and nx0 * nx1 <= 4096 bound the OPERAND.  The result may be x itself as the same view
+ * (possible at k == 0 only); every other overlap is refused.  Per item, with T::from_u32 the conversion and every operation rounded
+ * once, the loops along the axis (the other index, if any, carried along) are the handle operations' (mt:457-536):
+ *   derivative:                 out[j] = x[k + j] * ff_j;   ff_0 = ((1 * 1) * 2) ... * k,  ff_{j+1} = ff_j * (from(k + j + 1) / from(j + 1))
+ *   taylor_expansion_of_coeff:  out[0] = x[k];  out[j] = x[k + j] * f_j, j >= 1;   f_0 = 1,  f_j = f_{j-1} * (from(k + j) / from(j))
+ *   shift_down:                 out[0] = x[k] + S,  S the ordered sum of x[0 .. k) from 0.0;  out[j] = x[k + j], j >= 1;
+ *                               when the stored length is k + 1, out[0] is the ordered sum of ALL its slices instead
+ *   evaluate_all_one:           res = 0.0 + x[0] + x[1] + ... over the item in row-major order, one chain (mt:583-586); the result
+ *                               has the batch shape, strides rbs
+ * The quotient of a factor is rounded first, then the product: the factors are not the integers one would guess, and they depend on
+ * (operation, k, length) only, so they are computed once by the handle path's table functor and cached.  The order of S is ndarray's
+ * sum_axis: at rank 1 ascending; at rank 2 along axis 0 ascending over the rows, per column -- unless nx1 == 1, which, like every
+ * sum along axis 1, is the 8-way unrolled fold: eight partial sums p_u over whole groups of eight (p_u += x[8 g + u]), then
+ * (((0.0 + (p0 + p4)) + (p1 + p5)) + (p2 + p6)) + (p3 + p7), then the tail in order.  The additions of 0.0 are real: with k == 0
+ * out[0] = x[0] + 0.0, and -0.0 becomes +0.0.  No data-dependent shortcut is taken.  One launch per call, no workspace;
+ * gft_series_last_form() reports 0 afterwards. */
+int gft_series_derivative(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs, size_t n,
+                          const size_t* batch, size_t nbatch, void* stream);
+int gft_series_taylor_expansion_of_coeff(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs,
+                                         size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gft_series_shift_down(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs, size_t n,
+                          const size_t* batch, size_t nbatch, void* stream);
+int gft_series_evaluate_all_one(const double* x, const int64_t* xbs, size_t nx, double* res, const int64_t* rbs, const size_t* batch,
+                                size_t nbatch, void* stream);
+int gft_series2_derivative(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k, double* res,
+                           const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+int gft_series2_taylor_expansion_of_coeff(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k,
+                                          double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch,
+                                          size_t nbatch, void* stream);
+int gft_series2_shift_down(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k, double* res,
+                           const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+int gft_series2_evaluate_all_one(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, double* res,
+                                 const int64_t* rbs, const size_t* batch, size_t nbatch, void* stream);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI, collectives internal to the library --------
  * The reference is single-process; a host that wants one large product spread over the GPUs of a node starts one
  * process per GPU (each with its own gft_init(device)), lets rank 0 call gft_dist_unique_id, hands the 128 bytes to
@@ -494,6 +534,28 @@ int gfti_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_
                          size_t n1, const size_t* batch, size_t nbatch, void* stream);
 int gfti_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
                      const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+/* The observation ops over Interval<F64>: gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down /
+ * evaluate_all_one on (lo, hi) planes, the stride-array convention of gfti_series_* (the plane stride first; 0 on the operand: point
+ * intervals).  The same loops with every step one operation of the reference's interval arithmetic, its short-circuits included
+ * ([0,0] + b is b: the sums start from [0,0], so the first addition changes nothing).  evaluate_all_one's result is [2, B...].  The
+ * limits on the operand are nx <= 2048 and nx0 * nx1 <= 2048. */
+int gfti_series_derivative(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs, size_t n,
+                           const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_taylor_expansion_of_coeff(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs,
+                                          size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_shift_down(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs, size_t n,
+                           const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_evaluate_all_one(const double* x, const int64_t* xbs, size_t nx, double* res, const int64_t* rbs, const size_t* batch,
+                                 size_t nbatch, void* stream);
+int gfti_series2_derivative(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k, double* res,
+                            const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_taylor_expansion_of_coeff(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k,
+                                           double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch,
+                                           size_t nbatch, void* stream);
+int gfti_series2_shift_down(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k, double* res,
+                            const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_evaluate_all_one(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, double* res,
+                                  const int64_t* rbs, const size_t* batch, size_t nbatch, void* stream);
 size_t gfti_len_of(const gft_poly* p, size_t v);
 int gfti_is_constant(const gft_poly* p);
 int gfti_is_zero(const gft_poly* p);
