@@ -1,0 +1,267 @@
+"""The one host path of the batched series modules: ``series``, ``series2``, ``interval_series``, ``interval_series2`` (and the
+autograd Functions of ``series`` and ``series2_grad``) describe a call by data and hand it to ``run``.
+
+``OPS`` is the table of the operations: one row says what travels between the first operand and the result, which side is the long
+one, the operands' names in messages and whether ``var`` travels at rank 2.  The same rows build the ctypes declarations of every
+``gft[i]_series[2]_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart.  A ``Call``
+says the rest: the rank (1: the last axis is the series, 2: the last two axes are the coefficient array), ``planes`` (1: interval
+tensors ``[2, B..., item]``, the plane axis travelling as the first entry of every batch-stride array), the limit of the long side
+and the module's name for messages.  ``run`` works on ``t.shape[-rank:]`` and ``t.stride()[-rank:-1]``: rank 2 contributes its row
+stride and its second length because those tuples are one entry longer.
+
+Everything that needs no device is judged first, in one order for every module: type, dtype, planes, axes (per tensor), the orders,
+``out``, grad, then the placement, the devices and the library's device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+
+from .taylor import TaylorError
+
+# kind: "second" (a second series), "seed" (exp / log: one value per item, or None), "e" (pow's exponent), "k" (the order of an
+# observation op) or None (evaluate_all_one: the result has the batch shape).  long: the side that carries the limit and bounds the
+# others -- the result, or x for the transposed and the observation ops.  names: the operands (and, transposed, the result's
+# order) in messages.  var: the variable travels at rank 2, behind the operands.  label: the function's name in messages.
+Op = namedtuple("Op", "suffix kind long names var label")
+Call = namedtuple("Call", "module rank planes limit raw")  # raw: the module has no autograd and refuses an operand that requires grad
+
+
+def _op(suffix, kind, long="result", names=("x", "y"), var=False, label=None):
+    return Op(suffix, kind, long, names, var, label or suffix)
+
+
+OPS = {o.suffix: o for o in (
+    _op("mul", "second"),
+    _op("div", "second"),
+    _op("exp", "seed"),
+    _op("log", "seed"),
+    _op("compose", "second", names=("f", "g"), var=True),
+    _op("pow", "e"),
+    _op("corr", "second", long="x", names=("g", "y", "m")),
+    _op("compose_adj", "second", long="x", names=("gh", "g", "nf"), var=True, label="_compose_adj"),
+    _op("derivative", "k", long="x", var=True),
+    _op("taylor_expansion_of_coeff", "k", long="x", var=True),
+    _op("shift_down", "k", long="x", var=True),
+    _op("evaluate_all_one", None, long="x"),
+)}
+F64_ONLY = ("corr", "compose_adj")  # no gfti_ twin
+
+
+def _i64(seq):
+    seq = [int(s) for s in seq]
+    return (C.c_int64 * max(len(seq), 1))(*seq)
+
+
+_I64P, _SZP = C.POINTER(C.c_int64), C.POINTER(C.c_size_t)
+
+
+def _view_types(rank, lens=True):
+    """an operand in an entry point's argument list: the pointer, the batch strides, and with ``lens`` the row strides (rank 2
+    has one) and the lengths"""
+    return (C.c_void_p, _I64P) + ((C.c_int64,) * (rank - 1) + (C.c_size_t,) * rank if lens else ())
+
+
+def _view(rank, t, ns, lens=True):
+    """the values of _view_types for a tensor (None: no seeds); ``ns``: the leading strides that are batch strides"""
+    if t is None:
+        return (None, None)
+    v = (C.c_void_p(t.data_ptr()), _i64(t.stride()[:ns]))
+    return v + t.stride()[-rank:-1] + tuple(t.shape[-rank:]) if lens else v
+
+
+def _arguments(op, rank, view, e, var, k, tail):
+    """The argument list of gft[i]_series[2]_<op.suffix>, from the op's row.  ``view(which, lens)`` gives the part of an operand
+    ("x", "second", "out"), the others are the parts of the scalars and of the tail (the batch shape, its length, the stream):
+    ctypes for the declaration, values for a call -- one layout for both."""
+    a = view("x", True)
+    if op.kind == "second":
+        a += view("second", True)
+    elif op.kind == "seed":
+        a += view("second", False)
+    elif op.kind == "e":
+        a += e
+    if op.var and rank == 2:
+        a += var
+    if op.kind == "k":
+        a += k
+    return a + view("out", op.kind is not None) + tail
+
+
+_declared = None
+
+
+def _lib():
+    """The library with every batched series entry point declared from OPS."""
+    global _declared
+    if _declared is None:
+        from . import lib
+
+        L = lib()
+        for pre in ("gft_", "gfti_"):  # the interval twins take the same argument lists
+            for rank, mid in ((1, "series_"), (2, "series2_")):
+                for op in OPS.values():
+                    if pre == "gft_" or op.suffix not in F64_ONLY:
+                        f = getattr(L, pre + mid + op.suffix)
+                        f.restype = C.c_int
+                        f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,),
+                                                     (C.c_size_t,), (_SZP, C.c_size_t, C.c_void_p)))
+        L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
+        _declared = L
+    return _declared
+
+
+def _placed(t, what):
+    if t.device.type != "cuda":
+        raise TaylorError(f"{what}: the tensor is on {t.device}; it must be in device memory of the library's GPU")
+
+
+def _check(torch, t, what, planes=0):
+    """type, dtype and, for an interval tensor, the leading axis of the two planes"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != torch.float64:
+        raise TaylorError(f"{what}: the tensor is {t.dtype}; only torch.float64 is accepted (no implicit conversion)")
+    if planes and (t.dim() < 1 or t.shape[0] != 2):
+        lead = "no axes" if t.dim() < 1 else f"a first axis of {t.shape[0]}"
+        raise TaylorError(f"{what}: the tensor has {lead}; an interval tensor is stacked [2, ...] = (lo, hi) along its first axis")
+
+
+def _axes1(t, what, planes=0):
+    """the series axis of an operand or of ``out``"""
+    if t.dim() < 1 + planes:
+        raise TaylorError(f"{what}: a 0-dimensional tensor has no series axis")
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
+    if t.shape[-1] == 0:
+        raise TaylorError(f"{what}: the series (last) axis is empty")
+
+
+def _axes2(t, what, planes=0):
+    """the two series axes of an operand or of ``out``"""
+    if t.dim() < 2 + planes:
+        if planes:
+            raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate interval series needs at least 3 (the first holds the two "
+                              "planes, the last two are the coefficient array)")
+        raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate series needs at least 2 (the last two are the coefficient array)")
+    if t.shape[-1] == 0 or t.shape[-2] == 0:
+        raise TaylorError(f"{what}: a series axis is empty (the last two axes are {tuple(t.shape[-2:])})")
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
+
+
+_rank = {}
+
+
+def _rank_rules(rank):
+    """What differs by rank: the checks of the series axes, the order helpers (they stay with their modules, series._order ... and
+    series2._orders ...; here they take and give item shapes) and the texts that count "per series" or "per item"."""
+    if not _rank:
+        from .series import _order, _order_short
+        from .series2 import _orders, _orders_short
+
+        _rank[1] = (_axes1, lambda what, n, limit, *items: (_order(what, n, *[i[0] for i in items], max_n=limit),),
+                    lambda what, n, names, g, y: (_order_short(what, n, g[0], y[0], names),),
+                    "{what}: x has {count} coefficients, which exceeds the limit of {limit} per series of this version",
+                    "{what}: out has {got[0]} coefficients per series, the result has n = {want[0]}")
+        _rank[2] = (_axes2, lambda what, n, limit, *items: _orders(what, n, *items, max_elems=limit),
+                    lambda what, n, names, g, y: _orders_short(what, n, g, y, names),
+                    "{what}: x has {shape[0]} * {shape[1]} = {count} coefficients, which exceeds the limit of {limit} per item of this version",
+                    "{what}: out has {got} coefficients per item, the result has n = {want}")
+    return _rank[rank]
+
+
+def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
+    """One call of gft[i]_series[2]_<name>.  ``second``: the second series or the seeds; ``scalar``: pow's ``e`` or an observation
+    op's ``k``; ``var``: the variable at rank 2 (already judged by series2._var where it is compose's)."""
+    import torch
+
+    op, (module, rank, planes, limit, raw) = OPS[name], call
+    what = f"{module}.{op.label}"
+    axes, order, short, over_text, out_text = _rank_rules(rank)
+    observe, seeded = op.kind in ("k", None), op.kind == "seed"
+    xname, sname = op.names[0], "seed" if seeded else op.names[1]
+    # everything that needs no device first: types, shapes, strides, orders, out, grad -- then the placement
+    for t, w, item in ((x, xname, True), (second, sname, not seeded), (out, "out", op.kind is not None)):
+        if t is not None:
+            w = f"{what}: {w}"
+            _check(torch, t, w, planes)
+            if item:
+                axes(t, w, planes)
+    shape = tuple(x.shape[-rank:])
+    if observe:
+        count = shape[0] * shape[-1] if rank == 2 else shape[0]
+        if count > limit:
+            raise TaylorError(over_text.format(what=what, shape=shape, count=count, limit=limit))
+        axis = -1
+        if op.var and rank == 2:
+            from .series2 import _var
+
+            axis = _var(what, var, "the variable the operation acts on is 0 (axis -2) or 1 (axis -1)") - 2
+        rshape = ()
+        if op.kind == "k":
+            from .series import _order_k
+
+            scalar = _order_k(what, scalar, shape[axis], f" on axis {axis}" if rank == 2 else "")
+            rshape = shape[:axis] + (shape[axis] - scalar,) + shape[rank + axis + 1:]
+    elif op.long == "x":
+        rshape = short(what, n, op.names, shape, tuple(second.shape[-rank:]))
+    else:
+        rshape = order(what, n, limit, shape, *((tuple(second.shape[-rank:]),) if op.kind == "second" else ()))
+    lead, nr = (2,) * planes, len(rshape)
+    shapes = [x.shape[planes:-rank]]
+    if second is not None:
+        shapes.append(second.shape[planes:] if seeded else second.shape[planes:-rank])
+    same = all(s == shapes[0] for s in shapes)  # (the common case, without torch.broadcast_shapes)
+    if out is None:
+        batch = tuple(shapes[0] if same else torch.broadcast_shapes(*shapes))
+    else:
+        if out.dim() < planes + nr or tuple(out.shape[out.dim() - nr:]) != rshape:
+            if observe:
+                raise TaylorError(f"{what}: out has shape {tuple(out.shape)}; the result has {rshape if nr else 'no'} coefficients per item"
+                                  + (f" (x's {shape}, less k = {scalar} on the axis)" if nr else " (the batch shape alone)"))
+            raise TaylorError(out_text.format(what=what, got=tuple(out.shape[-rank:]), want=rshape))
+        batch = tuple(out.shape[planes:out.dim() - nr])
+        try:
+            fits = same and shapes[0] == batch or tuple(torch.broadcast_shapes(*shapes, batch)) == batch
+        except RuntimeError:
+            if not observe:  # (torch's own message for operands that do not broadcast against out)
+                raise
+            fits = False
+        if not fits:
+            if observe:
+                raise TaylorError(f"{what}: out has batch shape {batch}; the operand has {tuple(shapes[0])}")
+            raise TaylorError(f"{what}: out has batch shape {batch}; the operands broadcast to {tuple(torch.broadcast_shapes(*shapes))}")
+    if raw and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, second)):
+        raise TaylorError(f"{what}: an operand requires grad, and this version of {module} has no autograd; pass {xname}.detach() or call under "
+                          "torch.no_grad() (nothing is detached silently)")
+    _placed(x, f"{what}: {xname}")
+    if second is not None:
+        _placed(second, f"{what}: {sname}")
+    if out is not None:
+        _placed(out, f"{what}: out")
+    for t in (second, out):
+        if t is not None and t.device != x.device:
+            raise TaylorError(f"{what}: the tensors are on different devices ({x.device}, {t.device})")
+    if out is None:
+        out = torch.empty(lead + batch + rshape, dtype=torch.float64, device=x.device)
+    nb = len(batch)
+    if planes:  # torch aligns shapes from the right: the plane axis stays first, missing batch axes go behind it (a view)
+        lift = lambda t, dim: t if t.dim() >= dim else t[(slice(None),) + (None,) * (dim - t.dim())]  # noqa: E731
+        x = lift(x, nb + 1 + rank)
+        if second is not None:
+            second = lift(second, nb + 1 + (0 if seeded else rank))
+    L = _lib()
+    dev = int(L.gft_device())
+    if dev >= 0 and x.device.index != dev:
+        raise TaylorError(f"{what}: the tensors are on {x.device}, but the library runs on cuda:{dev}")
+    ns = nb + planes  # entries of a batch-stride array
+    x = x.expand(lead + batch + shape)
+    if second is not None:
+        second = second.expand(lead + batch + (() if seeded else tuple(second.shape[-rank:])))
+    tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_")[rank - 1] + op.suffix)
+    parts = {"x": x, "second": second, "out": out}
+    if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (scalar,), (var,), (scalar,), tail)) != 0:
+        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
+    return out

@@ -8,10 +8,11 @@
 #include <cstddef>
 
 #include "gft_kernels.hpp"  // MAXD
+#include "gft_series_args.hpp"  // IMAXD (HIP-free: the series argument layer sizes its arrays by it)
 
 namespace gft {
 
-constexpr int IMAXD = MAXD + 1;  // the shape's axes after collapsing, plus the lo / hi plane axis of an interval tensor
+static_assert(IMAXD == MAXD + 1, "the shape's axes after collapsing, plus the lo / hi plane axis of an interval tensor");
 
 enum InteropForm { IO_DENSE = 0, IO_ROWS = 1, IO_TILE = 2 };
 

@@ -8,63 +8,22 @@
 // the compact lengths min(la + lb - 1, n) of sum_shape (mt:150-170).  compose costs about nf * n^2 / 2 multiply-adds per item, all
 // of them on one workgroup at most.
 //
-// The host side (gft_api_series.inc) validates, collapses the batch axes into a SeriesBatch and joins the streams; this
+// The host side (gft_series_args.hpp, gft_api_series.inc) validates, collapses the batch axes into a SeriesBatch and joins the streams; this
 // file's planner picks a form and gft_series.hip (div form B: gft_div2d.hip) launches it on the library's stream.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
-#include "gft_interop.hpp"  // IMAXD, interop_copy
+#include "gft_interop.hpp"  // interop_copy
+#include "gft_series_args.hpp"
 
 namespace gft {
 
-enum SeriesOp {
-    SERIES_MUL = 0,
-    SERIES_DIV = 1,
-    SERIES_EXP = 2,
-    SERIES_LOG = 3,
-    SERIES_COMPOSE = 4,
-    SERIES_POW = 5,
-    // The transposed product, the adjoint of mul (f64 only): c[i] = 0 + sum_k g[k] * y[k-i], k DESCENDING from min(ng-1, i+ny-1) to i,
-    // i < m <= ng -- bit for bit mul_1d(flip(g), y) at index ng-1-i.  x is g (nx = ng: the LONG side), y is y (ny <= ng), n is m.
-    SERIES_CORR = 6,
-    // The transposed Horner loop, the gradient of compose with respect to f (f64 only): a_0 = gh[0 .. l_0), out[i] = a_i[0],
-    // a_{i+1} = corr(a_i, g) at the lengths l_i = min(1 + (nf-1-i)(ng-1), n).  x is gh (nx = n), y is g (ny = ng <= n), n is nf <= nx.
-    // One form (B: one workgroup per series for the whole loop).
-    SERIES_COMPOSE_ADJ = 7,
-    // The observation ops (gft_series_observe.hip): one operand, the result shorter by the order k on the axis they act on.
-    // derivative (mt:457-481), taylor_expansion_of_coeff (mt:484-509), shift_down (mt:514-536), evaluate_all_one (mt:583-586).
-    SERIES_DERIVATIVE = 8,
-    SERIES_COEFF = 9,
-    SERIES_SHIFT_DOWN = 10,
-    SERIES_EVAL_ONE = 11
-};
+// (SeriesOp, the limits, SeriesPlanes, SeriesBatch and Series2Dims: gft_series_args.hpp, the HIP-free argument layer)
 // A: one lane is one series, rows staged in LDS.  B: one wave / workgroup is one series (mul, div, compose); for exp / log the
 // lane-per-series loop of form A over a transposed global workspace.  pow is a sequence of mul launches, each planned by itself.
 enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
-
-constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
-// Interval<F64> series (gfti_series_*): two planes per row, so the same LDS footprints are reached at half the order
-constexpr unsigned SERIES_MAX_N_IV = 2048;
-inline unsigned series_max_n(int w) { return w == 2 ? SERIES_MAX_N_IV : SERIES_MAX_N; }
-
-// The element of a call: w = 1 is F64 (one plane, the strides below unused), w = 2 is Interval<F64>, stored as the planes
-// (lo, hi) x / y / s / r elements apart (operands, seeds, result; 0 on an operand: a point interval read twice).
-struct SeriesPlanes {
-    int w = 1;
-    size_t x = 0, y = 0, s = 0, r = 0;
-};
-
-// The collapsed batch: item (i_0, ..., i_{nd-1}), row-major over ext, has its rows at x + sum i_a * xs[a] (elements), and
-// likewise y (mul / div), the seeds (exp / log; one double per item) and the result.  Stride 0 repeats a row.
-struct SeriesBatch {
-    int nd = 0;
-    unsigned items = 1;  // prod ext, < 2^31
-    int inplace = 0;     // the result is one of the operands (the same view): a row is written by the workgroup that read it
-    unsigned ext[IMAXD];
-    size_t xs[IMAXD], ys[IMAXD], ss[IMAXD], rs[IMAXD];
-};
 
 // The form a call takes.  force: 0 = by the thresholds, SERIES_FORM_A = form A whenever the rows fit its LDS budget,
 // SERIES_FORM_B = never form A (gft_set_option("series_form")).
@@ -95,15 +54,6 @@ void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double*
 // compose is subst_var's Horner loop (mt:569-579) over the rows (var 0) or columns (var 1) of f and pow the square-and-multiply of
 // mt:441-450, both over that general product at the compact shapes min(la + lb - 1, n) per axis.  compose costs about
 // slices * (n0 * n1)^2 / 4 multiply-adds per item, all of them on one workgroup.
-constexpr unsigned SERIES2_MAX_ELEMS = 4096;  // n0 * n1 of the result: two resident arrays are then 64 KB
-// Interval<F64> items (gfti_series2_*): an LDS element is a 16-byte {lo, hi}, so two resident arrays are the same 64 KB at half that
-constexpr unsigned SERIES2_MAX_ELEMS_IV = 2048;
-inline unsigned series2_max_elems(int w) { return w == 2 ? SERIES2_MAX_ELEMS_IV : SERIES2_MAX_ELEMS; }
-struct Series2Dims {
-    unsigned nx0, nx1, ny0, ny1, n0, n1;  // stored shapes of x and y (exp / log / pow: ny* unused) and the result's; nx*, ny* <= n*
-                                          // (SERIES_CORR / SERIES_COMPOSE_ADJ at rank 2: x is g / gh, the LONG side: ny*, n* <= nx*)
-    size_t xr, yr, rr;                    // row strides in elements
-};
 // The geometry of a call of element width w (1: F64, 2: Interval<F64>): lanes per workgroup, scratch rows of n1 elements (div / exp / log: the row sums of one chunk of j), the
 // dynamic LDS in bytes, and for compose whether g is resident in LDS.  Throws std::runtime_error where the runtime grants less LDS
 // than the resident arrays and one scratch row need.

@@ -1,0 +1,327 @@
+// The host-side argument layer of the batched series calls (gft[i]_series[2]_*): the plain types a call is described and
+// planned with, and everything that is judged about a call without touching device state -- the shape rules, the batch, the
+// strides, the result's distinct addresses, the overlap proof and the collapse of the batch axes into a SeriesBatch.
+// No HIP include: this header compiles with a plain host compiler (tests/series_args_main.cpp replays refusals through it).
+// The device side (planners, launches, __device__ helpers) is gft_series.hpp; the caller with the device is gft_api_series.inc.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+
+namespace gft {
+
+constexpr int IMAXD = 13;  // MAXD + 1: the shape's axes after collapsing, plus the lo / hi plane axis of an interval tensor
+
+enum SeriesOp {
+    SERIES_MUL = 0,
+    SERIES_DIV = 1,
+    SERIES_EXP = 2,
+    SERIES_LOG = 3,
+    SERIES_COMPOSE = 4,
+    SERIES_POW = 5,
+    // The transposed product, the adjoint of mul (f64 only): c[i] = 0 + sum_k g[k] * y[k-i], k DESCENDING from min(ng-1, i+ny-1) to i,
+    // i < m <= ng -- bit for bit mul_1d(flip(g), y) at index ng-1-i.  x is g (nx = ng: the LONG side), y is y (ny <= ng), n is m.
+    SERIES_CORR = 6,
+    // The transposed Horner loop, the gradient of compose with respect to f (f64 only): a_0 = gh[0 .. l_0), out[i] = a_i[0],
+    // a_{i+1} = corr(a_i, g) at the lengths l_i = min(1 + (nf-1-i)(ng-1), n).  x is gh (nx = n), y is g (ny = ng <= n), n is nf <= nx.
+    // One form (B: one workgroup per series for the whole loop).
+    SERIES_COMPOSE_ADJ = 7,
+    // The observation ops (gft_series_observe.hip): one operand, the result shorter by the order k on the axis they act on.
+    // derivative (mt:457-481), taylor_expansion_of_coeff (mt:484-509), shift_down (mt:514-536), evaluate_all_one (mt:583-586).
+    SERIES_DERIVATIVE = 8,
+    SERIES_COEFF = 9,
+    SERIES_SHIFT_DOWN = 10,
+    SERIES_EVAL_ONE = 11
+};
+
+constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
+// Interval<F64> series (gfti_series_*): two planes per row, so the same LDS footprints are reached at half the order
+constexpr unsigned SERIES_MAX_N_IV = 2048;
+inline unsigned series_max_n(int w) { return w == 2 ? SERIES_MAX_N_IV : SERIES_MAX_N; }
+constexpr unsigned SERIES2_MAX_ELEMS = 4096;  // n0 * n1 of the result: two resident arrays are then 64 KB
+// Interval<F64> items (gfti_series2_*): an LDS element is a 16-byte {lo, hi}, so two resident arrays are the same 64 KB at half that
+constexpr unsigned SERIES2_MAX_ELEMS_IV = 2048;
+inline unsigned series2_max_elems(int w) { return w == 2 ? SERIES2_MAX_ELEMS_IV : SERIES2_MAX_ELEMS; }
+
+// The element of a call: w = 1 is F64 (one plane, the strides below unused), w = 2 is Interval<F64>, stored as the planes
+// (lo, hi) x / y / s / r elements apart (operands, seeds, result; 0 on an operand: a point interval read twice).
+struct SeriesPlanes {
+    int w = 1;
+    size_t x = 0, y = 0, s = 0, r = 0;
+};
+
+// The collapsed batch: item (i_0, ..., i_{nd-1}), row-major over ext, has its rows at x + sum i_a * xs[a] (elements), and
+// likewise y (mul / div), the seeds (exp / log; one double per item) and the result.  Stride 0 repeats a row.
+struct SeriesBatch {
+    int nd = 0;
+    unsigned items = 1;  // prod ext, < 2^31
+    int inplace = 0;     // the result is one of the operands (the same view): a row is written by the workgroup that read it
+    unsigned ext[IMAXD];
+    size_t xs[IMAXD], ys[IMAXD], ss[IMAXD], rs[IMAXD];
+};
+
+struct Series2Dims {
+    unsigned nx0, nx1, ny0, ny1, n0, n1;  // stored shapes of x and y (exp / log / pow: ny* unused) and the result's; nx*, ny* <= n*
+                                          // (SERIES_CORR / SERIES_COMPOSE_ADJ at rank 2: x is g / gh, the LONG side: ny*, n* <= nx*)
+    size_t xr, yr, rr;                    // row strides in elements
+};
+
+// One operand of a call as the C ABI states it: len0 rows of len1 elements (unit stride), `rst` elements apart.  Rank 1 is
+// len0 == 1 with row stride 0.  `bs`: nbatch batch strides in elements, for w == 2 preceded by the lo -> hi plane stride; null:
+// contiguous items of the operand's own shape (the planes back to back).
+struct SeriesView {
+    const double* p = nullptr;
+    const int64_t* bs = nullptr;
+    int64_t rst = 0;
+    size_t len0 = 1, len1 = 1;
+};
+
+// One call.  `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; p may be null; one double per
+// item, so its lengths stay 1); pow has neither, and `e`.  corr (x is g, y is y) and compose_adj (x is gh, y is g, the result has
+// nf coefficients) are the transposed operations: their result is the SHORT side, so x bounds y and the result, and the rows the
+// planner sizes are x's.  rank2 (gft[i]_series2_*): the limit bounds len0 * len1 of the long side; `var`: compose's variable there.
+// The observation ops (SERIES_DERIVATIVE ...): x is the one operand and the LONG side, `k` the order, `var` the axis at rank 2 (at
+// rank 1 it is 1, the series axis), and the result's shape must be x's with k taken off that axis (evaluate_all_one: one element
+// per item).
+struct SeriesCall {
+    int op = SERIES_MUL;
+    const char* fn = "";  // the name in messages
+    int w = 1;
+    bool rank2 = false;
+    uint32_t e = 0;
+    int var = 0;
+    size_t k = 0;
+    const size_t* batch = nullptr;
+    size_t nbatch = 0;
+    SeriesView x, y, r;
+};
+
+// What series_args makes of an accepted call: the collapsed batch, the plane strides and the lengths narrowed to unsigned (exact:
+// the limits have been judged) with the row strides.
+struct SeriesArgs {
+    SeriesBatch g;
+    SeriesPlanes pl;
+    Series2Dims d;
+};
+
+struct SeriesOperand {  // a view with its strides judged: batch strides in elements, the span it covers
+    const char* what;
+    const double* p;
+    size_t len;
+    size_t rows, rst;  // rank 2: an item is `rows` rows, `rst` elements apart; else 1 and 0
+    size_t st[32];
+    size_t plane;  // w == 2: elements from the lo plane to the hi plane (0 on an operand: a point interval), else 0
+    size_t span;   // elements from p to one past its last element (of the hi plane)
+};
+
+static inline SeriesOperand series_arg(const SeriesCall& c, const char* what, const SeriesView& v) {
+    const std::string fn(c.fn);
+    SeriesOperand a;
+    a.what = what;
+    a.p = v.p;
+    a.len = v.len1;
+    if (v.rst < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the row axis)");
+    a.rows = v.len0;
+    a.rst = v.len0 > 1 ? (size_t)v.rst : 0;
+    size_t cs = v.len1 * v.len0;  // NULL: contiguous items of the operand's own shape (the planes back to back)
+    a.span = v.len1 + (v.len0 - 1) * a.rst;
+    const int64_t* bs = v.bs;
+    if (c.w == 2 && bs) {
+        if (bs[0] < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the plane axis)");
+        ++bs;
+    }
+    for (size_t i = c.nbatch; i-- > 0;) {
+        if (bs && bs[i] < 0)
+            throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", batch axis " + std::to_string(i) + ")");
+        a.st[i] = bs ? (size_t)bs[i] : cs;
+        cs *= c.batch[i];
+        a.span += (c.batch[i] - 1) * a.st[i];
+    }
+    a.plane = c.w == 2 ? (bs ? (size_t)bs[-1] : cs) : 0;
+    a.span += a.plane;
+    return a;
+}
+
+static inline bool series_same_view(const SeriesOperand& a, const SeriesOperand& b, const size_t* batch, size_t nbatch) {
+    if (a.p != b.p || a.len != b.len || a.plane != b.plane || a.rows != b.rows || a.rst != b.rst) return false;
+    for (size_t i = 0; i < nbatch; ++i)
+        if (batch[i] > 1 && a.st[i] != b.st[i]) return false;
+    return true;
+}
+
+// The three shape rules, once over (rows, length) pairs: nothing is empty, the long side carries the limit, and the short sides
+// fit inside the long side.  The long side is the result, or x for the transposed and the observation ops.  The texts are per rank.
+// (static, as everything below: the library exports none of this layer)
+static inline void series_shapes(const SeriesCall& c) {
+    using std::to_string;
+    const std::string f(c.fn);
+    const int op = c.op;
+    const bool observe = op >= SERIES_DERIVATIVE, comp = op == SERIES_COMPOSE;
+    const bool corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
+    const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed;
+    const bool r2 = c.rank2, bad_var = r2 && c.var != 0 && c.var != 1;
+    if (bad_var && (comp || adj)) throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable of f that g replaces is 0 or 1)");
+    struct Names {
+        const char *x, *y, *r;
+    };
+    const Names len = corr ? Names{"ng", "ny", "m"} : (adj ? Names{"n", "ng", "nf"} : Names{"nx", "ny", "n"});  // rank 1: the lengths' names
+    const Names who = corr ? Names{"g", "y", "the result"} : (adj ? Names{"gh", "g", "the result"} : Names{"x", "y", "the result"});
+    const bool xlong = transposed || observe;
+    const SeriesView& L = xlong ? c.x : c.r;
+    const char *Llen = xlong ? len.x : len.r, *Lwho = xlong ? who.x : who.r;
+    auto empty = [](const SeriesView& v) { return v.len0 == 0 || v.len1 == 0; };
+    auto dims = [](const SeriesView& v, const char* sep) { return to_string(v.len0) + sep + to_string(v.len1); };
+    if (observe) {
+        if (empty(c.x)) throw std::runtime_error(f + ": x has no coefficients");
+    } else if (empty(c.r)) {
+        if (!r2) throw std::runtime_error(f + ": " + len.r + " == 0 (the result has no coefficients)");
+        throw std::runtime_error(f + (transposed ? ": the result has no coefficients (an axis of its shape is 0)" : ": n0 * n1 == 0 (the result has no coefficients)"));
+    }
+    const size_t most = r2 ? series2_max_elems(c.w) : series_max_n(c.w);
+    if (L.len0 > most || L.len1 > most || L.len0 * L.len1 > most) {
+        if (!r2)
+            throw std::runtime_error(f + ": " + Llen + " = " + to_string(L.len1) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
+        if (xlong)
+            throw std::runtime_error(f + ": " + Lwho + " has " + dims(L, " * ") + " coefficients, which exceeds the limit of " + to_string(most) +
+                                     " coefficients per item of this version");
+        throw std::runtime_error(f + ": n0 * n1 = " + dims(L, " * ") + " exceeds the limit of " + to_string(most) + " coefficients per item of this version");
+    }
+    if (observe) {
+        if (bad_var) throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable the operation acts on is 0 or 1)");
+        if (op == SERIES_EVAL_ONE) return;
+        const bool rows = r2 && c.var == 0;
+        const size_t n = rows ? c.x.len0 : c.x.len1, k = c.k;
+        if (k >= n)
+            throw std::runtime_error(f + ": k = " + to_string(k) + ", but x has " + to_string(n) + " stored coefficients" +
+                                     (r2 ? " on axis " + to_string(c.var) : std::string()) + " (the order must satisfy 0 <= k < " + to_string(n) + ")");
+        const size_t w0 = rows ? c.x.len0 - k : c.x.len0, w1 = rows ? c.x.len1 : c.x.len1 - k;
+        if (c.r.len0 != w0 || c.r.len1 != w1)
+            throw std::runtime_error(f + ": the result has " + (r2 ? to_string(c.r.len0) + " x " : std::string()) + to_string(c.r.len1) + " coefficients; with k = " +
+                                     to_string(k) + " it has " + (r2 ? to_string(w0) + " x " : std::string()) + to_string(w1) + " (x's, less k on the axis)");
+        return;
+    }
+    if (empty(c.x) || (binary && empty(c.y))) throw std::runtime_error(f + ": an operand has no coefficients");
+    auto fits = [&](const SeriesView& s, const char* slen, const char* swho) {
+        if (s.len0 <= L.len0 && s.len1 <= L.len1) return;
+        const char* why = &s == &c.r ? "the result of a transposed operation is its short side" : "an operand is longer than the truncation order";
+        if (r2) throw std::runtime_error(f + ": " + swho + " has " + dims(s, " x ") + " coefficients, " + Lwho + " " + dims(L, " x ") + " (" + why + ")");
+        throw std::runtime_error(f + ": " + slen + " = " + to_string(s.len1) + " > " + Llen + " = " + to_string(L.len1) + " (" + why + ")");
+    };
+    if (transposed) fits(c.r, len.r, who.r);
+    else fits(c.x, len.x, who.x);
+    if (binary) fits(c.y, len.y, who.y);
+}
+
+// Judges one call and plans its batch.  The order of the checks: the shapes; nbatch and a null batch; an empty batch (returns
+// false: nothing to do, no stride is looked at); 2^31 items; negative strides; zero or overlapping result strides; check_ptr(p,
+// what) on x, y and the result (the one step that needs the device: the caller's); the overlap proof; the collapse.  Throws
+// std::runtime_error with the message of the refusal.
+template <class CheckPtr>
+static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& check_ptr) {
+    const std::string f(c.fn);
+    const int op = c.op, w = c.w;
+    const bool comp = op == SERIES_COMPOSE, corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
+    const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed;
+    const size_t* batch = c.batch;
+    const size_t nbatch = c.nbatch;
+    series_shapes(c);
+    if (nbatch > 32) throw std::runtime_error(f + ": more than 32 batch axes");
+    if (nbatch && !batch) throw std::runtime_error(f + ": the batch shape is a null pointer");
+    size_t items = 1;
+    for (size_t i = 0; i < nbatch; ++i) {
+        if (batch[i] == 0) return false;  // an empty batch: nothing to do
+        items *= batch[i];
+        if (items >= ((size_t)1 << 31)) throw std::runtime_error(f + ": more than 2^31 - 1 series in one call");
+    }
+    const SeriesOperand ax = series_arg(c, comp ? "f" : (corr ? "g" : (adj ? "gh" : "x")), c.x);
+    const SeriesOperand ay = series_arg(c, comp || adj ? "g" : (binary ? "y" : "the seeds"), c.y);
+    const SeriesOperand ar = series_arg(c, "the result", c.r);
+    // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
+    {
+        struct Ax {
+            size_t ext, st;
+        } axes[35];
+        int k = 0;
+        if (w == 2) {  // the two planes are one more axis of the result
+            if (ar.plane == 0) throw std::runtime_error(f + ": the result has a zero plane stride: its lower and upper bounds overlap");
+            axes[k++] = Ax{2, ar.plane};
+        }
+        for (size_t i = 0; i < nbatch; ++i) {
+            if (batch[i] <= 1) continue;
+            if (ar.st[i] == 0) throw std::runtime_error(f + ": the result has a zero stride (batch axis " + std::to_string(i) + "): its series overlap");
+            axes[k++] = Ax{batch[i], ar.st[i]};
+        }
+        if (ar.rows > 1) {  // rank 2: the rows of an item are one more axis of the result
+            if (ar.rst == 0) throw std::runtime_error(f + ": the result has a zero row stride: the rows of an item overlap");
+            axes[k++] = Ax{ar.rows, ar.rst};
+        }
+        if (ar.len > 1) axes[k++] = Ax{ar.len, 1};
+        std::sort(axes, axes + k, [](const Ax& u, const Ax& v) { return u.st < v.st; });
+        for (int i = 1; i < k; ++i)
+            if (axes[i].st / axes[i - 1].ext < axes[i - 1].st)
+                throw std::runtime_error(f + ": the result's series overlap each other (its strides do not separate the rows)");
+    }
+    check_ptr(ax.p, ax.what);
+    if (binary || ay.p) check_ptr(ay.p, ay.what);
+    check_ptr(ar.p, ar.what);
+    // the result may be an input itself (the same view: every row is read before it is written); any other overlap is refused.
+    // Judged by address ranges, so two interleaved views of one buffer count as overlapping.
+    bool inplace = false;
+    auto overlap = [&](const SeriesOperand& a, bool same_ok) {
+        if (a.p + a.span <= ar.p || ar.p + ar.span <= a.p) return;
+        if (same_ok && series_same_view(a, ar, batch, nbatch)) {
+            inplace = true;
+            return;
+        }
+        throw std::runtime_error(f + ": the result partially overlaps " + a.what + " (it may alias an operand only as the same view)");
+    };
+    overlap(ax, true);
+    if (transposed) overlap(ay, false);  // corr's result may be g itself, compose_adj's gh; neither may be the second operand
+    else if (binary) overlap(ay, true);
+    else if (ay.p) overlap(ay, false);
+    // collapse the batch: unit axes go, axes contiguous with their inner neighbour on every operand merge
+    SeriesBatch& g = out.g;
+    g.nd = 0;
+    g.items = (unsigned)items;
+    g.inplace = inplace;
+    const bool seeds = !binary && ay.p;
+    for (size_t i = 0; i < nbatch; ++i) {
+        if (batch[i] == 1) continue;
+        const size_t e = batch[i], sx = ax.st[i], sy = binary ? ay.st[i] : 0, ss = seeds ? ay.st[i] : 0, sr = ar.st[i];
+        if (g.nd > 0) {
+            const int p = g.nd - 1;
+            // (merged extents stay below 2^31: items does)
+            if (g.xs[p] == sx * e && g.ys[p] == sy * e && g.ss[p] == ss * e && g.rs[p] == sr * e) {
+                g.ext[p] *= (unsigned)e;
+                g.xs[p] = sx;
+                g.ys[p] = sy;
+                g.ss[p] = ss;
+                g.rs[p] = sr;
+                continue;
+            }
+        }
+        // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow at rank 2 the row axis too)
+        const int most = IMAXD - w - (c.rank2 && op == SERIES_POW ? 1 : 0);
+        if (g.nd == most) throw std::runtime_error(f + ": the batch has more than " + std::to_string(most) + " non-contiguous axes");
+        g.ext[g.nd] = (unsigned)e;
+        g.xs[g.nd] = sx;
+        g.ys[g.nd] = sy;
+        g.ss[g.nd] = ss;
+        g.rs[g.nd] = sr;
+        ++g.nd;
+    }
+    out.pl.w = w;
+    out.pl.x = ax.plane;
+    out.pl.y = binary ? ay.plane : 0;
+    out.pl.s = seeds ? ay.plane : 0;
+    out.pl.r = ar.plane;
+    Series2Dims& d = out.d;
+    d.nx0 = (unsigned)c.x.len0, d.nx1 = (unsigned)c.x.len1, d.ny0 = (unsigned)c.y.len0, d.ny1 = (unsigned)c.y.len1;
+    d.n0 = (unsigned)c.r.len0, d.n1 = (unsigned)c.r.len1;
+    d.xr = ax.rst, d.yr = ay.rst, d.rr = ar.rst;
+    return true;
+}
+
+}  // namespace gft

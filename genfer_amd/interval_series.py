@@ -19,48 +19,51 @@ the operators' shortcuts.  The call is ordered on torch's current stream and doe
 """
 from __future__ import annotations
 
-from .series import FORMS, _exponent, _observe, _run, last_form, set_form  # noqa: F401  (one library, one form option, one last form)
+from ._series_call import Call
+from .series import FORMS, _exponent, _run, last_form, set_form  # noqa: F401  (one library, one form option, one last form)
 
 MAX_N = 2048  # gft_series.hpp SERIES_MAX_N_IV
 
 
-def _iv(what, name, x, second, n, out, second_is_seed, **kw):
-    return _run(f"interval_series.{what}", f"gfti_series_{name}", x, second, n, out, second_is_seed, planes=1, max_n=MAX_N, **kw)
+# The arithmetic ops do not refuse an operand that requires grad (they run on its values); the observation ops, like every op of
+# interval_series2, do.  Kept as it is.
+_CALL = Call("interval_series", 1, 1, MAX_N, raw=False)
+_OBSERVE = _CALL._replace(raw=True)
 
 
 def mul(x, y, n=None, out=None):
     """``z[b] = x[b] * y[b]`` truncated at order ``n`` (default ``max(nx, ny)``): the general product ``mul_1d`` over intervals."""
-    return _iv("mul", "mul", x, y, n, out, False)
+    return _run(_CALL, "mul", x, y, n, out)
 
 
 def div(x, y, n=None, out=None):
     """``r[b] = x[b] / y[b]`` to order ``n`` (default ``max(nx, ny)``): the general division recurrence over intervals."""
-    return _iv("div", "div", x, y, n, out, False)
+    return _run(_CALL, "div", x, y, n, out)
 
 
 def exp(x, n=None, seed=None, out=None):
     """``exp(x[b])`` to order ``n`` (default ``nx``).  ``seed``: the interval ``exp`` of coefficient 0 per item, ``[2, B...]``; with
     the host libm's values widened as the reference widens them the result carries its bits.  ``None``: formed on the device."""
-    return _iv("exp", "exp", x, seed, n, out, True)
+    return _run(_CALL, "exp", x, seed, n, out)
 
 
 def log(x, n=None, seed=None, out=None):
     """``log(x[b])`` to order ``n`` (default ``nx``).  ``seed``: the interval ``ln`` of coefficient 0 per item, ``[2, B...]``;
     ``None``: formed on the device (only coefficient 0 depends on it)."""
-    return _iv("log", "log", x, seed, n, out, True)
+    return _run(_CALL, "log", x, seed, n, out)
 
 
 def compose(f, g, n=None, out=None):
     """``f[b](g[b])`` truncated at order ``n`` (default ``max(nf, ng)``): Horner over the coefficients of ``f`` with the general
     interval product at every step, as ``series.compose``.  About ``nf * n**2 / 2`` interval multiply-adds per item, on one
     workgroup at most."""
-    return _iv("compose", "compose", f, g, n, out, False, names=("f", "g"))
+    return _run(_CALL, "compose", f, g, n, out)
 
 
 def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     """``x[b] ** e`` truncated at order ``n`` (default ``nx``) for an integer ``0 <= e < 2**32``: the reference's
     square-and-multiply over ``mul`` at compact lengths.  ``e = 0`` gives ``[[1, 1], [0, 0], ...]``."""
-    return _iv("pow", "pow", x, None, n, out, True, e=_exponent("interval_series.pow", e, div="interval_series.div"))
+    return _run(_CALL, "pow", x, None, n, out, scalar=_exponent("interval_series.pow", e, div="interval_series.div"))
 
 
 # ---- the observation ops: series.derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one over intervals --------
@@ -70,20 +73,20 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
 def derivative(x, k, out=None):
     """``out[:, b, j] = x[:, b, k + j] * ff_j`` with the reference's interval factors ``ff_j`` (``series.derivative``'s recurrence in
     interval arithmetic); ``[2, B..., nx - k]``."""
-    return _observe("interval_series.derivative", "derivative", x, k, out, planes=1, limit=MAX_N, raw=True)
+    return _run(_OBSERVE, "derivative", x, out=out, scalar=k)
 
 
 def taylor_expansion_of_coeff(x, k, out=None):
     """Coefficient ``k`` untouched, coefficient ``k + j`` times the interval factor ``f_j`` for ``j >= 1``."""
-    return _observe("interval_series.taylor_expansion_of_coeff", "taylor_expansion_of_coeff", x, k, out, planes=1, limit=MAX_N, raw=True)
+    return _run(_OBSERVE, "taylor_expansion_of_coeff", x, out=out, scalar=k)
 
 
 def shift_down(x, k, out=None):
     """``out[:, b, 0] = x[:, b, k] + S`` with ``S`` the ascending interval sum of coefficients ``0 .. k-1`` from ``[0, 0]`` (all of them
     when ``nx == k + 1``), the others copies."""
-    return _observe("interval_series.shift_down", "shift_down", x, k, out, planes=1, limit=MAX_N, raw=True)
+    return _run(_OBSERVE, "shift_down", x, out=out, scalar=k)
 
 
 def evaluate_all_one(x, out=None):
     """The ascending interval sum of every item's coefficients from ``[0, 0]``; ``[2, B...]``."""
-    return _observe("interval_series.evaluate_all_one", "evaluate_all_one", x, None, out, planes=1, limit=MAX_N, raw=True)
+    return _run(_OBSERVE, "evaluate_all_one", x, out=out)

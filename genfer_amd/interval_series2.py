@@ -22,53 +22,50 @@ No autograd: an operand that requires grad is refused while grad mode is on, as 
 """
 from __future__ import annotations
 
-from .series import _exponent, _observe
-from .series2 import _run
-from .taylor import TaylorError
+from ._series_call import Call
+from .series import _exponent
+from .series2 import _run, _var
 
 MAX_ELEMS = 2048  # gft_series.hpp SERIES2_MAX_ELEMS_IV: n0 * n1 of the result
 
 
-def _iv(what, x, second, n, out, second_is_seed, **kw):
-    return _run(f"interval_series2.{what}", f"gfti_series2_{what}", x, second, n, out, second_is_seed, planes=1, max_elems=MAX_ELEMS, **kw)
+_CALL = Call("interval_series2", 2, 1, MAX_ELEMS, raw=True)
 
 
 def mul(x, y, n=None, out=None):
     """``z[b] = x[b] * y[b]`` truncated at orders ``n = (n0, n1)`` (default: the larger stored length on each axis): the general
     product over intervals."""
-    return _iv("mul", x, y, n, out, False)
+    return _run(_CALL, "mul", x, y, n, out)
 
 
 def div(x, y, n=None, out=None):
     """``r[b] = x[b] / y[b]`` to orders ``n = (n0, n1)``: the general division recurrence over the rows, over intervals."""
-    return _iv("div", x, y, n, out, False)
+    return _run(_CALL, "div", x, y, n, out)
 
 
 def exp(x, n=None, seed=None, out=None):
     """``exp(x[b])`` to orders ``n``.  ``seed``: the interval ``exp`` of coefficient ``[0, 0]`` per item, ``[2, B...]``; with the host
     libm's values widened as the reference widens them the result carries its bits.  ``None``: formed on the device."""
-    return _iv("exp", x, seed, n, out, True)
+    return _run(_CALL, "exp", x, seed, n, out)
 
 
 def log(x, n=None, seed=None, out=None):
     """``log(x[b])`` to orders ``n``.  ``seed``: the interval ``ln`` of coefficient ``[0, 0]`` per item, ``[2, B...]``; ``None``:
     formed on the device (only coefficient ``[0, 0]`` depends on it)."""
-    return _iv("log", x, seed, n, out, True)
+    return _run(_CALL, "log", x, seed, n, out)
 
 
 def compose(f, g, var=0, n=None, out=None):
     """``f[b]`` with ``g[b]`` substituted for variable ``var`` (0: axis -2, 1: axis -1) of ``f``, truncated at ``n = (n0, n1)``:
     ``series2.compose``'s Horner loop with the general interval product at every step, the whole loop in one launch."""
-    if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
-        raise TaylorError(f"interval_series2.compose: var = {var!r}; the variable of f that g replaces is 0 or 1")
-    return _iv("compose", f, g, n, out, False, names=("f", "g"), scalar=var)
+    return _run(_CALL, "compose", f, g, n, out, var=_var("interval_series2.compose", var))
 
 
 def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     """``x[b] ** e`` truncated at ``n = (n0, n1)`` (default: the stored shape) for an integer ``0 <= e < 2**32``: the reference's
     square-and-multiply over ``mul`` at compact shapes.  ``e = 0`` gives the unit item: ``[1, 1]`` at ``[0, 0]``, ``[0, 0]`` elsewhere."""
     e = _exponent("interval_series2.pow", e, div="interval_series2.div")
-    return _iv("pow", x, None, n, out, True, scalar=e)
+    return _run(_CALL, "pow", x, None, n, out, scalar=e)
 
 
 # ---- the observation ops: series2's over intervals ----------------------------------------------------------------------------
@@ -76,20 +73,19 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
 
 def derivative(x, var, k, out=None):
     """``series2.derivative`` with the reference's interval factors; the axis of ``var`` is ``k`` shorter."""
-    return _observe("interval_series2.derivative", "derivative", x, k, out, rank=2, var=var, planes=1, limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "derivative", x, out=out, scalar=k, var=var)
 
 
 def taylor_expansion_of_coeff(x, var, k, out=None):
     """``series2.taylor_expansion_of_coeff`` over intervals: slice ``k`` untouched, slice ``k + j`` times the interval ``f_j``."""
-    return _observe("interval_series2.taylor_expansion_of_coeff", "taylor_expansion_of_coeff", x, k, out, rank=2, var=var, planes=1,
-                    limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "taylor_expansion_of_coeff", x, out=out, scalar=k, var=var)
 
 
 def shift_down(x, var, k, out=None):
     """``series2.shift_down`` over intervals: the same orders of summation, every step the reference's interval addition."""
-    return _observe("interval_series2.shift_down", "shift_down", x, k, out, rank=2, var=var, planes=1, limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "shift_down", x, out=out, scalar=k, var=var)
 
 
 def evaluate_all_one(x, out=None):
     """The row-major interval sum of every item from ``[0, 0]``; ``[2, B...]``."""
-    return _observe("interval_series2.evaluate_all_one", "evaluate_all_one", x, None, out, rank=2, planes=1, limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "evaluate_all_one", x, out=out)

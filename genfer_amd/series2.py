@@ -25,59 +25,14 @@ Horner loop).  float64 only; the ``Interval<F64>`` twins on ``[2, B..., n0, n1]`
 """
 from __future__ import annotations
 
-import ctypes as C
-
-from .series import _check, _exponent, _i64, _observe, _placed
+from ._series_call import Call, _lib  # noqa: F401  (one declared library for the four modules)
+from ._series_call import run as _run
+from .series import _exponent
 from .taylor import TaylorError
 
 MAX_ELEMS = 4096  # gft_series.hpp SERIES2_MAX_ELEMS: n0 * n1 of the result in this version
 
-_declared = None
-
-
-def _lib():
-    global _declared
-    if _declared is None:
-        from . import lib
-
-        L = lib()
-        i64, sz, vp, i, s = C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.c_void_p, C.c_int64, C.c_size_t
-        for pre in ("gft_series2_", "gfti_series2_"):  # the interval twins (interval_series2.py) take the same argument lists
-            for name in ("mul", "div"):
-                f = getattr(L, pre + name)
-                f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, vp, i64, i, s, s, sz, s, vp]
-            for name in ("exp", "log"):
-                f = getattr(L, pre + name)
-                f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, vp, i64, i, s, s, sz, s, vp]
-            f = getattr(L, pre + "compose")
-            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
-            f = getattr(L, pre + "pow")
-            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, C.c_uint32, vp, i64, i, s, s, sz, s, vp]
-            for name in ("derivative", "taylor_expansion_of_coeff", "shift_down"):  # the observation ops: x, var, k, the result
-                f = getattr(L, pre + name)
-                f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, C.c_int, s, vp, i64, i, s, s, sz, s, vp]
-            f = getattr(L, pre + "evaluate_all_one")
-            f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, sz, s, vp]
-        # the transposed operations (f64 only): mul's and compose's argument lists
-        L.gft_series2_corr.restype, L.gft_series2_corr.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, vp, i64, i, s, s, sz, s, vp]
-        f = L.gft_series2_compose_adj
-        f.restype, f.argtypes = C.c_int, [vp, i64, i, s, s, vp, i64, i, s, s, C.c_int, vp, i64, i, s, s, sz, s, vp]
-        L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
-        _declared = L
-    return _declared
-
-
-def _axes(t, what, planes=0):
-    """the two series axes of an operand or of ``out`` (type and dtype are judged by series._check)"""
-    if t.dim() < 2 + planes:
-        if planes:
-            raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate interval series needs at least 3 (the first holds the two "
-                              "planes, the last two are the coefficient array)")
-        raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate series needs at least 2 (the last two are the coefficient array)")
-    if t.shape[-1] == 0 or t.shape[-2] == 0:
-        raise TaylorError(f"{what}: a series axis is empty (the last two axes are {tuple(t.shape[-2:])})")
-    if t.shape[-1] > 1 and t.stride(-1) != 1:
-        raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
+_CALL = Call("series2", 2, 0, MAX_ELEMS, raw=True)  # rank 2, one plane; the differentiable twin is series2_grad
 
 
 def _orders(what, n, *shapes, max_elems=None):
@@ -123,111 +78,26 @@ def _orders_short(what, n, g, y, names):
     return n0, n1
 
 
-def _run(what, fn_name, x, second, n, out, second_is_seed, names=("x", "y"), scalar=None, planes=0, max_elems=None, short=False):
-    """``scalar``: compose's ``var`` (passed behind the second operand) or pow's ``e`` (in the place of the seeds).  planes = 1:
-    the tensors are interval tensors [2, B..., n0, n1] (seeds [2, B...]); the leading axis travels as the first entry of every
-    batch-stride array, which is where the gfti_series2_* entry points expect it.  short: a transposed operation (corr,
-    _compose_adj), whose result is no larger than its first operand; names[2] names it."""
-    import torch
-
-    # everything that needs no device first: types, shapes, strides, orders, out, grad -- then the placement
-    xname = names[0]
-    _check(torch, x, f"{what}: {xname}", series_axis=False, planes=planes, placement=False)
-    _axes(x, f"{what}: {xname}", planes)
-    sname = "seed" if second_is_seed else names[1]
-    if second is not None:
-        _check(torch, second, f"{what}: {sname}", series_axis=False, planes=planes, placement=False)
-        if not second_is_seed:
-            _axes(second, f"{what}: {sname}", planes)
-    if out is not None:
-        _check(torch, out, f"{what}: out", series_axis=False, planes=planes, placement=False)
-        _axes(out, f"{what}: out", planes)
-    operands = [x] if second_is_seed or second is None else [x, second]
-    if short:
-        n0, n1 = _orders_short(what, n, *(tuple(t.shape[-2:]) for t in operands), names)
-    else:
-        n0, n1 = _orders(what, n, *(tuple(t.shape[-2:]) for t in operands), max_elems=max_elems)
-    lead = (2,) * planes
-    shapes = [x.shape[planes:-2]]
-    if second is not None:
-        shapes.append(second.shape[planes:] if second_is_seed else second.shape[planes:-2])
-    if out is not None:
-        if tuple(out.shape[-2:]) != (n0, n1):
-            raise TaylorError(f"{what}: out has {tuple(out.shape[-2:])} coefficients per item, the result has n = ({n0}, {n1})")
-        batch = tuple(out.shape[planes:-2])
-        if tuple(torch.broadcast_shapes(*shapes, batch)) != batch:
-            raise TaylorError(f"{what}: out has batch shape {batch}; the operands broadcast to {tuple(torch.broadcast_shapes(*shapes))}")
-    else:
-        batch = tuple(torch.broadcast_shapes(*shapes))
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, second)):
-        mod = what.split(".")[0]
-        raise TaylorError(f"{what}: an operand requires grad, and this version of {mod} has no autograd; pass {xname}.detach() or call under "
-                          "torch.no_grad() (nothing is detached silently)")
-    _placed(x, f"{what}: {xname}")
-    if second is not None:
-        _placed(second, f"{what}: {sname}")
-    if out is not None:
-        _placed(out, f"{what}: out")
-    for t in (second, out):
-        if t is not None and t.device != x.device:
-            raise TaylorError(f"{what}: the tensors are on different devices ({x.device}, {t.device})")
-    if out is None:
-        out = torch.empty(lead + batch + (n0, n1), dtype=torch.float64, device=x.device)
-    nb = len(batch)
-    if planes:  # torch aligns shapes from the right: the plane axis stays first, missing batch axes go behind it (a view)
-        lift = lambda t, rank: t if t.dim() >= rank else t[(slice(None),) + (None,) * (rank - t.dim())]  # noqa: E731
-        x = lift(x, nb + 3)
-        if second is not None:
-            second = lift(second, nb + (1 if second_is_seed else 3))
-    L = _lib()
-    dev = int(L.gft_device())
-    if dev >= 0 and x.device.index != dev:
-        raise TaylorError(f"{what}: the tensors are on {x.device}, but the library runs on cuda:{dev}")
-    ns = nb + planes  # entries of a batch-stride array
-    xe = x.expand(lead + batch + tuple(x.shape[-2:]))
-    bsz = (C.c_size_t * max(nb, 1))(*batch)
-    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    fn = getattr(L, fn_name)
-    xa = (C.c_void_p(xe.data_ptr()), _i64(xe.stride()[:ns]), xe.stride(-2), xe.shape[-2], xe.shape[-1])
-    ra = (C.c_void_p(out.data_ptr()), _i64(out.stride()[:ns]), out.stride(-2), n0, n1, bsz, nb, stream)
-    if second_is_seed:
-        if scalar is not None:
-            sa = (C.c_uint32(scalar),)
-        elif second is None:
-            sa = (None, None)
-        else:
-            se = second.expand(lead + batch)
-            sa = (C.c_void_p(se.data_ptr()), _i64(se.stride()))
-        rc = fn(*xa, *sa, *ra)
-    else:
-        ye = second.expand(lead + batch + tuple(second.shape[-2:]))
-        va = () if scalar is None else (C.c_int(scalar),)
-        rc = fn(*xa, C.c_void_p(ye.data_ptr()), _i64(ye.stride()[:ns]), ye.stride(-2), ye.shape[-2], ye.shape[-1], *va, *ra)
-    if rc != 0:
-        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
-    return out
-
-
 def mul(x, y, n=None, out=None):
     """``z[b] = x[b] * y[b]`` truncated at orders ``n = (n0, n1)`` (default: the larger stored length on each axis)."""
-    return _run("series2.mul", "gft_series2_mul", x, y, n, out, False)
+    return _run(_CALL, "mul", x, y, n, out)
 
 
 def div(x, y, n=None, out=None):
     """``r[b] = x[b] / y[b]`` to orders ``n = (n0, n1)``: the general division recurrence over the rows."""
-    return _run("series2.div", "gft_series2_div", x, y, n, out, False)
+    return _run(_CALL, "div", x, y, n, out)
 
 
 def exp(x, n=None, seed=None, out=None):
     """``exp(x[b])`` to orders ``n``.  ``seed``: ``exp(x[b, 0, 0])`` per item (a tensor of the batch shape); with the host libm's
     values the result carries the reference's bits.  ``None``: formed on the device (a few ulps from libm)."""
-    return _run("series2.exp", "gft_series2_exp", x, seed, n, out, True)
+    return _run(_CALL, "exp", x, seed, n, out)
 
 
 def log(x, n=None, seed=None, out=None):
     """``log(x[b])`` to orders ``n``.  ``seed``: ``ln(x[b, 0, 0])`` per item; ``None``: formed on the device (only coefficient
     ``[0, 0]`` depends on it)."""
-    return _run("series2.log", "gft_series2_log", x, seed, n, out, True)
+    return _run(_CALL, "log", x, seed, n, out)
 
 
 def compose(f, g, var=0, n=None, out=None):
@@ -236,14 +106,13 @@ def compose(f, g, var=0, n=None, out=None):
     of ``f`` along the substituted axis, ``res = res * g + slice`` with the general product at the compact shape of every step,
     from ``res = 0.0 + the last slice``; the result stays in LDS across the steps of the one launch.  Cost: about
     ``nslices * (n0*n1)**2 / 4`` multiply-adds per item, all on one workgroup; no cap is imposed."""
-    if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
-        raise TaylorError(f"series2.compose: var = {var!r}; the variable of f that g replaces is 0 or 1")
-    return _run("series2.compose", "gft_series2_compose", f, g, n, out, False, names=("f", "g"), scalar=var)
+    return _run(_CALL, "compose", f, g, n, out, var=_var("series2.compose", var))
 
 
-def _var(what, var):
+def _var(what, var, role="the variable of f that g replaces is 0 or 1"):
+    """the one check of a variable's index, for every module (the observation ops state their own role)"""
     if isinstance(var, bool) or not isinstance(var, int) or var not in (0, 1):
-        raise TaylorError(f"{what}: var = {var!r}; the variable of f that g replaces is 0 or 1")
+        raise TaylorError(f"{what}: var = {var!r}; {role}")
     return var
 
 
@@ -257,7 +126,7 @@ def corr(g, y, m=None, out=None):
     with ``k0`` descending from ``min(g0 - 1, i0 + ny0 - 1)`` to ``i0`` and ``k1`` from ``min(g1 - 1, i1 + ny1 - 1)`` to ``i1``,
     multiply and add rounded separately, only stored coefficients entering a sum: bit for bit ``mul(flip(g), y, n=g.shape)`` at
     index ``[g0 - 1 - i0, g1 - 1 - i1]``, ``flip`` reversing both series axes.  ``out`` may be ``g`` itself, never ``y``."""
-    return _run("series2.corr", "gft_series2_corr", g, y, m, out, False, names=("g", "y", "m"), short=True)
+    return _run(_CALL, "corr", g, y, m, out)
 
 
 def _compose_adj(gh, g, var, nf, out=None):
@@ -265,39 +134,38 @@ def _compose_adj(gh, g, var, nf, out=None):
     gradient ``gh`` of the composition (shape ``n``).  With ``S`` slices of ``f`` of ``len`` coefficients along axis ``var`` and
     ``L_i = min(base + (S - 1 - i) * (ng - 1), n)`` per axis, ``base = (1, len)`` / ``(len, 1)``: ``a = gh[:L_0]``; slice ``i`` of the
     result is the first ``len`` entries of row 0 (var 0) / column 0 (var 1) of ``a``; then ``a = corr(a, g, L_{i+1})`` -- in one launch."""
-    _var("series2._compose_adj", var)
-    return _run("series2._compose_adj", "gft_series2_compose_adj", gh, g, nf, out, False, names=("gh", "g", "nf"), scalar=var, short=True)
+    return _run(_CALL, "compose_adj", gh, g, nf, out, var=_var("series2._compose_adj", var))
 
 
 def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     """``x[b] ** e`` truncated at ``n = (n0, n1)`` (default: the stored shape) for an integer ``0 <= e < 2**32``: the reference's
     square-and-multiply over ``mul`` at compact shapes.  ``e = 0`` gives the unit item ``[[1, 0, ...], [0, ...], ...]``."""
     e = _exponent("series2.pow", e, div="series2.div")
-    return _run("series2.pow", "gft_series2_pow", x, None, n, out, True, scalar=e)
+    return _run(_CALL, "pow", x, None, n, out, scalar=e)
 
 
-# ---- the observation ops (series._observe at rank 2; include/gftaylor.h states the loops) -------------------------------------
+# ---- the observation ops (include/gftaylor.h states the loops) ----------------------------------------------------------------
 
 
 def derivative(x, var, k, out=None):
     """The ``k``-th derivative in variable ``var`` (0: axis -2, 1: axis -1): slice ``j`` of the result is slice ``k + j`` of ``x`` times
     the reference's factor ``ff_j`` (``series.derivative``), one rounding per coefficient; the axis is ``k`` shorter."""
-    return _observe("series2.derivative", "derivative", x, k, out, rank=2, var=var, limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "derivative", x, out=out, scalar=k, var=var)
 
 
 def taylor_expansion_of_coeff(x, var, k, out=None):
     """The expansion of the coefficient of ``var**k``: slice 0 is slice ``k`` of ``x`` untouched, slice ``j >= 1`` is slice ``k + j``
     times ``f_j`` (``series.taylor_expansion_of_coeff``)."""
-    return _observe("series2.taylor_expansion_of_coeff", "taylor_expansion_of_coeff", x, k, out, rank=2, var=var, limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "taylor_expansion_of_coeff", x, out=out, scalar=k, var=var)
 
 
 def shift_down(x, var, k, out=None):
     """Variable ``var`` moved down by ``k``: slice 0 of the result is slice ``k`` of ``x`` plus the ordered sum of slices ``0 .. k-1``
     (all slices when the axis has ``k + 1``), the others are copies.  The order is ndarray's ``sum_axis``: along axis -2 ascending over
     the rows from 0.0 per column; along axis -1, and along axis -2 of a one-column item, the 8-way unrolled fold."""
-    return _observe("series2.shift_down", "shift_down", x, k, out, rank=2, var=var, limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "shift_down", x, out=out, scalar=k, var=var)
 
 
 def evaluate_all_one(x, out=None):
     """Every item at ``(1, 1)``: ``0.0 + x[b, 0, 0] + x[b, 0, 1] + ...`` in row-major order, one chain; the batch shape."""
-    return _observe("series2.evaluate_all_one", "evaluate_all_one", x, None, out, rank=2, limit=MAX_ELEMS, raw=True)
+    return _run(_CALL, "evaluate_all_one", x, out=out)

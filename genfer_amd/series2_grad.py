@@ -30,142 +30,14 @@ carries a gradient (it is ``exp(x[..., 0, 0])`` / ``ln(x[..., 0, 0])`` by contra
 from __future__ import annotations
 
 from . import series2
-from . import series as _series
 from .series import _exponent, _tracked
-
-_functions = None
 
 
 def _autograd():
-    """The torch.autograd.Function of every operation (built on first use: this module imports without torch)."""
-    global _functions
-    if _functions is not None:
-        return _functions
-    import types
+    """The torch.autograd.Function of every operation (one set for both ranks: _series_autograd.py)."""
+    from ._series_autograd import functions
 
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    run = series2._run
-
-    def unit_stride(g):  # z.sum().backward() hands over an expanded scalar: stride 0 on the series axes
-        return g if g.shape[-1] == 1 or g.stride(-1) == 1 else g.contiguous()
-
-    def one(t):
-        return torch.ones((1, 1), dtype=torch.float64, device=t.device)
-
-    class Mul(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x, y, n):
-            x, y = x.detach(), y.detach()
-            ctx.save_for_backward(x, y)
-            return run("series2_grad.mul", "gft_series2_mul", x, y, n, None, False)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gz):
-            x, y = ctx.saved_tensors
-            gz = unit_stride(gz)
-            gx = series2.corr(gz, y, x.shape[-2:]).sum_to_size(x.shape) if ctx.needs_input_grad[0] else None
-            gy = series2.corr(gz, x, y.shape[-2:]).sum_to_size(y.shape) if ctx.needs_input_grad[1] else None
-            return gx, gy, None
-
-    class Div(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x, y, n):
-            x, y = x.detach(), y.detach()
-            r = run("series2_grad.div", "gft_series2_div", x, y, n, None, False)
-            ctx.save_for_backward(r, y)
-            ctx.shapes = (x.shape, y.shape)
-            return r
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gr):
-            r, y = ctx.saved_tensors
-            xs, ys = ctx.shapes
-            n = tuple(r.shape[-2:])
-            u = series2.corr(unit_stride(gr), series2.div(one(y), y, n), n)  # the gradient of the dividend at the full shape
-            gx = u[..., :xs[-2], :xs[-1]].sum_to_size(xs) if ctx.needs_input_grad[0] else None
-            gy = (-series2.corr(u, r, ys[-2:])).sum_to_size(ys) if ctx.needs_input_grad[1] else None
-            return gx, gy, None
-
-    class Exp(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x, n, seed):
-            x = x.detach()
-            e = run("series2_grad.exp", "gft_series2_exp", x, seed, n, None, True)
-            ctx.save_for_backward(e)
-            ctx.shape = x.shape
-            return e
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, ge):
-            (e,) = ctx.saved_tensors
-            return series2.corr(unit_stride(ge), e, ctx.shape[-2:]).sum_to_size(ctx.shape), None, None
-
-    class Log(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x, n, seed):
-            x = x.detach()
-            ctx.save_for_backward(x)
-            return run("series2_grad.log", "gft_series2_log", x, seed, n, None, True)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gl):
-            (x,) = ctx.saved_tensors
-            n = tuple(gl.shape[-2:])
-            return series2.corr(unit_stride(gl), series2.div(one(x), x, n), x.shape[-2:]).sum_to_size(x.shape), None, None
-
-    class Pow(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x, e, n):
-            x = x.detach()
-            ctx.save_for_backward(x)
-            ctx.e = e
-            return run("series2_grad.pow", "gft_series2_pow", x, None, n, None, True, scalar=e)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gp):
-            (x,) = ctx.saved_tensors
-            if ctx.e == 0:
-                return torch.zeros_like(x), None, None
-            n = tuple(gp.shape[-2:])
-            return (ctx.e * series2.corr(unit_stride(gp), series2.pow(x, ctx.e - 1, n), x.shape[-2:])).sum_to_size(x.shape), None, None
-
-    class Compose(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, f, g, var, n):
-            f, g = f.detach(), g.detach()
-            ctx.save_for_backward(f, g)
-            ctx.var = var
-            return run("series2_grad.compose", "gft_series2_compose", f, g, n, None, False, names=("f", "g"), scalar=var)
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gh):
-            f, g = ctx.saved_tensors
-            var = ctx.var
-            gh = unit_stride(gh)
-            n = tuple(gh.shape[-2:])
-            gf = gg = None
-            if ctx.needs_input_grad[0]:
-                gf = series2._compose_adj(gh, g, var, f.shape[-2:]).sum_to_size(f.shape)
-            if ctx.needs_input_grad[1]:  # h = f(g): dh = (df / dvar)(g) * dg
-                slices = f.shape[var - 2]
-                if slices > 1:
-                    i = torch.arange(1, slices, dtype=torch.float64, device=f.device)
-                    fp = f[..., 1:, :] * i[:, None] if var == 0 else f[..., :, 1:] * i
-                else:
-                    fp = torch.zeros_like(f)
-                gg = series2.corr(gh, series2.compose(fp, g, var, n), g.shape[-2:]).sum_to_size(g.shape)
-            return gf, gg, None, None
-
-    _functions = types.SimpleNamespace(Mul=Mul, Div=Div, Exp=Exp, Log=Log, Pow=Pow, Compose=Compose)
-    return _functions
+    return functions("series2_grad", 2)
 
 
 def mul(x, y, n=None, out=None):
@@ -210,39 +82,35 @@ def pow(x, e, n=None, out=None):  # noqa: A001 (the reference's name)
     return series2.pow(x, e, n, out)
 
 
-# ---- the observation ops: linear maps, their adjoints torch indexing around series2's own calls (series._autograd().observe) ---
+# ---- the observation ops: linear maps, their adjoints torch indexing around series2's own calls ------------------------------
 #     derivative, taylor_expansion_of_coeff   gx[k + j] = gz[j] * factor_j along axis var (the factors: the op of ones), gx[< k] = +0.0
 #     shift_down                              gx[i] = gz[0] for i <= k, gx[k + j] = gz[j] for j >= 1, along axis var
 #     evaluate_all_one                        gz broadcast over the item
 
 
-def _observers():
-    return _series._autograd().observe("series2_grad", 2)
-
-
 def derivative(x, var, k, out=None):
     """``series2.derivative``, differentiable in ``x``."""
     if _tracked("series2_grad.derivative", (x,), out):
-        return _observers().Derivative.apply(x, var, k)
+        return _autograd().Derivative.apply(x, var, k)
     return series2.derivative(x, var, k, out)
 
 
 def taylor_expansion_of_coeff(x, var, k, out=None):
     """``series2.taylor_expansion_of_coeff``, differentiable in ``x``."""
     if _tracked("series2_grad.taylor_expansion_of_coeff", (x,), out):
-        return _observers().Coeff.apply(x, var, k)
+        return _autograd().Coeff.apply(x, var, k)
     return series2.taylor_expansion_of_coeff(x, var, k, out)
 
 
 def shift_down(x, var, k, out=None):
     """``series2.shift_down``, differentiable in ``x``."""
     if _tracked("series2_grad.shift_down", (x,), out):
-        return _observers().ShiftDown.apply(x, var, k)
+        return _autograd().ShiftDown.apply(x, var, k)
     return series2.shift_down(x, var, k, out)
 
 
 def evaluate_all_one(x, out=None):
     """``series2.evaluate_all_one``, differentiable in ``x``."""
     if _tracked("series2_grad.evaluate_all_one", (x,), out):
-        return _observers().EvalOne.apply(x)
+        return _autograd().EvalOne.apply(x)
     return series2.evaluate_all_one(x, out)

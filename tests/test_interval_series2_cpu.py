@@ -195,7 +195,10 @@ def test_module_is_re_exported_and_shares_the_runner():
     assert genfer_amd.interval_series2 is interval_series2
     for f in ("mul", "div", "exp", "log", "compose", "pow"):
         assert callable(getattr(interval_series2, f)) and getattr(interval_series2, f).__doc__
-    assert interval_series2._run is series2._run  # one runner for both families
+    from genfer_amd import _series_call, interval_series, series
+
+    # one runner for every family and both ranks
+    assert interval_series2._run is series2._run is series._run is interval_series._run is _series_call.run
     assert interval_series2.MAX_ELEMS == 2048 and series2.MAX_ELEMS == 4096
 
 

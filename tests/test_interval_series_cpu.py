@@ -189,7 +189,10 @@ def test_module_is_re_exported_and_shares_the_runner():
     assert genfer_amd.interval_series is interval_series
     for f in ("mul", "div", "exp", "log", "compose", "pow"):
         assert callable(getattr(interval_series, f)) and getattr(interval_series, f).__doc__
-    assert interval_series._run is series._run  # one runner for both families
+    from genfer_amd import _series_call, interval_series2, series2
+
+    # one runner for every family and both ranks
+    assert interval_series._run is series._run is series2._run is interval_series2._run is _series_call.run
     assert interval_series.last_form is series.last_form and interval_series.set_form is series.set_form
     assert interval_series.MAX_N == 2048 and series.MAX_N == 4096
 
