@@ -1,13 +1,13 @@
-"""The one host path of the batched series modules: ``series``, ``series2``, ``interval_series``, ``interval_series2`` (and the
+"""The one host path of the batched series modules: ``series``, ``series2``, ``series3``, ``interval_series``, ``interval_series2`` (and the
 autograd Functions of ``series`` and ``series2_grad``) describe a call by data and hand it to ``run``.
 
 ``OPS`` is the table of the operations: one row says what travels between the first operand and the result, which side is the long
 one, the operands' names in messages and whether ``var`` travels at rank 2.  The same rows build the ctypes declarations of every
 ``gft[i]_series[2]_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart.  A ``Call``
-says the rest: the rank (1: the last axis is the series, 2: the last two axes are the coefficient array), ``planes`` (1: interval
+says the rest: the rank (1: the last axis is the series, 2 / 3: the last two / three axes are the coefficient array), ``planes`` (1: interval
 tensors ``[2, B..., item]``, the plane axis travelling as the first entry of every batch-stride array), the limit of the long side
 and the module's name for messages.  ``run`` works on ``t.shape[-rank:]`` and ``t.stride()[-rank:-1]``: rank 2 contributes its row
-stride and its second length because those tuples are one entry longer.
+stride and its second length because those tuples are one entry longer, rank 3 its slab stride and third length likewise.
 
 Everything that needs no device is judged first, in one order for every module: type, dtype, planes, axes (per tensor), the orders,
 ``out``, grad, then the placement, the devices and the library's device.
@@ -46,6 +46,7 @@ OPS = {o.suffix: o for o in (
     _op("evaluate_all_one", None, long="x"),
 )}
 F64_ONLY = ("corr", "compose_adj")  # no gfti_ twin
+RANK3 = ("mul", "div", "exp", "log")  # gft_series3_*: the four core operations, f64 only
 
 
 def _i64(seq):
@@ -58,7 +59,7 @@ _I64P, _SZP = C.POINTER(C.c_int64), C.POINTER(C.c_size_t)
 
 def _view_types(rank, lens=True):
     """an operand in an entry point's argument list: the pointer, the batch strides, and with ``lens`` the row strides (rank 2
-    has one) and the lengths"""
+    has one, rank 3 the slab stride in front of it) and the lengths"""
     return (C.c_void_p, _I64P) + ((C.c_int64,) * (rank - 1) + (C.c_size_t,) * rank if lens else ())
 
 
@@ -106,6 +107,10 @@ def _lib():
                         f.restype = C.c_int
                         f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,),
                                                      (C.c_size_t,), (_SZP, C.c_size_t, C.c_void_p)))
+        for suffix in RANK3:
+            f = getattr(L, "gft_series3_" + suffix)
+            f.restype = C.c_int
+            f.argtypes = list(_arguments(OPS[suffix], 3, lambda which, lens: _view_types(3, lens), (), (), (), (_SZP, C.c_size_t, C.c_void_p)))
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
@@ -150,6 +155,16 @@ def _axes2(t, what, planes=0):
         raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
 
 
+def _axes3(t, what, planes=0):
+    """the three series axes of an operand or of ``out``"""
+    if t.dim() < 3 + planes:
+        raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a trivariate series needs at least 3 (the last three are the coefficient array)")
+    if 0 in t.shape[-3:]:
+        raise TaylorError(f"{what}: a series axis is empty (the last three axes are {tuple(t.shape[-3:])})")
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
+
+
 _rank = {}
 
 
@@ -159,6 +174,7 @@ def _rank_rules(rank):
     if not _rank:
         from .series import _order, _order_short
         from .series2 import _orders, _orders_short
+        from .series3 import _orders as _orders3
 
         _rank[1] = (_axes1, lambda what, n, limit, *items: (_order(what, n, *[i[0] for i in items], max_n=limit),),
                     lambda what, n, names, g, y: (_order_short(what, n, g[0], y[0], names),),
@@ -168,6 +184,8 @@ def _rank_rules(rank):
                     lambda what, n, names, g, y: _orders_short(what, n, g, y, names),
                     "{what}: x has {shape[0]} * {shape[1]} = {count} coefficients, which exceeds the limit of {limit} per item of this version",
                     "{what}: out has {got} coefficients per item, the result has n = {want}")
+        _rank[3] = (_axes3, lambda what, n, limit, *items: _orders3(what, n, *items, max_elems=limit), None, None,
+                    "{what}: out has {got} coefficients per item, the result has n = {want}")  # (no transposed or observation op at rank 3)
     return _rank[rank]
 
 
@@ -260,7 +278,7 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
     if second is not None:
         second = second.expand(lead + batch + (() if seeded else tuple(second.shape[-rank:])))
     tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_")[rank - 1] + op.suffix)
+    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_", "series3_")[rank - 1] + op.suffix)
     parts = {"x": x, "second": second, "out": out}
     if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (scalar,), (var,), (scalar,), tail)) != 0:
         raise TaylorError((L.gft_last_error() or b"unknown error").decode())

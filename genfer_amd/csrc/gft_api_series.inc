@@ -3,6 +3,8 @@
 // and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
 // and the bivariate gft_series2_mul / div / exp / log / compose / pow with their Interval<F64> twins gfti_series2_* (the same
 // validation with one row stride per operand), and the f64-only transposed gft_series2_corr / compose_adj
+// and the trivariate gft_series3_mul / div / exp / log (f64 only: a slab stride and a row stride per operand; computed at the
+// stored result shape S on the permuted item of gft::series3_dims)
 // and the observation ops gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one with
 // their gfti_ twins (one operand, the result shorter by the order k on one axis; the kernels: gft_series_observe.hip)
 // Every entry point fills one gft::SeriesCall (gft_series_args.hpp, which judges it without the device) and hands it to series_call.
@@ -38,6 +40,15 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         gft::series_observe(R.stream, op, x, res, d, c.var, (unsigned)c.k, g, pl, tab ? tab->p : nullptr, tlen, c.rank2);
         join_caller_out(cs);
         R.series_last = gft::SERIES_NONE;
+        return 0;
+    }
+    if (c.rank3) {  // one form on the permuted item of the stored result shape S; planned before the streams are joined
+        const gft::Series3Dims k = gft::series3_dims(op, a);
+        const gft::Series3Plan plan = gft::series3_plan(op, k);
+        join_caller_in(cs);
+        gft::series3_launch(R.stream, op, plan, x, y, res, k, g);
+        join_caller_out(cs);
+        R.series_last = gft::SERIES_FORM_B;
         return 0;
     }
     if (c.rank2) {  // one form; planned before the streams are joined (the planner may refuse)
@@ -77,6 +88,11 @@ static gft::SeriesView rows1(const double* p, const int64_t* bs, size_t len) {
 static gft::SeriesView rows2(const double* p, const int64_t* bs, int64_t rst, size_t len0, size_t len1) {
     gft::SeriesView v;
     v.p = p, v.bs = bs, v.rst = rst, v.len0 = len0, v.len1 = len1;
+    return v;
+}
+static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, int64_t rst, size_t len0, size_t len1, size_t len2) {
+    gft::SeriesView v = rows2(p, bs, rst, len1, len2);
+    v.sst = sst, v.slabs = len0;
     return v;
 }
 
@@ -120,6 +136,23 @@ static gft::SeriesView rows2(const double* p, const int64_t* bs, int64_t rst, si
     int SYM(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs, double* res,    \
             const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {                        \
         GFT_SERIES_ENTRY(OP, FN, W, true, (c.x = rows2(x, xbs, xrs, nx0, nx1), c.y = rows1(seed, sbs, 1), c.r = rows2(res, rbs, rrs, n0, n1))); \
+    }
+// rank 3 (f64 only): a slab stride and a row stride per operand, three lengths
+#define GFT_SERIES3_BINARY(SYM, OP, FN)                                                                                                       \
+    int SYM(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* y,               \
+            const int64_t* ybs, int64_t yss, int64_t yrs, size_t ny0, size_t ny1, size_t ny2, double* res, const int64_t* rbs, int64_t rss,   \
+            int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, void* stream) {                                 \
+        GFT_SERIES_ENTRY(OP, FN, 1, false,                                                                                                    \
+                         (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.y = rows3(y, ybs, yss, yrs, ny0, ny1, ny2),         \
+                          c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                                      \
+    }
+#define GFT_SERIES3_SEEDED(SYM, OP, FN)                                                                                                       \
+    int SYM(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,            \
+            const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,                   \
+            const size_t* batch, size_t nbatch, void* stream) {                                                                               \
+        GFT_SERIES_ENTRY(OP, FN, 1, false,                                                                                                    \
+                         (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.y = rows1(seed, sbs, 1),                            \
+                          c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                                      \
     }
 // The arithmetic ops at both ranks.  Interval<F64> (gfti_, W == 2): the same calls on (lo, hi) planes; every batch-stride array has
 // nbatch + 1 entries, the plane stride first.  Rank 2: the last two axes are an item's coefficient array, with a row stride each.
@@ -176,6 +209,10 @@ GFT_SERIES_BINARY(gft_series_corr, SERIES_CORR, "series_corr", 1)
 GFT_SERIES_BINARY(gft_series_compose_adj, SERIES_COMPOSE_ADJ, "series_compose_adj", 1)
 GFT_SERIES2_BINARY(gft_series2_corr, SERIES_CORR, "series2_corr", 1)
 GFT_SERIES2_BINARY_VAR(gft_series2_compose_adj, SERIES_COMPOSE_ADJ, "series2_compose_adj", 1)
+GFT_SERIES3_BINARY(gft_series3_mul, SERIES_MUL, "series3_mul")
+GFT_SERIES3_BINARY(gft_series3_div, SERIES_DIV, "series3_div")
+GFT_SERIES3_SEEDED(gft_series3_exp, SERIES_EXP, "series3_exp")
+GFT_SERIES3_SEEDED(gft_series3_log, SERIES_LOG, "series3_log")
 int gft_series_last_form(void) { return R.series_last; }
 }
 #undef GFT_SERIES_ENTRY
@@ -184,6 +221,8 @@ int gft_series_last_form(void) { return R.series_last; }
 #undef GFT_SERIES2_BINARY
 #undef GFT_SERIES2_BINARY_VAR
 #undef GFT_SERIES2_SEEDED
+#undef GFT_SERIES3_BINARY
+#undef GFT_SERIES3_SEEDED
 #undef GFT_SERIES_ARITH
 #undef GFT_SERIES_OBSERVE_K
 #undef GFT_SERIES_OBSERVE

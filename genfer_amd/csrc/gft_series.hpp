@@ -78,6 +78,23 @@ size_t series2_pow_workspace(unsigned items, const Series2Dims& d, int w = 1);
 void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws,
                  const SeriesPlanes& pl = SeriesPlanes());
 
+// ---- rank 3: batched trivariate series (gft_series3_mul / div / exp / log, F64 only) -------------------------------------------------
+// The last THREE axes of every operand are one item's coefficient array: axis -3 the slabs and axis -2 the rows (any non-negative
+// strides), axis -1 unit stride.  Per item the reference's general recursion over axis 0 at the stored result shape S, an S with
+// unit axes being the item without them: Series3Dims (gft_series_args.hpp) says what runs, gft_series3_kernels.hpp how.  One form,
+// one workgroup per item; gft_series_last_form() reports SERIES_FORM_B.
+// The geometry of a call: lanes per workgroup, the terms per chunk of the slab sums (div / exp / log), the scratch in elements and
+// the dynamic LDS in bytes.  Throws std::runtime_error where the runtime grants less LDS than the resident arrays and the smallest
+// scratch need.
+struct Series3Plan {
+    unsigned threads, tc = 0, selems = 0;
+    size_t lds;
+};
+Series3Plan series3_plan(int op, const Series3Dims& d);
+// Launches SERIES_MUL / DIV / EXP / LOG at rank 3 on `st`.  `y`: the divisor / second factor; for exp / log the seeds or nullptr.
+void series3_launch(hipStream_t st, int op, const Series3Plan& p, const double* x, const double* y, double* res, const Series3Dims& d,
+                    const SeriesBatch& g);
+
 // ---- the observation ops at ranks 1 and 2 (gft_series_observe.hip) ----------------------------------------------------------------
 // op is SERIES_DERIVATIVE / SERIES_COEFF / SERIES_SHIFT_DOWN / SERIES_EVAL_ONE.  `d`: the operand's stored shape (nx0, nx1), row
 // stride xr, and the result's (n0, n1), rr (rank 1: nx0 == n0 == 1; evaluate_all_one: n0 == n1 == 1); the axis `var` of the result

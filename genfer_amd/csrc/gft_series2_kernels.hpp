@@ -143,10 +143,12 @@ __device__ inline void s2_mul_body(typename S2L<E>::T* lds, const double* x, con
         }
     }
 }
+#ifndef GFT_SERIES2_BODIES_ONLY  // (the one kernel here that is no template: gft_series3_kernels.hpp takes the bodies without it)
 __global__ __launch_bounds__(256) void k_series2_mul(const double* x, const double* y, double* res, Series2Dims d, SeriesBatch g) {
     extern __shared__ double s2_lds[];
     s2_mul_body<EF64>(s2_lds, x, y, res, d, g, SeriesPlanes());
 }
+#endif
 template <class E>
 __global__ __launch_bounds__(256) void k_series2i_mul(const double* x, const double* y, double* res, Series2Dims d, SeriesBatch g, SeriesPlanes pl) {
     extern __shared__ S2Iv s2_lds_iv[];
@@ -386,31 +388,31 @@ __device__ __forceinline__ void s2_div1d(typename S2L<E>::T* row, const typename
 // `y`: div's divisor; exp / log: the seeds exp(x[0][0]) / ln(x[0][0]) per item, or null (formed here by the device library).
 // j and k enter as E::from_u32 (the reference's S::from_u32): with intervals the point [j, j], whose product with a coefficient is
 // the functor's mul, short-circuits included ([1,1] * b is b).
-template <class E, int OP>
-__device__ inline void s2_rec_body(typename S2L<E>::T* lds, const double* x, const double* y, double* res, const Series2Dims& d, unsigned srows,
-                                   const SeriesBatch& g, const SeriesPlanes& pl) {
+// The rows of one item on arrays that sit in LDS: A [a0][a1] | r [n0][n1] | `sl`: scratch of `srows` rows of n1.  `xg`: div's
+// dividend, the item's x in global memory (rows `xr` and coefficients `xc` apart -- 1 at rank 2 --, planes `xplane`); `seed`: the item's seed of exp / log, or null.
+// LDSDIV (div only): the dividend is r itself, all n0 x n1 of it, divided in place -- the slab step of rank 3
+// (gft_series3_kernels.hpp).  Row k of it is read in the step of row k, so the accumulator of that row lives in the first n1
+// elements of `sl` between the chunks and the row sums behind them: `sl` then holds n1 + srows * n1 elements.
+template <class E, int OP, bool LDSDIV = false>
+__device__ inline void s2_rec_rows(const typename S2L<E>::T* al, unsigned a0, unsigned a1, typename S2L<E>::T* rl, unsigned n0, unsigned n1,
+                                   typename S2L<E>::T* sl, unsigned srows, const double* xg, size_t xplane, size_t xr, size_t xc, unsigned nx0, unsigned nx1,
+                                   const double* seed, size_t splane) {
     typedef typename E::V V;
-    typedef typename S2L<E>::T T;  // A [a0][a1] | r [n0][n1] | scratch [srows][n1]
+    typedef typename S2L<E>::T T;
     constexpr bool DIV = OP == SERIES_DIV, EXP = OP == SERIES_EXP;
-    const unsigned a0 = DIV ? d.ny0 : d.nx0, a1 = DIV ? d.ny1 : d.nx1, n1 = d.n1;
-    T* al = lds;
-    T* rl = al + a0 * a1;
-    T* sl = rl + d.n0 * n1;
+    static_assert(DIV || !LDSDIV, "only div takes its dividend from LDS");
     const unsigned tid = threadIdx.x, nt = blockDim.x;
-    const SeriesOff o = series_offsets(g, blockIdx.x);
-    if (DIV) s2_stage<E>(al, y + o.y, pl.y, d.yr, a0, a1);
-    else s2_stage<E>(al, x + o.x, pl.x, d.xr, a0, a1);
-    __syncthreads();
+    if (LDSDIV) sl += n1;
     if (!DIV) {  // row 0: the univariate recurrence, a dependency chain on one lane
         if (tid == 0) {
-            const S2Row<E> xr{al}, rr{rl};
-            const V sd = y ? E::ld(y, pl.s, o.s) : (EXP ? E::exp(S2L<E>::get(al, 0)) : E::log(S2L<E>::get(al, 0)));
-            if (EXP) rec_exp<E>(xr, rr, a1, n1, sd);
-            else rec_log<E>(xr, rr, a1, n1, sd);
+            const S2Row<E> xr0{const_cast<T*>(al)}, rr{rl};
+            const V sd = seed ? E::ld(seed, splane, 0) : (EXP ? E::exp(S2L<E>::get(al, 0)) : E::log(S2L<E>::get(al, 0)));
+            if (EXP) rec_exp<E>(xr0, rr, a1, n1, sd);
+            else rec_log<E>(xr0, rr, a1, n1, sd);
         }
         lds_barrier();
     }
-    for (unsigned k = DIV ? 0u : 1u; k < d.n0; ++k) {
+    for (unsigned k = DIV ? 0u : 1u; k < n0; ++k) {
         unsigned jlo, jhi;  // the terms of row k, ascending
         if (EXP) {
             jlo = 1;
@@ -421,6 +423,7 @@ __device__ inline void s2_rec_body(typename S2L<E>::T* lds, const double* x, con
             jhi = k;
         }
         T* rk = rl + k * n1;
+        T* ck = LDSDIV ? sl - n1 : rk;  // the accumulator of row k between the chunks
         for (unsigned jb = jlo; jb < jhi; jb += srows) {
             const unsigned cnt = jhi - jb < srows ? jhi - jb : srows;
             // pass 1: the row sums of the chunk, one (j, k1) a lane
@@ -451,23 +454,24 @@ __device__ inline void s2_rec_body(typename S2L<E>::T* lds, const double* x, con
                 S2L<E>::put(sl, idx, s);
             }
             lds_barrier();
-            // pass 2: the ordered additions; r[k] carries the accumulator from chunk to chunk
+            // pass 2: the ordered additions; r[k] (LDSDIV: the head of the scratch) carries the accumulator from chunk to chunk
             for (unsigned k1 = tid; k1 < n1; k1 += nt) {
-                V c = jb == jlo ? E::zero() : S2L<E>::get(rk, (int)k1);
+                V c = jb == jlo ? E::zero() : S2L<E>::get(ck, (int)k1);
                 for (unsigned jj = 0; jj < cnt; ++jj) c = E::addw(c, S2L<E>::get(sl, (int)(jj * n1 + k1)));
-                S2L<E>::put(rk, k1, c);
+                S2L<E>::put(ck, k1, c);
             }
             lds_barrier();
         }
         // the row's own step (a lane meets the k1 it owned in pass 2)
         for (unsigned k1 = tid; k1 < n1; k1 += nt) {
-            V c = jlo < jhi ? S2L<E>::get(rk, (int)k1) : E::zero();
+            V c = jlo < jhi ? S2L<E>::get(ck, (int)k1) : E::zero();
             if (EXP) {
                 c = E::div(c, E::from_u32(k));
             } else {
                 c = E::neg(c);
-                if (k < d.nx0 && k1 < d.nx1)
-                    c = E::add(c, DIV ? E::ld(x, pl.x, o.x + (size_t)k * d.xr + k1) : E::mul(E::from_u32(k), S2L<E>::get(al, (int)(k * a1 + k1))));
+                if (LDSDIV) c = E::add(c, S2L<E>::get(rk, (int)k1));
+                else if (k < nx0 && k1 < nx1)
+                    c = E::add(c, DIV ? E::ld(xg, xplane, (size_t)k * xr + k1 * xc) : E::mul(E::from_u32(k), S2L<E>::get(al, (int)(k * a1 + k1))));
             }
             S2L<E>::put(rk, k1, c);
         }
@@ -485,6 +489,21 @@ __device__ inline void s2_rec_body(typename S2L<E>::T* lds, const double* x, con
             }
         }
     }
+}
+template <class E, int OP>
+__device__ inline void s2_rec_body(typename S2L<E>::T* lds, const double* x, const double* y, double* res, const Series2Dims& d, unsigned srows,
+                                   const SeriesBatch& g, const SeriesPlanes& pl) {
+    typedef typename S2L<E>::T T;  // A [a0][a1] | r [n0][n1] | scratch [srows][n1]
+    constexpr bool DIV = OP == SERIES_DIV;
+    const unsigned a0 = DIV ? d.ny0 : d.nx0, a1 = DIV ? d.ny1 : d.nx1, n1 = d.n1;
+    T* al = lds;
+    T* rl = al + a0 * a1;
+    T* sl = rl + d.n0 * n1;
+    const SeriesOff o = series_offsets(g, blockIdx.x);
+    if (DIV) s2_stage<E>(al, y + o.y, pl.y, d.yr, a0, a1);
+    else s2_stage<E>(al, x + o.x, pl.x, d.xr, a0, a1);
+    __syncthreads();
+    s2_rec_rows<E, OP>(al, a0, a1, rl, d.n0, n1, sl, srows, x + o.x, pl.x, d.xr, 1, d.nx0, d.nx1, !DIV && y ? y + o.s : nullptr, pl.s);
     __syncthreads();  // (every global load of this workgroup is done: the result may be an operand)
     s2_store<E>(res + o.r, pl.r, d.rr, rl, d.n0, n1);
 }

@@ -67,15 +67,23 @@ struct Series2Dims {
                                           // (SERIES_CORR / SERIES_COMPOSE_ADJ at rank 2: x is g / gh, the LONG side: ny*, n* <= nx*)
     size_t xr, yr, rr;                    // row strides in elements
 };
+// rank 3 (gft_series3_*): what Series2Dims does not say -- the slabs (axis -3) of x, y and the result and their strides in elements
+struct SeriesSlabs {
+    unsigned nx = 1, ny = 1, n = 1;
+    size_t xs = 0, ys = 0, rs = 0;
+};
+constexpr unsigned SERIES3_MAX_ELEMS = 4096;  // n0 * n1 * n2 of the result: the two-arrays-in-64-KB footprint of rank 2
 
 // One operand of a call as the C ABI states it: len0 rows of len1 elements (unit stride), `rst` elements apart.  Rank 1 is
-// len0 == 1 with row stride 0.  `bs`: nbatch batch strides in elements, for w == 2 preceded by the lo -> hi plane stride; null:
+// len0 == 1 with row stride 0; rank 3 is `slabs` such arrays `sst` elements apart (else one).  `bs`: nbatch batch strides in elements, for w == 2 preceded by the lo -> hi plane stride; null:
 // contiguous items of the operand's own shape (the planes back to back).
 struct SeriesView {
     const double* p = nullptr;
     const int64_t* bs = nullptr;
     int64_t rst = 0;
     size_t len0 = 1, len1 = 1;
+    int64_t sst = 0;
+    size_t slabs = 1;
 };
 
 // One call.  `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; p may be null; one double per
@@ -90,6 +98,7 @@ struct SeriesCall {
     const char* fn = "";  // the name in messages
     int w = 1;
     bool rank2 = false;
+    bool rank3 = false;  // gft_series3_*: mul / div / exp / log on F64; the limit bounds slabs * len0 * len1 of the result
     uint32_t e = 0;
     int var = 0;
     size_t k = 0;
@@ -104,6 +113,7 @@ struct SeriesArgs {
     SeriesBatch g;
     SeriesPlanes pl;
     Series2Dims d;
+    SeriesSlabs s;
 };
 
 struct SeriesOperand {  // a view with its strides judged: batch strides in elements, the span it covers
@@ -111,6 +121,7 @@ struct SeriesOperand {  // a view with its strides judged: batch strides in elem
     const double* p;
     size_t len;
     size_t rows, rst;  // rank 2: an item is `rows` rows, `rst` elements apart; else 1 and 0
+    size_t slabs, sst;  // rank 3: `slabs` arrays of rows, `sst` elements apart; else 1 and 0
     size_t st[32];
     size_t plane;  // w == 2: elements from the lo plane to the hi plane (0 on an operand: a point interval), else 0
     size_t span;   // elements from p to one past its last element (of the hi plane)
@@ -125,8 +136,11 @@ static inline SeriesOperand series_arg(const SeriesCall& c, const char* what, co
     if (v.rst < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the row axis)");
     a.rows = v.len0;
     a.rst = v.len0 > 1 ? (size_t)v.rst : 0;
-    size_t cs = v.len1 * v.len0;  // NULL: contiguous items of the operand's own shape (the planes back to back)
-    a.span = v.len1 + (v.len0 - 1) * a.rst;
+    if (v.sst < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the slab axis)");
+    a.slabs = v.slabs;
+    a.sst = v.slabs > 1 ? (size_t)v.sst : 0;
+    size_t cs = v.len1 * v.len0 * v.slabs;  // NULL: contiguous items of the operand's own shape (the planes back to back)
+    a.span = v.len1 + (v.len0 - 1) * a.rst + (v.slabs - 1) * a.sst;
     const int64_t* bs = v.bs;
     if (c.w == 2 && bs) {
         if (bs[0] < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the plane axis)");
@@ -145,7 +159,7 @@ static inline SeriesOperand series_arg(const SeriesCall& c, const char* what, co
 }
 
 static inline bool series_same_view(const SeriesOperand& a, const SeriesOperand& b, const size_t* batch, size_t nbatch) {
-    if (a.p != b.p || a.len != b.len || a.plane != b.plane || a.rows != b.rows || a.rst != b.rst) return false;
+    if (a.p != b.p || a.len != b.len || a.plane != b.plane || a.rows != b.rows || a.rst != b.rst || a.slabs != b.slabs || a.sst != b.sst) return false;
     for (size_t i = 0; i < nbatch; ++i)
         if (batch[i] > 1 && a.st[i] != b.st[i]) return false;
     return true;
@@ -154,9 +168,33 @@ static inline bool series_same_view(const SeriesOperand& a, const SeriesOperand&
 // The three shape rules, once over (rows, length) pairs: nothing is empty, the long side carries the limit, and the short sides
 // fit inside the long side.  The long side is the result, or x for the transposed and the observation ops.  The texts are per rank.
 // (static, as everything below: the library exports none of this layer)
+// rank 3: the same three rules over (slabs, rows, length) triples, the result the long side
+static inline void series3_shapes(const SeriesCall& c) {
+    using std::to_string;
+    const std::string f(c.fn);
+    if (c.w != 1 || c.op > SERIES_LOG) throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
+    const bool binary = c.op == SERIES_MUL || c.op == SERIES_DIV;
+    auto empty = [](const SeriesView& v) { return v.slabs == 0 || v.len0 == 0 || v.len1 == 0; };
+    auto dims = [](const SeriesView& v, const char* sep) { return to_string(v.slabs) + sep + to_string(v.len0) + sep + to_string(v.len1); };
+    const SeriesView& L = c.r;
+    if (empty(L)) throw std::runtime_error(f + ": n0 * n1 * n2 == 0 (the result has no coefficients)");
+    const size_t most = SERIES3_MAX_ELEMS;
+    if (L.slabs > most || L.len0 > most || L.len1 > most || L.slabs * L.len0 > most || L.slabs * L.len0 * L.len1 > most)
+        throw std::runtime_error(f + ": n0 * n1 * n2 = " + dims(L, " * ") + " exceeds the limit of " + to_string(most) + " coefficients per item of this version");
+    if (empty(c.x) || (binary && empty(c.y))) throw std::runtime_error(f + ": an operand has no coefficients");
+    auto fits = [&](const SeriesView& s, const char* who) {
+        if (s.slabs <= L.slabs && s.len0 <= L.len0 && s.len1 <= L.len1) return;
+        throw std::runtime_error(f + ": " + who + " has " + dims(s, " x ") + " coefficients, the result " + dims(L, " x ") +
+                                 " (an operand is longer than the truncation order)");
+    };
+    fits(c.x, "x");
+    if (binary) fits(c.y, "y");
+}
+
 static inline void series_shapes(const SeriesCall& c) {
     using std::to_string;
     const std::string f(c.fn);
+    if (c.rank3) return series3_shapes(c);
     const int op = c.op;
     const bool observe = op >= SERIES_DERIVATIVE, comp = op == SERIES_COMPOSE;
     const bool corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
@@ -242,7 +280,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     {
         struct Ax {
             size_t ext, st;
-        } axes[35];
+        } axes[36];
         int k = 0;
         if (w == 2) {  // the two planes are one more axis of the result
             if (ar.plane == 0) throw std::runtime_error(f + ": the result has a zero plane stride: its lower and upper bounds overlap");
@@ -256,6 +294,10 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         if (ar.rows > 1) {  // rank 2: the rows of an item are one more axis of the result
             if (ar.rst == 0) throw std::runtime_error(f + ": the result has a zero row stride: the rows of an item overlap");
             axes[k++] = Ax{ar.rows, ar.rst};
+        }
+        if (ar.slabs > 1) {  // rank 3: the slabs of an item are one more axis again
+            if (ar.sst == 0) throw std::runtime_error(f + ": the result has a zero slab stride: the slabs of an item overlap");
+            axes[k++] = Ax{ar.slabs, ar.sst};
         }
         if (ar.len > 1) axes[k++] = Ax{ar.len, 1};
         std::sort(axes, axes + k, [](const Ax& u, const Ax& v) { return u.st < v.st; });
@@ -321,7 +363,50 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     d.nx0 = (unsigned)c.x.len0, d.nx1 = (unsigned)c.x.len1, d.ny0 = (unsigned)c.y.len0, d.ny1 = (unsigned)c.y.len1;
     d.n0 = (unsigned)c.r.len0, d.n1 = (unsigned)c.r.len1;
     d.xr = ax.rst, d.yr = ay.rst, d.rr = ar.rst;
+    SeriesSlabs& s = out.s;
+    s.nx = (unsigned)c.x.slabs, s.ny = (unsigned)c.y.slabs, s.n = (unsigned)c.r.slabs;
+    s.xs = ax.sst, s.ys = ay.sst, s.rs = ar.sst;
     return true;
+}
+
+// ---- rank 3: what is computed, decided by the shapes alone -----------------------------------------------------------------------
+// An item in the order the kernels run it.  The reference computes on the stored result shape S, not on n (S_a per axis: mul
+// min(n_a, nx_a + ny_a - 1), sum_shape mt:150-170; div n_a, but nx_a where ny_a == 1, mt:1216-1221; exp / log n_a, but 1 where
+// nx_a == 1, mt:408-413), and an S with a unit axis is by definition the item WITHOUT that axis: the rank-2 item, the series row,
+// the scalar.  So the axes are permuted: the unit axes of S go to the front and the others keep their order behind them --
+// S = (5, 3, 1) runs as (1, 5, 3), the innermost axis then striding by the row stride.  With a leading unit axis the rank-3 loops
+// ARE the rank-2 loops (one slab, whose step is the rank-2 body), with two the rank-1 loops.  Everything of n outside S is +0.0.
+struct Series3Dims {
+    unsigned nx[3], ny[3], n[3];  // permuted: the stored shapes of x and y (exp / log: ny unused) and S
+    size_t xs[3], ys[3], rs[3];   // permuted: the element strides of the three axes of x, y and the result
+    unsigned full[3], keep[3];    // as the caller states them: n and S, for the zero fill
+    size_t fs[3];                 // and the result's strides
+};
+static inline Series3Dims series3_dims(int op, const SeriesArgs& a) {
+    const Series2Dims& d = a.d;
+    const unsigned nx[3] = {a.s.nx, d.nx0, d.nx1}, ny[3] = {a.s.ny, d.ny0, d.ny1}, n[3] = {a.s.n, d.n0, d.n1};
+    const size_t xs[3] = {a.s.xs, d.xr, 1}, ys[3] = {a.s.ys, d.yr, 1}, rs[3] = {a.s.rs, d.rr, 1};
+    Series3Dims k;
+    int order[3], m = 0;
+    for (int i = 0; i < 3; ++i) {
+        unsigned s = n[i];
+        if (op == SERIES_MUL) s = std::min(n[i], nx[i] + ny[i] - 1);
+        else if (op == SERIES_DIV) s = ny[i] == 1 ? nx[i] : n[i];
+        else if (nx[i] == 1) s = 1;
+        k.full[i] = n[i], k.keep[i] = s, k.fs[i] = rs[i];
+    }
+    for (int i = 0; i < 3; ++i)
+        if (k.keep[i] == 1) order[m++] = i;
+    for (int i = 0; i < 3; ++i)
+        if (k.keep[i] != 1) order[m++] = i;
+    const bool binary = op == SERIES_MUL || op == SERIES_DIV;
+    for (int i = 0; i < 3; ++i) {
+        const int o = order[i];
+        // (an operand axis under a unit axis of S has one coefficient: it is no longer than S)
+        k.nx[i] = nx[o], k.ny[i] = binary ? ny[o] : 1, k.n[i] = k.keep[o];
+        k.xs[i] = xs[o], k.ys[i] = binary ? ys[o] : 0, k.rs[i] = rs[o];
+    }
+    return k;
 }
 
 }  // namespace gft

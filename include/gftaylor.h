@@ -270,6 +270,57 @@ int gft_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t
 int gft_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
                     const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
                     void* stream);                                       /* pow                    mt:433-451   */
+/* ---- batched TRIVARIATE series on caller-owned device tensors (f64 only): mul / div / exp / log ----
+ * The last THREE axes of every operand are the coefficient array of one TaylorPoly<F64> in three variables: axis -3 is variable 0
+ * (`nx0` slabs, `xss` elements apart), axis -2 variable 1 (`nx1` rows, `xrs` elements apart) -- any non-negative strides -- and
+ * axis -1 variable 2 (`nx2` coefficients, UNIT stride).  Per operand the arguments are the pointer, the batch-stride array, the
+ * slab stride, the row stride and the three lengths; then the batch shape, nbatch and the stream.  x has stored shape
+ * (nx0, nx1, nx2), y (ny0, ny1, ny2), the result always (n0, n1, n2) with nx*, ny* <= n*, n* >= 1 and n0 * n1 * n2 <= 4096 in this
+ * version.  The result's slabs, rows and items must be distinct addresses (its slab stride joins the row and batch strides in
+ * that proof); the result may be an operand itself (the same view), any other overlap is refused by address range.  Per item the
+ * result is the reference's GENERAL recursion over axis 0 in its operation order, multiply and add rounded separately, only stored
+ * coefficients entering a sum, and none of the operator wrappers' zero / one / constant / linear shortcuts.  Two rules, both
+ * decided by the shapes alone and so the same for every item of a call, come before the loops:
+ *   1. The recursion runs on the STORED RESULT SHAPE S, not on n.  Per axis a:
+ *        mul        S_a = min(n_a, nx_a + ny_a - 1)                    (sum_shape, mt:150-170)
+ *        div        S_a = n_a, except S_a = nx_a where ny_a == 1       (mt:1216-1221)
+ *        exp, log   S_a = n_a, except S_a = 1 where nx_a == 1          (mt:408-413, 421-426)
+ *      Every coefficient of the result outside S is +0.0.
+ *   2. The unit axes of S are SQUEEZED: an item whose S has one axis of length 1 is by definition the gft_series2_* item without
+ *      that axis (its loops above, on the two remaining axes in their order), with two such axes the gft_series_* row, with three
+ *      the same loops at one coefficient.  (The reference forms a whole 1-d product from 0.0 before it adds it, so the loops
+ *      below, run over an axis of length 1, would associate differently.)
+ * With every S_a >= 2, mul1d the univariate product of gft_series_mul at S_2 coefficients (a sum from 0.0) and div2 / exp2 / log2
+ * the loops of gft_series2_div / exp / log at (S_1, S_2):
+ *   mul  for k0 < S_0:  z[k0] = 0;  for j0 ascending in max(0, k0+1-ny0) .. min(k0+1, nx0)-1, and for every row k1 < S_1, for j1
+ *        ascending in max(0, k1+1-ny1) .. min(k1+1, nx1)-1:  z[k0][k1] += mul1d(x[j0][j1], y[k0-j0][k1-j1])
+ *        (one accumulator per row (k0, k1); each mul1d is formed from 0.0 FIRST, then added).  Written a (*) b for two slabs below.
+ *   div  for k0 < S_0:  c = 0;  for j0 in max(0, k0+1-ny0) .. k0-1: c += r[j0] (*) y[k0-j0];  c = -c;
+ *        if k0 < nx0: c[:nx1][:nx2] += x[k0];  r[k0] = div2(c, y[0])
+ *   exp  r[0] = exp2(x[0], seed);  for k0 >= 1:  c = 0;  for j0 in 1 .. min(nx0, k0+1)-1: c += (x[j0] * (double)j0) (*) r[k0-j0];
+ *        r[k0] = c / (double)k0          (x[j0] * j0 is rounded before it meets r)
+ *   log  r[0] = log2(x[0], seed);  for k0 >= 1:  c = 0;  for j0 in max(1, k0+1-nx0) .. k0-1: c += x[k0-j0] (*) (r[j0] * (double)j0);
+ *        c = -c;  if k0 < nx0: c[:nx1][:nx2] += (double)k0 * x[k0];  c = div2(c, x[0]);  r[k0] = c / (double)k0
+ * These are the bits of the reference's general product (mul) and of its /, exp() and log() at rank 3 wherever those take no
+ * data-dependent shortcut; the one shortcut the shapes trigger is a divisor of ONE stored coefficient, where the loops are the
+ * definition.  `seed`: exp(x[b, 0, 0, 0]) / ln(x[b, 0, 0, 0]) per item, or NULL (formed on the device), as for gft_series_exp /
+ * log.  One kernel per call, one workgroup per item with the operands resident in LDS; where the runtime grants less LDS than an
+ * item needs the call fails and says so.  gft_series_last_form() reports 2 afterwards; the "series_form" option does not apply.
+ * Stream contract, NULL stride arrays, empty batches and return values: those of gft_series2_mul. */
+int gft_series3_mul(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* y,
+                    const int64_t* ybs, int64_t yss, int64_t yrs, size_t ny0, size_t ny1, size_t ny2, double* res, const int64_t* rbs,
+                    int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch,
+                    void* stream);                                       /* mul                    mt:984-1012  */
+int gft_series3_div(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* y,
+                    const int64_t* ybs, int64_t yss, int64_t yrs, size_t ny0, size_t ny1, size_t ny2, double* res, const int64_t* rbs,
+                    int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch,
+                    void* stream);                                       /* div                    mt:1162-1192 */
+int gft_series3_exp(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,
+                    const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,
+                    const size_t* batch, size_t nbatch, void* stream);   /* exp                    mt:1285-1317 */
+int gft_series3_log(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,
+                    const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,
+                    const size_t* batch, size_t nbatch, void* stream);   /* log                    mt:1335-1386 */
 /* corr at rank 2: the transposed product, the adjoint of gft_series2_mul in the truncated inner product,
  * <mul2(x, y, (g0, g1)), g> = <x, corr2(g, y)> (f64 only; no gfti_ twin, for the reason given at gft_series_corr: a gradient of
  * interval bounds is not defined).  g has stored shape (g0, g1) with g0 * g1 <= 4096, y has (ny0, ny1) <= (g0, g1) per axis, the

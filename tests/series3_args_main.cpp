@@ -1,0 +1,91 @@
+// The rank-3 side of the host-side argument layer (genfer_amd/csrc/gft_series_args.hpp) on its own: no HIP, no device.
+// Reads one gft_series3_* call per line on stdin (tests/test_series3_refusals.py writes them) and prints one line per call:
+// "E <message>" for a refusal, "EMPTY" for an empty batch, else the collapsed batch, the strides of the series axes and what
+// series3_dims makes of the shapes -- the stored result shape S and the permuted item the kernels run.
+//   op  nbatch|null b...  <x> <y> <r>  : fn
+//   a view is  off|null  nbs|null s...  sst rst len0 len1 len2      (off: doubles into one buffer that is never read)
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../genfer_amd/csrc/gft_series_args.hpp"
+
+static double buffer[8192];
+
+struct View {
+    gft::SeriesView v;
+    std::vector<int64_t> bs;
+};
+
+static bool count(std::istream& in, size_t& n) {  // "null" or a count
+    std::string t;
+    in >> t;
+    if (t == "null") return false;
+    n = std::stoull(t);
+    return true;
+}
+
+static void read_view(std::istream& in, View& w) {
+    size_t off = 0, nbs = 0;
+    w.v.p = count(in, off) ? buffer + off : nullptr;
+    const bool has = count(in, nbs);
+    w.bs.resize(nbs);
+    for (auto& s : w.bs) in >> s;
+    in >> w.v.sst >> w.v.rst >> w.v.slabs >> w.v.len0 >> w.v.len1;
+    w.v.bs = has ? w.bs.data() : nullptr;
+}
+
+template <class T>
+static void list(const char* name, const T* a, int n) {
+    std::printf(" %s=[", name);
+    for (int i = 0; i < n; ++i) std::printf(i ? ",%zu" : "%zu", (size_t)a[i]);
+    std::printf("]");
+}
+
+int main() {
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        if (line.empty()) continue;
+        std::istringstream in(line);
+        gft::SeriesCall c;
+        c.rank3 = true;
+        in >> c.op;
+        std::vector<size_t> batch;
+        const bool has_batch = count(in, c.nbatch);
+        batch.resize(has_batch ? c.nbatch : 0);
+        for (auto& b : batch) in >> b;
+        if (!has_batch) in >> c.nbatch;  // a null batch still states how many axes it claims
+        c.batch = has_batch ? batch.data() : nullptr;
+        View x, y, r;
+        read_view(in, x), read_view(in, y), read_view(in, r);
+        c.x = x.v, c.y = y.v, c.r = r.v;
+        std::string colon, fn;
+        in >> colon;
+        std::getline(in, fn);
+        fn.erase(0, fn.find_first_not_of(' '));
+        c.fn = fn.c_str();
+        if (!in || colon != ":") {
+            std::printf("BAD LINE %s\n", line.c_str());
+            return 2;
+        }
+        try {
+            gft::SeriesArgs a;
+            if (!gft::series_args(c, a, [](const double*, const char*) {})) {  // the pointer check needs the device: not here
+                std::printf("EMPTY\n");
+                continue;
+            }
+            const gft::SeriesBatch& g = a.g;
+            std::printf("OK nd=%d items=%u inplace=%d", g.nd, g.items, g.inplace);
+            list("ext", g.ext, g.nd), list("xs", g.xs, g.nd), list("ys", g.ys, g.nd), list("ss", g.ss, g.nd), list("rs", g.rs, g.nd);
+            std::printf(" rows=%zu,%zu,%zu slabs=%zu,%zu,%zu |", a.d.xr, a.d.yr, a.d.rr, a.s.xs, a.s.ys, a.s.rs);
+            const gft::Series3Dims k = gft::series3_dims(c.op, a);
+            list("S", k.keep, 3), list("run", k.n, 3), list("x", k.nx, 3), list("y", k.ny, 3), list("xst", k.xs, 3), list("yst", k.ys, 3), list("rst", k.rs, 3);
+            std::printf("\n");
+        } catch (const std::exception& e) {
+            std::printf("E %s\n", e.what());
+        }
+    }
+    return 0;
+}
