@@ -441,8 +441,11 @@ def test_recurrences_same_bits_in_both_reference_order_kernels(mode, OTP, GTP, O
 
 
 def test_exp_recurrence_steps_on_the_tiled_kernel(OTP, GTP):
-    """exp's slab steps above the tiled crossover run as plain slab products of shifted operand views on the tiled
-    kernel (1e-10 contract; measured 1e-14); div and log keep the reference-order kernel and stay bit-exact."""
+    """exp above the tiled crossover on the tiled kernel (1e-10 contract; measured 1e-14).  This shape, rank 3 with total
+    = 288.5 * 200.5 * 392.5 = 2.3e7 >= 64 * tiled_min_macs, takes the RIGHT-LOOKING path of exp_rec: as soon as slab i is
+    final one accumulate-mode product adds (j xs[j]) (*) res[i] into the slabs that follow (the left-looking slab step, a
+    product of shifted operand views, is what remains where the wavefront declines below that crossover, see
+    test_exp_right_gpu.py).  div and log keep the reference-order kernel and stay bit-exact."""
     shape = (24, 20, 28)
     a = rand(shape, 91, -0.2, 0.2)
     b = rand(shape, 92, -0.2, 0.2)
