@@ -1450,6 +1450,8 @@ int gft_set_option(const char* name, double value) {
     else if (n == "shallow_pair_min") shallow_set_pair_min(value == -1.0 ? 4096.0 : value);
     else if (n == "tiled_tile") tiled_set_lane_tile((int)value);
     else if (n == "tiled_peel") tiled_set_peel((int)value);
+    else if (n == "tiled_slots") tiled_set_slots((int)value);
+    else if (n == "tiled_taper") tiled_set_taper((int)value);
     else if (n == "host_max_elems") R.host_max_elems = value < 0 ? Runtime::HOST_MAX_ELEMS_DEFAULT : (size_t)value;  // < 0: default
     else if (n == "host_max_macs") R.host_max_macs = value < 0 ? Runtime::HOST_MAX_MACS_DEFAULT : value;
     else if (n == "series_form") R.series_force = (value == 1 || value == 2) ? (int)value : 0;  // test / measurement knob (gft_series.hpp)

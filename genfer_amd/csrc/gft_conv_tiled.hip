@@ -28,6 +28,11 @@
 //                       range >= ~190 steps; fewer for small products, cut_ranges below).  Tiles covered by a
 //                       single range are written straight to z; split tiles go through partial slabs
 //                       in a workspace and a fixed-order reduce kernel => deterministic results.
+//   persistent launch   a plan with more ranges than the device has resident workgroup slots is launched with one
+//                       workgroup per slot; each CLAIMS ranges (a ticket from one of eight XCD-local queues, the other
+//                       queues once its own is empty) until none is left, and the ranges taper along every queue: large
+//                       ones first, small ones last (claim_range, cut_ranges).  The cuts depend on the shape
+//                       and the slot count only, never on who runs a range: results do not depend on the schedule.
 //
 // Numerics: explicit fma (one rounding per MAC) and a different summation order than the
 // reference => 1e-10 relative parity, not bit-exact (the reference-order kernels — the LDS-staged and row-pair
@@ -36,6 +41,7 @@
 // device while it packs (a stamp in the guard word), the tiled kernels then leave z alone and the caller's guarded
 // reference-order launch computes it; operands read in place have no padding and need no verdict (operand_layout).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -86,6 +92,13 @@ struct TiledArgs {
     const unsigned* red_slots;
     const unsigned* guard;           // non-finite verdict word: main/reduce kernels do nothing if *guard == guard_epoch
     unsigned guard_epoch;
+    unsigned* claim;                 // persistent launch: the ticket counter of each queue (zero at launch); null: workgroup
+                                     // w runs range w (or its XCD-contiguous image, xcd_remap) on the VAR | 256 instantiation
+    unsigned n_ranges, n_queues;     // claim: queue q (of 1 or 8) holds the ranges [q, q + 1) * n_ranges / n_queues
+#ifdef GFT_TILED_DIAG
+    unsigned long long* stamps;      // timeline (GFT_TILED_STAMPS): per range its start and end in s_memrealtime ticks and the
+                                     // XCD that ran it (blockIdx & 7); no output is computed from it
+#endif
     unsigned char blk1[8], blk2[8];  // output blocks (8 consecutive k2) owned by wave w; 0xff = none
 };
 
@@ -107,7 +120,9 @@ constexpr unsigned PEEL_MIN_EXTENT = 112, PEEL_MIN_INNER = 64;
 // VAR bits: 1 = software-pipelined fast path for full inner extents; 128 = peel instantiation (per-lane row limit on
 // axis 1 and strided output, for the leftover products of a peeled product); diagnostics (wrong results, timing
 // only, built with -DGFT_TILED_DIAG): 16 = no LDS reads in the chunk loop, 32 = no scalar x loads,
-// 64 = no window maintenance / barriers.
+// 64 = no window maintenance / barriers.  256 = one range per workgroup, the static launch of a plan whose ranges all fit
+// the device's slots at once (small products): the same kernel without the claiming loop, so that such a launch runs the
+// code it ran before there was one; without the bit the workgroups claim (TiledArgs::claim is then never null).
 
 __device__ inline void loadx(double (&dst)[8], cptr_t p) {  // wave-uniform: 8 doubles -> 16 SGPRs
 #pragma unroll
@@ -327,6 +342,24 @@ __host__ __device__ inline TileGeom tile_geom(const TiledArgs& A, unsigned tsh, 
 
 constexpr unsigned YPAD = 8;  // front padding of every LDS row (doubles)
 
+// Persistent launch: the next range of this workgroup, or ~0u when every queue is empty.  Called by ONE thread.  A queue
+// is a contiguous run of ranges and a ticket counter; workgroup w serves queue w & 7 first — workgroups are dealt
+// round-robin over the 8 XCDs, so that is the XCD-contiguous eighth xcd_remap gives the static launch (neighbouring ranges
+// share y windows in one L2) — and once a queue has run out it moves on, for good, to the next one in the fixed
+// rotation (`rot` queues are behind it).  The atomic is relaxed and device-scope and nothing is fenced: the plan tables
+// are read-only and no workgroup reads what another one wrote (a device-scope release / acquire pair costs a write-back
+// and an invalidate of the XCD's L2 here, see the note below).  A workgroup overshoots every counter at most once.
+__device__ inline unsigned claim_range(const TiledArgs& A, unsigned& rot) {
+    const unsigned nq = A.n_queues, per_q = A.n_ranges / nq, home = blockIdx.x & (nq - 1u);
+    while (rot < nq) {
+        const unsigned q = (home + rot) & (nq - 1u);
+        const unsigned t = __hip_atomic_fetch_add(A.claim + q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t < per_q) return q * per_q + t;
+        ++rot;
+    }
+    return ~0u;
+}
+
 // (Round 4 tried the reduction of split tiles INSIDE this kernel once more — a two-level tree of last arrivers: the workgroup
 // that stores a piece arrives at its group of 8 consecutive pieces, a group's last arriver sums the group in slab order
 // and arrives at the tile, whose last arriver sums the group sums and writes z; deterministic, nobody waits.  Correct, and
@@ -373,6 +406,31 @@ k_conv_tiled(TiledArgs A) {
     // the stream-K ranges — neighbouring ranges sweep overlapping y-row windows and then share one L2.
     unsigned wg = blockIdx.x;
     if (A.xcd_remap) wg = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    // persistent launch: one thread claims, the ticket reaches the others through LDS.  Two words taken in turn, so one
+    // barrier per range is enough: word i is rewritten two claims later, behind the barrier of the claim in between.
+    // (The words lie behind the window in the dynamic allocation — Plan::lds_bytes — not in a static one: the kernel's
+    // dynamic limit is raised to the whole 160 KB, and a static byte on top of that makes the attribute call fail.)
+    unsigned* const ticket = reinterpret_cast<unsigned*>(lds + 64 * (size_t)A.P1);
+    unsigned& claim_rot = ticket[2];
+    constexpr bool claiming = (VAR & 256) == 0;
+    if (claiming && tid == 0) claim_rot = 0;
+    for (unsigned turn = 0;; turn ^= 1u) {  // (one pass for a static launch; the body keeps the indentation it had without the loop)
+    if (claiming) {
+        if (tid == 0) {
+            unsigned rot = claim_rot;
+            ticket[turn] = claim_range(A, rot);
+            claim_rot = rot;
+        }
+        __syncthreads();
+        wg = __builtin_amdgcn_readfirstlane(ticket[turn]);
+        if (wg == ~0u) break;
+    }
+#ifdef GFT_TILED_DIAG
+    if (A.stamps && tid == 0) {
+        A.stamps[3 * (size_t)wg] = __builtin_amdgcn_s_memrealtime();
+        A.stamps[3 * (size_t)wg + 2] = blockIdx.x & 7u;
+    }
+#endif
     const unsigned seg_begin = A.wg_begin[wg], seg_end = A.wg_begin[wg + 1];
     for (unsigned si = seg_begin; si < seg_end; ++si) {
         const TileSeg seg = A.segs[si];
@@ -514,6 +572,11 @@ k_conv_tiled(TiledArgs A) {
                 for (int r = 0; r < 8; ++r) d[r] = acc2[r];
             }
         }
+    }
+#ifdef GFT_TILED_DIAG
+    if (A.stamps && tid == 0) A.stamps[3 * (size_t)wg + 1] = __builtin_amdgcn_s_memrealtime();
+#endif
+    if (!claiming) break;
     }
 }
 
@@ -734,7 +797,8 @@ struct PlanKey {
 
 struct Plan {
     TiledArgs base;  // shapes/pitches filled in; pointers to device tables filled in
-    unsigned n_wg = 0, n_red = 0, n_slots = 0, NW = 0;
+    unsigned n_wg = 0, n_red = 0, n_slots = 0, NW = 0;  // n_wg: stream-K ranges (one workgroup each unless the launch claims)
+    unsigned n_resident = 0;                            // workgroup slots of the device for this kernel (CUs x workgroups per CU)
     size_t lds_bytes = 0;
     void* d_tables = nullptr;
 };
@@ -804,6 +868,21 @@ struct PeelSpec {
     unsigned cut = 0, lim1 = 0;             // TiledArgs::cut, TiledArgs::lim1
     size_t zsU = 0, zs0 = 0, zs1 = 0, zoff = 0;  // output strides (role 2 / 3; dense otherwise)
 };
+
+int& tiled_slots_cap() {  // A/B and test knob ("tiled_slots"): at most this many workgroups per main launch; 0: one per range or
+                          // slot; < 0: one per range whatever the slots (the static launch, A/B)
+    static int v = 0;
+    return v;
+}
+// Taper of a claiming plan's ranges, in per cent: along a queue the range sizes fall linearly from (1 + t) to (1 - t)
+// times their mean ("tiled_taper", A/B; the default is the sweep's choice, profiles/r18/tiled_taper_sweep.txt)
+#ifndef GFT_TILED_TAPER_DEFAULT
+#define GFT_TILED_TAPER_DEFAULT 80
+#endif
+int& tiled_taper_pct() {
+    static int v = GFT_TILED_TAPER_DEFAULT;
+    return v;
+}
 
 int& tiled_force_tsh() {  // A/B and test knob (GFT_TILED_TSH / "tiled_tile"): 3..6 forces the lane tile 8x8 .. 1x64
     static int v = 0;
@@ -937,7 +1016,7 @@ bool canonicalise(const ConvArgs& a, const Variant& V, const PeelSpec& ps, Plan&
     T.accumulate = a.accumulate;
     unsigned npairs = (T.nb + 1) / 2;
     P.NW = npairs <= 1 ? 1 : (npairs <= 2 ? 2 : (npairs <= 4 ? 4 : 8));
-    P.lds_bytes = (size_t)64 * T.P1 * sizeof(double);
+    P.lds_bytes = (size_t)64 * T.P1 * sizeof(double) + 16;  // the window, and the ticket words of a persistent launch
     assign_blocks(T, P.NW);
     return true;
 }
@@ -987,8 +1066,15 @@ bool cut_ranges(Plan& P, PlanTables& tb) {
     // TMAC/s in three alternating runs on one box; 96^3 and 100^3 four, +3 %; 64^3, 81 steps per slot, stays at one: two
     // are neutral, four lose 4 % to the extra partial slabs).
     unsigned long long n_wg = (unsigned long long)num_cus() * wg_per_cu;
+    P.n_resident = (unsigned)n_wg;
     const unsigned long long per_slot = S / n_wg;  // steps (one lane tile x one (ju, j0, j1)) per resident slot
-    const unsigned long long fit = per_slot / 190;  // ranges of >= ~190 steps
+    // The leftover products of a peeled product ran on one range per slot at 74 % wave-slot occupancy (their ranges are equal
+    // in steps but not in masked lanes; profiles/r18/pmc_tiled_occupancy_parent.json).  The ~190 steps were found on nb = 8
+    // (39 units a step, below); the leftover products of the sizes that peel have nb >= 8 and are cut by the same WORK, 190 x 39
+    // units a range: 53 steps at nb = 16, two ranges per slot at 128^3, evened out by the persistent launch.
+    const bool leftover = T.lim1 || T.zoff;
+    const unsigned long long range_steps = leftover ? std::min(190ull, 190ull * 39 / ((unsigned long long)T.nb * (T.nb + 1) / 2 + 3)) : 190;
+    const unsigned long long fit = per_slot / range_steps;  // ranges of >= ~190 steps
     n_wg *= fit >= 8 ? 8u : (fit >= 4 ? 4u : (fit >= 2 ? 2u : 1u));
     // Every range pays a window fill and, if it splits a tile, a 4 KB-per-block partial slab plus its share of the
     // reduction, so small products must not be cut into confetti.  A step costs ~ (chunk pairs + 3) units
@@ -1001,6 +1087,31 @@ bool cut_ranges(Plan& P, PlanTables& tb) {
         std::max<unsigned long long>(1, (MIN_UNITS + 20ull * T.nb + step_units / 2) / step_units);
     if (n_wg > S / min_steps) n_wg = std::max<unsigned long long>(1, S / min_steps);
     P.n_wg = (unsigned)n_wg;
+    // The cuts.  A plan with more ranges than slots is launched persistently (launch_grid) and its ranges TAPER: in each
+    // queue (an eighth of the ranges, or all of them: claim_range) the sizes fall linearly from (1 + t) to (1 - t) times the
+    // mean, so the ranges claimed last — the launch's tail — are the short ones: a slot that runs out of ranges idles for
+    // about half a last range (profiles/r18/tiled_slot_timeline.txt).  t is tiled_taper_pct(), less where the shortest range
+    // would drop below the WORK of ~190 steps at nb = 8, where that length was found (tail_steps; what it guards, a
+    // range's window fill and its 4 KB-per-block partial slab, is then under 2 % of the range).  Shape and slot count decide
+    // all of it: the same cuts whoever runs them.
+    std::vector<unsigned long long> cutpos(n_wg + 1);
+    for (unsigned long long w = 0; w <= n_wg; ++w) cutpos[w] = S * w / n_wg;
+    const unsigned long long mean = S / n_wg;
+    const unsigned long long tail_steps = std::max(min_steps, std::min(190ull, 190ull * 39 / step_units));
+    if (n_wg > P.n_resident && mean > tail_steps && tiled_taper_pct() > 0) {
+        const unsigned nq = n_wg % 8 == 0 ? 8u : 1u;
+        const unsigned long long k = n_wg / nq;  // ranges per queue (k >= 2: more ranges than slots)
+        const unsigned long long pct = std::min<unsigned long long>(std::min(tiled_taper_pct(), 90), 100 * (mean - tail_steps) / mean);
+        // weight of range i of a queue: 100 (k - 1) + pct (k - 1 - 2 i) > 0; the weights of a queue sum to 100 k (k - 1)
+        for (unsigned q = 0; q < nq; ++q) {
+            const unsigned long long qlo = cutpos[q * k], qS = cutpos[(q + 1) * k] - qlo;
+            unsigned long long W = 0;
+            for (unsigned long long i = 0; i < k; ++i) {
+                cutpos[q * k + i] = qlo + (unsigned long long)((unsigned __int128)qS * W / (100 * k * (k - 1)));
+                W += 100 * (k - 1) + pct * (k - 1) - 2 * pct * i;
+            }
+        }
+    }
 
     tb.wg_begin.assign(P.n_wg + 1, 0);
     std::vector<std::vector<unsigned>> tile_slots(tiles.size());
@@ -1009,7 +1120,7 @@ bool cut_ranges(Plan& P, PlanTables& tb) {
     size_t ti = 0;
     unsigned long long tile_start = 0;  // global step index where tile ti starts
     for (unsigned w = 0; w < P.n_wg; ++w) {
-        unsigned long long lo = S * w / n_wg, hi = S * (w + 1) / n_wg;
+        unsigned long long lo = cutpos[w], hi = cutpos[w + 1];
         tb.wg_begin[w] = (unsigned)tb.segs.size();
         unsigned long long pos = lo;
         while (pos < hi) {
@@ -1090,28 +1201,31 @@ bool build_plan(const ConvArgs& a, const Variant& V, const PeelSpec& ps, Plan& P
 }
 
 template <int NW, int VAR, int TSH>
-void launch_main_t(hipStream_t st, const Plan& P, const TiledArgs& T) {
+void launch_main_t(hipStream_t st, const Plan& P, const TiledArgs& T, unsigned grid) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_tiled<NW, VAR, TSH>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_tiled<NW, VAR | 256, TSH>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
     // (a failed launch is latched by the launch thread and raised by the next drain: gft_launch.hpp lq_note)
-    GFT_LAUNCH((k_conv_tiled<NW, VAR, TSH>), dim3(P.n_wg), dim3(NW * 64), P.lds_bytes, st, T);
+    if (T.claim) GFT_LAUNCH((k_conv_tiled<NW, VAR, TSH>), dim3(grid), dim3(NW * 64), P.lds_bytes, st, T);
+    else GFT_LAUNCH((k_conv_tiled<NW, VAR | 256, TSH>), dim3(grid), dim3(NW * 64), P.lds_bytes, st, T);
 }
 template <int NW, int VAR>
-void launch_main_nw(hipStream_t st, const Plan& P, const TiledArgs& T) {  // the 8x8 lane tile or the run-time one
-    if (T.tsh == 3) launch_main_t<NW, VAR, 3>(st, P, T);
-    else launch_main_t<NW, VAR, 0>(st, P, T);
+void launch_main_nw(hipStream_t st, const Plan& P, const TiledArgs& T, unsigned grid) {  // the 8x8 lane tile or the run-time one
+    if (T.tsh == 3) launch_main_t<NW, VAR, 3>(st, P, T, grid);
+    else launch_main_t<NW, VAR, 0>(st, P, T, grid);
 }
 template <int VAR>
-void launch_main(hipStream_t st, const Plan& P, const TiledArgs& T) {  // the plan's run-time NW as a compile-time one
+void launch_main(hipStream_t st, const Plan& P, const TiledArgs& T, unsigned grid) {  // the plan's run-time NW as a compile-time one
     switch (P.NW) {
-        case 1: launch_main_nw<1, VAR>(st, P, T); break;
-        case 2: launch_main_nw<2, VAR>(st, P, T); break;
-        case 4: launch_main_nw<4, VAR>(st, P, T); break;
-        default: launch_main_nw<8, VAR>(st, P, T); break;
+        case 1: launch_main_nw<1, VAR>(st, P, T, grid); break;
+        case 2: launch_main_nw<2, VAR>(st, P, T, grid); break;
+        case 4: launch_main_nw<4, VAR>(st, P, T, grid); break;
+        default: launch_main_nw<8, VAR>(st, P, T, grid); break;
     }
 }
 
@@ -1132,6 +1246,8 @@ void tiled_fold_rows_f64(hipStream_t st, const double* zt, double* z, size_t row
 }
 
 void tiled_set_lane_tile(int tsh) { tiled_force_tsh() = tsh; }
+void tiled_set_slots(int n) { tiled_slots_cap() = n; }
+void tiled_set_taper(int pct) { tiled_taper_pct() = pct < 0 ? GFT_TILED_TAPER_DEFAULT : std::min(pct, 90); }
 
 namespace {
 
@@ -1146,7 +1262,7 @@ const Plan* cached_plan(const ConvArgs& a, const Variant& V, const PeelSpec& ps,
     PlanKey key;
     std::memset(&key, 0, sizeof(key));
     if (a.nd < 2 || a.nd > 4) return nullptr;
-    key.v[0] = (unsigned)a.nd | ((unsigned)a.slab_axis << 8) | ((unsigned)tiled_force_tsh() << 16);
+    key.v[0] = (unsigned)a.nd | ((unsigned)a.slab_axis << 8) | ((unsigned)tiled_force_tsh() << 16) | ((unsigned)tiled_taper_pct() << 24);
     for (int i = 0; i < a.nd; ++i) {
         key.v[1 + i] = a.xs[i];
         key.v[5 + i] = a.ys[i];
@@ -1169,24 +1285,99 @@ const Plan* cached_plan(const ConvArgs& a, const Variant& V, const PeelSpec& ps,
     return &it->second;
 }
 
-// the main kernel of plan P on the filled-in arguments T, then the fixed-order reduce of its split tiles
-bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V) {
-    T.xcd_remap = (V.xcd && P.n_wg % 8 == 0) ? 1u : 0u;
-    switch (pick_var(V, P.NW)) {
-        case 131: launch_main<131>(st, P, T); break;  // leftover products of a peeled product
-        case 11: launch_main<11>(st, P, T); break;    // compact operands, pipelined
-        case 3: launch_main<3>(st, P, T); break;
-        case 0: launch_main<0>(st, P, T); break;
-        case 1: launch_main_nw<8, 1>(st, P, T); break;
+// Workgroups of plan P's main launch: one per range while they all fit the device's slots at once (the launch every plan
+// had before), otherwise one per slot, which then claim the ranges; "tiled_slots" caps it (and never touches the cuts).
+unsigned launch_grid(const Plan& P) {
+    if (tiled_slots_cap() < 0) return P.n_wg;
+    unsigned g = std::min(P.n_wg, P.n_resident);
+    if (tiled_slots_cap() > 0) g = std::min(g, (unsigned)tiled_slots_cap());
+    return g;
+}
+bool plan_claims(const Plan& P) { return launch_grid(P) < P.n_wg; }
+// The ticket counters of a call's claiming launches: the first CLAIM_BYTES of its workspace, eight words per launch
+// (claim_words(0 .. 2): plain or M, L0, L1).  They are zeroed by ONE memset per call, queued in stream order BEFORE the
+// launches — not returned to zero by the last workgroup out: the workspace belongs to the stream, not to a plan, and a
+// product that does not claim has no counters and puts its partial slabs over these bytes, so "zero on entry" cannot be
+// an invariant kept from call to call.  A memset is a node like any other under stream capture, and a launch that the
+// non-finite guard stands down never touches the words.
+constexpr size_t CLAIM_BYTES = 256;
+unsigned* claim_words(char* wb, unsigned launch) { return (unsigned*)wb + 8 * launch; }
+void zero_claim_words(hipStream_t st, char* wb) {
+    enqueue_task([=] { lq_note((hipMemsetAsync)(wb, 0, CLAIM_BYTES, st), nullptr, "hipMemsetAsync"); });
+}
+
 #ifdef GFT_TILED_DIAG
-        case 17: launch_main_nw<8, 17>(st, P, T); break;
-        case 33: launch_main_nw<8, 33>(st, P, T); break;
-        case 49: launch_main_nw<8, 49>(st, P, T); break;
-        case 65: launch_main_nw<8, 65>(st, P, T); break;
-        case 113: launch_main_nw<8, 113>(st, P, T); break;
+// Timeline of one main launch (diagnostic build, GFT_TILED_STAMPS=<file>, launches of at least GFT_TILED_STAMPS_MIN ranges,
+// default 1024): every range stamps its start and end; appended to the file per XCD: ranges run, and when its last range
+// ended relative to the launch's last (microseconds at the 100 MHz of s_memrealtime).  Synchronises: timing runs only.
+void dump_stamps(hipStream_t st, const unsigned long long* d_stamps, unsigned n, unsigned grid, bool claiming) {
+    std::vector<unsigned long long> h(3 * (size_t)n);
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    FILE* f = std::fopen(std::getenv("GFT_TILED_STAMPS"), "a");
+    if (!f) return;
+    unsigned long long t0 = ~0ull, t1 = 0, last[8] = {0}, busy[8] = {0};
+    unsigned cnt[8] = {0};
+    for (unsigned r = 0; r < n; ++r) {
+        const unsigned long long b = h[3 * (size_t)r], e = h[3 * (size_t)r + 1];
+        const unsigned x = (unsigned)h[3 * (size_t)r + 2] & 7u;
+        t0 = std::min(t0, b);
+        t1 = std::max(t1, e);
+        last[x] = std::max(last[x], e);
+        busy[x] += e - b;
+        cnt[x]++;
+    }
+    std::fprintf(f, "launch: %u ranges on %u workgroups (%s), %.1f us from first start to last end\n", n, grid,
+                 claiming ? "claiming" : "one range each", (t1 - t0) / 100.0);
+    for (int x = 0; x < 8; ++x)
+        std::fprintf(f, "  xcd %d: %5u ranges, range time %10.1f us in all, last range ends %8.1f us before the launch's last\n", x, cnt[x],
+                     busy[x] / 100.0, (t1 - last[x]) / 100.0);
+    std::fclose(f);
+}
+#endif
+
+// the main kernel of plan P on the filled-in arguments T, then the fixed-order reduce of its split tiles; `claim`: the
+// launch's ticket counters (used if the plan claims)
+bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V, unsigned* claim) {
+    const unsigned grid = launch_grid(P);
+    const bool eighths = V.xcd && P.n_wg % 8 == 0;
+    T.n_ranges = P.n_wg;
+    if (grid < P.n_wg) {
+        if (!claim) return false;
+        T.claim = claim;
+        T.n_queues = eighths ? 8u : 1u;
+        T.xcd_remap = 0;
+    } else {
+        T.claim = nullptr;
+        T.n_queues = 1;
+        T.xcd_remap = eighths ? 1u : 0u;
+    }
+#ifdef GFT_TILED_DIAG
+    static unsigned long long* d_stamps = nullptr;
+    const char* stamps_min = std::getenv("GFT_TILED_STAMPS_MIN");
+    T.stamps = nullptr;
+    if (std::getenv("GFT_TILED_STAMPS") && P.n_wg >= (stamps_min ? (unsigned)std::atoi(stamps_min) : 1024u) && P.n_wg <= 65536u) {
+        if (!d_stamps && hipMalloc((void**)&d_stamps, 3 * 65536 * sizeof(unsigned long long)) != hipSuccess) d_stamps = nullptr;
+        T.stamps = d_stamps;
+    }
+#endif
+    switch (pick_var(V, P.NW)) {
+        case 131: launch_main<131>(st, P, T, grid); break;  // leftover products of a peeled product
+        case 11: launch_main<11>(st, P, T, grid); break;    // compact operands, pipelined
+        case 3: launch_main<3>(st, P, T, grid); break;
+        case 0: launch_main<0>(st, P, T, grid); break;
+        case 1: launch_main_nw<8, 1>(st, P, T, grid); break;
+#ifdef GFT_TILED_DIAG
+        case 17: launch_main_nw<8, 17>(st, P, T, grid); break;
+        case 33: launch_main_nw<8, 33>(st, P, T, grid); break;
+        case 49: launch_main_nw<8, 49>(st, P, T, grid); break;
+        case 65: launch_main_nw<8, 65>(st, P, T, grid); break;
+        case 113: launch_main_nw<8, 113>(st, P, T, grid); break;
 #endif
         default: return false;
     }
+#ifdef GFT_TILED_DIAG
+    if (T.stamps) dump_stamps(st, T.stamps, P.n_wg, grid, grid < P.n_wg);
+#endif
     if (P.n_red) {
         GFT_LAUNCH(k_conv_reduce, dim3(P.n_red, T.nb), dim3(256), 0, st, T, P.n_red);
     }
@@ -1205,18 +1396,20 @@ bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V) {
 // which also takes the non-finite verdict; y alone stays in place if only x needs it.
 struct Operands {
     bool inplace, pack_y;
-    size_t o_xp, o_yp, end;  // byte offsets of the packed operands in the workspace, and the end of the common prefix
+    size_t o_ws, o_xp, o_yp, end;  // byte offsets of the partial slabs (behind the ticket counters of a call that claims) and
+                                   // of the packed operands in the workspace, and the end of the common prefix
 };
 // (sized for the packed layout whether or not this call packs: a query and the launches that follow it — the high-rank
 // loop's operand blocks, say — must agree on the workspace whatever their pointers' alignment)
-Operands operand_layout(const TiledArgs& B, size_t n_slots, const double* x, const double* y, int operands_slack) {
+Operands operand_layout(const TiledArgs& B, size_t n_slots, bool claims, const double* x, const double* y, int operands_slack) {
     auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t x_rows = (size_t)B.xU * B.x0 * B.x1, y_rows = (size_t)B.yU * B.y0 * B.y1;
     Operands o;
     o.inplace = operands_slack && B.nx8 == B.xI && B.ny8 == B.yI && B.nxc >= B.nb && B.nyc >= B.nb && !((uintptr_t)y & 15) &&
                 !((uintptr_t)x & 7);
     o.pack_y = !o.inplace && (B.ny8 != B.yI || ((uintptr_t)y & 15));
-    o.o_xp = al(n_slots * B.nb * 512 * sizeof(double));
+    o.o_ws = claims ? CLAIM_BYTES : 0;
+    o.o_xp = o.o_ws + al(n_slots * B.nb * 512 * sizeof(double));
     o.o_yp = o.o_xp + al((x_rows * B.nx8 + 8) * sizeof(double));
     o.end = o.o_yp + al(y_rows * B.ny8 * sizeof(double));
     return o;
@@ -1224,7 +1417,7 @@ Operands operand_layout(const TiledArgs& B, size_t n_slots, const double* x, con
 // Binds x and y to T as the layout says: in place, or packed into the workspace `wb` under the verdict (nf_flag, nf_epoch).
 void bind_operands(hipStream_t st, const Operands& o, const double* x, const double* y, char* wb, unsigned* nf_flag,
                    unsigned nf_epoch, TiledArgs& T) {
-    T.ws = (double*)wb;
+    T.ws = (double*)(wb + o.o_ws);
     if (o.inplace) {
         T.xp = x;
         T.yp = y;
@@ -1277,7 +1470,7 @@ bool peel_applies(const ConvArgs& a, const Variant& V) {
 //        aligned restriction k0 - j <= 8 (k0 / 8) as a per-lane limit on the window row (TiledArgs::lim1).
 // One stream, fixed order (pack, M and its reduce, L0 and its reduce, L1 and its reduce): deterministic.  All three carry
 // the same guard, so a product flagged non-finite is left to the caller's guarded reference-order launch as a whole.
-// Workspace: [partial slabs, shared by the three][packed x][packed y][L0 window][L1 scalar + slack][L1 window].
+// Workspace: [ticket counters, if any of the three claims][partial slabs, shared by the three][packed x][packed y][L0 window][L1 scalar + slack][L1 window].
 // Returns 1 done (or, for a query, sized), 0 a launch failed, -1 the peel cannot be planned or does not fit the workspace
 // it was given — nothing has been launched and the caller takes the plain plan.
 int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, const Variant& V, void* ws,
@@ -1317,7 +1510,8 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
     const TiledArgs& B = PM.base;
     if (B.tsh != 3) return -1;
     const size_t n8 = B.nx8;
-    const Operands o = operand_layout(B, std::max(PM.n_slots, std::max(P0.n_slots, P1.n_slots)), x, y, a.operands_slack);
+    const bool claims = plan_claims(PM) || plan_claims(P0) || plan_claims(P1);
+    const Operands o = operand_layout(B, std::max(PM.n_slots, std::max(P0.n_slots, P1.n_slots)), claims, x, y, a.operands_slack);
     const size_t e_w0 = (size_t)7 * (n0 / 8) * n1 * n8, e_s1 = (size_t)7 * n0 * n8, e_w1 = (size_t)7 * (n1 / 8) * n0 * n8;
     auto al = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t o_w0 = o.end, o_s1 = o_w0 + al(e_w0 * sizeof(double)), o_w1 = o_s1 + al((e_s1 + 8) * sizeof(double)),
@@ -1330,6 +1524,7 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
     char* wb = (char*)ws;
     double *w0 = (double*)(wb + o_w0), *s1 = (double*)(wb + o_s1), *w1 = (double*)(wb + o_w1);
     TiledArgs T = B;
+    if (claims) zero_claim_words(st, wb);
     bind_operands(st, o, x, y, wb, nf_flag, nf_epoch, T);
     {
         const size_t tot = e_w0 + e_s1 + e_w1;
@@ -1337,7 +1532,7 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
                    nI, (unsigned)n8);
     }
     T.z = z;
-    if (!launch_plan(st, PM, T, V)) return 0;
+    if (!launch_plan(st, PM, T, V, claim_words(wb, 0))) return 0;
     TiledArgs T0 = P0.base, T1 = P1.base;
     T0.ws = T1.ws = T.ws;
     T0.z = T1.z = z;
@@ -1347,7 +1542,7 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
     T0.yp = w0;
     T1.xp = s1;
     T1.yp = w1;
-    return launch_plan(st, P0, T0, VL) && launch_plan(st, P1, T1, VL) ? 1 : 0;
+    return launch_plan(st, P0, T0, VL, claim_words(wb, 1)) && launch_plan(st, P1, T1, VL, claim_words(wb, 2)) ? 1 : 0;
 }
 
 }  // namespace
@@ -1373,16 +1568,18 @@ bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z,
     }
     const Plan* P = cached_plan(a, V, PeelSpec(), st);
     if (!P) return false;
-    const Operands o = operand_layout(P->base, P->n_slots, x, y, a.operands_slack);
-    const size_t need = o.end + 256;  // workspace: [partial slabs][packed x][packed y]
+    const bool claims = plan_claims(*P);
+    const Operands o = operand_layout(P->base, P->n_slots, claims, x, y, a.operands_slack);
+    const size_t need = o.end + 256;  // workspace: [ticket counters, if the launch claims][partial slabs][packed x][packed y]
     if (guarded) *guarded = !o.inplace;
     if (ws_needed) *ws_needed = need;
     if (!ws) return true;  // query
     if (ws_bytes < need) return false;
     TiledArgs T = P->base;
+    if (claims) zero_claim_words(st, (char*)ws);
     bind_operands(st, o, x, y, (char*)ws, nf_flag, nf_epoch, T);
     T.z = z;
-    return launch_plan(st, *P, T, V);
+    return launch_plan(st, *P, T, V, claim_words((char*)ws, 0));
 }
 
 }  // namespace gft

@@ -458,6 +458,8 @@ size_t staged_scratch_bytes();  // bytes the grow-only kernel workspaces of gft_
 void staged_release_scratch();  // frees the register-blocked interval product's row-flag scratch (gft_shutdown)
 void dwf_release_orders();  // frees the row wavefront's cached claim-order tables (gft_shutdown)
 void tiled_set_lane_tile(int tsh);  // 0 = planner's choice, 3..6 = force T1 = 1 << tsh lanes along k1 (tests, A/B)
+void tiled_set_slots(int n);        // "tiled_slots": at most n workgroups per main launch of the tiled product; 0 = no cap (tests, A/B)
+void tiled_set_taper(int pct);      // "tiled_taper": taper of a claiming plan's ranges in per cent; < 0 = the default (A/B)
 void tiled_set_peel(int mode);      // -1 = by size (default), 0 = never, 1 = wherever the structural conditions hold (tests, A/B)
 void tiled_pad_rows_f64(hipStream_t st, const double* in, double* out, size_t rows, unsigned len, unsigned P, unsigned B);
 void tiled_fold_rows_f64(hipStream_t st, const double* zt, double* z, size_t rows, size_t row_lo, size_t row_hi, unsigned Pz,
