@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include <map>
 
 #include "gft_kernels.hpp"
+#include "gft_pair_plan.hpp"
 
 namespace gft {
 
@@ -724,37 +726,7 @@ __global__ void __launch_bounds__(1024) k_conv_rows_rb(const double* __restrict_
 // interleaved: 4.4 GB at 64^3, written and read once (1 ms each way against the 5 ms saved).
 // MI355X, positive / mixed-sign data (profiles/r04/interval_product.txt): 32^3 1.23 / 2.24 -> 0.22 / 0.39 ms, 48^3 3.03 / 5.44
 // -> 1.19 / 2.50, 64^3 10.5 / 19.3 -> 5.0 / 10.6, 72^3 24.6 / 49.1 -> 9.0 / 19.6, 80^3 28.5 / 59.3 -> 15.7 / 36.3.
-struct PairArgs {
-    unsigned xU, x0, x1, yU, y0, y1, zU, z0, z1;  // canonical outer extents (rank 2: U = axis 0 = 1; rank 3: U = 1)
-    unsigned n2, nx2, n8, nb, nxc;                // row lengths, padded row length, column blocks, x chunks
-    unsigned tsh;                                 // lane tile: T1 = 1 << tsh rows along axis 1, T0 = 64 >> tsh along axis 0
-    unsigned NW, xch;                             // waves and x rows of a phase-1 workgroup
-    unsigned tiles0, tiles1;                      // y tiles along the two lane axes
-    unsigned pitch;                               // LDS row pitch in doubles ((lo, hi) interleaved; pitch / 2 odd)
-    unsigned long long S0, S1;                    // terms summed over all k0 / all k1
-    // Bounded workspace (round 5): a launch covers the output slabs [klo, khi) of the LEADING outer axis only, and its slots
-    // start at slot_base.  band 2: the leading axis is U (rank 4) — the x rows' ju is restricted; band 1: it is axis 0 (rank 3),
-    // a lane axis — the y tile is the WINDOW d0 = klo - j0 + l0 of T0 = khi - klo rows under one j0 (every lane of it pairs with
-    // an output slab of the range), a workgroup's x rows share that j0.  band 0: the whole product (klo = 0).
-    unsigned band, klo, khi;
-    unsigned long long slot_base;
-    // Phase-1 grid: one workgroup per VALID (x rows, y tile) combination, in one dimension (see k_pair_sums): c1tot chunks of
-    // x rows over all tiles of axis 1, s0tot (j0, tile of axis 0) combinations (band 1: j0 from at_lo up, one window each)
-    unsigned c1tot, s0tot, at_lo;
-    unsigned kuf;  // band 1: the slab of U the range lies in (rank 3: 0) — the x rows' ju = kuf - ud for every y slab ud that has one
-};
-// terms of output index k on one axis: j in [max(0, k + 1 - ny), min(k + 1, nx)), and the number of terms of all k' < k
-__host__ __device__ inline unsigned pair_lo(unsigned k, unsigned ny) { return k + 1 > ny ? k + 1 - ny : 0u; }
-__host__ __device__ inline unsigned pair_cnt(unsigned k, unsigned nx, unsigned ny) {
-    const unsigned lo = pair_lo(k, ny), hi = k + 1 < nx ? k + 1 : nx;
-    return hi > lo ? hi - lo : 0u;
-}
-__host__ __device__ inline unsigned long long pair_pre(unsigned k, unsigned nx, unsigned ny) {  // sum_{i < k} pair_cnt(i) (for x, y <= z: no empty k)
-    const unsigned long long kk = k;
-    const unsigned long long A = k <= nx ? kk * (kk + 1) / 2 : (unsigned long long)nx * (nx + 1) / 2 + (kk - nx) * nx;  // sum min(i + 1, nx)
-    const unsigned long long B = k > ny ? (kk - ny) * (kk - ny + 1) / 2 : 0ull;                                   // sum max(0, i + 1 - ny)
-    return A - B;
-}
+// (PairArgs and the per-axis term counts pair_lo / pair_cnt / pair_pre: gft_pair_plan.hpp, with the planner that fills them)
 // slot of the row sum x row (ju, j0, j1) (*) y row (k - j): output rows in row-major order, each row's terms in the reference's
 // order (outer axes lexicographic ascending j) — phase 2 reads every output row's slots as ONE contiguous stream
 __device__ __forceinline__ unsigned long long pair_slot(const PairArgs& g, unsigned ju, unsigned j0, unsigned j1, unsigned ku, unsigned k0,
@@ -1271,299 +1243,140 @@ static PairLanes& pair_lanes() {
     return l;
 }
 
-// The plain full product of large contiguous interval tensors; false = not this kernel's case (nothing launched).
-template <class E>
-static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const double* y, size_t yp, double* z, size_t zp, const ConvArgs& a,
-                         bool pairs_only = false, double pairs_max_macs = 1e300) {
-    const int nd = a.nd;
-    if (nd < 2 || nd > 4) return false;
+static void pair_lanes_fork(hipStream_t st) {  // the lanes wait for everything queued on the product's stream (the operands)
+    PairLanes& L = pair_lanes();
+    hipEvent_t ev = L.fork;
+    hipStream_t a0 = L.st[0], a1 = L.st[1];
+    enqueue_task([=] {
+        lq_note((hipEventRecord)(ev, st), nullptr, "hipEventRecord (row-pair lanes, fork)");
+        lq_note((hipStreamWaitEvent)(a0, ev, 0), nullptr, "hipStreamWaitEvent (row-pair lane 0)");
+        lq_note((hipStreamWaitEvent)(a1, ev, 0), nullptr, "hipStreamWaitEvent (row-pair lane 1)");
+    });
+}
+static void pair_lanes_join(hipStream_t st) {  // the product's stream waits for both lanes
+    PairLanes& L = pair_lanes();
+    hipEvent_t e0 = L.join[0], e1 = L.join[1];
+    hipStream_t a0 = L.st[0], a1 = L.st[1];
+    enqueue_task([=] {
+        lq_note((hipEventRecord)(e0, a0), nullptr, "hipEventRecord (row-pair lane 0)");
+        lq_note((hipEventRecord)(e1, a1), nullptr, "hipEventRecord (row-pair lane 1)");
+        lq_note((hipStreamWaitEvent)(st, e0, 0), nullptr, "hipStreamWaitEvent (row-pair lanes, join)");
+        lq_note((hipStreamWaitEvent)(st, e1, 0), nullptr, "hipStreamWaitEvent (row-pair lanes, join)");
+    });
+}
+
+// One workspace of at least `most` bytes on stream s; false: no memory.
+static bool pair_ws_grow(hipStream_t s, unsigned long long most, PairWs& w) {
+    if (w.bytes >= most) return true;
+    launch_drain();  // (nothing queued may still be using the old block)
+    if (w.p) {
+        (void)(hipStreamSynchronize)(s);
+        (void)(hipFree)(w.p);
+    }
+    w.p = nullptr;
+    w.bytes = 0;
+    if (hipMalloc((void**)&w.p, most) != hipSuccess) {
+        (void)hipGetLastError();
+        w.p = nullptr;
+        return false;
+    }
+    w.bytes = most;
+    return true;
+}
+// The workspaces of a plan's launches, `most` bytes each: the product's stream's, or with two lanes one per lane stream; false:
+// no memory (nothing launched).  The cap bounds what ALL the streams' workspaces hold together: blocks of other streams go
+// when this one's need the room.
+static bool pair_workspaces(hipStream_t st, bool use_lanes, unsigned long long most, PairWs* (&ws)[2]) {
+    const hipStream_t mine[2] = {use_lanes ? pair_lanes().st[0] : st, use_lanes ? pair_lanes().st[1] : st};
+    unsigned long long others = 0, here = 0;
+    for (auto& kv : pair_ws()) {
+        if (kv.first == mine[0] || kv.first == mine[1]) here += std::max<unsigned long long>(kv.second.bytes, most);
+        else others += kv.second.bytes;
+    }
+    if (!pair_ws().count(mine[0])) here += most;
+    if (use_lanes && !pair_ws().count(mine[1])) here += most;
+    if (others && others + here > rb_pairs_cap) {
+        launch_drain();
+        for (auto& kv : pair_ws())
+            if (kv.first != mine[0] && kv.first != mine[1] && kv.second.p) {
+                (void)(hipStreamSynchronize)(kv.first);
+                (void)(hipFree)(kv.second.p);
+                kv.second.p = nullptr;
+                kv.second.bytes = 0;
+            }
+    }
+    ws[0] = ws[1] = nullptr;
+    for (int l = 0; l < (use_lanes ? 2 : 1); ++l) {
+        ws[l] = &pair_ws()[mine[l]];
+        if (!pair_ws_grow(mine[l], most, *ws[l])) return false;
+    }
+    return true;
+}
+
+// What the row-pair form and the fused rows kernel both ask of a product before they look at its shape: plain (from zero, every
+// term, unguarded), of rank 2 - 4; its multiply-adds.
+static bool conv_rows_plain(const ConvArgs& a) {
+    if (a.nd < 2 || a.nd > 4) return false;
     if (a.accumulate || a.j0_min || a.j0_excl || a.j0_desc || !a.inner_from_zero || a.guard) return false;
-    const int P = nd - 2;
-    const unsigned n2 = a.zs[nd - 1], nx2 = a.xs[nd - 1];
-    if (a.ys[nd - 1] != n2 || n2 < 8 || n2 > 256 || nx2 == 0) return false;
-    if (P == 0 && (a.slab_lo != 0 || a.slab_hi != a.zs[0])) return false;
-    // contiguous operands and result
-    size_t xs_ = 1, ys_ = 1, zs_ = 1;
-    for (int ax = nd - 1; ax >= 0; --ax) {
-        if (a.xstr[ax] != xs_ || a.ystr[ax] != ys_ || a.zstr[ax] != zs_) return false;
-        if (a.xs[ax] == 0 || a.ys[ax] == 0 || a.xs[ax] > a.zs[ax] || a.ys[ax] > a.zs[ax]) return false;
-        xs_ *= a.xs[ax];
-        ys_ *= a.ys[ax];
-        zs_ *= a.zs[ax];
-    }
-    const size_t xrows = xs_ / nx2, yrows = ys_ / n2;
-    // worth it from a few 10^7 multiply-adds (two passes over the operands, a block per output row pair)
+    return a.nd > 2 || (a.slab_lo == 0 && a.slab_hi == a.zs[0]);
+}
+static double conv_rows_macs(const ConvArgs& a) {
     double macs = 1.0;
-    for (int ax = 0; ax < nd; ++ax) macs *= 0.5 * (double)a.zs[ax] * (double)std::min(a.xs[ax], a.ys[ax]);
-    // ---- row-pair form
-    bool pairs_ok = (rb_pairs_mode == 2 || (rb_pairs_mode == 1 && macs >= (nd == 2 ? rb_pairs_min_rank2 : rb_pairs_min))) && macs <= pairs_max_macs && n2 <= (E::W == 2 ? 128u : 256u) && a.slab_lo == 0 && a.slab_hi == a.zs[0];
-    for (int ax = 0; ax + 1 < nd; ++ax)
-        if (a.zs[ax] > a.xs[ax] + a.ys[ax] - 1) pairs_ok = false;  // (an output row without terms: the slot prefix sums assume none)
-    if (!a.operands_slack && nx2 % PairCW<E>::value != 0) pairs_ok = false;  // (the scalar loads of x's last chunk read to the chunk's end: a caller's raw buffer may end with the row)
-    if (pairs_ok) {
-        PairArgs g;
-        std::memset(&g, 0, sizeof(g));
-        g.xU = g.x0 = g.x1 = g.yU = g.y0 = g.y1 = g.zU = g.z0 = g.z1 = 1;
-        const int no = nd - 1;
-        if (no == 1) {
-            g.x1 = a.xs[0]; g.y1 = a.ys[0]; g.z1 = a.zs[0];
-        } else if (no == 2) {
-            g.x0 = a.xs[0]; g.y0 = a.ys[0]; g.z0 = a.zs[0];
-            g.x1 = a.xs[1]; g.y1 = a.ys[1]; g.z1 = a.zs[1];
-        } else {
-            g.xU = a.xs[0]; g.yU = a.ys[0]; g.zU = a.zs[0];
-            g.x0 = a.xs[1]; g.y0 = a.ys[1]; g.z0 = a.zs[1];
-            g.x1 = a.xs[2]; g.y1 = a.ys[2]; g.z1 = a.zs[2];
-        }
-        g.n2 = n2;
-        g.nx2 = nx2;
-        g.n8 = (n2 + 7) / 8 * 8;
-        g.nb = g.n8 / 8;
-        g.nxc = (nx2 + 7) / 8;
-        {   // lane tile: the shape with the fewest lanes outside y's rows (ties: the squarest)
-            double best = -1.0;
-            for (unsigned tsh = 0; tsh <= 6; ++tsh) {
-                const unsigned T1 = 1u << tsh, T0 = 64u >> tsh;
-                const double e = (double)g.y0 / ((g.y0 + T0 - 1) / T0 * T0) * (double)g.y1 / ((g.y1 + T1 - 1) / T1 * T1);
-                const double pref = e - 1e-6 * (tsh > 3 ? tsh - 3 : 3 - tsh);
-                if (pref > best) {
-                    best = pref;
-                    g.tsh = tsh;
-                }
-            }
-        }
-        const unsigned T1 = 1u << g.tsh, T0 = 64u >> g.tsh;
-        g.tiles0 = (std::min(g.y0, g.z0) + T0 - 1) / T0;  // (y rows at or beyond z's extent pair with nothing)
-        g.tiles1 = (std::min(g.y1, g.z1) + T1 - 1) / T1;
-        g.pitch = E::W * g.n8 + 2;
-        // 16 waves per CU (the kernel holds <= 128 VGPRs): two workgroups of 8 where two tiles fit the LDS, else one of 16
-        g.NW = (size_t)64 * g.pitch * sizeof(double) * 2 + 1024 <= 160 * 1024 ? 8u : 16u;
-        constexpr unsigned PAIR_XCH = 8;  // x rows per phase-1 workgroup (sweep in profiles/r04/interval_pairs_sweep.txt: 4 .. 12 equal, 32 loses 10 % to the last round of workgroups)
-        g.xch = PAIR_XCH;
-        // (small products: fewer x rows per workgroup until there are ~1000 workgroups — half of the (tile, chunk) grid is
-        // outside the triangle)
-        while (g.xch > 1 && (unsigned long long)g.yU * g.tiles0 * g.tiles1 * ((xrows + g.xch - 1) / g.xch) < 2048ull) g.xch /= 2;
-        g.S0 = pair_pre(g.z0, g.x0, g.y0);  // terms over all k0 / all k1
-        g.S1 = pair_pre(g.z1, g.x1, g.y1);
-        const unsigned long long slots = pair_pre(g.zU, g.xU, g.yU) * g.S0 * g.S1;
-        const unsigned long long row_bytes = (unsigned long long)n2 * E::W * sizeof(double);
-        const unsigned long long need = slots * row_bytes;
-        // ---- the plan: one launch pair for the whole product, or slab ranges of the leading outer axis that fit the cap
-        struct Range {
-            unsigned lo, hi, band, ku;  // band 0: the whole product; 2: slabs [lo, hi) of U (rank 4); 1: slabs [lo, hi) of axis 0 inside slab ku of U (rank 3: ku = 0)
-            unsigned long long base, slots;
-        };
-        std::vector<Range> plan;
-        bool plan_ok = slots > 0 && zs_ / n2 <= 0x7fffffffull, use_lanes = false;
-        if (plan_ok && need <= rb_pairs_cap) {
-            plan.push_back(Range{0, 0, 0, 0, 0, slots});
-        } else if (plan_ok && no >= 2) {
-            // Two lanes (see PairLanes) need two workspaces, so each gets half the cap: taken when that does not make the ranges
-            // thinner — then one lane's phase 2 (a few hundred one-wave rows: latency, not bandwidth) runs under the other's phase 1.
-            // MI355X, positive / mixed-sign: 56^3 2.88 / 5.92 -> 2.55 / 5.05 ms, 64^3 5.31 / 11.5 -> 4.92 / 10.2, 72^3 9.40 / 21.0 -> 8.84 / 20.5;
-            // from 80^3 on half the cap halves the window's height and the lanes lose (88^3 29.9 -> 30.4, 96^3 49.8 -> 54.0): off there.
-            const int lanes_on = rb_pairs_lanes;  // 0 never, 1 always, negative: when the ranges stay the same
-            // rank 3: ranges of 1, 2, 4 or 8 slabs of axis 0 (a lane axis: the range's height is the window's).  Rank 4: ranges of slabs
-            // of U where a slab fits the cap, ranges of axis 0 INSIDE a slab of U where it does not (32^4: the top slab alone is 4.6 GB)
-            auto k0_ranges = [&](unsigned ku, size_t range_cap, std::vector<Range>& out) {
-                const unsigned long long cU = pair_cnt(ku, g.xU, g.yU), ubase = pair_pre(ku, g.xU, g.yU) * g.S0 * g.S1;
-                auto sl = [&](unsigned lo, unsigned hi) { return cU * (pair_pre(hi, g.x0, g.y0) - pair_pre(lo, g.x0, g.y0)) * g.S1; };
-                for (unsigned lo = 0; lo < g.z0;) {
-                    unsigned h = 0;
-                    for (unsigned c = 8; c >= 1; c /= 2)
-                        if (lo + c <= g.z0 && sl(lo, lo + c) * row_bytes <= range_cap) {
-                            h = c;
-                            break;
-                        }
-                    if (h == 0) return false;  // (one slab of axis 0 alone exceeds the cap: not this form's product)
-                    out.push_back(Range{lo, lo + h, 1u, ku, ubase + cU * pair_pre(lo, g.x0, g.y0) * g.S1, sl(lo, lo + h)});
-                    lo += h;
-                }
-                return true;
-            };
-            auto make_plan = [&](size_t range_cap, std::vector<Range>& out) {
-                out.clear();
-                if (no == 2) return k0_ranges(0, range_cap, out) && out.size() <= 4096;
-                auto sl = [&](unsigned lo, unsigned hi) { return (pair_pre(hi, g.xU, g.yU) - pair_pre(lo, g.xU, g.yU)) * g.S0 * g.S1; };
-                for (unsigned lo = 0; lo < g.zU;) {
-                    unsigned h = 0;
-                    while (lo + h < g.zU && sl(lo, lo + h + 1) * row_bytes <= range_cap) ++h;
-                    if (h) {
-                        out.push_back(Range{lo, lo + h, 2u, 0u, pair_pre(lo, g.xU, g.yU) * g.S0 * g.S1, sl(lo, lo + h)});
-                        lo += h;
-                    } else {
-                        if (!k0_ranges(lo, range_cap, out)) return false;
-                        lo += 1;
-                    }
-                }
-                return out.size() <= 4096;
-            };
-            plan_ok = make_plan(lanes_on == 1 && pair_lanes().ok ? rb_pairs_cap / 2 : rb_pairs_cap, plan);
-            use_lanes = plan_ok && lanes_on == 1 && pair_lanes().ok;
-            if (plan_ok && lanes_on < 0 && plan.size() >= 2 && pair_lanes().ok) {
-                std::vector<Range> half;
-                if (make_plan(rb_pairs_cap / 2, half) && half.size() == plan.size()) {
-                    plan.swap(half);
-                    use_lanes = true;
-                }
-            }
-        } else
-            plan_ok = false;
-        if (plan_ok) {
-            unsigned long long most = 0;
-            for (const Range& r : plan) most = std::max(most, r.slots * row_bytes);
-            if (plan.size() < 2) use_lanes = false;
-            bool ok = true;
-            PairWs* wsv[2] = {nullptr, nullptr};
-            {   // the cap bounds what ALL the streams' workspaces hold together: blocks of other streams go when this one's need the room
-                hipStream_t mine[2] = {use_lanes ? pair_lanes().st[0] : st, use_lanes ? pair_lanes().st[1] : st};
-                unsigned long long others = 0, here = 0;
-                for (auto& kv : pair_ws()) {
-                    if (kv.first == mine[0] || kv.first == mine[1]) here += std::max<unsigned long long>(kv.second.bytes, most);
-                    else others += kv.second.bytes;
-                }
-                if (!pair_ws().count(mine[0])) here += most;
-                if (use_lanes && !pair_ws().count(mine[1])) here += most;
-                if (others && others + here > rb_pairs_cap) {
-                    launch_drain();
-                    for (auto& kv : pair_ws())
-                        if (kv.first != mine[0] && kv.first != mine[1] && kv.second.p) {
-                            (void)(hipStreamSynchronize)(kv.first);
-                            (void)(hipFree)(kv.second.p);
-                            kv.second.p = nullptr;
-                            kv.second.bytes = 0;
-                        }
-                }
-            }
-            for (int l = 0; l < (use_lanes ? 2 : 1) && ok; ++l) {
-                PairWs& w = pair_ws()[use_lanes ? pair_lanes().st[l] : st];
-                if (w.bytes < most) {
-                    launch_drain();  // (nothing queued may still be using the old block)
-                    if (w.p) {
-                        (void)(hipStreamSynchronize)(use_lanes ? pair_lanes().st[l] : st);
-                        (void)(hipFree)(w.p);
-                    }
-                    w.p = nullptr;
-                    w.bytes = 0;
-                    if (hipMalloc((void**)&w.p, most) != hipSuccess) {
-                        (void)hipGetLastError();
-                        w.p = nullptr;
-                        ok = false;
-                    } else {
-                        w.bytes = most;
-                    }
-                }
-                wsv[l] = &w;
-            }
-            // grid limits (per launch)
-            if (ok) {
-                const size_t lds = (size_t)64 * g.pitch * sizeof(double);
-                static bool attr = false;
-                if (!attr) {
-                    // (the kernel also has 4 bytes of static LDS: the full 160 KB is refused — and a refused call leaves its error
-                    // in this thread's HIP state, where the CALLER's next HIP call finds it)
-                    if (hipFuncSetAttribute((const void*)k_pair_sums<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) (void)hipGetLastError();
-                    attr = true;
-                }
-                constexpr unsigned COLLECT_W = 64;  // threads (output columns) per k_pair_collect workgroup
-                // (checked for every range BEFORE the first launch: a false return promises that nothing was launched)
-                std::vector<PairArgs> gs;
-                std::vector<dim3> grids;
-                std::vector<unsigned long long> rows;
-                for (const Range& r : plan) {
-                    PairArgs q = g;
-                    const unsigned band = r.band;
-                    q.band = band;
-                    q.kuf = r.ku;
-                    q.klo = r.lo;
-                    q.khi = r.hi;
-                    q.slot_base = r.base;
-                    unsigned long long nrows = zs_ / n2, combos = 0;  // (x rows sharing (ju, j0)) x (tiles over U and axis 0)
-                    if (band == 1) {  // window tiles: T0 = the range's height, one per j0; a workgroup's x rows share j0
-                        const unsigned h = r.hi - r.lo;
-                        unsigned tsh = 6;
-                        while ((64u >> tsh) < h) --tsh;
-                        q.tsh = tsh;
-                        const unsigned T1w = 1u << tsh;
-                        q.tiles1 = (std::min(q.y1, q.z1) + T1w - 1) / T1w;
-                        q.tiles0 = std::min(q.x0, r.hi);                       // j0 <= k0 < khi
-                        q.at_lo = r.lo + 1 > q.y0 ? r.lo + 1 - q.y0 : 0u;      // (a compact y: the window of a lower j0 lies above y's last row)
-                        const unsigned ud_lo = r.ku + 1 > q.xU ? r.ku + 1 - q.xU : 0u, ud_hi = std::min(q.yU - 1, r.ku);  // y slabs ud with an x slab ju = ku - ud
-                        combos = q.tiles0 > q.at_lo && ud_hi >= ud_lo ? (unsigned long long)(q.tiles0 - q.at_lo) * (ud_hi - ud_lo + 1) : 0u;
-                        nrows = (unsigned long long)(r.hi - r.lo) * q.z1;
-                    } else {
-                        const unsigned T0w = 64u >> q.tsh;
-                        unsigned long long s0 = 0, sU = 0;
-                        for (unsigned at = 0; at < q.tiles0; ++at) s0 += std::min(q.z0 - T0w * at, q.x0);
-                        for (unsigned ud = 0; ud < std::min(q.yU, q.zU); ++ud) {
-                            unsigned nU = std::min(q.zU - ud, q.xU), ju_lo = 0;
-                            if (band == 2) {
-                                ju_lo = r.lo > ud ? r.lo - ud : 0u;
-                                const unsigned hi = r.hi > ud ? std::min(r.hi - ud, nU) : 0u;
-                                nU = hi > ju_lo ? hi - ju_lo : 0u;
-                            }
-                            sU += nU;
-                        }
-                        q.s0tot = (unsigned)s0;
-                        combos = s0 * sU;
-                        if (band == 2) nrows = (unsigned long long)(r.hi - r.lo) * q.z0 * q.z1;
-                    }
-                    {
-                        const unsigned T1w = 1u << q.tsh;
-                        unsigned long long c1 = 0;
-                        for (unsigned bt = 0; bt < q.tiles1; ++bt) c1 += (std::min(q.z1 - T1w * bt, q.x1) + q.xch - 1) / q.xch;
-                        q.c1tot = (unsigned)c1;
-                    }
-                    const unsigned long long nwg = combos * q.c1tot;
-                    if (nwg == 0 || nwg > 0x7fffffffull || nrows > 0x7fffffffull) ok = false;
-                    gs.push_back(q);
-                    grids.push_back(dim3((unsigned)nwg));
-                    rows.push_back(nrows);
-                }
-                if (ok) {
-                    PairLanes& L = pair_lanes();
-                    if (use_lanes) {  // fork: the lanes wait for everything queued on the product's stream (the operands)
-                        hipEvent_t ev = L.fork;
-                        hipStream_t a0 = L.st[0], a1 = L.st[1];
-                        enqueue_task([=] {
-                            lq_note((hipEventRecord)(ev, st), nullptr, "hipEventRecord (row-pair lanes, fork)");
-                            lq_note((hipStreamWaitEvent)(a0, ev, 0), nullptr, "hipStreamWaitEvent (row-pair lane 0)");
-                            lq_note((hipStreamWaitEvent)(a1, ev, 0), nullptr, "hipStreamWaitEvent (row-pair lane 1)");
-                        });
-                    }
-                    // heaviest ranges first (the top slabs), alternating between the lanes
-                    for (size_t k = plan.size(); k-- > 0;) {
-                        const size_t i = k;
-                        const int l = use_lanes ? (int)((plan.size() - 1 - k) & 1u) : 0;
-                        hipStream_t ls = use_lanes ? L.st[l] : st;
-                        double* wp = wsv[l]->p;
-                        const PairArgs& q = gs[i];
-                        GFT_LAUNCH(k_pair_sums<E>, grids[i], dim3(q.NW * 64), lds, ls, x, xp, y, yp, wp, q);
-                        if (E::W == 1 && n2 >= 64 && n2 % 2 == 0 && !((uintptr_t)z & 15))  // (shorter rows: too few threads per row — 32^3 0.104 -> 0.113 ms; 80^3 7.7 -> 7.1)
-                            GFT_LAUNCH(k_pair_collect2_f64, dim3((unsigned)rows[i], (n2 / 2 + 63) / 64), dim3(64), 0, ls, (const double*)wp, z, q);
-                        else
-                            GFT_LAUNCH(k_pair_collect<E>, dim3((unsigned)rows[i], (n2 + COLLECT_W - 1) / COLLECT_W), dim3(COLLECT_W), 0, ls, (const double*)wp, z, zp, q);
-                    }
-                    if (use_lanes) {  // join: the product's stream waits for both lanes
-                        hipEvent_t e0 = L.join[0], e1 = L.join[1];
-                        hipStream_t a0 = L.st[0], a1 = L.st[1];
-                        enqueue_task([=] {
-                            lq_note((hipEventRecord)(e0, a0), nullptr, "hipEventRecord (row-pair lane 0)");
-                            lq_note((hipEventRecord)(e1, a1), nullptr, "hipEventRecord (row-pair lane 1)");
-                            lq_note((hipStreamWaitEvent)(st, e0, 0), nullptr, "hipStreamWaitEvent (row-pair lanes, join)");
-                            lq_note((hipStreamWaitEvent)(st, e1, 0), nullptr, "hipStreamWaitEvent (row-pair lanes, join)");
-                        });
-                    }
-                    return true;
-                }
-            }
-        }
+    for (int ax = 0; ax < a.nd; ++ax) macs *= 0.5 * (double)a.zs[ax] * (double)std::min(a.xs[ax], a.ys[ax]);
+    return macs;
+}
+static PairShape pair_shape(const ConvArgs& a) { return PairShape{a.nd, a.xs, a.ys, a.zs, a.xstr, a.ystr, a.zstr, a.operands_slack != 0}; }
+
+// The row-pair form (k_pair_sums + k_pair_collect) of the plain full product of contiguous tensors, f64 and interval, of at
+// most max_macs multiply-adds; false = not its case (nothing launched).  The plan — ranges, lanes, grids — is pair_plan's.
+template <class E>
+static bool conv_pairs_run(hipStream_t st, const double* x, size_t xp, const double* y, size_t yp, double* z, size_t zp, const ConvArgs& a, double max_macs) {
+    if (!conv_rows_plain(a) || a.slab_lo != 0 || a.slab_hi != a.zs[0]) return false;
+    // worth it from a few 10^5 multiply-adds (two passes over the operands, a block per output row pair)
+    const double macs = conv_rows_macs(a);
+    if (!(rb_pairs_mode == 2 || (rb_pairs_mode == 1 && macs >= (a.nd == 2 ? rb_pairs_min_rank2 : rb_pairs_min))) || !(macs <= max_macs)) return false;
+    PairPlan plan;
+    if (!pair_plan(pair_shape(a), E::W, PairCW<E>::value, rb_pairs_cap, rb_pairs_lanes, pair_lanes().ok, plan)) return false;
+    PairWs* ws[2];
+    if (!pair_workspaces(st, plan.use_lanes, plan.most, ws)) return false;
+    static bool attr = false;
+    if (!attr) {
+        // (the kernel also has 4 bytes of static LDS: the full 160 KB is refused — and a refused call leaves its error
+        // in this thread's HIP state, where the CALLER's next HIP call finds it)
+        if (hipFuncSetAttribute((const void*)k_pair_sums<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) (void)hipGetLastError();
+        attr = true;
     }
-    if (pairs_only) return false;
-    if constexpr (!E::HAS_POS) {
-        return false;  // (f64: the row-pair form only)
-    } else {
-    if (rb_min_macs < 0.0 || macs < rb_min_macs || n2 < 64) return false;  // (rows shorter than 64: the row-pair form only)
+    constexpr unsigned COLLECT_W = 64;  // threads (output columns) per k_pair_collect workgroup
+    const unsigned n2 = a.zs[a.nd - 1];
+    // (shorter rows: too few threads per row — 32^3 0.104 -> 0.113 ms; 80^3 7.7 -> 7.1)
+    const bool collect2 = E::W == 1 && n2 >= 64 && n2 % 2 == 0 && !((uintptr_t)z & 15);
+    if (plan.use_lanes) pair_lanes_fork(st);
+    // heaviest ranges first (the top slabs), alternating between the lanes
+    for (size_t i = plan.size(); i-- > 0;) {
+        const int l = plan.use_lanes ? (int)((plan.size() - 1 - i) & 1u) : 0;
+        hipStream_t ls = plan.use_lanes ? pair_lanes().st[l] : st;
+        double* wp = ws[l]->p;
+        const PairRange& r = plan[i];
+        GFT_LAUNCH(k_pair_sums<E>, dim3(r.nwg), dim3(r.args.NW * 64), plan.lds, ls, x, xp, y, yp, wp, r.args);
+        if (collect2) GFT_LAUNCH(k_pair_collect2_f64, dim3(r.nrows, (n2 / 2 + 63) / 64), dim3(64), 0, ls, (const double*)wp, z, r.args);
+        else GFT_LAUNCH(k_pair_collect<E>, dim3(r.nrows, (n2 + COLLECT_W - 1) / COLLECT_W), dim3(COLLECT_W), 0, ls, (const double*)wp, z, zp, r.args);
+    }
+    if (plan.use_lanes) pair_lanes_join(st);
+    return true;
+}
+
+// The fused rows kernel (k_row_flags + k_conv_rows_rb) for the plain product of large contiguous interval tensors with rows of
+// 64 .. 256; false = not this kernel's case (nothing launched).
+template <class E>
+static bool conv_rows_fused(hipStream_t st, const double* x, size_t xp, const double* y, size_t yp, double* z, size_t zp, const ConvArgs& a) {
+    static_assert(E::HAS_POS, "interval elements only");
+    const int nd = a.nd, P = nd - 2;
+    if (!conv_rows_plain(a)) return false;
+    const unsigned n2 = a.zs[nd - 1], nx2 = a.xs[nd - 1];
+    if (a.ys[nd - 1] != n2 || n2 < 64 || n2 > 256 || nx2 == 0) return false;  // (rows shorter than 64: the row-pair form only)
+    size_t xrows, yrows, zrows;
+    if (!pair_rows(pair_shape(a), xrows, yrows, zrows)) return false;
+    if (rb_min_macs < 0.0 || conv_rows_macs(a) < rb_min_macs) return false;
     RbArgs g;
     std::memset(&g, 0, sizeof(g));
     g.no = nd - 1;
@@ -1575,9 +1388,9 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
     // groups cut the longest chain of a workgroup (what bounds mid sizes) but leave one workgroup per CU with nothing to
     // overlap its staging with; two groups once the workgroups outnumber the CUs ~6 times (128^3: 257 ms with 2, 299 with 4;
     // 96^3: 77 with 2, 68 with 4)
-    unsigned long long nblk = g.n_pg;
-    for (int ax = 0; ax < P; ++ax) nblk *= ax == 0 ? (a.slab_hi - a.slab_lo) : a.zs[ax];
-    const unsigned want = nblk >= 1536 ? 2u : 4u;
+    unsigned long long blocks = g.n_pg;
+    for (int ax = 0; ax < P; ++ax) blocks *= ax == 0 ? (a.slab_hi - a.slab_lo) : a.zs[ax];
+    const unsigned want = blocks >= 1536 ? 2u : 4u;
     g.tb = std::max(1u, std::min(want, 16u / g.ntw));
     auto lds_of = [&](unsigned tb) {
         return ((size_t)tb * 2 * n2 + 16 + (size_t)(tb + RB_ROWS - 1) * (2 * nx2 + 2) + (2 * tb + RB_ROWS + 8 + 7) / 8 + (size_t)(tb - 1) * g.ntw * 512) *
@@ -1590,8 +1403,6 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
         g.yrs[ax] = a.ystr[ax] / n2;
     }
     // (every "not this kernel" exit comes before the first launch: a false return promises that nothing was launched)
-    unsigned long long blocks = g.n_pg;
-    for (int ax = 0; ax < P; ++ax) blocks *= ax == 0 ? (a.slab_hi - a.slab_lo) : a.zs[ax];
     if (blocks == 0) return true;
     if (blocks > 0x7fffffffULL) return false;
     RbScratch& sc = rb_scratch()[st];
@@ -1622,7 +1433,6 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
     }
     GFT_LAUNCH(k_conv_rows_rb<E>, dim3((unsigned)blocks), dim3(threads), lds, st, x, xp, y, yp, z, zp, a, g);
     return true;
-    }
 }
 
 // The row-pair form alone (k_pair_sums + k_pair_collect) for plain products of at most max_macs multiply-adds; false: not its
@@ -1630,20 +1440,22 @@ static bool conv_rows_rb(hipStream_t st, const double* x, size_t xp, const doubl
 template <class E>
 bool conv_pairs(hipStream_t st, const double* x, size_t xp, const double* y, size_t yp, double* z, size_t zp, const ConvArgs& a, double max_macs) {
     if (a.slab_hi <= a.slab_lo) return false;
-    return conv_rows_rb<E>(st, x, xp, y, yp, z, zp, a, true, max_macs);
+    return conv_pairs_run<E>(st, x, xp, y, yp, z, zp, a, max_macs);
 }
 template bool conv_pairs<EF64>(hipStream_t, const double*, size_t, const double*, size_t, double*, size_t, const ConvArgs&, double);
 template bool conv_pairs<EIv>(hipStream_t, const double*, size_t, const double*, size_t, double*, size_t, const ConvArgs&, double);
 
 // Returns false (nothing launched) when the shape does not suit the staged kernel; the caller then
-// uses conv_naive.  `force`: ignore the "worth it" thresholds (tests).
+// uses conv_naive.
 template <class E>
 bool conv_staged(hipStream_t st, const double* x, size_t xp, const double* y, size_t yp, double* z, size_t zp,
-                 const ConvArgs& a, bool force) {
+                 const ConvArgs& a) {
     const int nd = a.nd;
     if (nd < 1) return false;
     if (a.slab_hi <= a.slab_lo) return true;  // nothing to do
-    if (conv_rows_rb<E>(st, x, xp, y, yp, z, zp, a)) return true;  // (the row-pair form, f64 and interval; the fused rows kernel, interval)
+    if (conv_pairs_run<E>(st, x, xp, y, yp, z, zp, a, HUGE_VAL)) return true;  // (the row-pair form, f64 and interval, of any size)
+    if constexpr (E::HAS_POS)
+        if (conv_rows_fused<E>(st, x, xp, y, yp, z, zp, a)) return true;  // (the fused rows kernel, interval)
     constexpr size_t LDS_MAX = 160 * 1024;
     const size_t W = E::W;
     StagedArgs g;
@@ -1694,7 +1506,6 @@ bool conv_staged(hipStream_t st, const double* x, size_t xp, const double* y, si
     }
     const unsigned long long span = g.sub_hi - g.sub_lo;
     if (span == 0 || n_outer == 0) return true;
-    (void)force;  // every supported shape is at least as fast here as on the one-thread-per-output kernel
     size_t lds = (size_t)(g.xcap + g.ycap) * 8 * W;
     unsigned threads = lds <= 40 * 1024 ? 256 : (lds <= 80 * 1024 ? 512 : 1024);
     // do not use more threads than one balanced chunk needs
@@ -1737,8 +1548,8 @@ bool conv_staged(hipStream_t st, const double* x, size_t xp, const double* y, si
 }
 
 template bool conv_staged<EF64>(hipStream_t, const double*, size_t, const double*, size_t, double*, size_t,
-                                const ConvArgs&, bool);
+                                const ConvArgs&);
 template bool conv_staged<EIv>(hipStream_t, const double*, size_t, const double*, size_t, double*, size_t,
-                               const ConvArgs&, bool);
+                               const ConvArgs&);
 
 }  // namespace gft

@@ -467,9 +467,9 @@ void tiled_fold_rows_f64(hipStream_t st, const double* zt, double* z, size_t row
 
 // LDS-staged reference-order convolution (gft_conv_staged.hip): bit-identical to K<E>::conv_naive, operands
 // staged through LDS once per workgroup step.  Returns false (nothing launched) if the shape does not suit
-// it; `force` ignores the "worth it" thresholds.
+// it.
 template <class E>
 bool conv_staged(hipStream_t st, const double* x, size_t x_plane, const double* y, size_t y_plane, double* z,
-                 size_t z_plane, const ConvArgs& a, bool force);
+                 size_t z_plane, const ConvArgs& a);
 
 }  // namespace gft

@@ -193,14 +193,14 @@
                 if (!guarded) return;  // operands read in place: no zero padding, no verdict, nothing to fall back from
                 a.guard = flag;
                 a.guard_epoch = R.nf_epoch;
-                if (!conv_staged<E>(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, a, false))
+                if (!conv_staged<E>(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, a))
                     K<E>::conv_naive(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, a);
                 return;
             }
             if (R.conv_mode == 2) throw Error("conv_mode=2 (tiled) requested but the shape is not supported by the tiled kernel");
         }
         if (R.conv_mode == 0 || R.conv_mode == 3) {
-            if (conv_staged<E>(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, a, R.conv_mode == 3)) {
+            if (conv_staged<E>(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, a)) {
                 R.stats[4]++;
                 return;
             }
@@ -293,7 +293,7 @@
         ConvArgs g = a;
         g.guard = flag;
         g.guard_epoch = R.nf_epoch;
-        if (!conv_staged<E>(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, g, false))
+        if (!conv_staged<E>(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, g))
             K<E>::conv_naive(R.stream, x.p, x.plane, y.p, y.plane, z.p, z.plane, g);
         return true;
     }

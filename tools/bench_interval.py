@@ -8,7 +8,8 @@ operand can short-circuit, unguarded outward steps validated on the finished sum
 (4 cycles per wave-instruction is what tools/microbench_int64.hip measures for v_lshl_add_u64, v_mul_f64 and v_add_f64 at 8 waves
 per SIMD: 4.4-4.6 cycles at the nominal 2.4 GHz; profiles/r03/microbench_int64.txt.)  Products of 3e5 multiply-adds and more (rank 2: 1e6; rows of at most 128)
 run as row-pair sums (k_pair_sums + k_pair_collect, gft_conv_staged.hip) while their row sums fit 24 GiB (88^3); beyond, from 1.5e10
-multiply-adds, on k_conv_rows_rb, else on k_conv_staged; GFT_RB_PAIRS=0 / GFT_CONV_RB=0 switch the first / second off.
+multiply-adds, on k_conv_rows_rb, else on k_conv_staged; gft_set_option("conv_rb_pairs", 0) / gft_set_option("conv_rb_min_macs", -1)
+switch the first / second off (as tools/bench_interval_shapes.py does).
 Usage: bench_interval.py [n ...]"""
 import sys
 sys.path.insert(0, __file__.rsplit('/', 2)[0])
