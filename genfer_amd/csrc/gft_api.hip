@@ -709,6 +709,12 @@ struct Support {
                 if (v > 0xffffu) b->nz = 0;
     }
 };
+// What a scalar stage does to a zero pattern (interval.rs:164-234).  x * s is [0,0] exactly where x is only for an s that is finite
+// and not [0,0]: [0,0] * s is NaN when a bound of s is infinite or NaN.  x / s is [0,0] exactly where x is for every s — one that
+// contains zero included — except [0,0] ([0,0] / [0,0] is NaN) and NaN.
+static inline bool is_finite2(const double* s) { return (s[0] - s[0] == 0.0) && (s[1] - s[1] == 0.0); }
+static inline bool scale_keeps_zero_pattern(const double* s) { return is_finite2(s) && !(s[0] == 0.0 && s[1] == 0.0); }
+static inline bool quotient_keeps_zero_pattern(const double* s) { return s[0] == s[0] && s[1] == s[1] && !(s[0] == 0.0 && s[1] == 0.0); }
 template <class E>
 static Support support_of_poly(const gft_poly& p) {
     Support s;
@@ -728,6 +734,8 @@ static Support support_of_poly(const gft_poly& p) {
                 const double* sv = p.pend->st[i].s;
                 if ((k == gft::CH_FIRST_ADD || k == gft::CH_FIRST_SUB || k == gft::CH_FIRST_SUB_NEG_ALL) && !(sv[0] == 0.0 && sv[1] == 0.0)) return Support{0};
                 if (k == gft::CH_DIV_S) return Support{0};  // (0 / 0)
+                if ((k == gft::CH_MUL_S || k == gft::CH_LMUL_S) && !is_finite2(sv)) return Support{0};  // (0 * inf; 0 * [0,0] stays all zero)
+                if (k == gft::CH_MUL_TAB) return Support{0};  // (the powers of an m with an infinite bound)
             }
         return s;
     }
@@ -765,15 +773,19 @@ static Support support_of_poly(const gft_poly& p) {
         switch (g.kind) {
             case gft::CH_LMUL_S:
             case gft::CH_MUL_S:
+                if (!scale_keeps_zero_pattern(g.s)) return Support{0};  // x * [0,0]; [0,0] * [.., inf]
+                break;
             case gft::CH_DIV_S:
-                if (g.s[0] == 0.0 && g.s[1] == 0.0) return Support{0};  // x * [0,0]
+                if (!quotient_keeps_zero_pattern(g.s)) return Support{0};  // [0,0] / [0,0]
                 break;
             case gft::CH_MUL_TAB: {
                 TabEntry& t = *g.tab;
                 if (t.nz < 0) {
                     t.nz = 1;
-                    for (size_t k = 0; k < t.len; ++k)
-                        if (t.host[k] == 0.0 && t.host[t.len + k] == 0.0) t.nz = 0;
+                    for (size_t k = 0; k < t.len; ++k) {  // (a power that is [0,0], or one with an infinite bound)
+                        const double e[2] = {t.host[k], t.host[t.len + k]};
+                        if (!scale_keeps_zero_pattern(e)) t.nz = 0;
+                    }
                 }
                 if (!t.nz) return Support{0};
                 break;
@@ -2074,6 +2086,20 @@ static int to_device(const gft_poly& p, double* dst, const int64_t* strides, voi
     gft_poly* PFX##extend(const gft_poly* a, const size_t* ns, size_t n) {                                    \
         return guard([&] { return Ops<E>::extend(*a, dims(ns, n)); });                                        \
     }                                                                                                         \
+    /* (test-only) the zero-pattern claim of THIS handle and its buffer's linearity memo: metadata only (support_of_poly */  \
+    /* may fill TabEntry::nz, a host-side memo of a scaling table's own values: deterministic, nothing is launched)     */  \
+    int PFX##support_claim(const gft_poly* p, size_t* kind, size_t* z, size_t* h, size_t* lin_state) {    \
+        return guard_int([&] {                                                                            \
+            const Support s = support_of_poly<E>(*p);                                                     \
+            *kind = (size_t)s.kind;                                                                       \
+            for (int u = 0; u < Buf::ZAX; ++u) {                                                          \
+                z[u] = s.z[u];                                                                            \
+                h[u] = s.h[u];                                                                            \
+            }                                                                                             \
+            *lin_state = p->buf ? (size_t)p->buf->lin_state : 0;                                          \
+            return 0;                                                                                     \
+        });                                                                                               \
+    }                                                                                                     \
     gft_poly* PFX##mul_var(const gft_poly* a, const double* m, size_t v, const size_t* sh, const size_t* dg, size_t n) { \
         return guard([&] { return Ops<E>::mul_var(*a, m, v, dims(sh, n), dims(dg, n)); });                    \
     }                                                                                                         \

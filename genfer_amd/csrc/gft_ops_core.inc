@@ -370,7 +370,7 @@
         P out = make(out_shape, out_deg, host);
         if (out.numel == 0) return out;
         if (W == 2 && !host && !tab && !keep && (op == OP_COPY || op == OP_MUL_S || op == OP_DIV_S || op == OP_NEG || op == OP_LMUL_S) &&
-            !((op == OP_MUL_S || op == OP_LMUL_S) && s && val_is_zero(s))) {
+            !((op == OP_MUL_S || op == OP_LMUL_S) && s && !scale_keeps_zero_pattern(s)) && !(op == OP_DIV_S && s && !quotient_keeps_zero_pattern(s))) {
             // (round 6, Support) a box of the source that lies inside it keeps the source's zero pattern, seen from its own origin
             Support sp = support_of_poly<E>(src);
             bool inside = sp.exact() && out_shape.size() <= src.shape.size() && out_shape.size() <= (size_t)Buf::ZAX;

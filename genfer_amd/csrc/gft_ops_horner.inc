@@ -548,7 +548,7 @@
             // (round 6, Support) leading zero slabs on the other axes stay where they are; along the substituted axis every
             // position receives a term from the top coefficient slab
             Support sp = support_of_poly<E>(ca);
-            if (sp.exact() && !val_is_zero(c) && !val_is_zero(m)) {
+            if (sp.exact() && scale_keeps_zero_pattern(c) && scale_keeps_zero_pattern(m)) {  // (a zero slab times an infinite bound is NaN)
                 if (v < (size_t)Buf::ZAX) sp.z[v] = 0;
                 sp.kind = 3;
                 sp.normalise();

@@ -511,6 +511,14 @@ gft_poly* gft_truncate_to_degree_p1(const gft_poly* a, size_t degree_p1); /*    
 gft_poly* gft_remove_last_variable(const gft_poly* a);                  /*                        mt:172-181 */
 gft_poly* gft_extend_to_dim(const gft_poly* a, size_t ndim, size_t degree_p1); /* extend          mt:81-89   */
 gft_poly* gft_extend(const gft_poly* a, const size_t* new_size, size_t n); /* (test-only) extend  mt:91-112  */
+/* (test-only) What the library currently claims, without looking at data, about where this handle's tensor holds coefficients
+ * that are exactly [0,0]: kind 0 unknown, 1 measured irregular, 2 none, 3 exactly the leading slabs k_u < z[u],
+ * 4 everything outside the box z[u] <= k_u < h[u], 5 all; z[8] and h[8] per axis (h is 0xffffffff where unbounded), and the
+ * buffer's memoised linearity verdict (0 unknown, 1 not linear, 2 linear; 0 for a handle without a buffer).  Launches nothing,
+ * reads nothing back and changes nothing a program can observe (the one thing it may fill is a host-side memo of whether a
+ * scaling table holds a zero or a non-finite power).  gft_ (F64) has no such claims: kind 0.  Returns 0, or -1 with
+ * gft_last_error() set if the library is not initialised. */
+int gft_support_claim(const gft_poly* p, size_t* kind, size_t* z, size_t* h, size_t* lin_state);
 gft_poly* gft_mul_var(const gft_poly* a, const double* m, size_t v, const size_t* shape,
                       const size_t* degrees_p1, size_t n);              /* mul_var                mt:589-608 */
 gft_poly* gft_mul_linear(const gft_poly* a, const double* c, const double* m, size_t v,
@@ -643,6 +651,7 @@ gft_poly* gfti_truncate_to_degree_p1(const gft_poly* a, size_t degree_p1);
 gft_poly* gfti_remove_last_variable(const gft_poly* a);
 gft_poly* gfti_extend_to_dim(const gft_poly* a, size_t ndim, size_t degree_p1);
 gft_poly* gfti_extend(const gft_poly* a, const size_t* new_size, size_t n);
+int gfti_support_claim(const gft_poly* p, size_t* kind, size_t* z, size_t* h, size_t* lin_state);
 gft_poly* gfti_mul_var(const gft_poly* a, const double* m, size_t v, const size_t* shape,
                        const size_t* degrees_p1, size_t n);
 gft_poly* gfti_mul_linear(const gft_poly* a, const double* c, const double* m, size_t v, const size_t* shape,
