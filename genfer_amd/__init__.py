@@ -23,7 +23,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 from . import series  # noqa: F401  (batched series on device tensors; loads the library on first use)
 from . import interval_series  # noqa: F401  (the same over Interval<F64>: [2, B..., n] tensors)
 from . import series2  # noqa: F401  (batched bivariate series: [B..., n0, n1] tensors)
-from . import series3  # noqa: F401  (batched trivariate series: [B..., n0, n1, n2] tensors; mul / div / exp / log)
+from . import series3  # noqa: F401  (batched trivariate series: [B..., n0, n1, n2] tensors; mul / div / exp / log / compose / pow)
 from . import interval_series2  # noqa: F401  (the same over Interval<F64>: [2, B..., n0, n1] tensors)
 from . import series2_grad  # noqa: F401  (series2's six operations with torch autograd)
 from .taylor import USIZE_MAX, TaylorError, bind  # noqa: F401

@@ -2,7 +2,7 @@
 autograd Functions of ``series`` and ``series2_grad``) describe a call by data and hand it to ``run``.
 
 ``OPS`` is the table of the operations: one row says what travels between the first operand and the result, which side is the long
-one, the operands' names in messages and whether ``var`` travels at rank 2.  The same rows build the ctypes declarations of every
+one, the operands' names in messages and whether ``var`` travels at ranks 2 and 3.  The same rows build the ctypes declarations of every
 ``gft[i]_series[2]_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart.  A ``Call``
 says the rest: the rank (1: the last axis is the series, 2 / 3: the last two / three axes are the coefficient array), ``planes`` (1: interval
 tensors ``[2, B..., item]``, the plane axis travelling as the first entry of every batch-stride array), the limit of the long side
@@ -22,7 +22,7 @@ from .taylor import TaylorError
 # kind: "second" (a second series), "seed" (exp / log: one value per item, or None), "e" (pow's exponent), "k" (the order of an
 # observation op) or None (evaluate_all_one: the result has the batch shape).  long: the side that carries the limit and bounds the
 # others -- the result, or x for the transposed and the observation ops.  names: the operands (and, transposed, the result's
-# order) in messages.  var: the variable travels at rank 2, behind the operands.  label: the function's name in messages.
+# order) in messages.  var: the variable travels at ranks 2 and 3, behind the operands.  label: the function's name in messages.
 Op = namedtuple("Op", "suffix kind long names var label")
 Call = namedtuple("Call", "module rank planes limit raw")  # raw: the module has no autograd and refuses an operand that requires grad
 
@@ -46,7 +46,7 @@ OPS = {o.suffix: o for o in (
     _op("evaluate_all_one", None, long="x"),
 )}
 F64_ONLY = ("corr", "compose_adj")  # no gfti_ twin
-RANK3 = ("mul", "div", "exp", "log")  # gft_series3_*: the four core operations, f64 only
+RANK3 = ("mul", "div", "exp", "log", "compose", "pow")  # gft_series3_*: the core operations, compose and pow, f64 only
 
 
 def _i64(seq):
@@ -82,7 +82,7 @@ def _arguments(op, rank, view, e, var, k, tail):
         a += view("second", False)
     elif op.kind == "e":
         a += e
-    if op.var and rank == 2:
+    if op.var and rank >= 2:
         a += var
     if op.kind == "k":
         a += k
@@ -110,7 +110,8 @@ def _lib():
         for suffix in RANK3:
             f = getattr(L, "gft_series3_" + suffix)
             f.restype = C.c_int
-            f.argtypes = list(_arguments(OPS[suffix], 3, lambda which, lens: _view_types(3, lens), (), (), (), (_SZP, C.c_size_t, C.c_void_p)))
+            f.argtypes = list(_arguments(OPS[suffix], 3, lambda which, lens: _view_types(3, lens), (C.c_uint32,), (C.c_int,), (),
+                                         (_SZP, C.c_size_t, C.c_void_p)))
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
@@ -191,7 +192,7 @@ def _rank_rules(rank):
 
 def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
     """One call of gft[i]_series[2]_<name>.  ``second``: the second series or the seeds; ``scalar``: pow's ``e`` or an observation
-    op's ``k``; ``var``: the variable at rank 2 (already judged by series2._var where it is compose's)."""
+    op's ``k``; ``var``: the variable at ranks 2 and 3 (already judged by series2._var / series3._var where it is compose's)."""
     import torch
 
     op, (module, rank, planes, limit, raw) = OPS[name], call

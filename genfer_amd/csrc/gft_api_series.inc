@@ -3,8 +3,8 @@
 // and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
 // and the bivariate gft_series2_mul / div / exp / log / compose / pow with their Interval<F64> twins gfti_series2_* (the same
 // validation with one row stride per operand), and the f64-only transposed gft_series2_corr / compose_adj
-// and the trivariate gft_series3_mul / div / exp / log (f64 only: a slab stride and a row stride per operand; computed at the
-// stored result shape S on the permuted item of gft::series3_dims)
+// and the trivariate gft_series3_mul / div / exp / log / compose / pow (f64 only: a slab stride and a row stride per operand; computed
+// at the stored result shape S on the permuted item of gft::series3_dims, compose on that of gft::series3_compose_dims)
 // and the observation ops gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one with
 // their gfti_ twins (one operand, the result shorter by the order k on one axis; the kernels: gft_series_observe.hip)
 // Every entry point fills one gft::SeriesCall (gft_series_args.hpp, which judges it without the device) and hands it to series_call.
@@ -40,6 +40,23 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         gft::series_observe(R.stream, op, x, res, d, c.var, (unsigned)c.k, g, pl, tab ? tab->p : nullptr, tlen, c.rank2);
         join_caller_out(cs);
         R.series_last = gft::SERIES_NONE;
+        return 0;
+    }
+    if (c.rank3 && (op == gft::SERIES_COMPOSE || op == gft::SERIES_POW)) {
+        const unsigned nx[3] = {a.s.nx, d.nx0, d.nx1}, n[3] = {a.s.n, d.n0, d.n1};
+        const size_t xs[3] = {a.s.xs, d.xr, 1}, rs[3] = {a.s.rs, d.rr, 1};
+        if (op == gft::SERIES_POW) {
+            Rc<Buf> ws = alloc_doubles(gft::series3_pow_workspace(g.items, n));  // (returned to the pool on exit: later launches follow)
+            join_caller_in(cs);
+            gft::series3_pow(R.stream, x, c.e, res, nx, xs, n, rs, g, ws->p);
+        } else {
+            const gft::Series3Compose k = gft::series3_compose_dims(a, c.var);
+            const gft::Series3Plan plan = gft::series3_compose_plan(k);
+            join_caller_in(cs);
+            gft::series3_compose_launch(R.stream, plan, x, y, res, k, g);
+        }
+        join_caller_out(cs);
+        R.series_last = gft::SERIES_FORM_B;
         return 0;
     }
     if (c.rank3) {  // one form on the permuted item of the stored result shape S; planned before the streams are joined
@@ -154,6 +171,21 @@ static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, in
                          (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.y = rows1(seed, sbs, 1),                            \
                           c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                                      \
     }
+#define GFT_SERIES3_COMPOSE_POW                                                                                                               \
+    int gft_series3_compose(const double* f, const int64_t* fbs, int64_t fss, int64_t frs, size_t nf0, size_t nf1, size_t nf2, const double* g, \
+                            const int64_t* gbs, int64_t gss, int64_t grs, size_t ng0, size_t ng1, size_t ng2, int var, double* res,          \
+                            const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, \
+                            void* stream) {                                                                                                   \
+        GFT_SERIES_ENTRY(SERIES_COMPOSE, "series3_compose", 1, false,                                                                         \
+                         (c.rank3 = true, c.x = rows3(f, fbs, fss, frs, nf0, nf1, nf2), c.y = rows3(g, gbs, gss, grs, ng0, ng1, ng2),         \
+                          c.var = var, c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                         \
+    }                                                                                                                                         \
+    int gft_series3_pow(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, uint32_t e,       \
+                        double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch,      \
+                        size_t nbatch, void* stream) {                                                                                        \
+        GFT_SERIES_ENTRY(SERIES_POW, "series3_pow", 1, false,                                                                                 \
+                         (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.e = e, c.r = rows3(res, rbs, rss, rrs, n0, n1, n2))); \
+    }
 // The arithmetic ops at both ranks.  Interval<F64> (gfti_, W == 2): the same calls on (lo, hi) planes; every batch-stride array has
 // nbatch + 1 entries, the plane stride first.  Rank 2: the last two axes are an item's coefficient array, with a row stride each.
 #define GFT_SERIES_ARITH(PFX, WHAT, W)                                                                                                        \
@@ -213,6 +245,7 @@ GFT_SERIES3_BINARY(gft_series3_mul, SERIES_MUL, "series3_mul")
 GFT_SERIES3_BINARY(gft_series3_div, SERIES_DIV, "series3_div")
 GFT_SERIES3_SEEDED(gft_series3_exp, SERIES_EXP, "series3_exp")
 GFT_SERIES3_SEEDED(gft_series3_log, SERIES_LOG, "series3_log")
+GFT_SERIES3_COMPOSE_POW
 int gft_series_last_form(void) { return R.series_last; }
 }
 #undef GFT_SERIES_ENTRY
@@ -223,6 +256,7 @@ int gft_series_last_form(void) { return R.series_last; }
 #undef GFT_SERIES2_SEEDED
 #undef GFT_SERIES3_BINARY
 #undef GFT_SERIES3_SEEDED
+#undef GFT_SERIES3_COMPOSE_POW
 #undef GFT_SERIES_ARITH
 #undef GFT_SERIES_OBSERVE_K
 #undef GFT_SERIES_OBSERVE

@@ -1,6 +1,7 @@
-// Batched trivariate series (gft_series.hpp, "rank 3"): the planner and the launches of gft_series3_mul / div / exp / log, F64 only.
-// The kernels are in gft_series3_kernels.hpp; gfx950 only.  Nothing about these choices has been measured beyond the table of
-// they are rank 2's (gft_series2.hip), counted the same way.
+// Batched trivariate series (gft_series.hpp, "rank 3"): the planner and the launches of gft_series3_mul / div / exp / log / compose, and
+// pow's sequence of mul launches, F64 only.  The kernels are in gft_series3_kernels.hpp; gfx950 only.  The choices for mul / div / exp /
+// log have not been measured beyond the table of DESIGN 3.22: they are rank 2's (gft_series2.hip), counted the same way; compose's lane
+// count has its own sweep.
 //
 // One form: one workgroup per item for the whole operation, on the permuted item of Series3Dims (the unit axes of S in front).
 //   lanes    one wave while the item has at most 64 units of parallel work, else up to 256 in whole waves: mul counts its output
@@ -11,6 +12,11 @@
 //            rank-2 step of a slab (one row of accumulators, one of row sums) fits inside it.  An item of ONE slab is the rank-2
 //            item and is sized as series2_plan sizes it: rows of n2 doubles, one at least.  Where the runtime grants only 64 KB an
 //            item whose arrays and smallest scratch do not fit is refused by name.
+//            compose: two result arrays of n0 * n1 * n2 doubles taking turns, at most 64 KB, and g compact behind them where the
+//            three fit 64 KB or the grant of that 80 KB request; otherwise g stays in global memory, so every admissible shape runs
+//            on 64 KB.
+// compose's lanes count mul's output pairs of the full shape, in whole waves up to S3_COMPOSE_LANES.  pow has no kernel of its own
+// beside the writer of the unit item.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,11 +33,12 @@ namespace {
 
 constexpr size_t S3_BUDGET = 80 * 1024, S3_BUDGET_PLAIN = 64 * 1024;
 
-// what the runtime grants the three recurrence kernels, asked once
+// what the runtime grants the three recurrence kernels and compose with g resident, asked once
 size_t s3_budget() {
     static size_t granted = 0;
     if (granted) return granted;
-    const void* ks[] = {(const void*)k_series3_rec<SERIES_DIV>, (const void*)k_series3_rec<SERIES_EXP>, (const void*)k_series3_rec<SERIES_LOG>};
+    const void* ks[] = {(const void*)k_series3_rec<SERIES_DIV>, (const void*)k_series3_rec<SERIES_EXP>, (const void*)k_series3_rec<SERIES_LOG>,
+                        (const void*)k_series3_compose<true>};
     granted = S3_BUDGET;
     for (const void* k : ks)
         if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S3_BUDGET) != hipSuccess) {
@@ -42,7 +49,22 @@ size_t s3_budget() {
     return granted;
 }
 
-unsigned s3_threads(unsigned work) { return work <= 64 ? 64u : std::min(256u, (work + 63) / 64 * 64); }
+unsigned s3_threads(unsigned work, unsigned most = 256) { return work <= 64 ? 64u : std::min(most, (work + 63) / 64 * 64); }
+// compose: rank 2's rule (S2_COMPOSE_LANES), whole waves over the output pairs up to two waves a SIMD; the sweep of 256 / 512 / 1024
+// lanes at rank 3 is in DESIGN 3.23 (profiles/r20/series3_compose_lanes.json).
+constexpr unsigned S3_COMPOSE_LANES = 512;
+
+// the unit item of pow: 1.0 at [0, 0, 0] and +0.0 elsewhere, through the result's three strides -- its first factor (one item of one
+// coefficient) and the whole result of e == 0
+__global__ __launch_bounds__(256) void k_series3_unit(double* res, size_t s0, size_t s1, size_t s2, unsigned n0, unsigned n1, unsigned n2,
+                                                      SeriesBatch b) {
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    const unsigned n12 = n1 * n2;
+    for (unsigned idx = threadIdx.x; idx < n0 * n12; idx += blockDim.x) {
+        const unsigned k0 = idx / n12, r = idx - k0 * n12, k1 = r / n2, k2 = r - k1 * n2;
+        res[o.r + (size_t)k0 * s0 + (size_t)k1 * s1 + (size_t)k2 * s2] = idx == 0 ? 1.0 : 0.0;
+    }
+}
 
 }  // namespace
 
@@ -76,6 +98,105 @@ Series3Plan series3_plan(int op, const Series3Dims& d) {
     p.tc = d.n[0] == 1 ? 0 : (unsigned)std::min<size_t>((size_t)terms0 * J1, p.selems / n12);
     p.lds = (resident + p.selems) * elem;
     return p;
+}
+
+Series3Plan series3_compose_plan(const Series3Compose& c) {
+    Series3Plan p;
+    const size_t N = (size_t)c.full[0] * c.full[1] * c.full[2];
+    const size_t arrays = 2 * N * sizeof(double), all = arrays + (size_t)c.ng[0] * c.ng[1] * c.ng[2] * sizeof(double);
+    p.threads = s3_threads((unsigned)((N + 1) / 2), S3_COMPOSE_LANES);
+    p.glds = all <= S3_BUDGET_PLAIN || all <= s3_budget();
+    p.lds = p.glds ? all : arrays;
+    return p;
+}
+
+void series3_compose_launch(hipStream_t st, const Series3Plan& p, const double* f, const double* g, double* res, const Series3Compose& c,
+                            const SeriesBatch& b) {
+    if (b.items == 0) return;
+    const dim3 grid(b.items), block(p.threads);
+    if (p.glds) GFT_LAUNCH(k_series3_compose<true>, grid, block, p.lds, st, f, g, res, c, b);
+    else GFT_LAUNCH(k_series3_compose<false>, grid, block, p.lds, st, f, g, res, c, b);
+}
+
+size_t series3_pow_workspace(unsigned items, const unsigned* n) { return 3 * (size_t)items * n[0] * n[1] * n[2] + 1; }
+
+// series2_pow (gft_series2.hip) with a slab axis
+void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
+                 const SeriesBatch& g, double* ws) {
+    if (g.items == 0) return;
+    const unsigned N = n[0] * n[1] * n[2];
+    if (e == 0) {
+        GFT_LAUNCH(k_series3_unit, dim3(g.items), dim3(s3_threads(N)), 0, st, res, rs[0], rs[1], rs[2], n[0], n[1], n[2], g);
+        return;
+    }
+    // three workspace arrays of items * N doubles each, whatever the compact shape of the items in it, and the unit item
+    const size_t arr = (size_t)g.items * N;
+    double* spare[2] = {ws + arr, ws + 2 * arr};
+    int nspare = 2;
+    double* unit = ws + 3 * arr;
+    SeriesBatch one;
+    one.nd = 0;
+    one.items = 1;
+    GFT_LAUNCH(k_series3_unit, dim3(1), dim3(64), 0, st, unit, (size_t)1, (size_t)1, (size_t)1, 1u, 1u, 1u, one);
+    // the operand, read once through its strides: base = x as compact items of nx
+    double* base = ws;
+    unsigned lb[3] = {nx[0], nx[1], nx[2]};
+    {
+        CopyGeom c;
+        size_t cs = (size_t)lb[0] * lb[1] * lb[2];
+        for (int a = g.nd - 1; a >= 0; --a) {
+            c.ext[a] = g.ext[a];
+            c.ss[a] = g.xs[a];
+            c.ds[a] = cs;
+            cs *= g.ext[a];
+        }
+        int k = g.nd;
+        c.ext[k] = lb[0], c.ss[k] = xs[0], c.ds[k] = (size_t)lb[1] * lb[2], ++k;
+        c.ext[k] = lb[1], c.ss[k] = xs[1], c.ds[k] = lb[2], ++k;
+        c.ext[k] = lb[2], c.ss[k] = 1, c.ds[k] = 1, ++k;
+        c.nd = k;
+        interop_copy(st, x, base, c);
+    }
+    double* acc = unit;  // res of mt:441: [[[1.0]]] for every item until the first product
+    unsigned la[3] = {1, 1, 1};
+    // a * b, compact workspace items of the stored shapes sa and sb (`a` may be the one unit item), into `out`: compact at L, or (last)
+    // the caller's result at all of n
+    auto product = [&](const double* a, const unsigned* sa, const double* b, const unsigned* sb, double* out, const unsigned* L, bool last) {
+        const Series3Dims m = last ? series3_product_dims(sa, sb, n, rs) : series3_product_dims(sa, sb, L);
+        SeriesBatch w = g;
+        w.inplace = 0;
+        const size_t xi = a == unit ? 0 : (size_t)sa[0] * sa[1] * sa[2], yi = (size_t)sb[0] * sb[1] * sb[2], ri = (size_t)L[0] * L[1] * L[2];
+        size_t cs = 1;
+        for (int ax = g.nd - 1; ax >= 0; --ax) {
+            w.xs[ax] = cs * xi;
+            w.ys[ax] = cs * yi;
+            w.ss[ax] = 0;
+            if (!last) w.rs[ax] = cs * ri;
+            cs *= g.ext[ax];
+        }
+        series3_launch(st, SERIES_MUL, series3_plan(SERIES_MUL, m), a, b, out, m, w);
+    };
+    while (e > 0) {
+        unsigned L[3];
+        if (e & 1) {
+            const bool last = (e >> 1) == 0;
+            series3_compact(la, lb, n, L);
+            double* out = last ? res : spare[--nspare];
+            product(acc, la, base, lb, out, L, last);
+            if (acc != unit) spare[nspare++] = acc;
+            acc = out;
+            la[0] = L[0], la[1] = L[1], la[2] = L[2];
+        }
+        e >>= 1;
+        if (e > 0) {
+            series3_compact(lb, lb, n, L);
+            double* out = spare[--nspare];
+            product(base, lb, base, lb, out, L, false);
+            spare[nspare++] = base;
+            base = out;
+            lb[0] = L[0], lb[1] = L[1], lb[2] = L[2];
+        }
+    }
 }
 
 void series3_launch(hipStream_t st, int op, const Series3Plan& p, const double* x, const double* y, double* res, const Series3Dims& d,

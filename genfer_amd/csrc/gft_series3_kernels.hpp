@@ -8,6 +8,7 @@
 // mul_1d(a, b)[k2] = 0.0 + sum_{j2} a[j2] * b[k2 - j2] of two rows, added for j0 ascending and inside it j1 ascending to the ONE
 // accumulator of row (k0, k1): "independent row sums, ordered additions".
 //   mul            a thread owns whole outputs (k0, k1, k2) and runs the three sums; no step depends on another.
+//   compose        the Horner chain of such products, the result resident in LDS from step to step (k_series3_compose).
 //   div, exp, log  slabs k0 one after the other.  The terms of output row k1 are the pairs (j0, j1), numbered t = j0' * J1 + j1'
 //                  with J1 = min(n1, a1) places for j1 of which row k1 uses the first min(k1 + 1, a1).  Pass 1 forms the row sums
 //                  of a chunk of t for every k1 in parallel over (t, k1, k2) into the LDS scratch, pass 2 adds them in ascending
@@ -37,8 +38,8 @@ __device__ inline void s3_stage(typename S2L<E>::T* lds, const double* src, size
     }
 }
 // everything of the caller's n outside S is +0.0 (in the caller's axis order)
-template <class E>
-__device__ inline void s3_zero_fill(double* res, size_t plane, const Series3Dims& d) {
+template <class E, class D>
+__device__ inline void s3_zero_fill(double* res, size_t plane, const D& d) {
     if (d.full[0] == d.keep[0] && d.full[1] == d.keep[1] && d.full[2] == d.keep[2]) return;
     const unsigned f12 = d.full[1] * d.full[2], total = d.full[0] * f12;
     for (unsigned i = threadIdx.x; i < total; i += blockDim.x) {
@@ -52,9 +53,27 @@ __device__ inline void s3_zero_fill(double* res, size_t plane, const Series3Dims
 // z[k0][k1][k2] = 0 + sum_{j0} sum_{j1} (0 + sum_{j2} x[j0][j1][j2] * y[k0-j0][k1-j1][k2-j2]), all ascending over the stored
 // coefficients, the row sum formed first and then added.  x and y staged compactly.  Thread t owns the outputs t and N - 1 - t of
 // the row-major item: a heavy output with a light one, as s2_mul_body pairs them.  Lanes of a wave take consecutive k2.
+// The second factor of s3_mul_out, as S2InLds / S2InGlobal at rank 2: compact in LDS at the pitches of its stored shape, or in global
+// memory at the element strides of its three (permuted) axes -- the innermost one too, which is the row or the slab stride where S has
+// unit axes.  row(i0, i1, k2) is the place of y[i0][i1][k2]; ld(-j2) then reads y[i0][i1][k2 - j2].
 template <class E>
-__device__ inline typename E::V s3_mul_out(const typename S2L<E>::T* xl, const typename S2L<E>::T* yl, const Series3Dims& d, unsigned k0, unsigned k1,
-                                           unsigned k2) {
+struct S3InLds {
+    const typename S2L<E>::T* p;
+    unsigned p0, p1;  // elements from slab to slab and from row to row
+    __device__ S3InLds row(unsigned i0, unsigned i1, unsigned k2) const { return S3InLds{p + (i0 * p0 + i1 * p1) + k2, p0, p1}; }
+    __device__ typename E::V ld(int i) const { return S2L<E>::get(p, i); }
+};
+template <class E>
+struct S3InGlobal {
+    const double* p;
+    size_t plane, s0, s1, s2;
+    __device__ S3InGlobal row(unsigned i0, unsigned i1, unsigned k2) const {
+        return S3InGlobal{p + ((size_t)i0 * s0 + (size_t)i1 * s1 + (size_t)k2 * s2), plane, s0, s1, s2};
+    }
+    __device__ typename E::V ld(int i) const { return E::ld(p + (ptrdiff_t)i * (ptrdiff_t)s2, plane, 0); }
+};
+template <class E, class YA>
+__device__ inline typename E::V s3_mul_out(const typename S2L<E>::T* xl, const YA yl, const Series3Dims& d, unsigned k0, unsigned k1, unsigned k2) {
     typedef typename E::V V;
     const unsigned lo0 = k0 + 1 > d.ny[0] ? k0 + 1 - d.ny[0] : 0, hi0 = k0 + 1 < d.nx[0] ? k0 + 1 : d.nx[0];
     const unsigned lo1 = k1 + 1 > d.ny[1] ? k1 + 1 - d.ny[1] : 0, hi1 = k1 + 1 < d.nx[1] ? k1 + 1 : d.nx[1];
@@ -63,10 +82,10 @@ __device__ inline typename E::V s3_mul_out(const typename S2L<E>::T* xl, const t
     for (unsigned j0 = lo0; j0 < hi0; ++j0)
         for (unsigned j1 = lo1; j1 < hi1; ++j1) {
             const typename S2L<E>::T* xr = xl + (j0 * d.nx[1] + j1) * d.nx[2];
-            const typename S2L<E>::T* yr = yl + ((k0 - j0) * d.ny[1] + (k1 - j1)) * d.ny[2] + k2;
+            const YA yr = yl.row(k0 - j0, k1 - j1, k2);
             V o = E::zero();
 #pragma unroll 4
-            for (unsigned j2 = lo2; j2 < hi2; ++j2) o = E::mac(o, S2L<E>::get(xr, (int)j2), S2L<E>::get(yr, -(int)j2));
+            for (unsigned j2 = lo2; j2 < hi2; ++j2) o = E::mac(o, S2L<E>::get(xr, (int)j2), yr.ld(-(int)j2));
             z = E::addw(z, o);
         }
     return z;
@@ -89,7 +108,7 @@ __device__ inline void s3_mul_body(typename S2L<E>::T* lds, const double* x, con
             const unsigned i = is[h];
             if (h == 1 && i == is[0]) break;  // the middle output of an odd N
             const unsigned k0 = i / n12, r = i - k0 * n12, k1 = r / d.n[2], k2 = r - k1 * d.n[2];
-            E::st(res, pl.r, o.r + (size_t)k0 * d.rs[0] + (size_t)k1 * d.rs[1] + (size_t)k2 * d.rs[2], s3_mul_out<E>(xl, yl, d, k0, k1, k2));
+            E::st(res, pl.r, o.r + (size_t)k0 * d.rs[0] + (size_t)k1 * d.rs[1] + (size_t)k2 * d.rs[2], s3_mul_out<E>(xl, S3InLds<E>{yl, d.ny[1] * d.ny[2], d.ny[2]}, d, k0, k1, k2));
         }
     }
     s3_zero_fill<E>(res + o.r, pl.r, d);
@@ -97,6 +116,87 @@ __device__ inline void s3_mul_body(typename S2L<E>::T* lds, const double* x, con
 __global__ __launch_bounds__(256) void k_series3_mul(const double* x, const double* y, double* res, Series3Dims d, SeriesBatch g) {
     extern __shared__ double s3_lds[];
     s3_mul_body<EF64>(s3_lds, x, y, res, d, g, SeriesPlanes());
+}
+
+// ---- compose (subst_var's Horner path, mt:569-579) ------------------------------------------------------------------------------
+// res = f(g) with g in the place of one variable of f, on the PERMUTED item of Series3Compose (gft_series_args.hpp: the unit axes of
+// the final stored shape S in front, the same for every step).  With `slices` slices of f along that variable's axis, each of the
+// stored shape sl (f's with 1 on the axis):
+//   res = 0.0 + the last slice, stored shape sl;  for i = slices-2 .. 0:  res = mul3(res, g) at the compact shape
+//   L = min(r + ng - 1, n) per axis;  res[index 0 on the axis][inside sl] += slice i
+// s2_compose_body with a slab axis: one workgroup runs the whole chain of its item.  Two result arrays of n0 * n1 * n2 elements take
+// turns in LDS, the current one compact at its own pitches; g sits compact behind them (GLDS) or stays in global memory at its three
+// strides (where 2 N + |g| elements exceed the granted LDS).  Every step is k_series3_mul's pairing on a Series3Dims built for the
+// step: a thread owns the outputs t and M - 1 - t, all bounds the same for every item.  The owner of an output on the added slice
+// loads f's coefficient before its sums and adds it after them.  f and g are read completely before the first store: the result
+// may be f or g itself.
+template <class E, bool GLDS>
+__device__ inline void s3_compose_body(typename S2L<E>::T* lds, const double* f, const double* g, double* res, const Series3Compose& c,
+                                       const SeriesBatch& b, const SeriesPlanes& pl) {
+    typedef typename E::V V;
+    typedef typename S2L<E>::T T;  // res [N] | res [N] | (GLDS) g [ng0][ng1][ng2]
+    const unsigned N = c.full[0] * c.full[1] * c.full[2], tid = threadIdx.x, nt = blockDim.x;
+    T* cur = lds;
+    T* nxt = lds + N;
+    T* gl = lds + 2 * N;
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    const double* fg = f + o.x;
+    if (GLDS) s3_stage<E>(gl, g + o.y, pl.y, c.ys, c.ng);
+    // the stored shape of res: it starts as a slice (1 on the substituted axis, so `inside sl` implies index 0 there)
+    unsigned r0 = c.sl[0], r1 = c.sl[1], r2 = c.sl[2];
+    {
+        const double* fl = fg + (size_t)(c.slices - 1) * c.fslice;
+        const unsigned r12 = r1 * r2, total = r0 * r12;
+        for (unsigned i = tid; i < total; i += nt) {
+            const unsigned k0 = i / r12, q = i - k0 * r12, k1 = q / r2, k2 = q - k1 * r2;
+            S2L<E>::put(cur, i, E::add(E::zero(), E::ld(fl, pl.x, (size_t)k0 * c.xs[0] + (size_t)k1 * c.xs[1] + (size_t)k2 * c.xs[2])));
+        }
+    }
+    __syncthreads();
+    for (unsigned i = c.slices - 1; i-- > 0;) {
+        Series3Dims s;
+        s.nx[0] = r0, s.nx[1] = r1, s.nx[2] = r2;
+        s.ny[0] = c.ng[0], s.ny[1] = c.ng[1], s.ny[2] = c.ng[2];
+        s.n[0] = r0 + c.ng[0] - 1 < c.n[0] ? r0 + c.ng[0] - 1 : c.n[0];
+        s.n[1] = r1 + c.ng[1] - 1 < c.n[1] ? r1 + c.ng[1] - 1 : c.n[1];
+        s.n[2] = r2 + c.ng[2] - 1 < c.n[2] ? r2 + c.ng[2] - 1 : c.n[2];
+        const unsigned m12 = s.n[1] * s.n[2], M = s.n[0] * m12, half = (M + 1) / 2;
+        const double* fi = fg + (size_t)i * c.fslice;
+        for (unsigned t = tid; t < half; t += nt) {
+            const unsigned is[2] = {t, M - 1 - t};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const unsigned idx = is[h];
+                if (h == 1 && idx == is[0]) break;  // the middle output of an odd M
+                const unsigned k0 = idx / m12, q = idx - k0 * m12, k1 = q / s.n[2], k2 = q - k1 * s.n[2];
+                const bool added = k0 < c.sl[0] && k1 < c.sl[1] && k2 < c.sl[2];
+                V fv = E::zero();
+                if (added) fv = E::ld(fi, pl.x, (size_t)k0 * c.xs[0] + (size_t)k1 * c.xs[1] + (size_t)k2 * c.xs[2]);  // in flight during the sums
+                V z;
+                if (GLDS) z = s3_mul_out<E>(cur, S3InLds<E>{gl, c.ng[1] * c.ng[2], c.ng[2]}, s, k0, k1, k2);
+                else z = s3_mul_out<E>(cur, S3InGlobal<E>{g + o.y, pl.y, c.ys[0], c.ys[1], c.ys[2]}, s, k0, k1, k2);
+                if (added) z = E::add(z, fv);
+                S2L<E>::put(nxt, idx, z);
+            }
+        }
+        lds_barrier();
+        T* sw = cur;
+        cur = nxt;
+        nxt = sw;
+        r0 = s.n[0], r1 = s.n[1], r2 = s.n[2];
+    }
+    __syncthreads();  // (every global load of this workgroup is done: the result may be f or g)
+    const unsigned r12 = r1 * r2, total = r0 * r12;  // (r is S: series3_compose_dims walked the same steps)
+    for (unsigned i = tid; i < total; i += nt) {
+        const unsigned k0 = i / r12, q = i - k0 * r12, k1 = q / r2, k2 = q - k1 * r2;
+        E::st(res, pl.r, o.r + (size_t)k0 * c.rs[0] + (size_t)k1 * c.rs[1] + (size_t)k2 * c.rs[2], S2L<E>::get(cur, (int)i));
+    }
+    s3_zero_fill<E>(res + o.r, pl.r, c);
+}
+template <bool GLDS>
+__global__ __launch_bounds__(512) void k_series3_compose(const double* f, const double* g, double* res, Series3Compose c, SeriesBatch b) {
+    extern __shared__ double s3_lds[];
+    s3_compose_body<EF64, GLDS>(s3_lds, f, g, res, c, b, SeriesPlanes());
 }
 
 // ---- div, exp, log --------------------------------------------------------------------------------------------------------------

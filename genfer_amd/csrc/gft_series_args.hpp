@@ -98,7 +98,8 @@ struct SeriesCall {
     const char* fn = "";  // the name in messages
     int w = 1;
     bool rank2 = false;
-    bool rank3 = false;  // gft_series3_*: mul / div / exp / log on F64; the limit bounds slabs * len0 * len1 of the result
+    bool rank3 = false;  // gft_series3_*: mul / div / exp / log / compose / pow on F64; the limit bounds slabs * len0 * len1 of the
+                         // result; `var`: compose's variable there (0: the slab axis, 1: the row axis, 2: the unit-stride axis)
     uint32_t e = 0;
     int var = 0;
     size_t k = 0;
@@ -172,8 +173,10 @@ static inline bool series_same_view(const SeriesOperand& a, const SeriesOperand&
 static inline void series3_shapes(const SeriesCall& c) {
     using std::to_string;
     const std::string f(c.fn);
-    if (c.w != 1 || c.op > SERIES_LOG) throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
-    const bool binary = c.op == SERIES_MUL || c.op == SERIES_DIV;
+    if (c.w != 1 || c.op > SERIES_POW) throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
+    const bool comp = c.op == SERIES_COMPOSE;
+    if (comp && (c.var < 0 || c.var > 2)) throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable of f that g replaces is 0, 1 or 2)");
+    const bool binary = c.op == SERIES_MUL || c.op == SERIES_DIV || comp;
     auto empty = [](const SeriesView& v) { return v.slabs == 0 || v.len0 == 0 || v.len1 == 0; };
     auto dims = [](const SeriesView& v, const char* sep) { return to_string(v.slabs) + sep + to_string(v.len0) + sep + to_string(v.len1); };
     const SeriesView& L = c.r;
@@ -187,8 +190,8 @@ static inline void series3_shapes(const SeriesCall& c) {
         throw std::runtime_error(f + ": " + who + " has " + dims(s, " x ") + " coefficients, the result " + dims(L, " x ") +
                                  " (an operand is longer than the truncation order)");
     };
-    fits(c.x, "x");
-    if (binary) fits(c.y, "y");
+    fits(c.x, comp ? "f" : "x");
+    if (binary) fits(c.y, comp ? "g" : "y");
 }
 
 static inline void series_shapes(const SeriesCall& c) {
@@ -344,8 +347,9 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
                 continue;
             }
         }
-        // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow at rank 2 the row axis too)
-        const int most = IMAXD - w - (c.rank2 && op == SERIES_POW ? 1 : 0);
+        // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow at rank 2 the row axis too, at
+        // rank 3 the row and the slab axis)
+        const int most = IMAXD - w - (op == SERIES_POW ? (c.rank3 ? 2 : (c.rank2 ? 1 : 0)) : 0);
         if (g.nd == most) throw std::runtime_error(f + ": the batch has more than " + std::to_string(most) + " non-contiguous axes");
         g.ext[g.nd] = (unsigned)e;
         g.xs[g.nd] = sx;
@@ -382,10 +386,9 @@ struct Series3Dims {
     unsigned full[3], keep[3];    // as the caller states them: n and S, for the zero fill
     size_t fs[3];                 // and the result's strides
 };
-static inline Series3Dims series3_dims(int op, const SeriesArgs& a) {
-    const Series2Dims& d = a.d;
-    const unsigned nx[3] = {a.s.nx, d.nx0, d.nx1}, ny[3] = {a.s.ny, d.ny0, d.ny1}, n[3] = {a.s.n, d.n0, d.n1};
-    const size_t xs[3] = {a.s.xs, d.xr, 1}, ys[3] = {a.s.ys, d.yr, 1}, rs[3] = {a.s.rs, d.rr, 1};
+// (on the shapes and element strides in the caller's axis order)
+static inline Series3Dims series3_dims(int op, const unsigned* nx, const unsigned* ny, const unsigned* n, const size_t* xs, const size_t* ys,
+                                       const size_t* rs) {
     Series3Dims k;
     int order[3], m = 0;
     for (int i = 0; i < 3; ++i) {
@@ -407,6 +410,87 @@ static inline Series3Dims series3_dims(int op, const SeriesArgs& a) {
         k.xs[i] = xs[o], k.ys[i] = binary ? ys[o] : 0, k.rs[i] = rs[o];
     }
     return k;
+}
+static inline Series3Dims series3_dims(int op, const SeriesArgs& a) {
+    const Series2Dims& d = a.d;
+    const unsigned nx[3] = {a.s.nx, d.nx0, d.nx1}, ny[3] = {a.s.ny, d.ny0, d.ny1}, n[3] = {a.s.n, d.n0, d.n1};
+    const size_t xs[3] = {a.s.xs, d.xr, 1}, ys[3] = {a.s.ys, d.yr, 1}, rs[3] = {a.s.rs, d.rr, 1};
+    return series3_dims(op, nx, ny, n, xs, ys, rs);
+}
+
+// mul3(a, b, L), the one product compose and pow are made of: series3.mul on two COMPACT (row-major) items of the stored shapes a
+// and b, truncated at L.  The result is compact at L too, or lies at the element strides `rs` (pow's last product, which writes the
+// caller's result).  Both of mul's rules apply through series3_dims: computed on S = min(L, a + b - 1), the unit axes of S in front.
+static inline Series3Dims series3_product_dims(const unsigned* a, const unsigned* b, const unsigned* L, const size_t* rs = nullptr) {
+    const size_t as[3] = {(size_t)a[1] * a[2], a[2], 1}, bs[3] = {(size_t)b[1] * b[2], b[2], 1}, ls[3] = {(size_t)L[1] * L[2], L[2], 1};
+    return series3_dims(SERIES_MUL, a, b, L, as, bs, rs ? rs : ls);
+}
+// the compact shape of a product in compose's and pow's chains: min(a + b - 1, n) per axis (sum_shape)
+static inline void series3_compact(const unsigned* a, const unsigned* b, const unsigned* n, unsigned* L) {
+    for (int i = 0; i < 3; ++i) L[i] = std::min(a[i] + b[i] - 1, n[i]);
+}
+
+// ---- rank 3: compose (subst_var's Horner path) ---------------------------------------------------------------------------------------
+// res = 0.0 + the last slice of f along axis `var` (stored shape: nf with 1 on that axis); for every earlier slice, last to first:
+// res = mul3(res, g, L) at L = series3_compact(res, g, n), then the slice is added into res[index 0 on axis var].  Every product is
+// series3.mul's, so it runs on the permuted item of ITS stored shape L -- and that permutation is the same for every step of a call:
+// L_a == 1 iff n_a == 1, or ng_a == 1 and res started with 1 on the axis (a == var, or nf_a == 1); an axis that starts longer, or that
+// g lengthens, has L_a >= 2 from the first step on and only grows.  So the unit axes of every step are those of the final stored shape
+// S, one permutation (the unit axes of S in front, as in series3_dims) serves the whole loop, and the kernel runs the chain on the
+// permuted item.  series3_compose_dims walks the steps and throws std::logic_error should a step ever disagree.
+struct Series3Compose {
+    unsigned sl[3], ng[3], n[3];  // permuted: a slice of f (nf with 1 on var's axis: where res starts), g's stored shape, the orders n
+    unsigned s[3];                // permuted: the final stored shape S of res
+    size_t xs[3], ys[3], rs[3];   // permuted: the element strides of f, g and the result
+    unsigned slices;              // of f along var, `fslice` elements apart
+    size_t fslice;
+    int var;                      // the permuted position of var
+    unsigned full[3], keep[3];    // as the caller states them: n and S, for the zero fill
+    size_t fs[3];                 // and the result's strides
+};
+static inline Series3Compose series3_compose_dims(const unsigned* nf, const unsigned* ng, const unsigned* n, const size_t* xs, const size_t* ys,
+                                                  const size_t* rs, int var) {
+    if (var < 0 || var > 2) throw std::logic_error("series3_compose_dims: var outside 0 .. 2");
+    Series3Compose k;
+    unsigned r[3] = {nf[0], nf[1], nf[2]}, L[3];
+    r[var] = 1;
+    const unsigned steps = nf[var] - 1;
+    // the final stored shape: every axis is non-decreasing and settles after at most n_a steps
+    unsigned S[3] = {r[0], r[1], r[2]};
+    for (unsigned i = 0; i < steps; ++i) {
+        series3_compact(S, ng, n, L);
+        if (L[0] == S[0] && L[1] == S[1] && L[2] == S[2]) break;
+        S[0] = L[0], S[1] = L[1], S[2] = L[2];
+    }
+    // the invariance of the unit axes over the steps (above)
+    for (unsigned i = 0; i < steps; ++i) {
+        series3_compact(r, ng, n, L);
+        for (int a = 0; a < 3; ++a)
+            if ((L[a] == 1) != (S[a] == 1)) throw std::logic_error("series3_compose_dims: the unit axes of a step differ from those of the final shape");
+        if (L[0] == r[0] && L[1] == r[1] && L[2] == r[2]) break;
+        r[0] = L[0], r[1] = L[1], r[2] = L[2];
+    }
+    int order[3], m = 0;
+    for (int i = 0; i < 3; ++i) k.full[i] = n[i], k.keep[i] = S[i], k.fs[i] = rs[i];
+    for (int i = 0; i < 3; ++i)
+        if (S[i] == 1) order[m++] = i;
+    for (int i = 0; i < 3; ++i)
+        if (S[i] != 1) order[m++] = i;
+    k.var = 0;
+    for (int i = 0; i < 3; ++i) {
+        const int o = order[i];
+        if (o == var) k.var = i;
+        k.sl[i] = o == var ? 1 : nf[o], k.ng[i] = ng[o], k.n[i] = n[o], k.s[i] = S[o];
+        k.xs[i] = xs[o], k.ys[i] = ys[o], k.rs[i] = rs[o];
+    }
+    k.slices = nf[var], k.fslice = xs[var];
+    return k;
+}
+static inline Series3Compose series3_compose_dims(const SeriesArgs& a, int var) {
+    const Series2Dims& d = a.d;
+    const unsigned nf[3] = {a.s.nx, d.nx0, d.nx1}, ng[3] = {a.s.ny, d.ny0, d.ny1}, n[3] = {a.s.n, d.n0, d.n1};
+    const size_t xs[3] = {a.s.xs, d.xr, 1}, ys[3] = {a.s.ys, d.yr, 1}, rs[3] = {a.s.rs, d.rr, 1};
+    return series3_compose_dims(nf, ng, n, xs, ys, rs, var);
 }
 
 }  // namespace gft

@@ -273,7 +273,7 @@ int gft_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t
 int gft_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
                     const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
                     void* stream);                                       /* pow                    mt:433-451   */
-/* ---- batched TRIVARIATE series on caller-owned device tensors (f64 only): mul / div / exp / log ----
+/* ---- batched TRIVARIATE series on caller-owned device tensors (f64 only): mul / div / exp / log / compose / pow ----
  * The last THREE axes of every operand are the coefficient array of one TaylorPoly<F64> in three variables: axis -3 is variable 0
  * (`nx0` slabs, `xss` elements apart), axis -2 variable 1 (`nx1` rows, `xrs` elements apart) -- any non-negative strides -- and
  * axis -1 variable 2 (`nx2` coefficients, UNIT stride).  Per operand the arguments are the pointer, the batch-stride array, the
@@ -324,6 +324,34 @@ int gft_series3_exp(const double* x, const int64_t* xbs, int64_t xss, int64_t xr
 int gft_series3_log(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,
                     const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,
                     const size_t* batch, size_t nbatch, void* stream);   /* log                    mt:1335-1386 */
+/* compose at rank 3: res[b] = f[b] with g[b] substituted for variable `var` of f (0: the slab axis, 1: the row axis, 2: the unit-stride
+ * axis; anything else is refused), f in the place of x (stored shape nf = (nf0, nf1, nf2)) and g in the place of y (ng), truncated at
+ * n = (n0, n1, n2) with nf, ng <= n per axis and n0 * n1 * n2 <= 4096.  With mul3(a, b, L) gft_series3_mul on the stored shapes of a and
+ * b truncated at L -- BOTH of its rules: computed on S = min(L, na + nb - 1), the unit axes of S squeezed -- it is subst_var's general
+ * Horner path (mt:569-579) with none of the shortcuts of subst_var (mt:547-568) or of Mul.  The slices of f are taken along axis var:
+ *   res = 0.0 + the last slice                                     (stored shape r: nf with 1 on axis var)
+ *   for i = nf[var]-2 .. 0:  L_a = min(r_a + ng_a - 1, n_a) per axis, r the stored shape of res (sum_shape);  res = mul3(res, g, L);
+ *                            slice i is added into res[... index 0 on axis var ...] over the slice's stored extent, one addition per
+ *                            coefficient
+ * and the result is res extended with +0.0 to n.  With one slice the result is 0.0 + f padded and g's values are not read.  L_a == 1
+ * holds iff n_a == 1, or ng_a == 1 and res started with 1 on the axis (a == var, or nf_a == 1), so the set of squeezed axes is the same
+ * for every step of a call and is that of the final stored shape.  One kernel, one workgroup per item for the whole loop, the result
+ * resident in LDS from step to step (g beside it where the granted LDS holds both, else read from global memory).  Cost: about
+ * nf[var] * (n0 * n1 * n2)^2 / 8 multiply-adds per item on that one workgroup; no cap is imposed.  The result may be f or g itself (the
+ * same view); any partial overlap is refused.
+ * pow at rank 3: res[b] = x[b]^e for 0 <= e < 2^32 by the reference's square-and-multiply (mt:433-451) without its wasted last squaring,
+ * over mul3 at the compact shapes min(la + lb - 1, n) per axis: res = [[[1.0]]], base = x; while e > 0: if e & 1 then res = mul3(res,
+ * base); e >>= 1; if e > 0 then base = mul3(base, base).  The result is padded with +0.0; e == 0 gives the unit item, e == 1 runs the
+ * loop (0.0 + 1.0 * x, so -0.0 becomes +0.0).  A sequence of gft_series3_mul's launches on pool workspace (3 * items * n0 * n1 * n2 + 1
+ * doubles) inside the one stream-ordered call, no host synchronisation; the result may be x itself.  A batch with more than 10
+ * non-contiguous axes is refused.  gft_series_last_form() reports 2 after either. */
+int gft_series3_compose(const double* f, const int64_t* fbs, int64_t fss, int64_t frs, size_t nf0, size_t nf1, size_t nf2, const double* g,
+                        const int64_t* gbs, int64_t gss, int64_t grs, size_t ng0, size_t ng1, size_t ng2, int var, double* res,
+                        const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch,
+                        void* stream);                                   /* subst_var (Horner)     mt:540-580   */
+int gft_series3_pow(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, uint32_t e,
+                    double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch,
+                    size_t nbatch, void* stream);                        /* pow                    mt:433-451   */
 /* corr at rank 2: the transposed product, the adjoint of gft_series2_mul in the truncated inner product,
  * <mul2(x, y, (g0, g1)), g> = <x, corr2(g, y)> (f64 only; no gfti_ twin, for the reason given at gft_series_corr: a gradient of
  * interval bounds is not defined).  g has stored shape (g0, g1) with g0 * g1 <= 4096, y has (ny0, ny1) <= (g0, g1) per axis, the

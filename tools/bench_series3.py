@@ -7,9 +7,14 @@ For each operation and each (B, n0, n1, n2) it times, between two events on torc
       (the only way to do this before the batched entry points existed),
 and prints one JSON line per case: both times, their ratio, and the GMAC/s of the batched call (multiply-adds of the row
 products, counted over the stored coefficients).  A summary line states the two standing targets of batched calls against the
-loop measured in the same run: at least 10x for B >= 256, no slower than 1.1x for B < 256.
+loop measured in the same run: at least 10x for B >= 256, no slower than 1.1x for B < 256; every row says whether it met its own.
+
+``--ops compose,pow`` times ``series3.compose(f, g, var)`` for var = 0, 1, 2 (f and g of the full shape) and ``series3.pow(x, 5)``
+against the handle loop (``subst_var`` / ``pow``) and, for compose, also against
+  (c) the Python chain of ``series3.mul`` calls with a slice add after each -- the other route a caller had before.
 
     python tools/bench_series3.py > profiles/r17/series3.json
+    python tools/bench_series3.py --ops compose,pow > profiles/r20/series3_compose.json
 """
 import argparse
 import json
@@ -23,18 +28,20 @@ if ROOT not in sys.path:
 
 SHAPES = "4096x4x4x4,65536x2x4x8,1024x8x8x8,256x16x16x16,64x8x8x64,1x16x16x16"
 OPS = "mul,div,exp,log"
+MORE_OPS = "compose,pow"  # on request: three rows per shape for compose (one per variable), one for pow
+POW_E = 5
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--ops", default=OPS, help=f"comma-separated operations out of {OPS} (default: all)")
+    ap.add_argument("--ops", default=OPS, help=f"comma-separated operations out of {OPS},{MORE_OPS} (default: {OPS})")
     ap.add_argument("--shapes", default=SHAPES, help=f"comma-separated BxN0xN1xN2 cases (default {SHAPES})")
     ap.add_argument("--loop-items", type=int, default=256, help="items the per-item loop is timed on (scaled to B)")
     ap.add_argument("--budget-ms", type=float, default=300.0, help="time each leg repeats for, roughly")
     ap.add_argument("--no-loop", action="store_true", help="skip leg (b)")
     args = ap.parse_args(argv)
     for op in args.ops.split(","):
-        if op not in OPS.split(","):
+        if op not in (OPS + "," + MORE_OPS).split(","):
             ap.error(f"unknown operation '{op}'")
     return args
 
@@ -65,6 +72,87 @@ def macs(n):
     return math.prod(k * (k + 1) / 2.0 for k in n)
 
 
+def product_macs(a, b, L):
+    """multiply-adds of the product of two items of the stored shapes a and b truncated at L"""
+    return math.prod(sum(min(k + 1, a[i]) - max(0, k + 1 - b[i]) for k in range(L[i])) for i in range(3))
+
+
+def compose_steps(n, var):
+    """(stored shape of res, compact shape of the product) for every step of compose with f and g of the full shape n"""
+    r = tuple(1 if a == var else n[a] for a in range(3))
+    for _ in range(n[var] - 1):
+        L = tuple(min(r[a] + n[a] - 1, n[a]) for a in range(3))
+        yield r, L
+        r = L
+
+
+def pow_macs(n, e):
+    res, base, total = (1, 1, 1), tuple(n), 0.0
+    compact = lambda a, b: tuple(min(a[i] + b[i] - 1, n[i]) for i in range(3))  # noqa: E731
+    while e > 0:
+        if e & 1:
+            total += product_macs(res, base, compact(res, base))
+            res = compact(res, base)
+        e >>= 1
+        if e > 0:
+            total += product_macs(base, base, compact(base, base))
+            base = compact(base, base)
+    return total
+
+
+def target(B, ratio):
+    """the standing targets of a batched call against the loop, for one row"""
+    return "met" if ratio >= (10.0 if B >= 256 else 1 / 1.1) else "missed"
+
+
+def bench_compose_pow(args, torch, series3, TP, op, B, n, f, g, out, results):
+    """compose: one row per variable; pow: one row at e = POW_E"""
+    for var in (0, 1, 2) if op == "compose" else (None,):
+        if op == "compose":
+            work = sum(product_macs(r, n, L) for r, L in compose_steps(n, var))
+
+            def batched():
+                series3.compose(f, g, var=var, out=out)
+
+            def chain():
+                res = 0.0 + f.narrow(1 + var, n[var] - 1, 1)
+                head = (slice(None),) + tuple(slice(0, 1) if a == var else slice(None) for a in range(3))
+                for i in range(n[var] - 2, -1, -1):
+                    res = series3.mul(res, g, n=tuple(min(res.shape[1 + a] + n[a] - 1, n[a]) for a in range(3)))
+                    res[head] += f.narrow(1 + var, i, 1)
+                out.zero_()
+                out[:, :res.shape[1], :res.shape[2], :res.shape[3]] = res
+        else:
+            work = pow_macs(n, POW_E)
+
+            def batched():
+                series3.pow(f, POW_E, out=out)
+
+        t_batch, reps_a = timed(torch, batched, args.budget_ms)
+        items = min(B, args.loop_items)
+
+        def loop():
+            for b in range(items):
+                p = TP.from_torch(f[b])
+                r = p.subst_var(var, TP.from_torch(g[b])) if op == "compose" else p.pow(POW_E)
+                r.to_torch(out=out[b])
+
+        rec = {"op": op, "B": B, "n0": n[0], "n1": n[1], "n2": n[2], "batched_ms": round(t_batch, 6), "batched_reps": reps_a,
+               "GMACps": round(B * work / (t_batch * 1e-3) / 1e9, 3)}
+        rec.update({"var": var} if op == "compose" else {"e": POW_E})
+        if not args.no_loop:
+            t_loop, reps_b = timed(torch, loop, args.budget_ms)
+            t_loop *= B / items
+            ratio = t_loop / t_batch
+            rec.update({"loop_ms": round(t_loop, 6), "loop_items": items, "loop_reps": reps_b, "loop_over_batched": round(ratio, 3),
+                        "target": target(B, ratio)})
+            if op == "compose":
+                t_chain, reps_c = timed(torch, chain, args.budget_ms)
+                rec.update({"chain_ms": round(t_chain, 6), "chain_reps": reps_c, "chain_over_batched": round(t_chain / t_batch, 3)})
+        results.append(rec)
+        print(json.dumps(rec), flush=True)
+
+
 def main(argv=None):
     args = parse_args(argv)
     import torch
@@ -86,6 +174,9 @@ def main(argv=None):
         y[:, 0, 0, 0] += 2.0
         out = torch.empty((B, *n), dtype=torch.float64, device=dev)
         for op in args.ops.split(","):
+            if op in MORE_OPS.split(","):
+                bench_compose_pow(args, torch, series3, TP, op, B, tuple(n), x, y if op == "compose" else None, out, results)
+                continue
             seed = None
             if op in ("exp", "log"):
                 seed = torch.tensor([getattr(math, op)(v) for v in x[:, 0, 0, 0].cpu().tolist()], dtype=torch.float64).to(dev)
@@ -115,7 +206,8 @@ def main(argv=None):
             if not args.no_loop:
                 t_loop, reps_b = timed(torch, loop, args.budget_ms)
                 t_loop *= B / items
-                rec.update({"loop_ms": round(t_loop, 6), "loop_items": items, "loop_reps": reps_b, "loop_over_batched": round(t_loop / t_batch, 3)})
+                rec.update({"loop_ms": round(t_loop, 6), "loop_items": items, "loop_reps": reps_b, "loop_over_batched": round(t_loop / t_batch, 3),
+                            "target": target(B, t_loop / t_batch)})
             results.append(rec)
             print(json.dumps(rec), flush=True)
     props = torch.cuda.get_device_properties(0)
