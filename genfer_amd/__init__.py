@@ -164,7 +164,7 @@ def run_sgcl(source: str, flags: str = ""):
 OP_STATS = ("linear_scans", "scalar_readbacks", "coefficient_readbacks", "tiled", "staged", "per_output", "host_tier_ops",
             "host_to_device_mirrors")
 OP_STATS_EX = ("launches", "deferred_ops", "chains_materialised", "chain_addsub_launches", "launches_in_place", "shallow_products",
-               "fused_horner_steps", "tiled_peeled", "unused_8", "riders", "fused_observe_adds", "scans_proven", "nested_adds",
+               "fused_horner_steps", "tiled_peeled", "tiled_peel_forked", "riders", "fused_observe_adds", "scans_proven", "nested_adds",
                "graph_executions", "graph_recordings", "batch_launches", "batch_items", "graph_us")
 
 

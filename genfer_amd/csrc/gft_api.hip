@@ -184,7 +184,7 @@ struct Runtime {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     size_t stats_peeled = 0;                // tiled products that took the peel (gft_conv_tiled.hip conv_tiled_peel)
-    size_t stats_side[4] = {0, 0, 0, 0};    // {-, -, recordings that rode along with another launch of their kind, lazy observations fused}
+    size_t stats_side[4] = {0, 0, 0, 0};    // {-, peeled tiled products whose leftover launches ran on the two lanes, recordings that rode along with another launch of their kind, lazy observations fused}
     size_t stats_nz = 0;                    // linearity scans answered by a "no exact zero" proof
     size_t stats_sum = 0;                   // Adds that evaluated a recorded Add of two chains in their own launch (K<E>::chain_nest)
     bool lazy_sum = true;                   // "lazy_sum" / GFT_LAZY_SUM: Adds of two chains are recorded, not launched (Ops::fuse_lazy_sums)
@@ -1462,6 +1462,7 @@ int gft_set_option(const char* name, double value) {
     else if (n == "shallow_pair_min") shallow_set_pair_min(value == -1.0 ? 4096.0 : value);
     else if (n == "tiled_tile") tiled_set_lane_tile((int)value);
     else if (n == "tiled_peel") tiled_set_peel((int)value);
+    else if (n == "tiled_peel_lanes") tiled_set_peel_lanes((int)value);
     else if (n == "tiled_slots") tiled_set_slots((int)value);
     else if (n == "tiled_taper") tiled_set_taper((int)value);
     else if (n == "host_max_elems") R.host_max_elems = value < 0 ? Runtime::HOST_MAX_ELEMS_DEFAULT : (size_t)value;  // < 0: default

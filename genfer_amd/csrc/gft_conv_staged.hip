@@ -1226,44 +1226,7 @@ void staged_release_scratch() {
 // (64^3 in 8 ranges: 7.1 ms against 5.1 ms in one piece).  With the ranges dealt to two streams, each with half the cap as its
 // own workspace, one lane's tails and phase 2 run under the other lane's phase 1.  Fork and join are one event each way per
 // product (HIP events cost ~20 us a pair, tools/microbench_streams.hip: nothing at these sizes).
-struct PairLanes {
-    hipStream_t st[2] = {nullptr, nullptr};
-    hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr};
-    bool ok = false, tried = false;
-};
-static PairLanes& pair_lanes() {
-    static PairLanes l;
-    if (!l.tried) {
-        l.tried = true;
-        l.ok = hipStreamCreateWithFlags(&l.st[0], hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&l.st[1], hipStreamNonBlocking) == hipSuccess &&
-               hipEventCreateWithFlags(&l.fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&l.join[0], hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&l.join[1], hipEventDisableTiming) == hipSuccess;
-        if (!l.ok) (void)hipGetLastError();
-    }
-    return l;
-}
-
-static void pair_lanes_fork(hipStream_t st) {  // the lanes wait for everything queued on the product's stream (the operands)
-    PairLanes& L = pair_lanes();
-    hipEvent_t ev = L.fork;
-    hipStream_t a0 = L.st[0], a1 = L.st[1];
-    enqueue_task([=] {
-        lq_note((hipEventRecord)(ev, st), nullptr, "hipEventRecord (row-pair lanes, fork)");
-        lq_note((hipStreamWaitEvent)(a0, ev, 0), nullptr, "hipStreamWaitEvent (row-pair lane 0)");
-        lq_note((hipStreamWaitEvent)(a1, ev, 0), nullptr, "hipStreamWaitEvent (row-pair lane 1)");
-    });
-}
-static void pair_lanes_join(hipStream_t st) {  // the product's stream waits for both lanes
-    PairLanes& L = pair_lanes();
-    hipEvent_t e0 = L.join[0], e1 = L.join[1];
-    hipStream_t a0 = L.st[0], a1 = L.st[1];
-    enqueue_task([=] {
-        lq_note((hipEventRecord)(e0, a0), nullptr, "hipEventRecord (row-pair lane 0)");
-        lq_note((hipEventRecord)(e1, a1), nullptr, "hipEventRecord (row-pair lane 1)");
-        lq_note((hipStreamWaitEvent)(st, e0, 0), nullptr, "hipStreamWaitEvent (row-pair lanes, join)");
-        lq_note((hipStreamWaitEvent)(st, e1, 0), nullptr, "hipStreamWaitEvent (row-pair lanes, join)");
-    });
-}
+// (The lanes are the library's two shared ones: stream_lanes(), gft_launch.hpp.)
 
 // One workspace of at least `most` bytes on stream s; false: no memory.
 static bool pair_ws_grow(hipStream_t s, unsigned long long most, PairWs& w) {
@@ -1287,7 +1250,7 @@ static bool pair_ws_grow(hipStream_t s, unsigned long long most, PairWs& w) {
 // no memory (nothing launched).  The cap bounds what ALL the streams' workspaces hold together: blocks of other streams go
 // when this one's need the room.
 static bool pair_workspaces(hipStream_t st, bool use_lanes, unsigned long long most, PairWs* (&ws)[2]) {
-    const hipStream_t mine[2] = {use_lanes ? pair_lanes().st[0] : st, use_lanes ? pair_lanes().st[1] : st};
+    const hipStream_t mine[2] = {use_lanes ? stream_lanes().st[0] : st, use_lanes ? stream_lanes().st[1] : st};
     unsigned long long others = 0, here = 0;
     for (auto& kv : pair_ws()) {
         if (kv.first == mine[0] || kv.first == mine[1]) here += std::max<unsigned long long>(kv.second.bytes, most);
@@ -1336,7 +1299,7 @@ static bool conv_pairs_run(hipStream_t st, const double* x, size_t xp, const dou
     const double macs = conv_rows_macs(a);
     if (!(rb_pairs_mode == 2 || (rb_pairs_mode == 1 && macs >= (a.nd == 2 ? rb_pairs_min_rank2 : rb_pairs_min))) || !(macs <= max_macs)) return false;
     PairPlan plan;
-    if (!pair_plan(pair_shape(a), E::W, PairCW<E>::value, rb_pairs_cap, rb_pairs_lanes, pair_lanes().ok, plan)) return false;
+    if (!pair_plan(pair_shape(a), E::W, PairCW<E>::value, rb_pairs_cap, rb_pairs_lanes, stream_lanes().ok, plan)) return false;
     PairWs* ws[2];
     if (!pair_workspaces(st, plan.use_lanes, plan.most, ws)) return false;
     static bool attr = false;
@@ -1350,18 +1313,18 @@ static bool conv_pairs_run(hipStream_t st, const double* x, size_t xp, const dou
     const unsigned n2 = a.zs[a.nd - 1];
     // (shorter rows: too few threads per row — 32^3 0.104 -> 0.113 ms; 80^3 7.7 -> 7.1)
     const bool collect2 = E::W == 1 && n2 >= 64 && n2 % 2 == 0 && !((uintptr_t)z & 15);
-    if (plan.use_lanes) pair_lanes_fork(st);
+    if (plan.use_lanes) lanes_fork(st);
     // heaviest ranges first (the top slabs), alternating between the lanes
     for (size_t i = plan.size(); i-- > 0;) {
         const int l = plan.use_lanes ? (int)((plan.size() - 1 - i) & 1u) : 0;
-        hipStream_t ls = plan.use_lanes ? pair_lanes().st[l] : st;
+        hipStream_t ls = plan.use_lanes ? stream_lanes().st[l] : st;
         double* wp = ws[l]->p;
         const PairRange& r = plan[i];
         GFT_LAUNCH(k_pair_sums<E>, dim3(r.nwg), dim3(r.args.NW * 64), plan.lds, ls, x, xp, y, yp, wp, r.args);
         if (collect2) GFT_LAUNCH(k_pair_collect2_f64, dim3(r.nrows, (n2 / 2 + 63) / 64), dim3(64), 0, ls, (const double*)wp, z, r.args);
         else GFT_LAUNCH(k_pair_collect<E>, dim3(r.nrows, (n2 + COLLECT_W - 1) / COLLECT_W), dim3(COLLECT_W), 0, ls, (const double*)wp, z, zp, r.args);
     }
-    if (plan.use_lanes) pair_lanes_join(st);
+    if (plan.use_lanes) lanes_join(st);
     return true;
 }
 

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "gft_kernels.hpp"
+#include "gft_peel_layout.hpp"
 
 namespace gft {
 
@@ -112,6 +113,9 @@ typedef const double __attribute__((address_space(4))) * cptr_t;
 #endif
 #ifndef GFT_TILED_PEEL_DEFAULT
 #define GFT_TILED_PEEL_DEFAULT -1  // "tiled_peel": -1 auto (by size), 0 never, 1 wherever the structure allows
+#endif
+#ifndef GFT_TILED_PEEL_LANES_DEFAULT
+#define GFT_TILED_PEEL_LANES_DEFAULT -1  // "tiled_peel_lanes": -1 where both leftover launches are persistent, 0 never, 1 wherever a product peels
 #endif
 // auto mode peels products whose two lane axes are at least PEEL_MIN_EXTENT long and whose inner axis at least
 // PEEL_MIN_INNER: the range the sweep covers (profiles/r07/tiled_peel_sweep.txt); a short inner axis leaves the same fixed
@@ -799,6 +803,8 @@ struct Plan {
     TiledArgs base;  // shapes/pitches filled in; pointers to device tables filled in
     unsigned n_wg = 0, n_red = 0, n_slots = 0, NW = 0;  // n_wg: stream-K ranges (one workgroup each unless the launch claims)
     unsigned n_resident = 0;                            // workgroup slots of the device for this kernel (CUs x workgroups per CU)
+    unsigned n_segs = 0;                                // segments of all ranges: n_slots plus the tiles written straight to z
+    bool all_slabs = false;                             // PeelSpec::all_slabs: no tile is written straight to z (n_slots == n_segs)
     size_t lds_bytes = 0;
     void* d_tables = nullptr;
 };
@@ -867,6 +873,7 @@ struct PeelSpec {
     unsigned role = 0;                      // 0 plain, 1 the aligned main part M, 2 / 3 the leftover products L0 / L1
     unsigned cut = 0, lim1 = 0;             // TiledArgs::cut, TiledArgs::lim1
     size_t zsU = 0, zs0 = 0, zs1 = 0, zoff = 0;  // output strides (role 2 / 3; dense otherwise)
+    unsigned all_slabs = 0;                 // role 2 / 3 on a lane: every tile goes through a partial slab (the same cuts)
 };
 
 int& tiled_slots_cap() {  // A/B and test knob ("tiled_slots"): at most this many workgroups per main launch; 0: one per range or
@@ -1131,7 +1138,13 @@ bool cut_ranges(Plan& P, PlanTables& tb) {
             unsigned long long tend = tile_start + tiles[ti].steps;
             unsigned long long e = hi < tend ? hi : tend;
             TileSeg sg = {tiles[ti].u, tiles[ti].a, tiles[ti].b, (unsigned)(pos - tile_start), (unsigned)(e - tile_start), -1};
-            if (sg.step_begin == 0 && sg.step_end == tiles[ti].steps) {
+            // A tile that one range covers is written straight to z — except by a leftover product of a peeled product that
+            // runs on a lane (Plan::all_slabs): its main kernel then runs BESIDE the main part's and the other leftover
+            // product's (conv_tiled_peel), which write the same rows of z, so everything it computes goes through a partial
+            // slab and reaches z in its reduce, in stream order.  Same bits: the reduce forms ((z + 0) + 0) + (0 + acc) where
+            // the direct write forms z + acc, and acc, a chain of fma from +0, is never -0.  (No cut moves; such tiles are
+            // the few short ones at the start of each (u, a) run.)
+            if (!P.all_slabs && sg.step_begin == 0 && sg.step_end == tiles[ti].steps) {
                 tile_direct[ti] = 1;
             } else {
                 sg.dest = (int)n_slots;
@@ -1153,6 +1166,7 @@ bool cut_ranges(Plan& P, PlanTables& tb) {
     }
     P.n_red = (unsigned)tb.red.size();
     P.n_slots = n_slots;
+    P.n_segs = (unsigned)tb.segs.size();
     return true;
 }
 
@@ -1197,6 +1211,7 @@ bool upload_tables(Plan& P, const PlanTables& tb, hipStream_t st) {
 
 bool build_plan(const ConvArgs& a, const Variant& V, const PeelSpec& ps, Plan& P, hipStream_t st) {
     PlanTables tb;
+    P.all_slabs = ps.all_slabs != 0;
     return canonicalise(a, V, ps, P) && cut_ranges(P, tb) && upload_tables(P, tb, st);
 }
 
@@ -1255,6 +1270,10 @@ int& tiled_peel_mode() {  // "tiled_peel": -1 auto, 0 never, 1 wherever the stru
     static int v = GFT_TILED_PEEL_DEFAULT;
     return v;
 }
+int& tiled_peel_lanes_mode() {  // "tiled_peel_lanes": 0 a peeled product stays on one stream, 1 its leftover launches take the lanes, -1 by plan
+    static int v = GFT_TILED_PEEL_LANES_DEFAULT;
+    return v;
+}
 
 // The plan of (problem, variant, peel role) from the cache, built on a miss.  The pointer is good until the cache is next
 // emptied (plan_generation()); nullptr: the tiled kernel does not support the shape.
@@ -1273,7 +1292,7 @@ const Plan* cached_plan(const ConvArgs& a, const Variant& V, const PeelSpec& ps,
     key.v[15] = (unsigned)a.accumulate;
     key.v[16] = (unsigned)(a.j0_min | (a.j0_excl << 8) | (a.j0_desc << 16));
     key.v[17] = V.b128;  // (all a plan takes from the variant is the LDS pitch)
-    key.v[18] = ps.role | (ps.cut << 4) | (ps.lim1 << 8);  // (the leftover products' output strides follow from role and shapes)
+    key.v[18] = ps.role | (ps.cut << 4) | (ps.lim1 << 8) | (ps.all_slabs << 12);  // (the leftover products' output strides follow from role and shapes)
     auto& cache = plan_cache();
     auto it = cache.find(key);
     if (it == cache.end()) {
@@ -1307,37 +1326,63 @@ void zero_claim_words(hipStream_t st, char* wb) {
 }
 
 #ifdef GFT_TILED_DIAG
-// Timeline of one main launch (diagnostic build, GFT_TILED_STAMPS=<file>, launches of at least GFT_TILED_STAMPS_MIN ranges,
-// default 1024): every range stamps its start and end; appended to the file per XCD: ranges run, and when its last range
-// ended relative to the launch's last (microseconds at the 100 MHz of s_memrealtime).  Synchronises: timing runs only.
-void dump_stamps(hipStream_t st, const unsigned long long* d_stamps, unsigned n, unsigned grid, bool claiming) {
-    std::vector<unsigned long long> h(3 * (size_t)n);
-    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(h.data(), d_stamps, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+// Timeline (diagnostic build, GFT_TILED_STAMPS=<file>, products whose first launch has at least GFT_TILED_STAMPS_MIN ranges,
+// default 1024): every range stamps its start and end in absolute s_memrealtime ticks.  A product has up to three main
+// launches (plain: one; peeled: M, L0, L1), each with a stamp area of its own, and ONE dump: per launch and XCD the ranges
+// run and when its last range ended relative to the launch's last, and for every launch after the first when its first
+// range started and its last ended relative to the FIRST launch's last range end (microseconds at 100 MHz).
+// Synchronises: timing runs only.
+constexpr unsigned STAMP_RANGES = 65536;
+unsigned long long* stamp_area(unsigned launch, const Plan& first) {
+    static unsigned long long* d_stamps = nullptr;
+    const char* stamps_min = std::getenv("GFT_TILED_STAMPS_MIN");
+    if (!std::getenv("GFT_TILED_STAMPS") || first.n_wg < (stamps_min ? (unsigned)std::atoi(stamps_min) : 1024u)) return nullptr;
+    if (!d_stamps && hipMalloc((void**)&d_stamps, 3 * (size_t)3 * STAMP_RANGES * sizeof(unsigned long long)) != hipSuccess) d_stamps = nullptr;
+    return d_stamps ? d_stamps + (size_t)launch * 3 * STAMP_RANGES : nullptr;
+}
+struct StampedLaunch {
+    const char* name;
+    const unsigned long long* d_stamps;
+    unsigned n, grid;
+    bool claiming;
+};
+void dump_stamps(hipStream_t st, const StampedLaunch* ls, unsigned n_launches) {
+    if (hipStreamSynchronize(st) != hipSuccess) return;
     FILE* f = std::fopen(std::getenv("GFT_TILED_STAMPS"), "a");
     if (!f) return;
-    unsigned long long t0 = ~0ull, t1 = 0, last[8] = {0}, busy[8] = {0};
-    unsigned cnt[8] = {0};
-    for (unsigned r = 0; r < n; ++r) {
-        const unsigned long long b = h[3 * (size_t)r], e = h[3 * (size_t)r + 1];
-        const unsigned x = (unsigned)h[3 * (size_t)r + 2] & 7u;
-        t0 = std::min(t0, b);
-        t1 = std::max(t1, e);
-        last[x] = std::max(last[x], e);
-        busy[x] += e - b;
-        cnt[x]++;
+    unsigned long long first_end = 0;
+    for (unsigned l = 0; l < n_launches; ++l) {
+        const unsigned n = ls[l].n;
+        std::vector<unsigned long long> h(3 * (size_t)n);
+        if (!ls[l].d_stamps || hipMemcpy(h.data(), ls[l].d_stamps, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) continue;
+        unsigned long long t0 = ~0ull, t1 = 0, last[8] = {0}, busy[8] = {0};
+        unsigned cnt[8] = {0};
+        for (unsigned r = 0; r < n; ++r) {
+            const unsigned long long b = h[3 * (size_t)r], e = h[3 * (size_t)r + 1];
+            const unsigned x = (unsigned)h[3 * (size_t)r + 2] & 7u;
+            t0 = std::min(t0, b);
+            t1 = std::max(t1, e);
+            last[x] = std::max(last[x], e);
+            busy[x] += e - b;
+            cnt[x]++;
+        }
+        std::fprintf(f, "launch %s: %u ranges on %u workgroups (%s), %.1f us from first start to last end\n", ls[l].name, n, ls[l].grid,
+                     ls[l].claiming ? "claiming" : "one range each", (t1 - t0) / 100.0);
+        if (l == 0) first_end = t1;
+        else
+            std::fprintf(f, "  first range starts %+.1f us, last range ends %+.1f us relative to the last range end of launch %s\n",
+                         ((double)t0 - (double)first_end) / 100.0, ((double)t1 - (double)first_end) / 100.0, ls[0].name);
+        for (int x = 0; x < 8; ++x)
+            std::fprintf(f, "  xcd %d: %5u ranges, range time %10.1f us in all, last range ends %8.1f us before the launch's last\n", x, cnt[x],
+                         busy[x] / 100.0, (t1 - last[x]) / 100.0);
     }
-    std::fprintf(f, "launch: %u ranges on %u workgroups (%s), %.1f us from first start to last end\n", n, grid,
-                 claiming ? "claiming" : "one range each", (t1 - t0) / 100.0);
-    for (int x = 0; x < 8; ++x)
-        std::fprintf(f, "  xcd %d: %5u ranges, range time %10.1f us in all, last range ends %8.1f us before the launch's last\n", x, cnt[x],
-                     busy[x] / 100.0, (t1 - last[x]) / 100.0);
     std::fclose(f);
 }
 #endif
 
-// the main kernel of plan P on the filled-in arguments T, then the fixed-order reduce of its split tiles; `claim`: the
-// launch's ticket counters (used if the plan claims)
-bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V, unsigned* claim) {
+// The main kernel of plan P on the filled-in arguments T, on stream st; `claim`: the launch's ticket counters (used if the
+// plan claims).  T leaves with the launch's claim fields set.
+bool launch_plan_main(hipStream_t st, const Plan& P, TiledArgs& T, const Variant& V, unsigned* claim) {
     const unsigned grid = launch_grid(P);
     const bool eighths = V.xcd && P.n_wg % 8 == 0;
     T.n_ranges = P.n_wg;
@@ -1352,13 +1397,7 @@ bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V, u
         T.xcd_remap = eighths ? 1u : 0u;
     }
 #ifdef GFT_TILED_DIAG
-    static unsigned long long* d_stamps = nullptr;
-    const char* stamps_min = std::getenv("GFT_TILED_STAMPS_MIN");
-    T.stamps = nullptr;
-    if (std::getenv("GFT_TILED_STAMPS") && P.n_wg >= (stamps_min ? (unsigned)std::atoi(stamps_min) : 1024u) && P.n_wg <= 65536u) {
-        if (!d_stamps && hipMalloc((void**)&d_stamps, 3 * 65536 * sizeof(unsigned long long)) != hipSuccess) d_stamps = nullptr;
-        T.stamps = d_stamps;
-    }
+    if (P.n_wg > STAMP_RANGES) T.stamps = nullptr;
 #endif
     switch (pick_var(V, P.NW)) {
         case 131: launch_main<131>(st, P, T, grid); break;  // leftover products of a peeled product
@@ -1375,12 +1414,27 @@ bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V, u
 #endif
         default: return false;
     }
-#ifdef GFT_TILED_DIAG
-    if (T.stamps) dump_stamps(st, T.stamps, P.n_wg, grid, grid < P.n_wg);
-#endif
+    return true;
+}
+// the fixed-order reduce of plan P's split tiles, on stream st
+void launch_plan_reduce(hipStream_t st, const Plan& P, const TiledArgs& T) {
     if (P.n_red) {
         GFT_LAUNCH(k_conv_reduce, dim3(P.n_red, T.nb), dim3(256), 0, st, T, P.n_red);
     }
+}
+// both on one stream: the plain product
+bool launch_plan(hipStream_t st, const Plan& P, TiledArgs T, const Variant& V, unsigned* claim) {
+#ifdef GFT_TILED_DIAG
+    T.stamps = stamp_area(0, P);
+#endif
+    if (!launch_plan_main(st, P, T, V, claim)) return false;
+#ifdef GFT_TILED_DIAG
+    if (T.stamps) {
+        const StampedLaunch l = {"plain", T.stamps, P.n_wg, launch_grid(P), plan_claims(P)};
+        dump_stamps(st, &l, 1);
+    }
+#endif
+    launch_plan_reduce(st, P, T);
     return true;
 }
 
@@ -1468,13 +1522,21 @@ bool peel_applies(const ConvArgs& a, const Variant& V) {
 //        wave-uniform axis (no masks), the tile index a a pure batch axis;
 //   L1   rank 4 (u = m, k0c = b, k1c = k0, k2):  z[k0][8b+1+m] += sum_{ju <= m, j} y[j][ju] x[k0-j][8b+1+m-ju] with the
 //        aligned restriction k0 - j <= 8 (k0 / 8) as a per-lane limit on the window row (TiledArgs::lim1).
-// One stream, fixed order (pack, M and its reduce, L0 and its reduce, L1 and its reduce): deterministic.  All three carry
-// the same guard, so a product flagged non-finite is left to the caller's guarded reference-order launch as a whole.
-// Workspace: [ticket counters, if any of the three claims][partial slabs, shared by the three][packed x][packed y][L0 window][L1 scalar + slack][L1 window].
+// z is written in a fixed order, all on the product's stream: M and its reduce, L0 and its reduce, L1 and its reduce —
+// deterministic.  With "tiled_peel_lanes" the leftover products run on plans whose MAIN kernels write nothing but partial
+// slabs (PeelSpec::all_slabs: the same cuts, no tile straight to z) into regions of their own, and read only the operands
+// and what k_pack_peel gathered; those main kernels are issued on the library's two lanes (gft_launch.hpp) beside M: forked
+// behind the pack, joined before L0's reduce, and they fill the wave slots that M's workgroups leave as M's queues run dry
+// (DESIGN 3.1).  z is still written by M, M's reduce, L0's reduce, L1's reduce in that order, and the bits are the same
+// (cut_ranges).  No fork while the stream is being captured, without lanes, or with the option off: then the launches, the
+// plans and their order are what they were without lanes.  All three carry the same guard, so a product flagged non-finite
+// is left to the caller's guarded reference-order launch as a whole.
+// Workspace: gft_peel_layout.hpp — ONE layout, forked or not: the leftover launches' slab regions are sized for a slab per
+// segment (Plan::n_segs, which both kinds of plan share), so a query and the launches after it agree whatever they decide.
 // Returns 1 done (or, for a query, sized), 0 a launch failed, -1 the peel cannot be planned or does not fit the workspace
 // it was given — nothing has been launched and the caller takes the plain plan.
 int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, const Variant& V, void* ws,
-                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded) {
+                    size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded, bool* forked) {
     const unsigned n0 = a.zs[0], n1 = a.zs[1], nI = a.zs[2];
     ConvArgs l0, l1;
     std::memset(&l0, 0, sizeof(l0));
@@ -1490,6 +1552,14 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
         l0.xs[i] = s0x[i]; l0.ys[i] = l0.zs[i] = s0y[i];
         l1.xs[i] = s1x[i]; l1.ys[i] = l1.zs[i] = s1y[i];
     }
+    const int lanes_mode = tiled_peel_lanes_mode();
+    bool can_fork = lanes_mode != 0 && stream_lanes().ok;
+    if (can_fork) {  // (a captured graph with parallel branches is fragile where hardware queues are few)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        if (cs != hipStreamCaptureStatusNone) can_fork = false;
+    }
+    bool fork = can_fork && lanes_mode > 0;
     PeelSpec pm, p0, p1;
     pm.role = 1; pm.cut = 3;
     p0.role = 2; p0.zsU = (size_t)n1 * nI; p0.zs0 = 8 * p0.zsU; p0.zs1 = nI; p0.zoff = p0.zsU;
@@ -1500,41 +1570,55 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
         const Plan* q = cached_plan(a, V, pm, st);
         if (!q) return -1;
         PM = *q;
-        if (!(q = cached_plan(l0, VL, p0, st))) return -1;
-        P0 = *q;
-        if (!(q = cached_plan(l1, VL, p1, st))) return -1;
-        P1 = *q;
+        for (int pass = 0; pass < 2; ++pass) {
+            p0.all_slabs = p1.all_slabs = fork ? 1u : 0u;
+            if (!(q = cached_plan(l0, VL, p0, st))) return -1;
+            P0 = *q;
+            if (!(q = cached_plan(l1, VL, p1, st))) return -1;
+            P1 = *q;
+            // By default the lanes are for leftover launches that are persistent by themselves (more ranges than slots: from
+            // 128^3): those fill M's tail and each other's.  Static ones — one short range per workgroup, 112^3, 128 x 128 x 64
+            // — gain nothing there and pay the fork, the join and their all-slabs reduces: 1.6 - 2 % slower
+            // (profiles/r21/tiled_peel_lanes_sweep.txt).  The cuts, hence the answer, are the same for both kinds of plan.
+            if (fork || !can_fork || !(plan_claims(P0) && plan_claims(P1))) break;
+            fork = true;
+        }
         if (gen == plan_generation()) break;
         if (attempt) return -1;
     }
     const TiledArgs& B = PM.base;
     if (B.tsh != 3) return -1;
-    const size_t n8 = B.nx8;
     const bool claims = plan_claims(PM) || plan_claims(P0) || plan_claims(P1);
-    const Operands o = operand_layout(B, std::max(PM.n_slots, std::max(P0.n_slots, P1.n_slots)), claims, x, y, a.operands_slack);
-    const size_t e_w0 = (size_t)7 * (n0 / 8) * n1 * n8, e_s1 = (size_t)7 * n0 * n8, e_w1 = (size_t)7 * (n1 / 8) * n0 * n8;
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_w0 = o.end, o_s1 = o_w0 + al(e_w0 * sizeof(double)), o_w1 = o_s1 + al((e_s1 + 8) * sizeof(double)),
-                 need = o_w1 + al(e_w1 * sizeof(double)) + 256;
-    if (ws && ws_bytes < need) return -1;  // (sized by a query that could not plan the peel)
-    if (ws_needed) *ws_needed = need;
+    Operands o = operand_layout(B, 0, claims, x, y, a.operands_slack);  // (in place or packed; the offsets are the peel layout's)
+    const size_t slots[3] = {PM.n_slots, P0.n_segs, P1.n_segs};
+    const PeelLayout L = peel_layout_for(slots, n0, n1, B.nx8, claims);
+    o.o_ws = L.o_slab[0];
+    o.o_xp = L.o_xp;
+    o.o_yp = L.o_yp;
+    if (ws && ws_bytes < L.need) return -1;  // (sized by a query that could not plan the peel)
+    if (ws_needed) *ws_needed = L.need;
     if (guarded) *guarded = !o.inplace;
     if (!ws) return 1;  // query
 
+    const hipStream_t st0 = fork ? stream_lanes().st[0] : st, st1 = fork ? stream_lanes().st[1] : st;
+    if (forked) *forked = fork;
+
     char* wb = (char*)ws;
-    double *w0 = (double*)(wb + o_w0), *s1 = (double*)(wb + o_s1), *w1 = (double*)(wb + o_w1);
+    double *w0 = (double*)(wb + L.o_w0), *s1 = (double*)(wb + L.o_s1), *w1 = (double*)(wb + L.o_w1);
     TiledArgs T = B;
-    if (claims) zero_claim_words(st, wb);
+    // the ticket words, the guard word (k_prep_operands) and the gathered operands: all before the fork, the lanes see them
+    if (claims) zero_claim_words(st, wb + L.o_claim);
     bind_operands(st, o, x, y, wb, nf_flag, nf_epoch, T);
     {
-        const size_t tot = e_w0 + e_s1 + e_w1;
+        const size_t tot = L.b_w0 / sizeof(double) + (L.b_s1 / sizeof(double) - 8) + L.b_w1 / sizeof(double);
         GFT_LAUNCH(k_pack_peel, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 4096)), dim3(256), 0, st, x, y, w0, s1, w1, n0, n1,
-                   nI, (unsigned)n8);
+                   nI, B.nx8);
     }
+    if (fork) lanes_fork(st);
     T.z = z;
-    if (!launch_plan(st, PM, T, V, claim_words(wb, 0))) return 0;
     TiledArgs T0 = P0.base, T1 = P1.base;
-    T0.ws = T1.ws = T.ws;
+    T0.ws = (double*)(wb + L.o_slab[1]);
+    T1.ws = (double*)(wb + L.o_slab[2]);
     T0.z = T1.z = z;
     T0.guard = T1.guard = T.guard;
     T0.guard_epoch = T1.guard_epoch = T.guard_epoch;
@@ -1542,15 +1626,46 @@ int conv_tiled_peel(hipStream_t st, const double* x, const double* y, double* z,
     T0.yp = w0;
     T1.xp = s1;
     T1.yp = w1;
-    return launch_plan(st, P0, T0, VL, claim_words(wb, 1)) && launch_plan(st, P1, T1, VL, claim_words(wb, 2)) ? 1 : 0;
+#ifdef GFT_TILED_DIAG
+    T.stamps = stamp_area(0, PM);
+    T0.stamps = stamp_area(1, PM);
+    T1.stamps = stamp_area(2, PM);
+#endif
+    unsigned *const c = claim_words(wb + L.o_claim, 0), *const c0 = claim_words(wb + L.o_claim, 1), *const c1 = claim_words(wb + L.o_claim, 2);
+    if (fork) {
+        // M first: of the launches pending at the fork it is the one the dispatcher should see first
+        const bool ok = launch_plan_main(st, PM, T, V, c) && launch_plan_main(st0, P0, T0, VL, c0) && launch_plan_main(st1, P1, T1, VL, c1);
+        if (ok) launch_plan_reduce(st, PM, T);
+        lanes_join(st);  // (also after a failed launch: the lanes never stay forked)
+        if (!ok) return 0;
+        launch_plan_reduce(st, P0, T0);
+        launch_plan_reduce(st, P1, T1);
+    } else {  // one stream: a leftover launch may write tiles straight to z, so each follows the reduce before it
+        if (!launch_plan_main(st, PM, T, V, c)) return 0;
+        launch_plan_reduce(st, PM, T);
+        if (!launch_plan_main(st, P0, T0, VL, c0)) return 0;
+        launch_plan_reduce(st, P0, T0);
+        if (!launch_plan_main(st, P1, T1, VL, c1)) return 0;
+        launch_plan_reduce(st, P1, T1);
+    }
+#ifdef GFT_TILED_DIAG
+    if (T.stamps) {
+        const StampedLaunch ls[3] = {{"M", T.stamps, PM.n_wg, launch_grid(PM), plan_claims(PM)},
+                                     {"L0", T0.stamps, P0.n_wg, launch_grid(P0), plan_claims(P0)},
+                                     {"L1", T1.stamps, P1.n_wg, launch_grid(P1), plan_claims(P1)}};
+        dump_stamps(st, ls, 3);
+    }
+#endif
+    return 1;
 }
 
 }  // namespace
 
 void tiled_set_peel(int mode) { tiled_peel_mode() = mode < 0 ? -1 : (mode ? 1 : 0); }
+void tiled_set_peel_lanes(int mode) { tiled_peel_lanes_mode() = mode < 0 ? GFT_TILED_PEEL_LANES_DEFAULT : (mode ? 1 : 0); }  // (< 0: the default, by plan)
 
 bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, void* ws, size_t ws_bytes,
-                    size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded, bool* peeled) {
+                    size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded, bool* peeled, bool* forked) {
     bool compact_operands = false;
     if (a.nd >= 2 && a.nd <= 4) {
         const unsigned nb = (a.zs[a.nd - 1] + 7) / 8;
@@ -1558,8 +1673,9 @@ bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z,
     }
     const Variant V = decode_variant(a.variant, compact_operands);
     if (peeled) *peeled = false;
+    if (forked) *forked = false;
     if (peel_applies(a, V)) {
-        const int r = conv_tiled_peel(st, x, y, z, a, V, ws, ws_bytes, ws_needed, nf_flag, nf_epoch, guarded);
+        const int r = conv_tiled_peel(st, x, y, z, a, V, ws, ws_bytes, ws_needed, nf_flag, nf_epoch, guarded, forked);
         if (r >= 0) {
             if (peeled) *peeled = r == 1;
             return r == 1;

@@ -211,6 +211,42 @@ void lq_commit() {
     }
 }
 
+StreamLanes& stream_lanes() {
+    static StreamLanes l;
+    if (!l.tried) {
+        l.tried = true;
+        int least = 0, greatest = 0;  // (numerically: the lowest priority is the largest value)
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
+        l.ok = hipStreamCreateWithPriority(&l.st[0], hipStreamNonBlocking, least) == hipSuccess &&
+               hipStreamCreateWithPriority(&l.st[1], hipStreamNonBlocking, least) == hipSuccess &&
+               hipEventCreateWithFlags(&l.fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&l.join[0], hipEventDisableTiming) == hipSuccess &&
+               hipEventCreateWithFlags(&l.join[1], hipEventDisableTiming) == hipSuccess;
+        if (!l.ok) (void)hipGetLastError();
+    }
+    return l;
+}
+void lanes_fork(hipStream_t st) {
+    StreamLanes& L = stream_lanes();
+    hipEvent_t ev = L.fork;
+    hipStream_t a0 = L.st[0], a1 = L.st[1];
+    enqueue_task([=] {
+        lq_note((hipEventRecord)(ev, st), nullptr, "hipEventRecord (lanes, fork)");
+        lq_note((hipStreamWaitEvent)(a0, ev, 0), nullptr, "hipStreamWaitEvent (lane 0)");
+        lq_note((hipStreamWaitEvent)(a1, ev, 0), nullptr, "hipStreamWaitEvent (lane 1)");
+    });
+}
+void lanes_join(hipStream_t st) {
+    StreamLanes& L = stream_lanes();
+    hipEvent_t e0 = L.join[0], e1 = L.join[1];
+    hipStream_t a0 = L.st[0], a1 = L.st[1];
+    enqueue_task([=] {
+        lq_note((hipEventRecord)(e0, a0), nullptr, "hipEventRecord (lane 0)");
+        lq_note((hipEventRecord)(e1, a1), nullptr, "hipEventRecord (lane 1)");
+        lq_note((hipStreamWaitEvent)(st, e0, 0), nullptr, "hipStreamWaitEvent (lanes, join)");
+        lq_note((hipStreamWaitEvent)(st, e1, 0), nullptr, "hipStreamWaitEvent (lanes, join)");
+    });
+}
+
 
 // ------------------------------------------------------------------------------------------
 // gather: structured strided copy with optional scaling / per-slab table / keep-mask

@@ -441,9 +441,12 @@ enum SumMode { SUM_SEQ = 0, SUM_UNROLL8 = 1, SUM_WAVE = 2 };
 // no guarded fallback launch needed (ConvArgs::operands_slack; round 4) — true otherwise.
 // `peeled` (optional): set to true when the product ran as the aligned main part plus the two leftover products of its
 // diagonal lane triangles (rank 3, full extents; "tiled_peel", tiled_set_peel).
+// `forked` (optional): set to true when the two leftover products' main launches were issued on the library's two lanes
+// (gft_launch.hpp stream_lanes; "tiled_peel_lanes") beside the main part; everything is joined on `st` before this returns
+// its last launch there.
 bool conv_tiled_f64(hipStream_t st, const double* x, const double* y, double* z, const ConvArgs& a, void* ws,
                     size_t ws_bytes, size_t* ws_needed, unsigned* nf_flag, unsigned nf_epoch, bool* guarded = nullptr,
-                    bool* peeled = nullptr);
+                    bool* peeled = nullptr, bool* forked = nullptr);
 
 // Inner-axis splitting helpers for the tiled kernel (see gft_conv_tiled.hip): zero-pad rows to `plen`, and the
 // overlap-add that folds the (Pz, 2B-1) pieces of every row back into a row of zI coefficients.
@@ -461,6 +464,7 @@ void tiled_set_lane_tile(int tsh);  // 0 = planner's choice, 3..6 = force T1 = 1
 void tiled_set_slots(int n);        // "tiled_slots": at most n workgroups per main launch of the tiled product; 0 = no cap (tests, A/B)
 void tiled_set_taper(int pct);      // "tiled_taper": taper of a claiming plan's ranges in per cent; < 0 = the default (A/B)
 void tiled_set_peel(int mode);      // -1 = by size (default), 0 = never, 1 = wherever the structural conditions hold (tests, A/B)
+void tiled_set_peel_lanes(int mode);  // "tiled_peel_lanes": 0 = a peeled product stays on one stream, 1 = its leftover launches take the two lanes, < 0 = the default (1 where both are persistent launches)
 void tiled_pad_rows_f64(hipStream_t st, const double* in, double* out, size_t rows, unsigned len, unsigned P, unsigned B);
 void tiled_fold_rows_f64(hipStream_t st, const double* zt, double* z, size_t rows, size_t row_lo, size_t row_hi, unsigned Pz,
                          unsigned B, unsigned zI, int accumulate, const unsigned* guard, unsigned epoch);

@@ -121,6 +121,24 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, 
     lq_commit();
 }
 
+// The library's two internal LANES: side streams that one product deals independent launches to while its own stream goes
+// on — the slab ranges of a row-pair product (gft_conv_staged.hip), the leftover launches of a peeled tiled product
+// (gft_conv_tiled.hip).  One pair for the whole library: hardware queues are few.  Created on first use, at the LOWEST
+// priority the device offers, so that of two pending launches the one on the product's own stream is placed first (a
+// product that puts all its work on the lanes, the row-pair one, has nothing to compete with).  A use is always
+//   lanes_fork(st) ... launches on stream_lanes().st[0 / 1] ... lanes_join(st)
+// and everything queued on st after the join is ordered behind both lanes; between uses the lanes are idle, so the uses
+// of different products never meet.  ok == false (a stream or an event could not be created): there are no lanes, and the
+// callers keep everything on one stream — never an error.
+struct StreamLanes {
+    hipStream_t st[2] = {nullptr, nullptr};
+    hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr};
+    bool ok = false, tried = false;
+};
+StreamLanes& stream_lanes();     // (creates them on first use: call it on the API thread, not in a queued task)
+void lanes_fork(hipStream_t st);  // queued: both lanes wait for everything queued on st so far
+void lanes_join(hipStream_t st);  // queued: st waits for everything queued on the two lanes so far
+
 }  // namespace gft
 
 #define GFT_LAUNCH(...) ::gft::launch(__VA_ARGS__)

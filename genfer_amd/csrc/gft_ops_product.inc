@@ -160,10 +160,11 @@
                 unsigned* flag = R.next_nf_epoch();
                 bool guarded = true;
                 if (!split) {
-                    bool peeled = false;
-                    if (!conv_tiled_f64(R.stream, tx, ty, tz, ash, R.conv_ws, R.conv_ws_bytes, &need, flag, R.nf_epoch, &guarded, &peeled))
+                    bool peeled = false, forked = false;
+                    if (!conv_tiled_f64(R.stream, tx, ty, tz, ash, R.conv_ws, R.conv_ws_bytes, &need, flag, R.nf_epoch, &guarded, &peeled, &forked))
                         throw Error("tiled convolution launch failed");
                     if (peeled) R.stats_peeled++;
+                    if (forked) R.stats_side[1]++;
                 } else {
                     const ConvArgs& a = ash;  // the (possibly shifted) problem; the guarded fallback below uses the original
                     const double* xsrc = tx;

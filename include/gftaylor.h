@@ -117,7 +117,10 @@ int gft_set_conv_mode(int mode);
  * default 2 GiB), "conv_rb_pairs_lanes" (its slab ranges on two lanes: 0 never, 1 always, negative: the default rule),
  * "tiled_tile" (3..6 force the tiled product's lane tile 8x8 .. 1x64; 0: the planner's choice), "tiled_peel" (the peel of
  * the diagonal lane triangles of rank-3 products of full operands: -1 by size, 0 never, 1 wherever the structure allows;
- * gft_op_stats_ex slot 7 counts the peeled products), "tiled_slots" (at most this many workgroups per main launch of the tiled
+ * gft_op_stats_ex slot 7 counts the peeled products), "tiled_peel_lanes" (0: a peeled product stays on one stream; 1: the
+ * main kernels of its two leftover launches run on the library's two internal lanes beside the main part, joined before
+ * their reduces — the same bits, and never while the stream is being captured; negative: the default, 1 where both leftover
+ * launches have more ranges than the device has workgroup slots, 0 elsewhere; slot 8 counts the products that forked), "tiled_slots" (at most this many workgroups per main launch of the tiled
  * product, which then claim the plan's stream-K ranges; 0: the default, one per range or per resident slot; negative: one per
  * range, the static launch; never changes the cuts, so results do not depend on it), "tiled_taper" (how far the ranges of a
  * claiming plan taper along a queue, in per cent of their mean; negative: the default), "dist_min_macs" (smallest
