@@ -116,13 +116,16 @@ struct SlabDiv<EF64> {
     __device__ explicit SlabDiv(double y) : f(fd_make(y)) {}
     __device__ double operator()(double n) const { return fd_div(n, f); }
     // the three-instruction quotient WITHOUT the window test (the caller checks fast_ok(n) off the critical path and
-    // redoes the row with operator() if some numerator was outside); an exact zero is fine: 0 * r = 0, both residual
-    // steps keep it, and the sign is IEEE's
+    // redoes the row with operator() if some numerator was outside).  +0 is fine: q = +-0 with the quotient's sign, the
+    // residual -d * q + 0 is +0 (the two zeros differ in sign) and +0 * r + q == q.  -0 is NOT when d > 0: q = -0, the
+    // residual (+0) + (-0) is +0, and (+0) + (-0) == +0 where IEEE's -0 / d is -0 — so -0 counts as outside the window
+    // (a row beyond the dividend's box whose partial sums are all zero has the numerators -(+0) = -0:
+    // test_recur_edges_gpu.py, 70x24-decay-compact_dividend).
     __device__ double fast(double n) const {
         const double q = n * f.r;
         return __builtin_fma(__builtin_fma(-f.d, q, n), f.r, q);
     }
-    __device__ bool fast_ok(double n) const { return f.ok && (n == 0.0 || fd_mid(n)); }
+    __device__ bool fast_ok(double n) const { return f.ok && (f64_bits(n) == 0 || fd_mid(n)); }
 };
 
 template <class E>
