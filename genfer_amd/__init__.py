@@ -25,6 +25,7 @@ from . import interval_series  # noqa: F401  (the same over Interval<F64>: [2, B
 from . import series2  # noqa: F401  (batched bivariate series: [B..., n0, n1] tensors)
 from . import series3  # noqa: F401  (batched trivariate series: [B..., n0, n1, n2] tensors; mul / div / exp / log / compose / pow)
 from . import interval_series2  # noqa: F401  (the same over Interval<F64>: [2, B..., n0, n1] tensors)
+from . import interval_series3  # noqa: F401  (series3 over Interval<F64>: [2, B..., n0, n1, n2] tensors)
 from . import series2_grad  # noqa: F401  (series2's six operations with torch autograd)
 from .taylor import USIZE_MAX, TaylorError, bind  # noqa: F401
 

@@ -1,4 +1,5 @@
-"""The one host path of the batched series modules: ``series``, ``series2``, ``series3``, ``interval_series``, ``interval_series2`` (and the
+"""The one host path of the batched series modules: ``series``, ``series2``, ``series3``, ``interval_series``, ``interval_series2``,
+``interval_series3`` (and the
 autograd Functions of ``series`` and ``series2_grad``) describe a call by data and hand it to ``run``.
 
 ``OPS`` is the table of the operations: one row says what travels between the first operand and the result, which side is the long
@@ -46,7 +47,7 @@ OPS = {o.suffix: o for o in (
     _op("evaluate_all_one", None, long="x"),
 )}
 F64_ONLY = ("corr", "compose_adj")  # no gfti_ twin
-RANK3 = ("mul", "div", "exp", "log", "compose", "pow")  # gft_series3_*: the core operations, compose and pow, f64 only
+RANK3 = ("mul", "div", "exp", "log", "compose", "pow")  # gft[i]_series3_*: the core operations, compose and pow
 
 
 def _i64(seq):
@@ -107,11 +108,12 @@ def _lib():
                         f.restype = C.c_int
                         f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,),
                                                      (C.c_size_t,), (_SZP, C.c_size_t, C.c_void_p)))
-        for suffix in RANK3:
-            f = getattr(L, "gft_series3_" + suffix)
-            f.restype = C.c_int
-            f.argtypes = list(_arguments(OPS[suffix], 3, lambda which, lens: _view_types(3, lens), (C.c_uint32,), (C.c_int,), (),
-                                         (_SZP, C.c_size_t, C.c_void_p)))
+        for pre in ("gft_", "gfti_"):
+            for suffix in RANK3:
+                f = getattr(L, pre + "series3_" + suffix)
+                f.restype = C.c_int
+                f.argtypes = list(_arguments(OPS[suffix], 3, lambda which, lens: _view_types(3, lens), (C.c_uint32,), (C.c_int,), (),
+                                             (_SZP, C.c_size_t, C.c_void_p)))
         L.gft_series_last_form.restype, L.gft_series_last_form.argtypes = C.c_int, []
         _declared = L
     return _declared
@@ -159,6 +161,9 @@ def _axes2(t, what, planes=0):
 def _axes3(t, what, planes=0):
     """the three series axes of an operand or of ``out``"""
     if t.dim() < 3 + planes:
+        if planes:
+            raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a trivariate interval series needs at least 4 (the first holds the two "
+                              "planes, the last three are the coefficient array)")
         raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a trivariate series needs at least 3 (the last three are the coefficient array)")
     if 0 in t.shape[-3:]:
         raise TaylorError(f"{what}: a series axis is empty (the last three axes are {tuple(t.shape[-3:])})")

@@ -3,7 +3,7 @@
 // and the first six's Interval<F64> twins gfti_series_* (w == 2: every stride array starts with the lo -> hi plane stride)
 // and the bivariate gft_series2_mul / div / exp / log / compose / pow with their Interval<F64> twins gfti_series2_* (the same
 // validation with one row stride per operand), and the f64-only transposed gft_series2_corr / compose_adj
-// and the trivariate gft_series3_mul / div / exp / log / compose / pow (f64 only: a slab stride and a row stride per operand; computed
+// and the trivariate gft_series3_mul / div / exp / log / compose / pow with their Interval<F64> twins gfti_series3_* (a slab stride and a row stride per operand; computed
 // at the stored result shape S on the permuted item of gft::series3_dims, compose on that of gft::series3_compose_dims)
 // and the observation ops gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one with
 // their gfti_ twins (one operand, the result shorter by the order k on one axis; the kernels: gft_series_observe.hip)
@@ -46,14 +46,14 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         const unsigned nx[3] = {a.s.nx, d.nx0, d.nx1}, n[3] = {a.s.n, d.n0, d.n1};
         const size_t xs[3] = {a.s.xs, d.xr, 1}, rs[3] = {a.s.rs, d.rr, 1};
         if (op == gft::SERIES_POW) {
-            Rc<Buf> ws = alloc_doubles(gft::series3_pow_workspace(g.items, n));  // (returned to the pool on exit: later launches follow)
+            Rc<Buf> ws = alloc_doubles(gft::series3_pow_workspace(g.items, n, w));  // (returned to the pool on exit: later launches follow)
             join_caller_in(cs);
-            gft::series3_pow(R.stream, x, c.e, res, nx, xs, n, rs, g, ws->p);
+            gft::series3_pow(R.stream, x, c.e, res, nx, xs, n, rs, g, ws->p, pl);
         } else {
             const gft::Series3Compose k = gft::series3_compose_dims(a, c.var);
-            const gft::Series3Plan plan = gft::series3_compose_plan(k);
+            const gft::Series3Plan plan = gft::series3_compose_plan(k, w);
             join_caller_in(cs);
-            gft::series3_compose_launch(R.stream, plan, x, y, res, k, g);
+            gft::series3_compose_launch(R.stream, plan, x, y, res, k, g, pl);
         }
         join_caller_out(cs);
         R.series_last = gft::SERIES_FORM_B;
@@ -61,9 +61,9 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
     }
     if (c.rank3) {  // one form on the permuted item of the stored result shape S; planned before the streams are joined
         const gft::Series3Dims k = gft::series3_dims(op, a);
-        const gft::Series3Plan plan = gft::series3_plan(op, k);
+        const gft::Series3Plan plan = gft::series3_plan(op, k, w);
         join_caller_in(cs);
-        gft::series3_launch(R.stream, op, plan, x, y, res, k, g);
+        gft::series3_launch(R.stream, op, plan, x, y, res, k, g, pl);
         join_caller_out(cs);
         R.series_last = gft::SERIES_FORM_B;
         return 0;
@@ -154,38 +154,44 @@ static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, in
             const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {                        \
         GFT_SERIES_ENTRY(OP, FN, W, true, (c.x = rows2(x, xbs, xrs, nx0, nx1), c.y = rows1(seed, sbs, 1), c.r = rows2(res, rbs, rrs, n0, n1))); \
     }
-// rank 3 (f64 only): a slab stride and a row stride per operand, three lengths
-#define GFT_SERIES3_BINARY(SYM, OP, FN)                                                                                                       \
+// rank 3: a slab stride and a row stride per operand, three lengths
+#define GFT_SERIES3_BINARY(SYM, OP, FN, W)                                                                                                     \
     int SYM(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* y,               \
             const int64_t* ybs, int64_t yss, int64_t yrs, size_t ny0, size_t ny1, size_t ny2, double* res, const int64_t* rbs, int64_t rss,   \
             int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, void* stream) {                                 \
-        GFT_SERIES_ENTRY(OP, FN, 1, false,                                                                                                    \
+        GFT_SERIES_ENTRY(OP, FN, W, false,                                                                                                    \
                          (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.y = rows3(y, ybs, yss, yrs, ny0, ny1, ny2),         \
                           c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                                      \
     }
-#define GFT_SERIES3_SEEDED(SYM, OP, FN)                                                                                                       \
+#define GFT_SERIES3_SEEDED(SYM, OP, FN, W)                                                                                                     \
     int SYM(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,            \
             const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,                   \
             const size_t* batch, size_t nbatch, void* stream) {                                                                               \
-        GFT_SERIES_ENTRY(OP, FN, 1, false,                                                                                                    \
+        GFT_SERIES_ENTRY(OP, FN, W, false,                                                                                                    \
                          (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.y = rows1(seed, sbs, 1),                            \
                           c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                                      \
     }
-#define GFT_SERIES3_COMPOSE_POW                                                                                                               \
-    int gft_series3_compose(const double* f, const int64_t* fbs, int64_t fss, int64_t frs, size_t nf0, size_t nf1, size_t nf2, const double* g, \
+#define GFT_SERIES3_COMPOSE_POW(PFX, WHAT, W)                                                                                                 \
+    int PFX##series3_compose(const double* f, const int64_t* fbs, int64_t fss, int64_t frs, size_t nf0, size_t nf1, size_t nf2, const double* g, \
                             const int64_t* gbs, int64_t gss, int64_t grs, size_t ng0, size_t ng1, size_t ng2, int var, double* res,          \
                             const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, \
                             void* stream) {                                                                                                   \
-        GFT_SERIES_ENTRY(SERIES_COMPOSE, "series3_compose", 1, false,                                                                         \
+        GFT_SERIES_ENTRY(SERIES_COMPOSE, WHAT "series3_compose", W, false,                                                                       \
                          (c.rank3 = true, c.x = rows3(f, fbs, fss, frs, nf0, nf1, nf2), c.y = rows3(g, gbs, gss, grs, ng0, ng1, ng2),         \
                           c.var = var, c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                         \
     }                                                                                                                                         \
-    int gft_series3_pow(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, uint32_t e,       \
+    int PFX##series3_pow(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, uint32_t e,       \
                         double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch,      \
                         size_t nbatch, void* stream) {                                                                                        \
-        GFT_SERIES_ENTRY(SERIES_POW, "series3_pow", 1, false,                                                                                 \
+        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series3_pow", W, false,                                                                               \
                          (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.e = e, c.r = rows3(res, rbs, rss, rrs, n0, n1, n2))); \
     }
+#define GFT_SERIES3_ARITH(PFX, WHAT, W)                                        \
+    GFT_SERIES3_BINARY(PFX##series3_mul, SERIES_MUL, WHAT "series3_mul", W)    \
+    GFT_SERIES3_BINARY(PFX##series3_div, SERIES_DIV, WHAT "series3_div", W)    \
+    GFT_SERIES3_SEEDED(PFX##series3_exp, SERIES_EXP, WHAT "series3_exp", W)    \
+    GFT_SERIES3_SEEDED(PFX##series3_log, SERIES_LOG, WHAT "series3_log", W)    \
+    GFT_SERIES3_COMPOSE_POW(PFX, WHAT, W)
 // The arithmetic ops at both ranks.  Interval<F64> (gfti_, W == 2): the same calls on (lo, hi) planes; every batch-stride array has
 // nbatch + 1 entries, the plane stride first.  Rank 2: the last two axes are an item's coefficient array, with a row stride each.
 #define GFT_SERIES_ARITH(PFX, WHAT, W)                                                                                                        \
@@ -241,11 +247,8 @@ GFT_SERIES_BINARY(gft_series_corr, SERIES_CORR, "series_corr", 1)
 GFT_SERIES_BINARY(gft_series_compose_adj, SERIES_COMPOSE_ADJ, "series_compose_adj", 1)
 GFT_SERIES2_BINARY(gft_series2_corr, SERIES_CORR, "series2_corr", 1)
 GFT_SERIES2_BINARY_VAR(gft_series2_compose_adj, SERIES_COMPOSE_ADJ, "series2_compose_adj", 1)
-GFT_SERIES3_BINARY(gft_series3_mul, SERIES_MUL, "series3_mul")
-GFT_SERIES3_BINARY(gft_series3_div, SERIES_DIV, "series3_div")
-GFT_SERIES3_SEEDED(gft_series3_exp, SERIES_EXP, "series3_exp")
-GFT_SERIES3_SEEDED(gft_series3_log, SERIES_LOG, "series3_log")
-GFT_SERIES3_COMPOSE_POW
+GFT_SERIES3_ARITH(gft_, "", 1)
+GFT_SERIES3_ARITH(gfti_, "interval ", 2)
 int gft_series_last_form(void) { return R.series_last; }
 }
 #undef GFT_SERIES_ENTRY
@@ -257,6 +260,7 @@ int gft_series_last_form(void) { return R.series_last; }
 #undef GFT_SERIES3_BINARY
 #undef GFT_SERIES3_SEEDED
 #undef GFT_SERIES3_COMPOSE_POW
+#undef GFT_SERIES3_ARITH
 #undef GFT_SERIES_ARITH
 #undef GFT_SERIES_OBSERVE_K
 #undef GFT_SERIES_OBSERVE

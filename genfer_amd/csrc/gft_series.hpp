@@ -78,12 +78,13 @@ size_t series2_pow_workspace(unsigned items, const Series2Dims& d, int w = 1);
 void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws,
                  const SeriesPlanes& pl = SeriesPlanes());
 
-// ---- rank 3: batched trivariate series (gft_series3_mul / div / exp / log / compose / pow, F64 only) ---------------------------------
+// ---- rank 3: batched trivariate series (gft_series3_* on F64, gfti_series3_* on Interval<F64>: mul / div / exp / log / compose / pow) ---
 // The last THREE axes of every operand are one item's coefficient array: axis -3 the slabs and axis -2 the rows (any non-negative
 // strides), axis -1 unit stride.  Per item the reference's general recursion over axis 0 at the stored result shape S, an S with
 // unit axes being the item without them: Series3Dims (gft_series_args.hpp) says what runs, gft_series3_kernels.hpp how.  One form,
 // one workgroup per item; gft_series_last_form() reports SERIES_FORM_B.
-// The geometry of a call: lanes per workgroup, the terms per chunk of the slab sums (div / exp / log), the scratch in elements and
+// The geometry of a call of element width w (1: F64, 2: Interval<F64>, an LDS element of 16 bytes): lanes per workgroup, the terms per
+// chunk of the slab sums (div / exp / log), the scratch in elements and
 // the dynamic LDS in bytes.  Throws std::runtime_error where the runtime grants less LDS than the resident arrays and the smallest
 // scratch need.
 struct Series3Plan {
@@ -91,24 +92,26 @@ struct Series3Plan {
     size_t lds;
     bool glds = false;  // compose: g is resident in LDS
 };
-Series3Plan series3_plan(int op, const Series3Dims& d);
+Series3Plan series3_plan(int op, const Series3Dims& d, int w = 1);
 // Launches SERIES_MUL / DIV / EXP / LOG at rank 3 on `st`.  `y`: the divisor / second factor; for exp / log the seeds or nullptr.
+// `pl`: the element width and the plane strides.
 void series3_launch(hipStream_t st, int op, const Series3Plan& p, const double* x, const double* y, double* res, const Series3Dims& d,
-                    const SeriesBatch& g);
+                    const SeriesBatch& g, const SeriesPlanes& pl = SeriesPlanes());
 
 // compose at rank 3 (gft_series3_compose): subst_var's Horner loop over the slices of f along `var`, every step series3.mul's product at
 // the compact shape, the whole chain one launch on the permuted item of Series3Compose (gft_series_args.hpp).  The plan: lanes, the
 // dynamic LDS and whether g is resident in it (else it is read from global memory: every admissible shape runs).
-Series3Plan series3_compose_plan(const Series3Compose& c);
+Series3Plan series3_compose_plan(const Series3Compose& c, int w = 1);
 void series3_compose_launch(hipStream_t st, const Series3Plan& p, const double* f, const double* g, double* res, const Series3Compose& c,
-                            const SeriesBatch& b);
+                            const SeriesBatch& b, const SeriesPlanes& pl = SeriesPlanes());
 // pow at rank 3 (gft_series3_pow), series2_pow with a slab axis: x (stored shape nx, element strides xs of its three axes) is copied
 // once into the workspace, every product but the last is a SERIES_MUL launch on compact workspace items, the last one writes all of n
 // through the result's strides rs.  e == 0 only writes the unit item.  `ws`: series3_pow_workspace() doubles -- the base and two
-// results taking turns, each items * n0 * n1 * n2, and the factor [[[1.0]]].
-size_t series3_pow_workspace(unsigned items, const unsigned* n);
+// results taking turns, each items * n0 * n1 * n2, and the factor [[[1.0]]]; w planes of that, plane-major (the operand's planes are
+// one more axis of the copy).
+size_t series3_pow_workspace(unsigned items, const unsigned* n, int w = 1);
 void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
-                 const SeriesBatch& g, double* ws);
+                 const SeriesBatch& g, double* ws, const SeriesPlanes& pl = SeriesPlanes());
 
 // ---- the observation ops at ranks 1 and 2 (gft_series_observe.hip) ----------------------------------------------------------------
 // op is SERIES_DERIVATIVE / SERIES_COEFF / SERIES_SHIFT_DOWN / SERIES_EVAL_ONE.  `d`: the operand's stored shape (nx0, nx1), row

@@ -1,7 +1,8 @@
 // Batched trivariate series (gft_series.hpp, "rank 3"): the planner and the launches of gft_series3_mul / div / exp / log / compose, and
-// pow's sequence of mul launches, F64 only.  The kernels are in gft_series3_kernels.hpp; gfx950 only.  The choices for mul / div / exp /
-// log have not been measured beyond the table of DESIGN 3.22: they are rank 2's (gft_series2.hip), counted the same way; compose's lane
-// count has its own sweep.
+// pow's sequence of mul launches, for F64 and for Interval<F64> (the element width w of the entry point: SeriesPlanes).  The kernels
+// are in gft_series3_kernels.hpp; gfx950 only.  The choices for mul / div / exp / log have not been measured beyond the tables of
+// they are rank 2's (gft_series2.hip), counted the same way; compose's lane count has its own sweep (DESIGN
+// 3.23).
 //
 // One form: one workgroup per item for the whole operation, on the permuted item of Series3Dims (the unit axes of S in front).
 //   lanes    one wave while the item has at most 64 units of parallel work, else up to 256 in whole waves: mul counts its output
@@ -15,6 +16,10 @@
 //            compose: two result arrays of n0 * n1 * n2 doubles taking turns, at most 64 KB, and g compact behind them where the
 //            three fit 64 KB or the grant of that 80 KB request; otherwise g stays in global memory, so every admissible shape runs
 //            on 64 KB.
+// Intervals (w == 2): an LDS element is 16 bytes, so every footprint above is reached at half the coefficients -- the limit is 2048
+// (SERIES3_MAX_ELEMS_IV), two resident arrays are the same 64 KB, an item with a second slab has slabs of at most 1024 elements
+// (16 KB: one chunk fits), and the scratch, compose's GLDS decision and the refusal scale with the width.  The LDS requests and what
+// the runtime answered are kept per element type.
 // compose's lanes count mul's output pairs of the full shape, in whole waves up to S3_COMPOSE_LANES.  pow has no kernel of its own
 // beside the writer of the unit item.
 #include <hip/hip_runtime.h>
@@ -34,13 +39,16 @@ namespace {
 constexpr size_t S3_BUDGET = 80 * 1024, S3_BUDGET_PLAIN = 64 * 1024;
 
 // what the runtime grants the three recurrence kernels and compose with g resident, asked once
-size_t s3_budget() {
-    static size_t granted = 0;
+size_t s3_budget(int w) {
+    static size_t answers[2] = {0, 0};
+    size_t& granted = answers[w == 2];
     if (granted) return granted;
-    const void* ks[] = {(const void*)k_series3_rec<SERIES_DIV>, (const void*)k_series3_rec<SERIES_EXP>, (const void*)k_series3_rec<SERIES_LOG>,
+    const void* kf[] = {(const void*)k_series3_rec<SERIES_DIV>, (const void*)k_series3_rec<SERIES_EXP>, (const void*)k_series3_rec<SERIES_LOG>,
                         (const void*)k_series3_compose<true>};
+    const void* ki[] = {(const void*)k_series3i_rec<EIv, SERIES_DIV>, (const void*)k_series3i_rec<EIv, SERIES_EXP>,
+                        (const void*)k_series3i_rec<EIv, SERIES_LOG>, (const void*)k_series3i_compose<EIv, true>};
     granted = S3_BUDGET;
-    for (const void* k : ks)
+    for (const void* k : w == 2 ? ki : kf)
         if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S3_BUDGET) != hipSuccess) {
             (void)hipGetLastError();  // no stale error for the caller's next HIP call
             granted = S3_BUDGET_PLAIN;
@@ -55,102 +63,109 @@ unsigned s3_threads(unsigned work, unsigned most = 256) { return work <= 64 ? 64
 constexpr unsigned S3_COMPOSE_LANES = 512;
 
 // the unit item of pow: 1.0 at [0, 0, 0] and +0.0 elsewhere, through the result's three strides -- its first factor (one item of one
-// coefficient) and the whole result of e == 0
-__global__ __launch_bounds__(256) void k_series3_unit(double* res, size_t s0, size_t s1, size_t s2, unsigned n0, unsigned n1, unsigned n2,
-                                                      SeriesBatch b) {
+// coefficient) and the whole result of e == 0 (an interval item: [1,1] and [0,0], both planes `plane` apart)
+template <class E>
+__global__ __launch_bounds__(256) void k_series3_unit(double* res, size_t plane, size_t s0, size_t s1, size_t s2, unsigned n0, unsigned n1,
+                                                      unsigned n2, SeriesBatch b) {
     const SeriesOff o = series_offsets(b, blockIdx.x);
     const unsigned n12 = n1 * n2;
     for (unsigned idx = threadIdx.x; idx < n0 * n12; idx += blockDim.x) {
         const unsigned k0 = idx / n12, r = idx - k0 * n12, k1 = r / n2, k2 = r - k1 * n2;
-        res[o.r + (size_t)k0 * s0 + (size_t)k1 * s1 + (size_t)k2 * s2] = idx == 0 ? 1.0 : 0.0;
+        E::st(res, plane, o.r + (size_t)k0 * s0 + (size_t)k1 * s1 + (size_t)k2 * s2, idx == 0 ? E::one() : E::zero());
     }
 }
 
 }  // namespace
 
-Series3Plan series3_plan(int op, const Series3Dims& d) {
+Series3Plan series3_plan(int op, const Series3Dims& d, int w) {
     Series3Plan p;
-    const size_t elem = sizeof(double);
+    const size_t elem = (size_t)w * sizeof(double);  // of an LDS element
     const unsigned n12 = d.n[1] * d.n[2], N = d.n[0] * n12;
     if (op == SERIES_MUL) {
         p.threads = s3_threads((N + 1) / 2);
         p.lds = ((size_t)d.nx[0] * d.nx[1] * d.nx[2] + (size_t)d.ny[0] * d.ny[1] * d.ny[2]) * elem;
         return p;
     }
-    const unsigned* a = op == SERIES_DIV ? d.ny : d.nx;
-    const size_t resident = (size_t)a[0] * a[1] * a[2] + N;                    // elements
-    const unsigned terms0 = std::min(d.n[0], a[0]) - 1, J1 = std::min(d.n[1], a[1]);  // of the longest j0 range; places of j1
-    const unsigned terms2 = J1 - 1;                                            // of the longest j range of a rank-2 row
-    // the smallest scratch and the one that takes every term at once
-    size_t need, want;
-    if (d.n[0] == 1) need = terms2 ? d.n[2] : 0, want = (size_t)terms2 * d.n[2];
-    else need = n12, want = std::max<size_t>((size_t)terms0 * J1, 1) * n12;
+    // the device-free arithmetic is series3_sizes (gft_series_args.hpp); the grant is asked only where an item needs scratch
+    Series3Sizes z = series3_sizes(op, d, w, S3_BUDGET);
     p.threads = s3_threads(N);
-    if (need) {
-        const size_t budget = s3_budget();
-        if ((resident + need) * elem > budget)
+    if (z.need) {
+        const size_t budget = s3_budget(w);
+        if (budget != S3_BUDGET) z = series3_sizes(op, d, w, budget);
+        if (!z.fits)
             throw std::runtime_error("series3: an item of " + std::to_string(d.n[0]) + " x " + std::to_string(d.n[1]) + " x " + std::to_string(d.n[2]) +
-                                     " coefficients needs " + std::to_string((resident + need) * elem) +
+                                     " coefficients" + (w == 2 ? " of two bounds" : "") + " needs " + std::to_string((z.resident + z.need) * elem) +
                                      " bytes of LDS (two resident arrays and the smallest scratch), but the runtime grants " + std::to_string(budget) +
                                      " bytes per workgroup");
-        p.selems = (unsigned)std::min(want, budget / elem - resident);
     }
-    p.tc = d.n[0] == 1 ? 0 : (unsigned)std::min<size_t>((size_t)terms0 * J1, p.selems / n12);
-    p.lds = (resident + p.selems) * elem;
+    p.selems = z.selems;
+    p.tc = z.tc;
+    p.lds = (z.resident + z.selems) * elem;
     return p;
 }
 
-Series3Plan series3_compose_plan(const Series3Compose& c) {
+Series3Plan series3_compose_plan(const Series3Compose& c, int w) {
     Series3Plan p;
-    const size_t N = (size_t)c.full[0] * c.full[1] * c.full[2];
-    const size_t arrays = 2 * N * sizeof(double), all = arrays + (size_t)c.ng[0] * c.ng[1] * c.ng[2] * sizeof(double);
+    const size_t N = (size_t)c.full[0] * c.full[1] * c.full[2], elem = (size_t)w * sizeof(double);
+    const size_t arrays = 2 * N * elem, all = arrays + (size_t)c.ng[0] * c.ng[1] * c.ng[2] * elem;
     p.threads = s3_threads((unsigned)((N + 1) / 2), S3_COMPOSE_LANES);
-    p.glds = all <= S3_BUDGET_PLAIN || all <= s3_budget();
+    p.glds = all <= S3_BUDGET_PLAIN || all <= s3_budget(w);
     p.lds = p.glds ? all : arrays;
     return p;
 }
 
 void series3_compose_launch(hipStream_t st, const Series3Plan& p, const double* f, const double* g, double* res, const Series3Compose& c,
-                            const SeriesBatch& b) {
+                            const SeriesBatch& b, const SeriesPlanes& pl) {
     if (b.items == 0) return;
     const dim3 grid(b.items), block(p.threads);
+    if (pl.w == 2) {
+        if (p.glds) GFT_LAUNCH((k_series3i_compose<EIv, true>), grid, block, p.lds, st, f, g, res, c, b, pl);
+        else GFT_LAUNCH((k_series3i_compose<EIv, false>), grid, block, p.lds, st, f, g, res, c, b, pl);
+        return;
+    }
     if (p.glds) GFT_LAUNCH(k_series3_compose<true>, grid, block, p.lds, st, f, g, res, c, b);
     else GFT_LAUNCH(k_series3_compose<false>, grid, block, p.lds, st, f, g, res, c, b);
 }
 
-size_t series3_pow_workspace(unsigned items, const unsigned* n) { return 3 * (size_t)items * n[0] * n[1] * n[2] + 1; }
+size_t series3_pow_workspace(unsigned items, const unsigned* n, int w) { return (size_t)w * (3 * (size_t)items * n[0] * n[1] * n[2] + 1); }
+
+namespace {
 
 // series2_pow (gft_series2.hip) with a slab axis
-void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
-                 const SeriesBatch& g, double* ws) {
+template <class E>
+void s3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
+            const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
     if (g.items == 0) return;
     const unsigned N = n[0] * n[1] * n[2];
     if (e == 0) {
-        GFT_LAUNCH(k_series3_unit, dim3(g.items), dim3(s3_threads(N)), 0, st, res, rs[0], rs[1], rs[2], n[0], n[1], n[2], g);
+        GFT_LAUNCH(k_series3_unit<E>, dim3(g.items), dim3(s3_threads(N)), 0, st, res, pl.r, rs[0], rs[1], rs[2], n[0], n[1], n[2], g);
         return;
     }
-    // three workspace arrays of items * N doubles each, whatever the compact shape of the items in it, and the unit item
-    const size_t arr = (size_t)g.items * N;
+    // three workspace arrays of items * N elements each, whatever the compact shape of the items in it, and the unit item; plane-major:
+    // the upper bounds of everything in the workspace lie `wp` doubles behind the lower ones
+    const size_t arr = (size_t)g.items * N, wp = 3 * arr + 1;
     double* spare[2] = {ws + arr, ws + 2 * arr};
     int nspare = 2;
     double* unit = ws + 3 * arr;
     SeriesBatch one;
     one.nd = 0;
     one.items = 1;
-    GFT_LAUNCH(k_series3_unit, dim3(1), dim3(64), 0, st, unit, (size_t)1, (size_t)1, (size_t)1, 1u, 1u, 1u, one);
+    GFT_LAUNCH(k_series3_unit<E>, dim3(1), dim3(64), 0, st, unit, wp, (size_t)1, (size_t)1, (size_t)1, 1u, 1u, 1u, one);
     // the operand, read once through its strides: base = x as compact items of nx
     double* base = ws;
     unsigned lb[3] = {nx[0], nx[1], nx[2]};
     {
         CopyGeom c;
+        int k = 0;
+        if (E::W == 2) c.ext[k] = 2, c.ss[k] = pl.x, c.ds[k] = wp, ++k;
         size_t cs = (size_t)lb[0] * lb[1] * lb[2];
         for (int a = g.nd - 1; a >= 0; --a) {
-            c.ext[a] = g.ext[a];
-            c.ss[a] = g.xs[a];
-            c.ds[a] = cs;
+            c.ext[k + a] = g.ext[a];
+            c.ss[k + a] = g.xs[a];
+            c.ds[k + a] = cs;
             cs *= g.ext[a];
         }
-        int k = g.nd;
+        k += g.nd;
         c.ext[k] = lb[0], c.ss[k] = xs[0], c.ds[k] = (size_t)lb[1] * lb[2], ++k;
         c.ext[k] = lb[1], c.ss[k] = xs[1], c.ds[k] = lb[2], ++k;
         c.ext[k] = lb[2], c.ss[k] = 1, c.ds[k] = 1, ++k;
@@ -174,7 +189,10 @@ void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const
             if (!last) w.rs[ax] = cs * ri;
             cs *= g.ext[ax];
         }
-        series3_launch(st, SERIES_MUL, series3_plan(SERIES_MUL, m), a, b, out, m, w);
+        SeriesPlanes wpl;
+        wpl.w = E::W;
+        if (E::W == 2) wpl.x = wpl.y = wp, wpl.r = last ? pl.r : wp;
+        series3_launch(st, SERIES_MUL, series3_plan(SERIES_MUL, m, E::W), a, b, out, m, w, wpl);
     };
     while (e > 0) {
         unsigned L[3];
@@ -199,10 +217,28 @@ void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const
     }
 }
 
+}  // namespace
+
+void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
+                 const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
+    if (pl.w == 2) s3_pow<EIv>(st, x, e, res, nx, xs, n, rs, g, ws, pl);
+    else s3_pow<EF64>(st, x, e, res, nx, xs, n, rs, g, ws, pl);
+}
+
 void series3_launch(hipStream_t st, int op, const Series3Plan& p, const double* x, const double* y, double* res, const Series3Dims& d,
-                    const SeriesBatch& g) {
+                    const SeriesBatch& g, const SeriesPlanes& pl) {
     if (g.items == 0) return;
     const dim3 grid(g.items), block(p.threads);
+    if (pl.w == 2) {
+        switch (op) {
+            case SERIES_MUL: GFT_LAUNCH(k_series3i_mul<EIv>, grid, block, p.lds, st, x, y, res, d, g, pl); break;
+            case SERIES_DIV: GFT_LAUNCH((k_series3i_rec<EIv, SERIES_DIV>), grid, block, p.lds, st, x, y, res, d, p.tc, p.selems, g, pl); break;
+            case SERIES_EXP: GFT_LAUNCH((k_series3i_rec<EIv, SERIES_EXP>), grid, block, p.lds, st, x, y, res, d, p.tc, p.selems, g, pl); break;
+            case SERIES_LOG: GFT_LAUNCH((k_series3i_rec<EIv, SERIES_LOG>), grid, block, p.lds, st, x, y, res, d, p.tc, p.selems, g, pl); break;
+            default: throw std::runtime_error("series3: no such operation at rank 3");
+        }
+        return;
+    }
     switch (op) {
         case SERIES_MUL: GFT_LAUNCH(k_series3_mul, grid, block, p.lds, st, x, y, res, d, g); break;
         case SERIES_DIV: GFT_LAUNCH(k_series3_rec<SERIES_DIV>, grid, block, p.lds, st, x, y, res, d, p.tc, p.selems, g); break;

@@ -18,7 +18,10 @@
 //                  Chunking changes how many row sums are in flight, never the order of an addition.
 // With n0 == 1 these ARE the rank-2 loops (one slab, no terms), with n0 == n1 == 1 the rank-1 loops: how an S with unit axes
 // is computed.  Multiply and add are rounded separately (-ffp-contract=off) and no explicit fma is written.
-// The bodies are templates over the element functor (gft_elem.hpp) as at rank 2; only EF64 is instantiated and exported.
+// The bodies are templates over the element functor (gft_elem.hpp) as at rank 2.  k_series3_mul, k_series3_rec<OP> and
+// k_series3_compose<GLDS> are the EF64 kernels; k_series3i_mul<E>, k_series3i_rec<E, OP> and k_series3i_compose<E, GLDS> run the same
+// bodies on Interval<F64> (E = EIv, emitted where gft_series3.hip instantiates them): two planes a plane stride apart in global
+// memory, ONE 16-byte element {lo, hi} in LDS (S2Iv), so every LDS size below is in elements of 8 (EF64) or 16 bytes (EIv).
 // Every barrier stands under loops whose trip counts come from the shapes in Series3Dims and the plan, the same for every lane.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -117,6 +120,11 @@ __global__ __launch_bounds__(256) void k_series3_mul(const double* x, const doub
     extern __shared__ double s3_lds[];
     s3_mul_body<EF64>(s3_lds, x, y, res, d, g, SeriesPlanes());
 }
+template <class E>
+__global__ __launch_bounds__(256) void k_series3i_mul(const double* x, const double* y, double* res, Series3Dims d, SeriesBatch g, SeriesPlanes pl) {
+    extern __shared__ S2Iv s3_lds_iv[];
+    s3_mul_body<E>(s3_lds_iv, x, y, res, d, g, pl);
+}
 
 // ---- compose (subst_var's Horner path, mt:569-579) ------------------------------------------------------------------------------
 // res = f(g) with g in the place of one variable of f, on the PERMUTED item of Series3Compose (gft_series_args.hpp: the unit axes of
@@ -197,6 +205,12 @@ template <bool GLDS>
 __global__ __launch_bounds__(512) void k_series3_compose(const double* f, const double* g, double* res, Series3Compose c, SeriesBatch b) {
     extern __shared__ double s3_lds[];
     s3_compose_body<EF64, GLDS>(s3_lds, f, g, res, c, b, SeriesPlanes());
+}
+template <class E, bool GLDS>
+__global__ __launch_bounds__(512) void k_series3i_compose(const double* f, const double* g, double* res, Series3Compose c, SeriesBatch b,
+                                                          SeriesPlanes pl) {
+    extern __shared__ S2Iv s3_lds_iv[];
+    s3_compose_body<E, GLDS>(s3_lds_iv, f, g, res, c, b, pl);
 }
 
 // ---- div, exp, log --------------------------------------------------------------------------------------------------------------
@@ -310,7 +324,10 @@ __device__ inline void s3_rec_body(typename S2L<E>::T* lds, const double* x, con
         lds_barrier();
         if (!EXP) {  // the rank-2 division of the slab, in place, by slab 0 of the resident operand
             const unsigned sr = terms2 + 1 < fit ? terms2 : (fit ? fit - 1 : 0);  // (one row of the scratch holds the accumulators)
-            s2_rec_rows<E, SERIES_DIV, true>(al, a1, a2, rk, n1, n2, sl, sr, nullptr, 0, 0, 0, n1, n2, nullptr, 0);
+            // (intervals: div and log share this instantiation, which the inliner then leaves a call with a scratch frame -- forced
+            // at this call only, the f64 kernels compile as before)
+            if constexpr (E::W == 2) [[clang::always_inline]] s2_rec_rows<E, SERIES_DIV, true>(al, a1, a2, rk, n1, n2, sl, sr, nullptr, 0, 0, 0, n1, n2, nullptr, 0);
+            else s2_rec_rows<E, SERIES_DIV, true>(al, a1, a2, rk, n1, n2, sl, sr, nullptr, 0, 0, 0, n1, n2, nullptr, 0);
             if (!DIV) {
                 for (unsigned i = tid; i < n12; i += nt) S2L<E>::put(rk, i, E::div(S2L<E>::get(rk, (int)i), E::from_u32(k0)));
                 lds_barrier();
@@ -330,6 +347,12 @@ __global__ __launch_bounds__(256) void k_series3_rec(const double* x, const doub
                                                      SeriesBatch g) {
     extern __shared__ double s3_lds[];
     s3_rec_body<EF64, OP>(s3_lds, x, y, res, d, tc, selems, g, SeriesPlanes());
+}
+template <class E, int OP>
+__global__ __launch_bounds__(256) void k_series3i_rec(const double* x, const double* y, double* res, Series3Dims d, unsigned tc, unsigned selems,
+                                                      SeriesBatch g, SeriesPlanes pl) {
+    extern __shared__ S2Iv s3_lds_iv[];
+    s3_rec_body<E, OP>(s3_lds_iv, x, y, res, d, tc, selems, g, pl);
 }
 
 }  // namespace gft

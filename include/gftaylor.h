@@ -276,7 +276,7 @@ int gft_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_t
 int gft_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
                     const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,
                     void* stream);                                       /* pow                    mt:433-451   */
-/* ---- batched TRIVARIATE series on caller-owned device tensors (f64 only): mul / div / exp / log / compose / pow ----
+/* ---- batched TRIVARIATE series on caller-owned device tensors (f64; gfti_series3_* below): mul / div / exp / log / compose / pow ----
  * The last THREE axes of every operand are the coefficient array of one TaylorPoly<F64> in three variables: axis -3 is variable 0
  * (`nx0` slabs, `xss` elements apart), axis -2 variable 1 (`nx1` rows, `xrs` elements apart) -- any non-negative strides -- and
  * axis -1 variable 2 (`nx2` coefficients, UNIT stride).  Per operand the arguments are the pointer, the batch-stride array, the
@@ -627,6 +627,48 @@ int gfti_series2_compose(const double* f, const int64_t* fbs, int64_t frs, size_
                          size_t n1, const size_t* batch, size_t nbatch, void* stream);
 int gfti_series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,
                      const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+/* Batched trivariate series over Interval<F64>: gft_series3_* on tensors [2, B..., n0, n1, n2] = (lo, hi).  The argument lists are those
+ * of gft_series3_* (slab strides `xss` / `yss` / `rss` and row strides `xrs` / `yrs` / `rrs` included, one each per operand: both
+ * planes share them); the stride-array convention is gfti_series_*'s: every batch-stride array (xbs / ybs / sbs / rbs) has nbatch + 1
+ * entries, the lo -> hi plane stride FIRST, NULL = C-contiguous items with the two planes back to back.  An operand's or the seeds'
+ * plane stride may be 0 (a point interval read twice); the result's planes are distinct memory, the planes, the slabs and the rows all
+ * join the proof that the result's elements are distinct addresses, and "the same view" of an in-place result includes the plane
+ * stride.  Seeds are [2, B...]; NULL: formed on the device by the interval exp / log of coefficient [0, 0, 0].  n0 * n1 * n2 <= 2048: an
+ * interval occupies 16 bytes of LDS, so the footprints of gft_series3_* at 4096 are reached there.  Per item the results are the loops
+ * stated above for gft_series3_mul / div / exp / log / compose / pow -- BOTH rules first: the stored result shape S decided by the
+ * shapes alone, its unit axes squeezed, everything outside S [+0.0, +0.0] -- with every step one operation of Interval<F64>
+ * (interval.rs: round to nearest, one ulp outwards, with its short-circuits):
+ *   mul  z[k0][k1] = [0,0];  for j0, j1 ascending:  o = [0,0];  for j2 ascending: o = o + x[j0][j1][j2] * y[k0-j0][k1-j1][k2-j2];
+ *        z[k0][k1][k2] = z[k0][k1][k2] + o       (the row sum from [0,0] first, then added; [0,0] + b is b)
+ *   div  c = the sum over j0 in max(0, k0+1-ny0) .. k0-1 of r[j0] (*) y[k0-j0];  c = -c;  c[:nx1][:nx2] += x[k0];  r[k0] = div2(c, y[0])
+ *   exp  r[0] = exp2(x[0], seed);  c = the sum over j0 in 1 .. min(nx0, k0+1)-1 of (x[j0] * from_u32(j0)) (*) r[k0-j0];
+ *        r[k0] = c / from_u32(k0)
+ *   log  r[0] = log2(x[0], seed);  c = the sum over j0 in max(1, k0+1-nx0) .. k0-1 of x[k0-j0] (*) (r[j0] * from_u32(j0));  c = -c;
+ *        c[:nx1][:nx2] += from_u32(k0) * x[k0];  c = div2(c, x[0]);  r[k0] = c / from_u32(k0)
+ * with (*) the slab product above and div2 / exp2 / log2 the loops of gfti_series2_div / exp / log; compose and pow are the chains of
+ * gft_series3_compose / pow over that mul at the compact shapes, pow from [[[[1,1]]]].  Each bound carries the oracle's bits under the
+ * same rule as for gft_series3_*, NaN for NaN.  pow's workspace is 2 * (3 * items * n0 * n1 * n2 + 1) doubles, plane-major, and the
+ * plane axis joins its one copy of the operand: a batch with more than 9 non-contiguous axes is refused.  One workgroup per item;
+ * where the runtime grants less LDS than an item needs the call fails and says so.  gft_series_last_form() reports 2 afterwards. */
+int gfti_series3_mul(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* y,
+                     const int64_t* ybs, int64_t yss, int64_t yrs, size_t ny0, size_t ny1, size_t ny2, double* res, const int64_t* rbs,
+                     int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series3_div(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* y,
+                     const int64_t* ybs, int64_t yss, int64_t yrs, size_t ny0, size_t ny1, size_t ny2, double* res, const int64_t* rbs,
+                     int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series3_exp(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,
+                     const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,
+                     const size_t* batch, size_t nbatch, void* stream);
+int gfti_series3_log(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,
+                     const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,
+                     const size_t* batch, size_t nbatch, void* stream);
+int gfti_series3_compose(const double* f, const int64_t* fbs, int64_t fss, int64_t frs, size_t nf0, size_t nf1, size_t nf2, const double* g,
+                         const int64_t* gbs, int64_t gss, int64_t grs, size_t ng0, size_t ng1, size_t ng2, int var, double* res,
+                         const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch,
+                         void* stream);
+int gfti_series3_pow(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, uint32_t e,
+                     double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch,
+                     size_t nbatch, void* stream);
 /* The observation ops over Interval<F64>: gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down /
  * evaluate_all_one on (lo, hi) planes, the stride-array convention of gfti_series_* (the plane stride first; 0 on the operand: point
  * intervals).  The same loops with every step one operation of the reference's interval arithmetic, its short-circuits included

@@ -13,7 +13,13 @@ loop measured in the same run: at least 10x for B >= 256, no slower than 1.1x fo
 against the handle loop (``subst_var`` / ``pow``) and, for compose, also against
   (c) the Python chain of ``series3.mul`` calls with a slice add after each -- the other route a caller had before.
 
+``--interval``: the same on ``Interval<F64>`` tensors ``[2, B, n0, n1, n2]`` (genfer_amd.interval_series3) against the loop over
+``IntervalTaylorPoly`` handles, every shape with ``n0 * n1 * n2`` capped at 2048 (the longest axis is halved until the item fits), over
+mul, div, exp, log, compose (var 0, 1, 2) and pow e = 5 by default; the chain of leg (c) is ``interval_series3.mul`` plus the slice add (a plain ``+=`` on both
+planes, not an outward-rounded interval add: a timing leg only).
+
     python tools/bench_series3.py > profiles/r17/series3.json
+    python tools/bench_series3.py --interval > profiles/r21/series3_interval.json
     python tools/bench_series3.py --ops compose,pow > profiles/r20/series3_compose.json
 """
 import argparse
@@ -34,12 +40,16 @@ POW_E = 5
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--ops", default=OPS, help=f"comma-separated operations out of {OPS},{MORE_OPS} (default: {OPS})")
+    ap.add_argument("--ops", default=None, help=f"comma-separated operations out of {OPS},{MORE_OPS} (default: {OPS}; with --interval all six)")
+    ap.add_argument("--interval", action="store_true",
+                    help="Interval<F64> tensors [2, B, n0, n1, n2] (interval_series3), n0 * n1 * n2 capped at 2048")
     ap.add_argument("--shapes", default=SHAPES, help=f"comma-separated BxN0xN1xN2 cases (default {SHAPES})")
     ap.add_argument("--loop-items", type=int, default=256, help="items the per-item loop is timed on (scaled to B)")
     ap.add_argument("--budget-ms", type=float, default=300.0, help="time each leg repeats for, roughly")
     ap.add_argument("--no-loop", action="store_true", help="skip leg (b)")
     args = ap.parse_args(argv)
+    if args.ops is None:
+        args.ops = OPS + "," + MORE_OPS if args.interval else OPS
     for op in args.ops.split(","):
         if op not in (OPS + "," + MORE_OPS).split(","):
             ap.error(f"unknown operation '{op}'")
@@ -105,8 +115,18 @@ def target(B, ratio):
     return "met" if ratio >= (10.0 if B >= 256 else 1 / 1.1) else "missed"
 
 
-def bench_compose_pow(args, torch, series3, TP, op, B, n, f, g, out, results):
-    """compose: one row per variable; pow: one row at e = POW_E"""
+def cap_item(n, most):
+    """halve the longest axis until n0 * n1 * n2 <= most"""
+    n = list(n)
+    while math.prod(n) > most:
+        a = n.index(max(n))
+        n[a] = (n[a] + 1) // 2
+    return tuple(n)
+
+
+def bench_compose_pow(args, torch, series3, TP, op, B, n, f, g, out, results, item, tag):
+    """compose: one row per variable; pow: one row at e = POW_E.  The series axes are addressed from the right: an interval tensor has
+    the plane axis in front of the batch"""
     for var in (0, 1, 2) if op == "compose" else (None,):
         if op == "compose":
             work = sum(product_macs(r, n, L) for r, L in compose_steps(n, var))
@@ -115,13 +135,13 @@ def bench_compose_pow(args, torch, series3, TP, op, B, n, f, g, out, results):
                 series3.compose(f, g, var=var, out=out)
 
             def chain():
-                res = 0.0 + f.narrow(1 + var, n[var] - 1, 1)
-                head = (slice(None),) + tuple(slice(0, 1) if a == var else slice(None) for a in range(3))
+                res = 0.0 + f.narrow(var - 3, n[var] - 1, 1)
+                head = (Ellipsis,) + tuple(slice(0, 1) if a == var else slice(None) for a in range(3))
                 for i in range(n[var] - 2, -1, -1):
-                    res = series3.mul(res, g, n=tuple(min(res.shape[1 + a] + n[a] - 1, n[a]) for a in range(3)))
-                    res[head] += f.narrow(1 + var, i, 1)
+                    res = series3.mul(res, g, n=tuple(min(res.shape[a - 3] + n[a] - 1, n[a]) for a in range(3)))
+                    res[head] += f.narrow(var - 3, i, 1)
                 out.zero_()
-                out[:, :res.shape[1], :res.shape[2], :res.shape[3]] = res
+                out[..., :res.shape[-3], :res.shape[-2], :res.shape[-1]] = res
         else:
             work = pow_macs(n, POW_E)
 
@@ -133,11 +153,11 @@ def bench_compose_pow(args, torch, series3, TP, op, B, n, f, g, out, results):
 
         def loop():
             for b in range(items):
-                p = TP.from_torch(f[b])
-                r = p.subst_var(var, TP.from_torch(g[b])) if op == "compose" else p.pow(POW_E)
-                r.to_torch(out=out[b])
+                p = TP.from_torch(item(f, b))
+                r = p.subst_var(var, TP.from_torch(item(g, b))) if op == "compose" else p.pow(POW_E)
+                r.to_torch(out=item(out, b))
 
-        rec = {"op": op, "B": B, "n0": n[0], "n1": n[1], "n2": n[2], "batched_ms": round(t_batch, 6), "batched_reps": reps_a,
+        rec = {**tag, "op": op, "B": B, "n0": n[0], "n1": n[1], "n2": n[2], "batched_ms": round(t_batch, 6), "batched_reps": reps_a,
                "GMACps": round(B * work / (t_batch * 1e-3) / 1e9, 3)}
         rec.update({"var": var} if op == "compose" else {"e": POW_E})
         if not args.no_loop:
@@ -158,27 +178,40 @@ def main(argv=None):
     import torch
 
     import genfer_amd
-    from genfer_amd import series3
+    from genfer_amd import interval_series3, series3
 
     genfer_amd.init(0)
-    TP = genfer_amd.TaylorPoly
+    iv = args.interval
+    TP = genfer_amd.IntervalTaylorPoly if iv else genfer_amd.TaylorPoly
+    if iv:
+        series3 = interval_series3
+    item = (lambda t, b: t[:, b]) if iv else (lambda t, b: t[b])
+    tag = {"element": "interval"} if iv else {}
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device="cpu").manual_seed(7)
     results = []
     for shape in args.shapes.split(","):
         B, *n = (int(t) for t in shape.lower().split("x"))
+        if iv:
+            n = list(cap_item(n, interval_series3.MAX_ELEMS))
         N = math.prod(n)
         # bounded results at every order: a dominant constant term in the divisor, a small argument for exp
         x = (0.5 + torch.rand((B, *n), dtype=torch.float64, generator=gen) / N).to(dev)
         y = (0.5 + torch.rand((B, *n), dtype=torch.float64, generator=gen) / N).to(dev)
         y[:, 0, 0, 0] += 2.0
-        out = torch.empty((B, *n), dtype=torch.float64, device=dev)
+        if iv:  # (lo, hi) planes about 2^-20 apart; the loop indexes items behind the plane axis
+            x = torch.stack([x, x * (1.0 + 2.0**-20)])
+            y = torch.stack([y, y * (1.0 + 2.0**-20)])
+        out = torch.empty(((2,) if iv else ()) + (B, *n), dtype=torch.float64, device=dev)
         for op in args.ops.split(","):
             if op in MORE_OPS.split(","):
-                bench_compose_pow(args, torch, series3, TP, op, B, tuple(n), x, y if op == "compose" else None, out, results)
+                bench_compose_pow(args, torch, series3, TP, op, B, tuple(n), x, y if op == "compose" else None, out, results, item, tag)
                 continue
             seed = None
-            if op in ("exp", "log"):
+            if op in ("exp", "log") and iv:  # a host's seeds: libm, one ulp outwards
+                s = torch.tensor([[getattr(math, op)(v) for v in pl] for pl in x[:, :, 0, 0, 0].cpu().tolist()], dtype=torch.float64)
+                seed = torch.stack([torch.nextafter(s[0], s[0] - 1.0), torch.nextafter(s[1], s[1] + 1.0)]).to(dev)
+            elif op in ("exp", "log"):
                 seed = torch.tensor([getattr(math, op)(v) for v in x[:, 0, 0, 0].cpu().tolist()], dtype=torch.float64).to(dev)
 
             def batched():
@@ -192,16 +225,16 @@ def main(argv=None):
 
             def loop():
                 for b in range(items):
-                    p = TP.from_torch(x[b])
+                    p = TP.from_torch(item(x, b))
                     if op == "mul":
-                        r = p * TP.from_torch(y[b])
+                        r = p * TP.from_torch(item(y, b))
                     elif op == "div":
-                        r = p / TP.from_torch(y[b])
+                        r = p / TP.from_torch(item(y, b))
                     else:
                         r = p.exp() if op == "exp" else p.log()
-                    r.to_torch(out=out[b])
+                    r.to_torch(out=item(out, b))
 
-            rec = {"op": op, "B": B, "n0": n[0], "n1": n[1], "n2": n[2], "batched_ms": round(t_batch, 6), "batched_reps": reps_a,
+            rec = {**tag, "op": op, "B": B, "n0": n[0], "n1": n[1], "n2": n[2], "batched_ms": round(t_batch, 6), "batched_reps": reps_a,
                    "GMACps": round(B * macs(n) / (t_batch * 1e-3) / 1e9, 3)}
             if not args.no_loop:
                 t_loop, reps_b = timed(torch, loop, args.budget_ms)
