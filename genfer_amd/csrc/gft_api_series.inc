@@ -7,7 +7,8 @@
 // at the stored result shape S on the permuted item of gft::series3_dims, compose on that of gft::series3_compose_dims)
 // and the observation ops gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one with
 // their gfti_ twins (one operand, the result shorter by the order k on one axis; the kernels: gft_series_observe.hip)
-// Every entry point fills one gft::SeriesCall (gft_series_args.hpp, which judges it without the device) and hands it to series_call.
+// Every entry point fills one gft::SeriesCall with its rank (gft_series_args.hpp, which judges it without the device and states the
+// item of any rank as one gft::SeriesItem) and hands it to series_call, which dispatches on the rank once; pow is one driver.
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -22,7 +23,7 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
     const int op = c.op, w = c.w;
     const double *x = c.x.p, *y = c.y.p;
     double* res = const_cast<double*>(c.r.p);
-    const gft::Series2Dims& d = a.d;
+    const gft::SeriesItem& it = a.it;
     const gft::SeriesBatch& g = a.g;
     const gft::SeriesPlanes& pl = a.pl;
     const hipStream_t cs = (hipStream_t)stream;
@@ -32,94 +33,79 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         Rc<Buf> tab;
         size_t tlen = 0;
         if (op == gft::SERIES_DERIVATIVE || op == gft::SERIES_COEFF) {
-            tlen = c.rank2 && c.var == 0 ? d.n0 : d.n1;
+            tlen = c.rank == 2 && c.var == 0 ? it.n[1] : it.n[2];
             const int top = op == gft::SERIES_DERIVATIVE ? TAB_DERIV : TAB_COEFF;
             tab = w == 2 ? Ops<EIv>::cached_table(top, c.k, tlen) : Ops<EF64>::cached_table(top, c.k, tlen);
         }
         join_caller_in(cs);
-        gft::series_observe(R.stream, op, x, res, d, c.var, (unsigned)c.k, g, pl, tab ? tab->p : nullptr, tlen, c.rank2);
+        gft::series_observe(R.stream, op, x, res, gft::series2_dims(it), c.var, (unsigned)c.k, g, pl, tab ? tab->p : nullptr, tlen, c.rank == 2);
         join_caller_out(cs);
         R.series_last = gft::SERIES_NONE;
         return 0;
     }
-    if (c.rank3 && (op == gft::SERIES_COMPOSE || op == gft::SERIES_POW)) {
-        const unsigned nx[3] = {a.s.nx, d.nx0, d.nx1}, n[3] = {a.s.n, d.n0, d.n1};
-        const size_t xs[3] = {a.s.xs, d.xr, 1}, rs[3] = {a.s.rs, d.rr, 1};
-        if (op == gft::SERIES_POW) {
-            Rc<Buf> ws = alloc_doubles(gft::series3_pow_workspace(g.items, n, w));  // (returned to the pool on exit: later launches follow)
-            join_caller_in(cs);
-            gft::series3_pow(R.stream, x, c.e, res, nx, xs, n, rs, g, ws->p, pl);
-        } else {
-            const gft::Series3Compose k = gft::series3_compose_dims(a, c.var);
+    if (op == gft::SERIES_POW) {  // one driver for every rank
+        Rc<Buf> ws = alloc_doubles(gft::series_pow_workspace(g.items, it.n, w));  // (returned to the pool on exit: later launches follow)
+        join_caller_in(cs);
+        R.series_last = gft::series_pow(R.stream, c.rank, x, c.e, res, it, g, ws->p, R.series_force, pl);
+        join_caller_out(cs);
+        return 0;
+    }
+    // ranks 2 and 3 have one form, planned before the streams are joined (the planner may refuse)
+    if (c.rank == 3) {  // on the permuted item of the stored result shape S (compose: of the chain's final shape)
+        if (op == gft::SERIES_COMPOSE) {
+            const gft::Series3Compose k = gft::series3_compose_dims(it, c.var);
             const gft::Series3Plan plan = gft::series3_compose_plan(k, w);
             join_caller_in(cs);
             gft::series3_compose_launch(R.stream, plan, x, y, res, k, g, pl);
-        }
-        join_caller_out(cs);
-        R.series_last = gft::SERIES_FORM_B;
-        return 0;
-    }
-    if (c.rank3) {  // one form on the permuted item of the stored result shape S; planned before the streams are joined
-        const gft::Series3Dims k = gft::series3_dims(op, a);
-        const gft::Series3Plan plan = gft::series3_plan(op, k, w);
-        join_caller_in(cs);
-        gft::series3_launch(R.stream, op, plan, x, y, res, k, g, pl);
-        join_caller_out(cs);
-        R.series_last = gft::SERIES_FORM_B;
-        return 0;
-    }
-    if (c.rank2) {  // one form; planned before the streams are joined (the planner may refuse)
-        if (op == gft::SERIES_POW) {
-            Rc<Buf> ws = alloc_doubles(gft::series2_pow_workspace(g.items, d, w));  // (returned to the pool on exit, as below)
-            join_caller_in(cs);
-            gft::series2_pow(R.stream, x, c.e, res, d, g, ws->p, pl);
         } else {
-            const gft::Series2Plan plan = gft::series2_plan(op, d, w);
+            const gft::Series3Dims k = gft::series3_dims(op, it);
+            const gft::Series3Plan plan = gft::series3_plan(op, k, w);
             join_caller_in(cs);
-            gft::series2_launch(R.stream, op, plan, x, y, res, d, g, c.var, pl);
+            gft::series3_launch(R.stream, op, plan, x, y, res, k, g, pl);
         }
         join_caller_out(cs);
         R.series_last = gft::SERIES_FORM_B;
         return 0;
     }
+    if (c.rank == 2) {
+        const gft::Series2Dims d = gft::series2_dims(it);
+        const gft::Series2Plan plan = gft::series2_plan(op, d, w);
+        join_caller_in(cs);
+        gft::series2_launch(R.stream, op, plan, x, y, res, d, g, c.var, pl);
+        join_caller_out(cs);
+        R.series_last = gft::SERIES_FORM_B;
+        return 0;
+    }
+    const unsigned nx = it.nx[2], ny = it.ny[2], n = it.n[2];
     const bool transposed = op == gft::SERIES_CORR || op == gft::SERIES_COMPOSE_ADJ;  // their planner sizes the long rows: x's
-    const int form = op == gft::SERIES_POW ? gft::SERIES_NONE : gft::series_plan(op, g.items, transposed ? d.nx1 : d.n1, R.series_force, w);
-    const size_t wsn = gft::series_workspace(op, form, g.items, d.nx1, d.n1, w);
+    const int form = gft::series_plan(op, g.items, transposed ? nx : n, R.series_force, w);
+    const size_t wsn = gft::series_workspace(op, form, g.items, nx, n, w);
     Rc<Buf> ws;
     if (wsn) ws = alloc_doubles(wsn);  // (returned to the pool on exit: later launches follow these on the one stream)
     join_caller_in(cs);
-    int ran = form;
-    if (op == gft::SERIES_POW) ran = gft::series_pow(R.stream, x, d.nx1, c.e, res, d.n1, g, ws->p, R.series_force, pl);
-    else gft::series_launch(R.stream, op, form, x, d.nx1, y, d.ny1, res, d.n1, g, wsn ? ws->p : nullptr, pl);
+    gft::series_launch(R.stream, op, form, x, nx, y, ny, res, n, g, wsn ? ws->p : nullptr, pl);
     join_caller_out(cs);
-    R.series_last = ran;
+    R.series_last = form;
     return 0;
 }
 
-// an operand as the entry points receive it: rank 1 (pointer, batch strides, length), rank 2 with the row stride and both lengths
-static gft::SeriesView rows1(const double* p, const int64_t* bs, size_t len) {
+// an operand as the entry points receive it, from the unit-stride axis outwards: its length, then stride and length of the row axis
+// (rank 2 up) and of the slab axis (rank 3)
+static gft::SeriesView view(const double* p, const int64_t* bs, size_t len2, int64_t rst = 0, size_t len1 = 1, int64_t sst = 0, size_t len0 = 1) {
     gft::SeriesView v;
-    v.p = p, v.bs = bs, v.len1 = len;
-    return v;
-}
-static gft::SeriesView rows2(const double* p, const int64_t* bs, int64_t rst, size_t len0, size_t len1) {
-    gft::SeriesView v;
-    v.p = p, v.bs = bs, v.rst = rst, v.len0 = len0, v.len1 = len1;
-    return v;
-}
-static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, int64_t rst, size_t len0, size_t len1, size_t len2) {
-    gft::SeriesView v = rows2(p, bs, rst, len1, len2);
-    v.sst = sst, v.slabs = len0;
+    v.p = p, v.bs = bs;
+    v.st[0] = sst, v.st[1] = rst;
+    v.len[0] = len0, v.len[1] = len1, v.len[2] = len2;
     return v;
 }
 
 }  // namespace
 
 // An entry point: the descriptor `c` with the call's common fields, FILL names the rest (the operands, e, var, k).
-#define GFT_SERIES_ENTRY(OP, FN, W, RANK2, FILL)                                   \
+#define GFT_SERIES_ENTRY(OP, FN, W, RANK, FILL)                                    \
     return guard_int([&] {                                                         \
         gft::SeriesCall c;                                                         \
-        c.op = gft::OP, c.fn = FN, c.w = W, c.rank2 = RANK2, c.batch = batch, c.nbatch = nbatch; \
+        c.op = gft::OP, c.fn = FN, c.w = W, c.rank = RANK, c.batch = batch, c.nbatch = nbatch; \
         FILL;                                                                      \
         return series_call(c, stream);                                             \
     })
@@ -127,64 +113,64 @@ static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, in
 #define GFT_SERIES_BINARY(SYM, OP, FN, W)                                                                                                     \
     int SYM(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny, double* res, const int64_t* rbs,  \
             size_t n, const size_t* batch, size_t nbatch, void* stream) {                                                                     \
-        GFT_SERIES_ENTRY(OP, FN, W, false, (c.x = rows1(x, xbs, nx), c.y = rows1(y, ybs, ny), c.r = rows1(res, rbs, n)));                     \
+        GFT_SERIES_ENTRY(OP, FN, W, 1, (c.x = view(x, xbs, nx), c.y = view(y, ybs, ny), c.r = view(res, rbs, n)));                            \
     }
 #define GFT_SERIES_SEEDED(SYM, OP, FN, W)                                                                                                     \
     int SYM(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs, double* res, const int64_t* rbs, size_t n, \
             const size_t* batch, size_t nbatch, void* stream) {                                                                               \
-        GFT_SERIES_ENTRY(OP, FN, W, false, (c.x = rows1(x, xbs, nx), c.y = rows1(seed, sbs, 1), c.r = rows1(res, rbs, n)));                   \
+        GFT_SERIES_ENTRY(OP, FN, W, 1, (c.x = view(x, xbs, nx), c.y = view(seed, sbs, 1), c.r = view(res, rbs, n)));                          \
     }
 #define GFT_SERIES2_BINARY(SYM, OP, FN, W)                                                                                                    \
     int SYM(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,       \
             size_t ny0, size_t ny1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch,   \
             void* stream) {                                                                                                                   \
-        GFT_SERIES_ENTRY(OP, FN, W, true,                                                                                                     \
-                         (c.x = rows2(x, xbs, xrs, nx0, nx1), c.y = rows2(y, ybs, yrs, ny0, ny1), c.r = rows2(res, rbs, rrs, n0, n1)));       \
+        GFT_SERIES_ENTRY(OP, FN, W, 2,                                                                                                        \
+                         (c.x = view(x, xbs, nx1, xrs, nx0), c.y = view(y, ybs, ny1, yrs, ny0), c.r = view(res, rbs, n1, rrs, n0)));          \
     }
 #define GFT_SERIES2_BINARY_VAR(SYM, OP, FN, W)                                                                                                \
     int SYM(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,       \
             size_t ny0, size_t ny1, int var, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch,         \
             size_t nbatch, void* stream) {                                                                                                    \
-        GFT_SERIES_ENTRY(OP, FN, W, true,                                                                                                     \
-                         (c.x = rows2(x, xbs, xrs, nx0, nx1), c.y = rows2(y, ybs, yrs, ny0, ny1), c.var = var,                                \
-                          c.r = rows2(res, rbs, rrs, n0, n1)));                                                                               \
+        GFT_SERIES_ENTRY(OP, FN, W, 2,                                                                                                        \
+                         (c.x = view(x, xbs, nx1, xrs, nx0), c.y = view(y, ybs, ny1, yrs, ny0), c.var = var,                                  \
+                          c.r = view(res, rbs, n1, rrs, n0)));                                                                                \
     }
 #define GFT_SERIES2_SEEDED(SYM, OP, FN, W)                                                                                                    \
     int SYM(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* seed, const int64_t* sbs, double* res,    \
             const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {                        \
-        GFT_SERIES_ENTRY(OP, FN, W, true, (c.x = rows2(x, xbs, xrs, nx0, nx1), c.y = rows1(seed, sbs, 1), c.r = rows2(res, rbs, rrs, n0, n1))); \
+        GFT_SERIES_ENTRY(OP, FN, W, 2, (c.x = view(x, xbs, nx1, xrs, nx0), c.y = view(seed, sbs, 1), c.r = view(res, rbs, n1, rrs, n0)));     \
     }
 // rank 3: a slab stride and a row stride per operand, three lengths
-#define GFT_SERIES3_BINARY(SYM, OP, FN, W)                                                                                                     \
+#define GFT_SERIES3_BINARY(SYM, OP, FN, W)                                                                                                    \
     int SYM(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* y,               \
             const int64_t* ybs, int64_t yss, int64_t yrs, size_t ny0, size_t ny1, size_t ny2, double* res, const int64_t* rbs, int64_t rss,   \
             int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, void* stream) {                                 \
-        GFT_SERIES_ENTRY(OP, FN, W, false,                                                                                                    \
-                         (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.y = rows3(y, ybs, yss, yrs, ny0, ny1, ny2),         \
-                          c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                                      \
+        GFT_SERIES_ENTRY(OP, FN, W, 3,                                                                                                        \
+                         (c.x = view(x, xbs, nx2, xrs, nx1, xss, nx0), c.y = view(y, ybs, ny2, yrs, ny1, yss, ny0),                           \
+                          c.r = view(res, rbs, n2, rrs, n1, rss, n0)));                                                                       \
     }
-#define GFT_SERIES3_SEEDED(SYM, OP, FN, W)                                                                                                     \
+#define GFT_SERIES3_SEEDED(SYM, OP, FN, W)                                                                                                    \
     int SYM(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, const double* seed,            \
             const int64_t* sbs, double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2,                   \
             const size_t* batch, size_t nbatch, void* stream) {                                                                               \
-        GFT_SERIES_ENTRY(OP, FN, W, false,                                                                                                    \
-                         (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.y = rows1(seed, sbs, 1),                            \
-                          c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                                      \
+        GFT_SERIES_ENTRY(OP, FN, W, 3,                                                                                                        \
+                         (c.x = view(x, xbs, nx2, xrs, nx1, xss, nx0), c.y = view(seed, sbs, 1),                                              \
+                          c.r = view(res, rbs, n2, rrs, n1, rss, n0)));                                                                       \
     }
 #define GFT_SERIES3_COMPOSE_POW(PFX, WHAT, W)                                                                                                 \
     int PFX##series3_compose(const double* f, const int64_t* fbs, int64_t fss, int64_t frs, size_t nf0, size_t nf1, size_t nf2, const double* g, \
-                            const int64_t* gbs, int64_t gss, int64_t grs, size_t ng0, size_t ng1, size_t ng2, int var, double* res,          \
+                            const int64_t* gbs, int64_t gss, int64_t grs, size_t ng0, size_t ng1, size_t ng2, int var, double* res,           \
                             const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch, size_t nbatch, \
                             void* stream) {                                                                                                   \
-        GFT_SERIES_ENTRY(SERIES_COMPOSE, WHAT "series3_compose", W, false,                                                                       \
-                         (c.rank3 = true, c.x = rows3(f, fbs, fss, frs, nf0, nf1, nf2), c.y = rows3(g, gbs, gss, grs, ng0, ng1, ng2),         \
-                          c.var = var, c.r = rows3(res, rbs, rss, rrs, n0, n1, n2)));                                                         \
+        GFT_SERIES_ENTRY(SERIES_COMPOSE, WHAT "series3_compose", W, 3,                                                                        \
+                         (c.x = view(f, fbs, nf2, frs, nf1, fss, nf0), c.y = view(g, gbs, ng2, grs, ng1, gss, ng0),                           \
+                          c.var = var, c.r = view(res, rbs, n2, rrs, n1, rss, n0)));                                                          \
     }                                                                                                                                         \
     int PFX##series3_pow(const double* x, const int64_t* xbs, int64_t xss, int64_t xrs, size_t nx0, size_t nx1, size_t nx2, uint32_t e,       \
                         double* res, const int64_t* rbs, int64_t rss, int64_t rrs, size_t n0, size_t n1, size_t n2, const size_t* batch,      \
                         size_t nbatch, void* stream) {                                                                                        \
-        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series3_pow", W, false,                                                                               \
-                         (c.rank3 = true, c.x = rows3(x, xbs, xss, xrs, nx0, nx1, nx2), c.e = e, c.r = rows3(res, rbs, rss, rrs, n0, n1, n2))); \
+        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series3_pow", W, 3,                                                                                \
+                         (c.x = view(x, xbs, nx2, xrs, nx1, xss, nx0), c.e = e, c.r = view(res, rbs, n2, rrs, n1, rss, n0)));                 \
     }
 #define GFT_SERIES3_ARITH(PFX, WHAT, W)                                        \
     GFT_SERIES3_BINARY(PFX##series3_mul, SERIES_MUL, WHAT "series3_mul", W)    \
@@ -202,7 +188,7 @@ static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, in
     GFT_SERIES_BINARY(PFX##series_compose, SERIES_COMPOSE, WHAT "series_compose", W)                                                          \
     int PFX##series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,                \
                         const size_t* batch, size_t nbatch, void* stream) {                                                                   \
-        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series_pow", W, false, (c.x = rows1(x, xbs, nx), c.e = e, c.r = rows1(res, rbs, n)));              \
+        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series_pow", W, 1, (c.x = view(x, xbs, nx), c.e = e, c.r = view(res, rbs, n)));                    \
     }                                                                                                                                         \
     GFT_SERIES2_BINARY(PFX##series2_mul, SERIES_MUL, WHAT "series2_mul", W)                                                                   \
     GFT_SERIES2_BINARY(PFX##series2_div, SERIES_DIV, WHAT "series2_div", W)                                                                   \
@@ -211,18 +197,18 @@ static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, in
     GFT_SERIES2_BINARY_VAR(PFX##series2_compose, SERIES_COMPOSE, WHAT "series2_compose", W)                                                   \
     int PFX##series2_pow(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, uint32_t e, double* res,                   \
                          const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {           \
-        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series2_pow", W, true, (c.x = rows2(x, xbs, xrs, nx0, nx1), c.e = e, c.r = rows2(res, rbs, rrs, n0, n1))); \
+        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series2_pow", W, 2, (c.x = view(x, xbs, nx1, xrs, nx0), c.e = e, c.r = view(res, rbs, n1, rrs, n0))); \
     }
 // the observation ops: one operand, the order k (at rank 2 behind the variable), the result k shorter on that axis
 #define GFT_SERIES_OBSERVE_K(PFX, NAME, OP, WHAT, W)                                                                                          \
     int PFX##series_##NAME(const double* x, const int64_t* xbs, size_t nx, size_t k, double* res, const int64_t* rbs, size_t n,               \
                            const size_t* batch, size_t nbatch, void* stream) {                                                                \
-        GFT_SERIES_ENTRY(OP, WHAT "series_" #NAME, W, false, (c.x = rows1(x, xbs, nx), c.var = 1, c.k = k, c.r = rows1(res, rbs, n)));        \
+        GFT_SERIES_ENTRY(OP, WHAT "series_" #NAME, W, 1, (c.x = view(x, xbs, nx), c.var = 1, c.k = k, c.r = view(res, rbs, n)));              \
     }                                                                                                                                         \
     int PFX##series2_##NAME(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, int var, size_t k, double* res,         \
                             const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {        \
-        GFT_SERIES_ENTRY(OP, WHAT "series2_" #NAME, W, true,                                                                                  \
-                         (c.x = rows2(x, xbs, xrs, nx0, nx1), c.var = var, c.k = k, c.r = rows2(res, rbs, rrs, n0, n1)));                     \
+        GFT_SERIES_ENTRY(OP, WHAT "series2_" #NAME, W, 2,                                                                                     \
+                         (c.x = view(x, xbs, nx1, xrs, nx0), c.var = var, c.k = k, c.r = view(res, rbs, n1, rrs, n0)));                       \
     }
 #define GFT_SERIES_OBSERVE(PFX, WHAT, W)                                                                                                      \
     GFT_SERIES_OBSERVE_K(PFX, derivative, SERIES_DERIVATIVE, WHAT, W)                                                                         \
@@ -230,11 +216,11 @@ static gft::SeriesView rows3(const double* p, const int64_t* bs, int64_t sst, in
     GFT_SERIES_OBSERVE_K(PFX, shift_down, SERIES_SHIFT_DOWN, WHAT, W)                                                                         \
     int PFX##series_evaluate_all_one(const double* x, const int64_t* xbs, size_t nx, double* res, const int64_t* rbs, const size_t* batch,    \
                                      size_t nbatch, void* stream) {                                                                           \
-        GFT_SERIES_ENTRY(SERIES_EVAL_ONE, WHAT "series_evaluate_all_one", W, false, (c.x = rows1(x, xbs, nx), c.var = 1, c.r = rows1(res, rbs, 1))); \
+        GFT_SERIES_ENTRY(SERIES_EVAL_ONE, WHAT "series_evaluate_all_one", W, 1, (c.x = view(x, xbs, nx), c.var = 1, c.r = view(res, rbs, 1))); \
     }                                                                                                                                         \
     int PFX##series2_evaluate_all_one(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, double* res,                  \
                                       const int64_t* rbs, const size_t* batch, size_t nbatch, void* stream) {                                 \
-        GFT_SERIES_ENTRY(SERIES_EVAL_ONE, WHAT "series2_evaluate_all_one", W, true, (c.x = rows2(x, xbs, xrs, nx0, nx1), c.r = rows1(res, rbs, 1))); \
+        GFT_SERIES_ENTRY(SERIES_EVAL_ONE, WHAT "series2_evaluate_all_one", W, 2, (c.x = view(x, xbs, nx1, xrs, nx0), c.r = view(res, rbs, 1))); \
     }
 
 extern "C" {

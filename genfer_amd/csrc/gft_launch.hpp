@@ -121,6 +121,17 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, 
     lq_commit();
 }
 
+// Asks the runtime to let each of the `nk` kernels launch with `want` bytes of dynamic LDS (above the 64 KB every kernel may have).
+// Returns `want` where every request was granted, else `plain`; a refusal leaves no stale error for the caller's next HIP call.
+inline size_t grant_dynamic_lds(const void* const* ks, size_t nk, size_t want, size_t plain) {
+    for (size_t i = 0; i < nk; ++i)
+        if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)want) != hipSuccess) {
+            (void)hipGetLastError();
+            return plain;
+        }
+    return want;
+}
+
 // The library's two internal LANES: side streams that one product deals independent launches to while its own stream goes
 // on — the slab ranges of a row-pair product (gft_conv_staged.hip), the leftover launches of a peeled tiled product
 // (gft_conv_tiled.hip).  One pair for the whole library: hardware queues are few.  Created on first use, at the LOWEST

@@ -18,7 +18,8 @@
 // compose (res = f(g), Horner) keeps the result row resident across its nf - 1 steps.  Form A: three arrays per wave (f, g, the
 // result; a step runs in place from the top output down).  Form B: one workgroup per series for the whole loop, two result rows
 // and g in LDS, every step mul form B's balanced product, steps separated by an LDS-only barrier.  pow has no kernel of its
-// own: series_pow plans a sequence of mul launches on workspace rows.
+// own beside the writer of the unit item: series_pow, the one driver of ranks 1, 2 and 3, walks the steps of series_pow_steps
+// (gft_series_args.hpp) as SERIES_MUL launches of the call's rank on workspace items.
 //
 // corr (the transposed product, the adjoint of mul; f64 only) has mul's two forms with the roles turned round: form A's outputs
 // overwrite g's row from the bottom up, form B's wave walks the offset k - i downwards in lock step.  compose_adj (the transposed
@@ -93,13 +94,7 @@ unsigned budget_kb() {
     if (kb) return kb;
     const void* ks[] = {(const void*)k_series_mul_a<E>, (const void*)k_series_div_a<E>, (const void*)k_series_explog_a<E, false>,
                         (const void*)k_series_explog_a<E, true>, (const void*)k_series_compose_a<E>, (const void*)k_series_corr_a<E>};
-    kb = SA_BUDGET_KB;
-    for (const void* k : ks)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SA_BUDGET_KB * 1024) != hipSuccess) {
-            (void)hipGetLastError();  // no stale error for the caller's next HIP call
-            kb = SA_BUDGET_KB_PLAIN;
-            break;
-        }
+    kb = (unsigned)(grant_dynamic_lds(ks, sizeof(ks) / sizeof(*ks), SA_BUDGET_KB * 1024, SA_BUDGET_KB_PLAIN * 1024) / 1024);
     return kb;
 }
 
@@ -110,7 +105,7 @@ bool compose_b_big() {
     int& big = Granted<E>::compose_b_big;
     if (big < 0) {
         big = hipFuncSetAttribute((const void*)k_series_compose_b<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  3 * E::W * series_max_n(E::W) * sizeof(double)) == hipSuccess;
+                                  3 * E::W * series_limit(1, E::W) * sizeof(double)) == hipSuccess;
         if (!big) (void)hipGetLastError();
     }
     return big != 0;
@@ -122,7 +117,7 @@ bool compose_adj_big() {
     int& big = Granted<E>::compose_adj_big;
     if (big < 0) {
         big = hipFuncSetAttribute((const void*)k_series_compose_adj_b<E, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  3 * E::W * series_max_n(E::W) * sizeof(double)) == hipSuccess;
+                                  3 * E::W * series_limit(1, E::W) * sizeof(double)) == hipSuccess;
         if (!big) (void)hipGetLastError();
     }
     return big != 0;
@@ -263,59 +258,83 @@ void launch(hipStream_t st, int op, int form, const double* x, unsigned nx, cons
     ws_copy<E>(st, rT, res, g, g.rs, pl.r, n, (size_t)n * g.items, 1, g.items, false);
 }
 
+// the unit item of pow: 1.0 at [0, 0, 0] and +0.0 elsewhere, through the result's three strides -- its first factor (one item of one
+// coefficient) and the whole result of e == 0 (an interval item: [1,1] and [0,0], both planes `plane` apart); a lower rank has
+// leading lengths of 1
 template <class E>
-int pow_seq(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws, int force,
-            const SeriesPlanes& pl) {
-    if (g.items == 0) return SERIES_NONE;
-    if (e == 0) {
-        GFT_LAUNCH(k_series_unit_rows<E>, dim3(g.items), dim3(std::min(256u, (n + 63) / 64 * 64)), 0, st, res, pl.r, n, g);
-        return SERIES_NONE;
+__global__ __launch_bounds__(256) void k_series_unit(double* res, size_t plane, size_t s0, size_t s1, size_t s2, unsigned n0, unsigned n1,
+                                                     unsigned n2, SeriesBatch b) {
+    const SeriesOff o = series_offsets(b, blockIdx.x);
+    const unsigned n12 = n1 * n2;
+    for (unsigned idx = threadIdx.x; idx < n0 * n12; idx += blockDim.x) {
+        const unsigned k0 = idx / n12, r = idx - k0 * n12, k1 = r / n2, k2 = r - k1 * n2;
+        E::st(res, plane, o.r + (size_t)k0 * s0 + (size_t)k1 * s1 + (size_t)k2 * s2, idx == 0 ? E::one() : E::zero());
     }
-    // three workspace arrays of E::W planes, each plane items * n doubles whatever the compact length of the rows in it
-    const size_t wp = (size_t)g.items * n, rows = (size_t)E::W * wp;
-    double* spare[2] = {ws + rows, ws + 2 * rows};
-    int nspare = 2;
-    double* unit = ws + 3 * rows;  // E::W doubles: the planes of the one coefficient are neighbours
-    SeriesBatch one_row;
-    one_row.nd = 0;
-    one_row.items = 1;
-    GFT_LAUNCH(k_series_unit_rows<E>, dim3(1), dim3(64), 0, st, unit, (size_t)(E::W - 1), 1u, one_row);
-    // the operand, read once through its strides: base = x as rows of nx
-    double* base = ws;
-    unsigned lb = nx;
-    ws_copy<E>(st, x, base, g, g.xs, pl.x, nx, wp, nx, 1, true);
-    double* acc = unit;  // res of mt:441: [1.0] for every item until the first product
-    unsigned la = 1;
-    int form = SERIES_NONE;
-    auto product = [&](const double* a, unsigned na, size_t ap, const double* b, unsigned nb, double* out, unsigned len, bool last) {
-        form = plan<E>(SERIES_MUL, g.items, len, force);
+}
+
+// pow at every rank: the steps of series_pow_steps on workspace items, every product the rank's own SERIES_MUL launch
+template <class E>
+int pow_steps(hipStream_t st, int rank, const double* x, unsigned e, double* res, const SeriesItem& it, const SeriesBatch& g, double* ws, int force,
+              const SeriesPlanes& pl) {
+    int form = rank == 1 ? SERIES_NONE : SERIES_FORM_B;
+    if (g.items == 0) return form;
+    const unsigned* n = it.n;
+    const unsigned N = n[0] * n[1] * n[2];
+    if (e == 0) {
+        GFT_LAUNCH(k_series_unit<E>, dim3(g.items), dim3(series_threads(N)), 0, st, res, pl.r, it.rs[0], it.rs[1], it.rs[2], n[0], n[1], n[2], g);
+        return form;
+    }
+    // three workspace arrays of items * N elements each, whatever the compact shape of the items in it, and the unit item; plane-major:
+    // the upper bounds of everything in the workspace lie `wp` doubles behind the lower ones.  wp is odd where items * N is even, so
+    // the planes share no 16-byte alignment -- which costs nothing: every global access of the series kernels is one double wide
+    // (checked in the gfx950 code of gft_series*.hip and gft_div2d.hip: no 128-bit global load or store), and the interop copy
+    // takes two at a time only in its dense form and only between 16-byte aligned pointers.
+    const size_t arr = (size_t)g.items * N, wp = 3 * arr + 1;
+    double* const slot[5] = {ws + 3 * arr, ws, ws + arr, ws + 2 * arr, res};  // by SeriesPowSlot
+    SeriesBatch one;
+    one.nd = 0;
+    one.items = 1;
+    GFT_LAUNCH(k_series_unit<E>, dim3(1), dim3(64), 0, st, slot[POW_UNIT], wp, (size_t)1, (size_t)1, (size_t)1, 1u, 1u, 1u, one);
+    {
+        // the operand, read once through its strides into compact items of nx: the planes, the batch, the series axes of the rank
+        CopyGeom c;
+        int k = 0;
+        if (E::W == 2) c.ext[k] = 2, c.ss[k] = pl.x, c.ds[k] = wp, ++k;
+        size_t cs = (size_t)it.nx[0] * it.nx[1] * it.nx[2];
+        for (int a = g.nd - 1; a >= 0; --a) {
+            c.ext[k + a] = g.ext[a];
+            c.ss[k + a] = g.xs[a];
+            c.ds[k + a] = cs;
+            cs *= g.ext[a];
+        }
+        k += g.nd;
+        const size_t xc[3] = {(size_t)it.nx[1] * it.nx[2], it.nx[2], 1};
+        for (int a = 3 - rank; a < 3; ++a) c.ext[k] = it.nx[a], c.ss[k] = it.xs[a], c.ds[k] = xc[a], ++k;
+        c.nd = k;
+        interop_copy(st, x, slot[POW_WS0], c);
+    }
+    const SeriesPowSteps steps = series_pow_steps(e, it.nx, n);
+    for (int i = 0; i < steps.count; ++i) {
+        const SeriesPowStep& s = steps.step[i];
+        // a (stored shape sa; maybe the one unit item) * b (sb), compact workspace items, into `out`: compact at L, or (last) the
+        // caller's result at all of n
+        const unsigned *sa = s.sa, *sb = s.sb, *lo = s.last ? n : s.L;
+        const size_t lc[3] = {(size_t)s.L[1] * s.L[2], s.L[2], 1}, *os = s.last ? it.rs : lc;
+        const double *a = slot[s.a], *b = slot[s.b];
+        double* out = slot[s.out];
+        const SeriesBatch w = ws_batch(g, s.a == POW_UNIT ? 0 : (size_t)sa[0] * sa[1] * sa[2], (size_t)sb[0] * sb[1] * sb[2], s.last ? 0 : lc[0] * s.L[0]);
         SeriesPlanes wpl;
         wpl.w = E::W;
-        if (E::W > 1) {  // (one plane: the strides stay 0)
-            wpl.x = a == unit ? 1 : wp;
-            wpl.y = wp;
-            wpl.r = last ? pl.r : wp;
-        }
-        launch<E>(st, SERIES_MUL, form, a, na, b, nb, out, len, ws_batch(g, ap, nb, last ? 0 : len), nullptr, wpl);
-    };
-    while (e > 0) {
-        if (e & 1) {
-            const bool last = (e >> 1) == 0;
-            const unsigned len = std::min(la + lb - 1, n);
-            double* out = last ? res : spare[--nspare];
-            product(acc, la, acc == unit ? 0 : la, base, lb, out, last ? n : len, last);
-            if (acc != unit) spare[nspare++] = acc;
-            acc = out;
-            la = len;
-        }
-        e >>= 1;
-        if (e > 0) {
-            const unsigned len = std::min(2 * lb - 1, n);
-            double* out = spare[--nspare];
-            product(base, lb, lb, base, lb, out, len, false);
-            spare[nspare++] = base;
-            base = out;
-            lb = len;
+        if (E::W == 2) wpl.x = wpl.y = wp, wpl.r = s.last ? pl.r : wp;  // (one plane: the strides stay 0)
+        if (rank == 1) {
+            form = plan<E>(SERIES_MUL, g.items, lo[2], force);
+            launch<E>(st, SERIES_MUL, form, a, sa[2], b, sb[2], out, lo[2], w, nullptr, wpl);
+        } else if (rank == 2) {
+            const Series2Dims m{sa[1], sa[2], sb[1], sb[2], lo[1], lo[2], sa[2], sb[2], os[1]};
+            series2_launch(st, SERIES_MUL, series2_plan(SERIES_MUL, m, E::W), a, b, out, m, w, 0, wpl);
+        } else {
+            const Series3Dims m = series3_product_dims(sa, sb, lo, os);
+            series3_launch(st, SERIES_MUL, series3_plan(SERIES_MUL, m, E::W), a, b, out, m, w, wpl);
         }
     }
     return form;
@@ -328,7 +347,6 @@ int series_plan(int op, unsigned items, unsigned n, int force, int w) {
 }
 
 size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n, int w) {
-    if (op == SERIES_POW) return (size_t)w * (3 * (size_t)items * n + 1);
     if (form != SERIES_FORM_B || (op != SERIES_EXP && op != SERIES_LOG)) return 0;
     return (size_t)w * items * ((size_t)nx + n);
 }
@@ -339,9 +357,11 @@ void series_launch(hipStream_t st, int op, int form, const double* x, unsigned n
     else launch<EF64>(st, op, form, x, nx, y, ny, res, n, g, ws, pl);
 }
 
-int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws,
+size_t series_pow_workspace(unsigned items, const unsigned* n, int w) { return (size_t)w * (3 * (size_t)items * n[0] * n[1] * n[2] + 1); }
+
+int series_pow(hipStream_t st, int rank, const double* x, unsigned e, double* res, const SeriesItem& it, const SeriesBatch& g, double* ws,
                int force, const SeriesPlanes& pl) {
-    return pl.w == 2 ? pow_seq<EIv>(st, x, nx, e, res, n, g, ws, force, pl) : pow_seq<EF64>(st, x, nx, e, res, n, g, ws, force, pl);
+    return pl.w == 2 ? pow_steps<EIv>(st, rank, x, e, res, it, g, ws, force, pl) : pow_steps<EF64>(st, rank, x, e, res, it, g, ws, force, pl);
 }
 
 }  // namespace gft

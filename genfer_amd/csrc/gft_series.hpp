@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 
 #include "gft_interop.hpp"  // interop_copy
@@ -20,7 +21,7 @@
 
 namespace gft {
 
-// (SeriesOp, the limits, SeriesPlanes, SeriesBatch and Series2Dims: gft_series_args.hpp, the HIP-free argument layer)
+// (SeriesOp, the limits, SeriesPlanes, SeriesBatch, SeriesItem and Series2Dims: gft_series_args.hpp, the HIP-free argument layer)
 // A: one lane is one series, rows staged in LDS.  B: one wave / workgroup is one series (mul, div, compose); for exp / log the
 // lane-per-series loop of form A over a transposed global workspace.  pow is a sequence of mul launches, each planned by itself.
 enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
@@ -28,19 +29,26 @@ enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
 // The form a call takes.  force: 0 = by the thresholds, SERIES_FORM_A = form A whenever the rows fit its LDS budget,
 // SERIES_FORM_B = never form A (gft_set_option("series_form")).
 int series_plan(int op, unsigned items, unsigned n, int force, int w = 1);
-// doubles of device workspace the call needs (form B of exp / log: the transposed operand and result; pow: the base, two results
-// taking turns and the factor [1.0]; each of w planes), else 0
+// doubles of device workspace the call needs (form B of exp / log: the transposed operand and result, each of w planes), else 0.
+// Not for SERIES_POW (series_pow_workspace).
 size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n, int w = 1);
 // Launches the call on `st`.  `y`: the second operand of mul / div / compose (x is f, y is g); for exp / log the seeds or nullptr
 // (seeds formed on the device by the HIP device library's exp / log).  `ws`: series_workspace() doubles.  Not for SERIES_POW.
 // corr and compose_adj: the result is the SHORT side, n <= nx, and series_plan takes the long side nx (the rows held in LDS).
 void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
                    unsigned n, const SeriesBatch& g, double* ws, const SeriesPlanes& pl = SeriesPlanes());
-// x^e on `st`: x is copied once into the workspace, every product but the last is a mul launch on workspace rows of the compact
-// length, the last one writes the n coefficients through the result's strides.  `force` as for series_plan; returns the form of
-// the last product (SERIES_NONE for e == 0, which only writes [1, 0, ...]).
-int series_pow(hipStream_t st, const double* x, unsigned nx, unsigned e, double* res, unsigned n, const SeriesBatch& g, double* ws,
+// pow at every rank (gft[i]_series_pow, _series2_pow, _series3_pow): x^e on `st` by the steps of series_pow_steps
+// (gft_series_args.hpp).  x is copied once through its strides into the workspace, every product but the last is the rank's
+// SERIES_MUL launch (series_launch, series2_launch, series3_launch, each planned by itself) on compact workspace items, the last one
+// writes all of n through the result's strides.  e == 0 only writes the unit item.  `ws`: series_pow_workspace() doubles, plane-major
+// -- three arrays of items * n0 * n1 * n2 and the unit item [1.0], and the upper bounds of all of that behind the lower ones.
+// `force` as for series_plan (rank 1 only).  Returns what gft_series_last_form() reports: at rank 1 the form of the last product
+// (SERIES_NONE for e == 0), above it SERIES_FORM_B.
+size_t series_pow_workspace(unsigned items, const unsigned* n, int w = 1);
+int series_pow(hipStream_t st, int rank, const double* x, unsigned e, double* res, const SeriesItem& it, const SeriesBatch& g, double* ws,
                int force, const SeriesPlanes& pl = SeriesPlanes());
+// lanes of a one-workgroup-per-item launch: one wave up to 64 units of parallel work, else whole waves up to `most`
+inline unsigned series_threads(unsigned work, unsigned most = 256) { return work <= 64 ? 64u : std::min(most, (work + 63) / 64 * 64); }
 // form B of div: k_div_1d_wave / k_div_1d with blockIdx.x as the item (gft_div2d.hip)
 void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
                      const SeriesBatch& g, const SeriesPlanes& pl = SeriesPlanes());
@@ -65,18 +73,10 @@ struct Series2Plan {
 Series2Plan series2_plan(int op, const Series2Dims& d, int w = 1);
 // Launches SERIES_MUL / DIV / EXP / LOG / COMPOSE at rank 2 on `st`.  `y`: the divisor / second factor / compose's g (x is f, and
 // `var` the variable of f that g replaces); for exp / log the seeds or nullptr.  `pl`: the element width and the plane strides.  Not
-// for SERIES_POW.  SERIES_CORR and SERIES_COMPOSE_ADJ (w == 1 only): the transposed product and the transposed Horner loop of
+// for SERIES_POW (series_pow).  SERIES_CORR and SERIES_COMPOSE_ADJ (w == 1 only): the transposed product and the transposed Horner loop of
 // gft_series2_corr / gft_series2_compose_adj, x the long side (g; gh with y = g and `var`), the result the short one.
 void series2_launch(hipStream_t st, int op, const Series2Plan& p, const double* x, const double* y, double* res, const Series2Dims& d,
                     const SeriesBatch& g, int var = 0, const SeriesPlanes& pl = SeriesPlanes());
-// doubles of device workspace series2_pow needs: the base and two results taking turns, each items * n0 * n1, and the factor [[1.0]];
-// w planes of that, plane-major
-size_t series2_pow_workspace(unsigned items, const Series2Dims& d, int w = 1);
-// x^e on `st`, series_pow at rank 2: x is copied once into the workspace, every product but the last is a SERIES_MUL launch on
-// compact workspace items, the last one writes all (n0, n1) coefficients through the result's strides.  e == 0 only writes the
-// unit item.
-void series2_pow(hipStream_t st, const double* x, unsigned e, double* res, const Series2Dims& d, const SeriesBatch& g, double* ws,
-                 const SeriesPlanes& pl = SeriesPlanes());
 
 // ---- rank 3: batched trivariate series (gft_series3_* on F64, gfti_series3_* on Interval<F64>: mul / div / exp / log / compose / pow) ---
 // The last THREE axes of every operand are one item's coefficient array: axis -3 the slabs and axis -2 the rows (any non-negative
@@ -104,14 +104,6 @@ void series3_launch(hipStream_t st, int op, const Series3Plan& p, const double* 
 Series3Plan series3_compose_plan(const Series3Compose& c, int w = 1);
 void series3_compose_launch(hipStream_t st, const Series3Plan& p, const double* f, const double* g, double* res, const Series3Compose& c,
                             const SeriesBatch& b, const SeriesPlanes& pl = SeriesPlanes());
-// pow at rank 3 (gft_series3_pow), series2_pow with a slab axis: x (stored shape nx, element strides xs of its three axes) is copied
-// once into the workspace, every product but the last is a SERIES_MUL launch on compact workspace items, the last one writes all of n
-// through the result's strides rs.  e == 0 only writes the unit item.  `ws`: series3_pow_workspace() doubles -- the base and two
-// results taking turns, each items * n0 * n1 * n2, and the factor [[[1.0]]]; w planes of that, plane-major (the operand's planes are
-// one more axis of the copy).
-size_t series3_pow_workspace(unsigned items, const unsigned* n, int w = 1);
-void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
-                 const SeriesBatch& g, double* ws, const SeriesPlanes& pl = SeriesPlanes());
 
 // ---- the observation ops at ranks 1 and 2 (gft_series_observe.hip) ----------------------------------------------------------------
 // op is SERIES_DERIVATIVE / SERIES_COEFF / SERIES_SHIFT_DOWN / SERIES_EVAL_ONE.  `d`: the operand's stored shape (nx0, nx1), row

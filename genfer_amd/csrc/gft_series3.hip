@@ -1,6 +1,6 @@
-// Batched trivariate series (gft_series.hpp, "rank 3"): the planner and the launches of gft_series3_mul / div / exp / log / compose, and
-// pow's sequence of mul launches, for F64 and for Interval<F64> (the element width w of the entry point: SeriesPlanes).  The kernels
-// are in gft_series3_kernels.hpp; gfx950 only.  The choices for mul / div / exp / log have not been measured beyond the tables of
+// Batched trivariate series (gft_series.hpp, "rank 3"): the planner and the launches of gft_series3_mul / div / exp / log / compose,
+// for F64 and for Interval<F64> (the element width w of the entry point: SeriesPlanes).  The kernels are in gft_series3_kernels.hpp;
+// gfx950 only.  pow is series_pow (gft_series.hip) over this file's SERIES_MUL launch.  The choices for mul / div / exp / log have not been measured beyond the tables of
 // they are rank 2's (gft_series2.hip), counted the same way; compose's lane count has its own sweep (DESIGN
 // 3.23).
 //
@@ -20,8 +20,7 @@
 // (SERIES3_MAX_ELEMS_IV), two resident arrays are the same 64 KB, an item with a second slab has slabs of at most 1024 elements
 // (16 KB: one chunk fits), and the scratch, compose's GLDS decision and the refusal scale with the width.  The LDS requests and what
 // the runtime answered are kept per element type.
-// compose's lanes count mul's output pairs of the full shape, in whole waves up to S3_COMPOSE_LANES.  pow has no kernel of its own
-// beside the writer of the unit item.
+// compose's lanes count mul's output pairs of the full shape, in whole waves up to S3_COMPOSE_LANES.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,33 +46,13 @@ size_t s3_budget(int w) {
                         (const void*)k_series3_compose<true>};
     const void* ki[] = {(const void*)k_series3i_rec<EIv, SERIES_DIV>, (const void*)k_series3i_rec<EIv, SERIES_EXP>,
                         (const void*)k_series3i_rec<EIv, SERIES_LOG>, (const void*)k_series3i_compose<EIv, true>};
-    granted = S3_BUDGET;
-    for (const void* k : w == 2 ? ki : kf)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S3_BUDGET) != hipSuccess) {
-            (void)hipGetLastError();  // no stale error for the caller's next HIP call
-            granted = S3_BUDGET_PLAIN;
-            break;
-        }
+    granted = grant_dynamic_lds(w == 2 ? ki : kf, 4, S3_BUDGET, S3_BUDGET_PLAIN);
     return granted;
 }
 
-unsigned s3_threads(unsigned work, unsigned most = 256) { return work <= 64 ? 64u : std::min(most, (work + 63) / 64 * 64); }
 // compose: rank 2's rule (S2_COMPOSE_LANES), whole waves over the output pairs up to two waves a SIMD; the sweep of 256 / 512 / 1024
 // lanes at rank 3 is in DESIGN 3.23 (profiles/r20/series3_compose_lanes.json).
 constexpr unsigned S3_COMPOSE_LANES = 512;
-
-// the unit item of pow: 1.0 at [0, 0, 0] and +0.0 elsewhere, through the result's three strides -- its first factor (one item of one
-// coefficient) and the whole result of e == 0 (an interval item: [1,1] and [0,0], both planes `plane` apart)
-template <class E>
-__global__ __launch_bounds__(256) void k_series3_unit(double* res, size_t plane, size_t s0, size_t s1, size_t s2, unsigned n0, unsigned n1,
-                                                      unsigned n2, SeriesBatch b) {
-    const SeriesOff o = series_offsets(b, blockIdx.x);
-    const unsigned n12 = n1 * n2;
-    for (unsigned idx = threadIdx.x; idx < n0 * n12; idx += blockDim.x) {
-        const unsigned k0 = idx / n12, r = idx - k0 * n12, k1 = r / n2, k2 = r - k1 * n2;
-        E::st(res, plane, o.r + (size_t)k0 * s0 + (size_t)k1 * s1 + (size_t)k2 * s2, idx == 0 ? E::one() : E::zero());
-    }
-}
 
 }  // namespace
 
@@ -82,13 +61,13 @@ Series3Plan series3_plan(int op, const Series3Dims& d, int w) {
     const size_t elem = (size_t)w * sizeof(double);  // of an LDS element
     const unsigned n12 = d.n[1] * d.n[2], N = d.n[0] * n12;
     if (op == SERIES_MUL) {
-        p.threads = s3_threads((N + 1) / 2);
+        p.threads = series_threads((N + 1) / 2);
         p.lds = ((size_t)d.nx[0] * d.nx[1] * d.nx[2] + (size_t)d.ny[0] * d.ny[1] * d.ny[2]) * elem;
         return p;
     }
     // the device-free arithmetic is series3_sizes (gft_series_args.hpp); the grant is asked only where an item needs scratch
     Series3Sizes z = series3_sizes(op, d, w, S3_BUDGET);
-    p.threads = s3_threads(N);
+    p.threads = series_threads(N);
     if (z.need) {
         const size_t budget = s3_budget(w);
         if (budget != S3_BUDGET) z = series3_sizes(op, d, w, budget);
@@ -108,7 +87,7 @@ Series3Plan series3_compose_plan(const Series3Compose& c, int w) {
     Series3Plan p;
     const size_t N = (size_t)c.full[0] * c.full[1] * c.full[2], elem = (size_t)w * sizeof(double);
     const size_t arrays = 2 * N * elem, all = arrays + (size_t)c.ng[0] * c.ng[1] * c.ng[2] * elem;
-    p.threads = s3_threads((unsigned)((N + 1) / 2), S3_COMPOSE_LANES);
+    p.threads = series_threads((unsigned)((N + 1) / 2), S3_COMPOSE_LANES);
     p.glds = all <= S3_BUDGET_PLAIN || all <= s3_budget(w);
     p.lds = p.glds ? all : arrays;
     return p;
@@ -125,104 +104,6 @@ void series3_compose_launch(hipStream_t st, const Series3Plan& p, const double* 
     }
     if (p.glds) GFT_LAUNCH(k_series3_compose<true>, grid, block, p.lds, st, f, g, res, c, b);
     else GFT_LAUNCH(k_series3_compose<false>, grid, block, p.lds, st, f, g, res, c, b);
-}
-
-size_t series3_pow_workspace(unsigned items, const unsigned* n, int w) { return (size_t)w * (3 * (size_t)items * n[0] * n[1] * n[2] + 1); }
-
-namespace {
-
-// series2_pow (gft_series2.hip) with a slab axis
-template <class E>
-void s3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
-            const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
-    if (g.items == 0) return;
-    const unsigned N = n[0] * n[1] * n[2];
-    if (e == 0) {
-        GFT_LAUNCH(k_series3_unit<E>, dim3(g.items), dim3(s3_threads(N)), 0, st, res, pl.r, rs[0], rs[1], rs[2], n[0], n[1], n[2], g);
-        return;
-    }
-    // three workspace arrays of items * N elements each, whatever the compact shape of the items in it, and the unit item; plane-major:
-    // the upper bounds of everything in the workspace lie `wp` doubles behind the lower ones
-    const size_t arr = (size_t)g.items * N, wp = 3 * arr + 1;
-    double* spare[2] = {ws + arr, ws + 2 * arr};
-    int nspare = 2;
-    double* unit = ws + 3 * arr;
-    SeriesBatch one;
-    one.nd = 0;
-    one.items = 1;
-    GFT_LAUNCH(k_series3_unit<E>, dim3(1), dim3(64), 0, st, unit, wp, (size_t)1, (size_t)1, (size_t)1, 1u, 1u, 1u, one);
-    // the operand, read once through its strides: base = x as compact items of nx
-    double* base = ws;
-    unsigned lb[3] = {nx[0], nx[1], nx[2]};
-    {
-        CopyGeom c;
-        int k = 0;
-        if (E::W == 2) c.ext[k] = 2, c.ss[k] = pl.x, c.ds[k] = wp, ++k;
-        size_t cs = (size_t)lb[0] * lb[1] * lb[2];
-        for (int a = g.nd - 1; a >= 0; --a) {
-            c.ext[k + a] = g.ext[a];
-            c.ss[k + a] = g.xs[a];
-            c.ds[k + a] = cs;
-            cs *= g.ext[a];
-        }
-        k += g.nd;
-        c.ext[k] = lb[0], c.ss[k] = xs[0], c.ds[k] = (size_t)lb[1] * lb[2], ++k;
-        c.ext[k] = lb[1], c.ss[k] = xs[1], c.ds[k] = lb[2], ++k;
-        c.ext[k] = lb[2], c.ss[k] = 1, c.ds[k] = 1, ++k;
-        c.nd = k;
-        interop_copy(st, x, base, c);
-    }
-    double* acc = unit;  // res of mt:441: [[[1.0]]] for every item until the first product
-    unsigned la[3] = {1, 1, 1};
-    // a * b, compact workspace items of the stored shapes sa and sb (`a` may be the one unit item), into `out`: compact at L, or (last)
-    // the caller's result at all of n
-    auto product = [&](const double* a, const unsigned* sa, const double* b, const unsigned* sb, double* out, const unsigned* L, bool last) {
-        const Series3Dims m = last ? series3_product_dims(sa, sb, n, rs) : series3_product_dims(sa, sb, L);
-        SeriesBatch w = g;
-        w.inplace = 0;
-        const size_t xi = a == unit ? 0 : (size_t)sa[0] * sa[1] * sa[2], yi = (size_t)sb[0] * sb[1] * sb[2], ri = (size_t)L[0] * L[1] * L[2];
-        size_t cs = 1;
-        for (int ax = g.nd - 1; ax >= 0; --ax) {
-            w.xs[ax] = cs * xi;
-            w.ys[ax] = cs * yi;
-            w.ss[ax] = 0;
-            if (!last) w.rs[ax] = cs * ri;
-            cs *= g.ext[ax];
-        }
-        SeriesPlanes wpl;
-        wpl.w = E::W;
-        if (E::W == 2) wpl.x = wpl.y = wp, wpl.r = last ? pl.r : wp;
-        series3_launch(st, SERIES_MUL, series3_plan(SERIES_MUL, m, E::W), a, b, out, m, w, wpl);
-    };
-    while (e > 0) {
-        unsigned L[3];
-        if (e & 1) {
-            const bool last = (e >> 1) == 0;
-            series3_compact(la, lb, n, L);
-            double* out = last ? res : spare[--nspare];
-            product(acc, la, base, lb, out, L, last);
-            if (acc != unit) spare[nspare++] = acc;
-            acc = out;
-            la[0] = L[0], la[1] = L[1], la[2] = L[2];
-        }
-        e >>= 1;
-        if (e > 0) {
-            series3_compact(lb, lb, n, L);
-            double* out = spare[--nspare];
-            product(base, lb, base, lb, out, L, false);
-            spare[nspare++] = base;
-            base = out;
-            lb[0] = L[0], lb[1] = L[1], lb[2] = L[2];
-        }
-    }
-}
-
-}  // namespace
-
-void series3_pow(hipStream_t st, const double* x, unsigned e, double* res, const unsigned* nx, const size_t* xs, const unsigned* n, const size_t* rs,
-                 const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
-    if (pl.w == 2) s3_pow<EIv>(st, x, e, res, nx, xs, n, rs, g, ws, pl);
-    else s3_pow<EF64>(st, x, e, res, nx, xs, n, rs, g, ws, pl);
 }
 
 void series3_launch(hipStream_t st, int op, const Series3Plan& p, const double* x, const double* y, double* res, const Series3Dims& d,

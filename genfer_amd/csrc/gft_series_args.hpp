@@ -1,6 +1,7 @@
-// The host-side argument layer of the batched series calls (gft[i]_series[2]_*): the plain types a call is described and
-// planned with, and everything that is judged about a call without touching device state -- the shape rules, the batch, the
-// strides, the result's distinct addresses, the overlap proof and the collapse of the batch axes into a SeriesBatch.
+// The host-side argument layer of the batched series calls (gft[i]_series[2|3]_*): the plain types a call of any rank is described
+// and planned with (one SeriesCall in, one SeriesItem out), and everything that is judged about a call without touching device
+// state -- the shape rules, the batch, the strides, the result's distinct addresses, the overlap proof and the collapse of the
+// batch axes into a SeriesBatch; then what is planned from the shapes alone: the rank-3 item, compose's chain and pow's steps.
 // No HIP include: this header compiles with a plain host compiler (tests/series_args_main.cpp replays refusals through it).
 // The device side (planners, launches, __device__ helpers) is gft_series.hpp; the caller with the device is gft_api_series.inc.
 #pragma once
@@ -39,11 +40,17 @@ enum SeriesOp {
 constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
 // Interval<F64> series (gfti_series_*): two planes per row, so the same LDS footprints are reached at half the order
 constexpr unsigned SERIES_MAX_N_IV = 2048;
-inline unsigned series_max_n(int w) { return w == 2 ? SERIES_MAX_N_IV : SERIES_MAX_N; }
 constexpr unsigned SERIES2_MAX_ELEMS = 4096;  // n0 * n1 of the result: two resident arrays are then 64 KB
 // Interval<F64> items (gfti_series2_*): an LDS element is a 16-byte {lo, hi}, so two resident arrays are the same 64 KB at half that
 constexpr unsigned SERIES2_MAX_ELEMS_IV = 2048;
-inline unsigned series2_max_elems(int w) { return w == 2 ? SERIES2_MAX_ELEMS_IV : SERIES2_MAX_ELEMS; }
+constexpr unsigned SERIES3_MAX_ELEMS = 4096;  // n0 * n1 * n2 of the result: the two-arrays-in-64-KB footprint of rank 2
+// Interval<F64> items (gfti_series3_*): 16-byte LDS elements, the same 64 KB at half that
+constexpr unsigned SERIES3_MAX_ELEMS_IV = 2048;
+// the most coefficients of an item's long side, by the rank (1, 2, 3) and the element width (1: F64, 2: Interval<F64>)
+inline unsigned series_limit(int rank, int w) {
+    constexpr unsigned most[3][2] = {{SERIES_MAX_N, SERIES_MAX_N_IV}, {SERIES2_MAX_ELEMS, SERIES2_MAX_ELEMS_IV}, {SERIES3_MAX_ELEMS, SERIES3_MAX_ELEMS_IV}};
+    return most[rank - 1][w == 2];
+}
 
 // The element of a call: w = 1 is F64 (one plane, the strides below unused), w = 2 is Interval<F64>, stored as the planes
 // (lo, hi) x / y / s / r elements apart (operands, seeds, result; 0 on an operand: a point interval read twice).
@@ -62,47 +69,45 @@ struct SeriesBatch {
     size_t xs[IMAXD], ys[IMAXD], ss[IMAXD], rs[IMAXD];
 };
 
+// One item of an accepted call, at every rank: the stored shapes of x and y and the result's over the three series axes (slabs, rows,
+// the unit-stride axis), right-aligned -- a lower rank has leading lengths of 1 -- and the element strides of those axes (0 under
+// a length of 1, the last one 1).  exp / log / pow: ny is 1.
+struct SeriesItem {
+    unsigned nx[3], ny[3], n[3];
+    size_t xs[3], ys[3], rs[3];
+};
+// the by-value parameter of the rank-2 kernels and of series_observe: the last two axes of an item
 struct Series2Dims {
     unsigned nx0, nx1, ny0, ny1, n0, n1;  // stored shapes of x and y (exp / log / pow: ny* unused) and the result's; nx*, ny* <= n*
                                           // (SERIES_CORR / SERIES_COMPOSE_ADJ at rank 2: x is g / gh, the LONG side: ny*, n* <= nx*)
     size_t xr, yr, rr;                    // row strides in elements
 };
-// rank 3 (gft_series3_*): what Series2Dims does not say -- the slabs (axis -3) of x, y and the result and their strides in elements
-struct SeriesSlabs {
-    unsigned nx = 1, ny = 1, n = 1;
-    size_t xs = 0, ys = 0, rs = 0;
-};
-constexpr unsigned SERIES3_MAX_ELEMS = 4096;  // n0 * n1 * n2 of the result: the two-arrays-in-64-KB footprint of rank 2
-// Interval<F64> items (gfti_series3_*): 16-byte LDS elements, the same 64 KB at half that
-constexpr unsigned SERIES3_MAX_ELEMS_IV = 2048;
-inline unsigned series3_max_elems(int w) { return w == 2 ? SERIES3_MAX_ELEMS_IV : SERIES3_MAX_ELEMS; }
+static inline Series2Dims series2_dims(const SeriesItem& i) { return Series2Dims{i.nx[1], i.nx[2], i.ny[1], i.ny[2], i.n[1], i.n[2], i.xs[1], i.ys[1], i.rs[1]}; }
 
-// One operand of a call as the C ABI states it: len0 rows of len1 elements (unit stride), `rst` elements apart.  Rank 1 is
-// len0 == 1 with row stride 0; rank 3 is `slabs` such arrays `sst` elements apart (else one).  `bs`: nbatch batch strides in elements, for w == 2 preceded by the lo -> hi plane stride; null:
-// contiguous items of the operand's own shape (the planes back to back).
+// One operand of a call as the C ABI states it: its lengths over the three series axes (slabs, rows, the unit-stride axis),
+// right-aligned, and their strides in elements (st[2] is not read: that axis has unit stride).  A lower rank has leading lengths of
+// 1 and strides of 0.  `bs`: nbatch batch strides in elements, for w == 2 preceded by the lo -> hi plane stride; null: contiguous
+// items of the operand's own shape (the planes back to back).
 struct SeriesView {
     const double* p = nullptr;
     const int64_t* bs = nullptr;
-    int64_t rst = 0;
-    size_t len0 = 1, len1 = 1;
-    int64_t sst = 0;
-    size_t slabs = 1;
+    size_t len[3] = {1, 1, 1};
+    int64_t st[3] = {0, 0, 1};
 };
 
-// One call.  `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; p may be null; one double per
-// item, so its lengths stay 1); pow has neither, and `e`.  corr (x is g, y is y) and compose_adj (x is gh, y is g, the result has
-// nf coefficients) are the transposed operations: their result is the SHORT side, so x bounds y and the result, and the rows the
-// planner sizes are x's.  rank2 (gft[i]_series2_*): the limit bounds len0 * len1 of the long side; `var`: compose's variable there.
-// The observation ops (SERIES_DERIVATIVE ...): x is the one operand and the LONG side, `k` the order, `var` the axis at rank 2 (at
-// rank 1 it is 1, the series axis), and the result's shape must be x's with k taken off that axis (evaluate_all_one: one element
-// per item).
+// One call of rank 1, 2 or 3 (gft[i]_series_*, _series2_*, _series3_*): the limit bounds the product of the long side's lengths.
+// `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; p may be null; one double per item, so its
+// lengths stay 1); pow has neither, and `e`.  corr (x is g, y is y) and compose_adj (x is gh, y is g, the result has nf
+// coefficients) are the transposed operations (ranks 1 and 2): their result is the SHORT side, so x bounds y and the result, and
+// the rows the planner sizes are x's.  `var`: compose's variable above rank 1, counted over the call's own axes (rank 3: 0 the
+// slab axis, 1 the row axis, 2 the unit-stride axis).  The observation ops (SERIES_DERIVATIVE ..., ranks 1 and 2): x is the one
+// operand and the LONG side, `k` the order, `var` the axis at rank 2 (at rank 1 it is 1, the series axis), and the result's shape
+// must be x's with k taken off that axis (evaluate_all_one: one element per item).  Rank 3 has mul / div / exp / log / compose / pow.
 struct SeriesCall {
     int op = SERIES_MUL;
     const char* fn = "";  // the name in messages
     int w = 1;
-    bool rank2 = false;
-    bool rank3 = false;  // gft[i]_series3_*: mul / div / exp / log / compose / pow; the limit bounds slabs * len0 * len1 of the
-                         // result; `var`: compose's variable there (0: the slab axis, 1: the row axis, 2: the unit-stride axis)
+    int rank = 1;
     uint32_t e = 0;
     int var = 0;
     size_t k = 0;
@@ -111,21 +116,18 @@ struct SeriesCall {
     SeriesView x, y, r;
 };
 
-// What series_args makes of an accepted call: the collapsed batch, the plane strides and the lengths narrowed to unsigned (exact:
-// the limits have been judged) with the row strides.
+// What series_args makes of an accepted call: the collapsed batch, the plane strides and the item -- the lengths narrowed to
+// unsigned (exact: the limits have been judged) with the strides of the series axes.
 struct SeriesArgs {
     SeriesBatch g;
     SeriesPlanes pl;
-    Series2Dims d;
-    SeriesSlabs s;
+    SeriesItem it;
 };
 
 struct SeriesOperand {  // a view with its strides judged: batch strides in elements, the span it covers
     const char* what;
     const double* p;
-    size_t len;
-    size_t rows, rst;  // rank 2: an item is `rows` rows, `rst` elements apart; else 1 and 0
-    size_t slabs, sst;  // rank 3: `slabs` arrays of rows, `sst` elements apart; else 1 and 0
+    size_t len[3], ist[3];  // the series axes: a stride of 0 under a length of 1, the last one 1
     size_t st[32];
     size_t plane;  // w == 2: elements from the lo plane to the hi plane (0 on an operand: a point interval), else 0
     size_t span;   // elements from p to one past its last element (of the hi plane)
@@ -136,15 +138,15 @@ static inline SeriesOperand series_arg(const SeriesCall& c, const char* what, co
     SeriesOperand a;
     a.what = what;
     a.p = v.p;
-    a.len = v.len1;
-    if (v.rst < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the row axis)");
-    a.rows = v.len0;
-    a.rst = v.len0 > 1 ? (size_t)v.rst : 0;
-    if (v.sst < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the slab axis)");
-    a.slabs = v.slabs;
-    a.sst = v.slabs > 1 ? (size_t)v.sst : 0;
-    size_t cs = v.len1 * v.len0 * v.slabs;  // NULL: contiguous items of the operand's own shape (the planes back to back)
-    a.span = v.len1 + (v.len0 - 1) * a.rst + (v.slabs - 1) * a.sst;
+    a.len[2] = v.len[2], a.ist[2] = 1;
+    a.span = v.len[2];
+    for (int i = 1; i >= 0; --i) {
+        if (v.st[i] < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + (i ? ", the row axis)" : ", the slab axis)"));
+        a.len[i] = v.len[i];
+        a.ist[i] = v.len[i] > 1 ? (size_t)v.st[i] : 0;
+        a.span += (v.len[i] - 1) * a.ist[i];
+    }
+    size_t cs = v.len[2] * v.len[1] * v.len[0];  // NULL: contiguous items of the operand's own shape (the planes back to back)
     const int64_t* bs = v.bs;
     if (c.w == 2 && bs) {
         if (bs[0] < 0) throw std::runtime_error(fn + ": negative strides are not supported (" + what + ", the plane axis)");
@@ -163,97 +165,85 @@ static inline SeriesOperand series_arg(const SeriesCall& c, const char* what, co
 }
 
 static inline bool series_same_view(const SeriesOperand& a, const SeriesOperand& b, const size_t* batch, size_t nbatch) {
-    if (a.p != b.p || a.len != b.len || a.plane != b.plane || a.rows != b.rows || a.rst != b.rst || a.slabs != b.slabs || a.sst != b.sst) return false;
+    if (a.p != b.p || a.plane != b.plane) return false;
+    for (int i = 0; i < 3; ++i)
+        if (a.len[i] != b.len[i] || a.ist[i] != b.ist[i]) return false;
     for (size_t i = 0; i < nbatch; ++i)
         if (batch[i] > 1 && a.st[i] != b.st[i]) return false;
     return true;
 }
 
-// The three shape rules, once over (rows, length) pairs: nothing is empty, the long side carries the limit, and the short sides
-// fit inside the long side.  The long side is the result, or x for the transposed and the observation ops.  The texts are per rank.
+// The three shape rules, once over the call's `rank` series axes: nothing is empty, the long side carries the limit, and the short
+// sides fit inside the long side.  The long side is the result, or x for the transposed and the observation ops (ranks 1 and 2).
+// The texts are per rank: rank 1 names its lengths, the higher ranks print the last `rank` lengths of a view.
 // (static, as everything below: the library exports none of this layer)
-// rank 3: the same three rules over (slabs, rows, length) triples, the result the long side
-static inline void series3_shapes(const SeriesCall& c) {
-    using std::to_string;
-    const std::string f(c.fn);
-    // (the text is pinned byte for byte by tests/series3_compose_args_main.cpp and tests/series_refusals.json; its "on f64" dates from
-    // before gfti_series3_* and misleads an interval caller or one with another width -- to be retired with those pins)
-    if ((c.w != 1 && c.w != 2) || c.op > SERIES_POW) throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
-    const bool comp = c.op == SERIES_COMPOSE;
-    if (comp && (c.var < 0 || c.var > 2)) throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable of f that g replaces is 0, 1 or 2)");
-    const bool binary = c.op == SERIES_MUL || c.op == SERIES_DIV || comp;
-    auto empty = [](const SeriesView& v) { return v.slabs == 0 || v.len0 == 0 || v.len1 == 0; };
-    auto dims = [](const SeriesView& v, const char* sep) { return to_string(v.slabs) + sep + to_string(v.len0) + sep + to_string(v.len1); };
-    const SeriesView& L = c.r;
-    if (empty(L)) throw std::runtime_error(f + ": n0 * n1 * n2 == 0 (the result has no coefficients)");
-    const size_t most = series3_max_elems(c.w);
-    if (L.slabs > most || L.len0 > most || L.len1 > most || L.slabs * L.len0 > most || L.slabs * L.len0 * L.len1 > most)
-        throw std::runtime_error(f + ": n0 * n1 * n2 = " + dims(L, " * ") + " exceeds the limit of " + to_string(most) + " coefficients per item of this version");
-    if (empty(c.x) || (binary && empty(c.y))) throw std::runtime_error(f + ": an operand has no coefficients");
-    auto fits = [&](const SeriesView& s, const char* who) {
-        if (s.slabs <= L.slabs && s.len0 <= L.len0 && s.len1 <= L.len1) return;
-        throw std::runtime_error(f + ": " + who + " has " + dims(s, " x ") + " coefficients, the result " + dims(L, " x ") +
-                                 " (an operand is longer than the truncation order)");
-    };
-    fits(c.x, comp ? "f" : "x");
-    if (binary) fits(c.y, comp ? "g" : "y");
-}
-
 static inline void series_shapes(const SeriesCall& c) {
     using std::to_string;
     const std::string f(c.fn);
-    if (c.rank3) return series3_shapes(c);
-    const int op = c.op;
+    const int op = c.op, rank = c.rank;
+    // (the text is pinned byte for byte by tests/series3_compose_args_main.cpp and tests/series_refusals.json; its "on f64" dates from
+    // before gfti_series3_* and misleads an interval caller or one with another width -- to be retired with those pins)
+    if (rank == 3 && ((c.w != 1 && c.w != 2) || op > SERIES_POW))
+        throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
     const bool observe = op >= SERIES_DERIVATIVE, comp = op == SERIES_COMPOSE;
     const bool corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
     const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed;
-    const bool r2 = c.rank2, bad_var = r2 && c.var != 0 && c.var != 1;
-    if (bad_var && (comp || adj)) throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable of f that g replaces is 0 or 1)");
+    const bool r2 = rank > 1, bad_var = r2 && (c.var < 0 || c.var >= rank);
+    if (bad_var && (comp || adj))
+        throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable of f that g replaces is " + (rank == 3 ? "0, 1 or 2)" : "0 or 1)"));
     struct Names {
         const char *x, *y, *r;
     };
     const Names len = corr ? Names{"ng", "ny", "m"} : (adj ? Names{"n", "ng", "nf"} : Names{"nx", "ny", "n"});  // rank 1: the lengths' names
-    const Names who = corr ? Names{"g", "y", "the result"} : (adj ? Names{"gh", "g", "the result"} : Names{"x", "y", "the result"});
+    const Names who = corr ? Names{"g", "y", "the result"}
+                           : (adj ? Names{"gh", "g", "the result"} : (rank == 3 && comp ? Names{"f", "g", "the result"} : Names{"x", "y", "the result"}));
+    const char* const shape = rank == 3 ? "n0 * n1 * n2" : "n0 * n1";  // above rank 1: the result's lengths by name
     const bool xlong = transposed || observe;
     const SeriesView& L = xlong ? c.x : c.r;
     const char *Llen = xlong ? len.x : len.r, *Lwho = xlong ? who.x : who.r;
-    auto empty = [](const SeriesView& v) { return v.len0 == 0 || v.len1 == 0; };
-    auto dims = [](const SeriesView& v, const char* sep) { return to_string(v.len0) + sep + to_string(v.len1); };
+    auto empty = [](const SeriesView& v) { return v.len[0] == 0 || v.len[1] == 0 || v.len[2] == 0; };
+    auto dims = [rank](const SeriesView& v, const char* sep) {  // the last `rank` lengths
+        std::string t = to_string(v.len[2]);
+        for (int i = 1; i >= 3 - rank; --i) t = to_string(v.len[i]) + sep + t;
+        return t;
+    };
     if (observe) {
         if (empty(c.x)) throw std::runtime_error(f + ": x has no coefficients");
     } else if (empty(c.r)) {
         if (!r2) throw std::runtime_error(f + ": " + len.r + " == 0 (the result has no coefficients)");
-        throw std::runtime_error(f + (transposed ? ": the result has no coefficients (an axis of its shape is 0)" : ": n0 * n1 == 0 (the result has no coefficients)"));
+        throw std::runtime_error(f + (transposed ? ": the result has no coefficients (an axis of its shape is 0)" : std::string(": ") + shape + " == 0 (the result has no coefficients)"));
     }
-    const size_t most = r2 ? series2_max_elems(c.w) : series_max_n(c.w);
-    if (L.len0 > most || L.len1 > most || L.len0 * L.len1 > most) {
+    const size_t most = series_limit(rank, c.w);
+    bool over = false;  // a length or a partial product of the lengths (none overflows: every factor is within the limit)
+    for (size_t i = 0, prod = 1; i < 3 && !over; ++i) over = L.len[i] > most || (prod *= L.len[i]) > most;
+    if (over) {
         if (!r2)
-            throw std::runtime_error(f + ": " + Llen + " = " + to_string(L.len1) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
+            throw std::runtime_error(f + ": " + Llen + " = " + to_string(L.len[2]) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
         if (xlong)
             throw std::runtime_error(f + ": " + Lwho + " has " + dims(L, " * ") + " coefficients, which exceeds the limit of " + to_string(most) +
                                      " coefficients per item of this version");
-        throw std::runtime_error(f + ": n0 * n1 = " + dims(L, " * ") + " exceeds the limit of " + to_string(most) + " coefficients per item of this version");
+        throw std::runtime_error(f + ": " + shape + " = " + dims(L, " * ") + " exceeds the limit of " + to_string(most) + " coefficients per item of this version");
     }
     if (observe) {
         if (bad_var) throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable the operation acts on is 0 or 1)");
         if (op == SERIES_EVAL_ONE) return;
         const bool rows = r2 && c.var == 0;
-        const size_t n = rows ? c.x.len0 : c.x.len1, k = c.k;
+        const size_t n = rows ? c.x.len[1] : c.x.len[2], k = c.k;
         if (k >= n)
             throw std::runtime_error(f + ": k = " + to_string(k) + ", but x has " + to_string(n) + " stored coefficients" +
                                      (r2 ? " on axis " + to_string(c.var) : std::string()) + " (the order must satisfy 0 <= k < " + to_string(n) + ")");
-        const size_t w0 = rows ? c.x.len0 - k : c.x.len0, w1 = rows ? c.x.len1 : c.x.len1 - k;
-        if (c.r.len0 != w0 || c.r.len1 != w1)
-            throw std::runtime_error(f + ": the result has " + (r2 ? to_string(c.r.len0) + " x " : std::string()) + to_string(c.r.len1) + " coefficients; with k = " +
+        const size_t w0 = rows ? c.x.len[1] - k : c.x.len[1], w1 = rows ? c.x.len[2] : c.x.len[2] - k;
+        if (c.r.len[1] != w0 || c.r.len[2] != w1)
+            throw std::runtime_error(f + ": the result has " + (r2 ? to_string(c.r.len[1]) + " x " : std::string()) + to_string(c.r.len[2]) + " coefficients; with k = " +
                                      to_string(k) + " it has " + (r2 ? to_string(w0) + " x " : std::string()) + to_string(w1) + " (x's, less k on the axis)");
         return;
     }
     if (empty(c.x) || (binary && empty(c.y))) throw std::runtime_error(f + ": an operand has no coefficients");
     auto fits = [&](const SeriesView& s, const char* slen, const char* swho) {
-        if (s.len0 <= L.len0 && s.len1 <= L.len1) return;
+        if (s.len[0] <= L.len[0] && s.len[1] <= L.len[1] && s.len[2] <= L.len[2]) return;
         const char* why = &s == &c.r ? "the result of a transposed operation is its short side" : "an operand is longer than the truncation order";
         if (r2) throw std::runtime_error(f + ": " + swho + " has " + dims(s, " x ") + " coefficients, " + Lwho + " " + dims(L, " x ") + " (" + why + ")");
-        throw std::runtime_error(f + ": " + slen + " = " + to_string(s.len1) + " > " + Llen + " = " + to_string(L.len1) + " (" + why + ")");
+        throw std::runtime_error(f + ": " + slen + " = " + to_string(s.len[2]) + " > " + Llen + " = " + to_string(L.len[2]) + " (" + why + ")");
     };
     if (transposed) fits(c.r, len.r, who.r);
     else fits(c.x, len.x, who.x);
@@ -299,15 +289,15 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
             if (ar.st[i] == 0) throw std::runtime_error(f + ": the result has a zero stride (batch axis " + std::to_string(i) + "): its series overlap");
             axes[k++] = Ax{batch[i], ar.st[i]};
         }
-        if (ar.rows > 1) {  // rank 2: the rows of an item are one more axis of the result
-            if (ar.rst == 0) throw std::runtime_error(f + ": the result has a zero row stride: the rows of an item overlap");
-            axes[k++] = Ax{ar.rows, ar.rst};
+        if (ar.len[1] > 1) {  // rank 2: the rows of an item are one more axis of the result
+            if (ar.ist[1] == 0) throw std::runtime_error(f + ": the result has a zero row stride: the rows of an item overlap");
+            axes[k++] = Ax{ar.len[1], ar.ist[1]};
         }
-        if (ar.slabs > 1) {  // rank 3: the slabs of an item are one more axis again
-            if (ar.sst == 0) throw std::runtime_error(f + ": the result has a zero slab stride: the slabs of an item overlap");
-            axes[k++] = Ax{ar.slabs, ar.sst};
+        if (ar.len[0] > 1) {  // rank 3: the slabs of an item are one more axis again
+            if (ar.ist[0] == 0) throw std::runtime_error(f + ": the result has a zero slab stride: the slabs of an item overlap");
+            axes[k++] = Ax{ar.len[0], ar.ist[0]};
         }
-        if (ar.len > 1) axes[k++] = Ax{ar.len, 1};
+        if (ar.len[2] > 1) axes[k++] = Ax{ar.len[2], 1};
         std::sort(axes, axes + k, [](const Ax& u, const Ax& v) { return u.st < v.st; });
         for (int i = 1; i < k; ++i)
             if (axes[i].st / axes[i - 1].ext < axes[i - 1].st)
@@ -352,9 +342,8 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
                 continue;
             }
         }
-        // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow at rank 2 the row axis too, at
-        // rank 3 the row and the slab axis)
-        const int most = IMAXD - w - (op == SERIES_POW ? (c.rank3 ? 2 : (c.rank2 ? 1 : 0)) : 0);
+        // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow's copy every series axis of the rank)
+        const int most = IMAXD - w - (op == SERIES_POW ? c.rank - 1 : 0);
         if (g.nd == most) throw std::runtime_error(f + ": the batch has more than " + std::to_string(most) + " non-contiguous axes");
         g.ext[g.nd] = (unsigned)e;
         g.xs[g.nd] = sx;
@@ -368,13 +357,11 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     out.pl.y = binary ? ay.plane : 0;
     out.pl.s = seeds ? ay.plane : 0;
     out.pl.r = ar.plane;
-    Series2Dims& d = out.d;
-    d.nx0 = (unsigned)c.x.len0, d.nx1 = (unsigned)c.x.len1, d.ny0 = (unsigned)c.y.len0, d.ny1 = (unsigned)c.y.len1;
-    d.n0 = (unsigned)c.r.len0, d.n1 = (unsigned)c.r.len1;
-    d.xr = ax.rst, d.yr = ay.rst, d.rr = ar.rst;
-    SeriesSlabs& s = out.s;
-    s.nx = (unsigned)c.x.slabs, s.ny = (unsigned)c.y.slabs, s.n = (unsigned)c.r.slabs;
-    s.xs = ax.sst, s.ys = ay.sst, s.rs = ar.sst;
+    SeriesItem& it = out.it;
+    for (int i = 0; i < 3; ++i) {
+        it.nx[i] = (unsigned)ax.len[i], it.ny[i] = (unsigned)ay.len[i], it.n[i] = (unsigned)ar.len[i];
+        it.xs[i] = ax.ist[i], it.ys[i] = ay.ist[i], it.rs[i] = ar.ist[i];
+    }
     return true;
 }
 
@@ -416,12 +403,7 @@ static inline Series3Dims series3_dims(int op, const unsigned* nx, const unsigne
     }
     return k;
 }
-static inline Series3Dims series3_dims(int op, const SeriesArgs& a) {
-    const Series2Dims& d = a.d;
-    const unsigned nx[3] = {a.s.nx, d.nx0, d.nx1}, ny[3] = {a.s.ny, d.ny0, d.ny1}, n[3] = {a.s.n, d.n0, d.n1};
-    const size_t xs[3] = {a.s.xs, d.xr, 1}, ys[3] = {a.s.ys, d.yr, 1}, rs[3] = {a.s.rs, d.rr, 1};
-    return series3_dims(op, nx, ny, n, xs, ys, rs);
-}
+static inline Series3Dims series3_dims(int op, const SeriesItem& i) { return series3_dims(op, i.nx, i.ny, i.n, i.xs, i.ys, i.rs); }
 
 // The scratch of div / exp / log at rank 3 (gft_series3.hip's planner, here without the device): behind the resident operand and the
 // result, `selems` elements (w * 8 bytes each) of row sums out of `budget` bytes of LDS, and the terms per chunk `tc`.  An item of one
@@ -518,11 +500,51 @@ static inline Series3Compose series3_compose_dims(const unsigned* nf, const unsi
     k.slices = nf[var], k.fslice = xs[var];
     return k;
 }
-static inline Series3Compose series3_compose_dims(const SeriesArgs& a, int var) {
-    const Series2Dims& d = a.d;
-    const unsigned nf[3] = {a.s.nx, d.nx0, d.nx1}, ng[3] = {a.s.ny, d.ny0, d.ny1}, n[3] = {a.s.n, d.n0, d.n1};
-    const size_t xs[3] = {a.s.xs, d.xr, 1}, ys[3] = {a.s.ys, d.yr, 1}, rs[3] = {a.s.rs, d.rr, 1};
-    return series3_compose_dims(nf, ng, n, xs, ys, rs, var);
+static inline Series3Compose series3_compose_dims(const SeriesItem& i, int var) { return series3_compose_dims(i.nx, i.ny, i.n, i.xs, i.ys, i.rs, var); }
+
+// ---- pow at every rank: the products of the square-and-multiply loop (mt:441-450), decided by e and the shapes alone ------------------
+// res = [1.0]; while e > 0: if e is odd, res = res * base; e >>= 1; if e > 0, base = base * base -- every product at the compact
+// shape series3_compact(a, b, n).  The operands live in slots: the unit item, three workspace arrays (x is copied into the first,
+// the other two take turns as outputs, and an array is free again once its item has been multiplied away) and the caller's result,
+// which the last product writes at all of n.  An output slot is never one of its operands'.
+enum SeriesPowSlot { POW_UNIT = 0, POW_WS0 = 1, POW_WS1 = 2, POW_WS2 = 3, POW_RESULT = 4 };
+struct SeriesPowStep {
+    int a, b, out;               // slots: out = a * b (accumulator times base, or base times base)
+    unsigned sa[3], sb[3], L[3];  // the stored shapes of a and b, and the compact shape of the product
+    bool last;
+};
+struct SeriesPowSteps {
+    int count = 0;  // popcount(e) + floor(log2 e): at most 63 of a 32-bit e, none of e == 0
+    SeriesPowStep step[63];
+};
+// (nx: the stored shape of x, n: the orders; three right-aligned lengths each)
+static inline SeriesPowSteps series_pow_steps(uint32_t e, const unsigned* nx, const unsigned* n) {
+    SeriesPowSteps p;
+    int acc = POW_UNIT, base = POW_WS0, spare[2] = {POW_WS1, POW_WS2}, nspare = 2;
+    unsigned la[3] = {1, 1, 1}, lb[3] = {nx[0], nx[1], nx[2]};
+    auto product = [&](int a, const unsigned* sa, int b, const unsigned* sb, bool last) -> SeriesPowStep& {
+        SeriesPowStep& s = p.step[p.count++];
+        s.a = a, s.b = b, s.out = last ? (int)POW_RESULT : spare[--nspare], s.last = last;
+        for (int i = 0; i < 3; ++i) s.sa[i] = sa[i], s.sb[i] = sb[i];
+        series3_compact(sa, sb, n, s.L);
+        return s;
+    };
+    while (e > 0) {
+        if (e & 1) {
+            const SeriesPowStep& s = product(acc, la, base, lb, (e >> 1) == 0);
+            if (acc != POW_UNIT) spare[nspare++] = acc;
+            acc = s.out;
+            for (int i = 0; i < 3; ++i) la[i] = s.L[i];
+        }
+        e >>= 1;
+        if (e > 0) {
+            const SeriesPowStep& s = product(base, lb, base, lb, false);
+            spare[nspare++] = base;
+            base = s.out;
+            for (int i = 0; i < 3; ++i) lb[i] = s.L[i];
+        }
+    }
+    return p;
 }
 
 }  // namespace gft

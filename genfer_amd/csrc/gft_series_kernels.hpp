@@ -416,13 +416,6 @@ __global__ __launch_bounds__(256) void k_series_compose_adj_b(const double* gh, 
     }
 }
 
-// the rows [1, 0, ..., 0] of pow: its first factor (one row: items == 1) and the whole result of e == 0
-template <class E>
-__global__ __launch_bounds__(256) void k_series_unit_rows(double* res, size_t rp, unsigned n, SeriesBatch b) {
-    const SeriesOff o = series_offsets(b, blockIdx.x);
-    for (unsigned k = threadIdx.x; k < n; k += blockDim.x) E::st(res + o.r, rp, k, k == 0 ? E::one() : E::zero());
-}
-
 // exp / log over the transposed workspace: xT [nx][items], rT [n][items], one lane per item
 template <class E, bool LOG>
 __global__ __launch_bounds__(64) void k_series_explog_ws(double* xT, unsigned nx, const double* seed, size_t sp, double* rT, unsigned n,

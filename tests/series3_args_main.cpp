@@ -33,7 +33,7 @@ static void read_view(std::istream& in, View& w) {
     const bool has = count(in, nbs);
     w.bs.resize(nbs);
     for (auto& s : w.bs) in >> s;
-    in >> w.v.sst >> w.v.rst >> w.v.slabs >> w.v.len0 >> w.v.len1;
+    in >> w.v.st[0] >> w.v.st[1] >> w.v.len[0] >> w.v.len[1] >> w.v.len[2];
     w.v.bs = has ? w.bs.data() : nullptr;
 }
 
@@ -50,7 +50,7 @@ int main() {
         if (line.empty()) continue;
         std::istringstream in(line);
         gft::SeriesCall c;
-        c.rank3 = true;
+        c.rank = 3;
         in >> c.op;
         std::vector<size_t> batch;
         const bool has_batch = count(in, c.nbatch);
@@ -79,8 +79,8 @@ int main() {
             const gft::SeriesBatch& g = a.g;
             std::printf("OK nd=%d items=%u inplace=%d", g.nd, g.items, g.inplace);
             list("ext", g.ext, g.nd), list("xs", g.xs, g.nd), list("ys", g.ys, g.nd), list("ss", g.ss, g.nd), list("rs", g.rs, g.nd);
-            std::printf(" rows=%zu,%zu,%zu slabs=%zu,%zu,%zu |", a.d.xr, a.d.yr, a.d.rr, a.s.xs, a.s.ys, a.s.rs);
-            const gft::Series3Dims k = gft::series3_dims(c.op, a);
+            std::printf(" rows=%zu,%zu,%zu slabs=%zu,%zu,%zu |", a.it.xs[1], a.it.ys[1], a.it.rs[1], a.it.xs[0], a.it.ys[0], a.it.rs[0]);
+            const gft::Series3Dims k = gft::series3_dims(c.op, a.it);
             list("S", k.keep, 3), list("run", k.n, 3), list("x", k.nx, 3), list("y", k.ny, 3), list("xst", k.xs, 3), list("yst", k.ys, 3), list("rst", k.rs, 3);
             std::printf("\n");
         } catch (const std::exception& e) {

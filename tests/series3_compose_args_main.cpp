@@ -27,8 +27,8 @@ static long checks = 0, failures = 0;
 static gft::SeriesView view(size_t off, const unsigned* s, const int64_t* bs = nullptr, int64_t sst = -1, int64_t rst = -1) {
     gft::SeriesView v;
     v.p = buffer + off, v.bs = bs;
-    v.slabs = s[0], v.len0 = s[1], v.len1 = s[2];
-    v.sst = sst >= 0 ? sst : (int64_t)(s[1] * s[2]), v.rst = rst >= 0 ? rst : (int64_t)s[2];
+    v.len[0] = s[0], v.len[1] = s[1], v.len[2] = s[2];
+    v.st[0] = sst >= 0 ? sst : (int64_t)(s[1] * s[2]), v.st[1] = rst >= 0 ? rst : (int64_t)s[2];
     return v;
 }
 
@@ -46,7 +46,7 @@ static std::string verdict(const gft::SeriesCall& c, gft::SeriesArgs* out = null
 
 static gft::SeriesCall compose_call(const unsigned* nf, const unsigned* ng, const unsigned* n, int var, const size_t* batch, size_t nbatch) {
     gft::SeriesCall c;
-    c.op = gft::SERIES_COMPOSE, c.fn = "series3_compose", c.rank3 = true, c.var = var, c.batch = batch, c.nbatch = nbatch;
+    c.op = gft::SERIES_COMPOSE, c.fn = "series3_compose", c.rank = 3, c.var = var, c.batch = batch, c.nbatch = nbatch;
     c.x = view(0, nf), c.y = view(8192, ng), c.r = view(16384, n);
     return c;
 }
@@ -74,7 +74,7 @@ static void grid() {
             }
             CHECK(got.empty());
             if (!got.empty()) continue;
-            const gft::Series3Compose k = gft::series3_compose_dims(args, var);
+            const gft::Series3Compose k = gft::series3_compose_dims(args.it, var);
             // the definition's loop, in the caller's order
             unsigned r[3] = {nf[0], nf[1], nf[2]}, L[3];
             r[var] = 1;
@@ -134,16 +134,16 @@ static void refusals() {
     expect(compose_call(zero, N, N, 0, batch, 1), "series3_compose: an operand has no coefficients");
     expect(compose_call(N, zero, N, 0, batch, 1), "series3_compose: an operand has no coefficients");
     gft::SeriesCall c = compose_call(N, N, N, 1, batch, 1);
-    c.x.sst = -12;
+    c.x.st[0] = -12;
     expect(c, "series3_compose: negative strides are not supported (f, the slab axis)");
     c = compose_call(N, N, N, 1, batch, 1);
-    c.y.rst = -4;
+    c.y.st[1] = -4;
     expect(c, "series3_compose: negative strides are not supported (g, the row axis)");
     c = compose_call(N, N, N, 1, batch, 1);
-    c.r.sst = 0;
+    c.r.st[0] = 0;
     expect(c, "series3_compose: the result has a zero slab stride: the slabs of an item overlap");
     c = compose_call(N, N, N, 1, batch, 1);
-    c.r.sst = 8;
+    c.r.st[0] = 8;
     expect(c, "series3_compose: the result's series overlap each other (its strides do not separate the rows)");
     // the slab axis in the overlap proof: a result one slab into f, and one that differs from g by its slab stride alone
     c = compose_call(N, N, N, 2, batch, 1);
@@ -163,7 +163,7 @@ static void refusals() {
     CHECK(verdict(c, &a).empty() && a.g.inplace == 1);
     // pow: admitted at rank 3, no second operand; the copy carries the batch axes, the slabs, the rows and the series
     gft::SeriesCall p;
-    p.op = gft::SERIES_POW, p.fn = "series3_pow", p.rank3 = true, p.e = 5, p.batch = batch, p.nbatch = 1;
+    p.op = gft::SERIES_POW, p.fn = "series3_pow", p.rank = 3, p.e = 5, p.batch = batch, p.nbatch = 1;
     p.x = view(0, N), p.r = view(16384, N);
     CHECK(verdict(p, &a).empty() && a.g.inplace == 0 && a.g.items == 3);
     p.r = p.x;

@@ -26,8 +26,8 @@ static long checks = 0, failures = 0;
 static gft::SeriesView view(size_t off, const unsigned* s, const int64_t* bs = nullptr) {
     gft::SeriesView v;
     v.p = buffer + off, v.bs = bs;
-    v.slabs = s[0], v.len0 = s[1], v.len1 = s[2];
-    v.sst = (int64_t)(s[1] * s[2]), v.rst = (int64_t)s[2];
+    v.len[0] = s[0], v.len[1] = s[1], v.len[2] = s[2];
+    v.st[0] = (int64_t)(s[1] * s[2]), v.st[1] = (int64_t)s[2];
     return v;
 }
 
@@ -56,7 +56,7 @@ static const char* NAMES[6] = {"interval series3_mul", "interval series3_div", "
 // a call of operation `op` on items of n, x at 0, y at 16384, the result at 32768 (planes back to back unless bs says otherwise)
 static gft::SeriesCall call(int op, const unsigned* nx, const unsigned* n, const size_t* batch, size_t nbatch, int w = 2) {
     gft::SeriesCall c;
-    c.op = op, c.fn = w == 2 ? NAMES[op] : NAMES[op] + 9, c.w = w, c.rank3 = true, c.batch = batch, c.nbatch = nbatch, c.e = 5;
+    c.op = op, c.fn = w == 2 ? NAMES[op] : NAMES[op] + 9, c.w = w, c.rank = 3, c.batch = batch, c.nbatch = nbatch, c.e = 5;
     c.x = view(0, nx), c.r = view(32768, n);
     const unsigned one[3] = {1, 1, 1};
     if (op == gft::SERIES_MUL || op == gft::SERIES_DIV || op == gft::SERIES_COMPOSE) c.y = view(16384, nx);
@@ -77,7 +77,7 @@ static void limits() {
         CHECK(verdict(call(op, one, over, batch, 1, 1)).empty());  // f64 keeps 4096
         expect(call(op, N, f64over, batch, 1, 1), f.substr(9) + ": n0 * n1 * n2 = 17 * 241 * 1 exceeds the limit of 4096 coefficients per item of this version");
     }
-    CHECK(gft::series3_max_elems(1) == 4096 && gft::series3_max_elems(2) == 2048 && gft::SERIES3_MAX_ELEMS_IV == 2048);
+    CHECK(gft::series_limit(3, 1) == 4096 && gft::series_limit(3, 2) == 2048 && gft::SERIES3_MAX_ELEMS_IV == 2048);
     // an operation rank 3 lacks keeps its text byte for byte, for both widths
     for (int w = 1; w <= 2; ++w)
         for (int op : {gft::SERIES_CORR, gft::SERIES_COMPOSE_ADJ, gft::SERIES_DERIVATIVE, gft::SERIES_EVAL_ONE}) {
@@ -121,8 +121,8 @@ static void planes() {
     c.r.bs = close;
     expect(c, "interval series3_mul: the result's series overlap each other (its strides do not separate the rows)");
     const int64_t slabwise[3] = {12, 96, 48};  // planes interleaved per SLAB: slab stride 24, planes 12 apart, items 48 apart
-    c.r.bs = slabwise, c.r.sst = 24;
-    CHECK(verdict(c, &a).empty() && a.pl.r == 12 && a.s.rs == 24);
+    c.r.bs = slabwise, c.r.st[0] = 24;
+    CHECK(verdict(c, &a).empty() && a.pl.r == 12 && a.it.rs[0] == 24);
     // the overlap proof spans both planes: a result that starts inside x's upper plane
     c = call(gft::SERIES_MUL, N, N, batch, 2);
     c.r.p = buffer + 144 + 24;

@@ -32,7 +32,7 @@ static void read_view(std::istream& in, View& w) {
     const bool has = count(in, nbs);
     w.bs.resize(nbs);
     for (auto& s : w.bs) in >> s;
-    in >> w.v.rst >> w.v.len0 >> w.v.len1;
+    in >> w.v.st[1] >> w.v.len[1] >> w.v.len[2];
     w.v.bs = has ? w.bs.data() : nullptr;
 }
 
@@ -51,7 +51,7 @@ int main() {
         gft::SeriesCall c;
         int rank2 = 0;
         in >> c.op >> c.w >> rank2 >> c.e >> c.var >> c.k;
-        c.rank2 = rank2 != 0;
+        c.rank = rank2 ? 2 : 1;
         std::vector<size_t> batch;
         const bool has_batch = count(in, c.nbatch);
         batch.resize(has_batch ? c.nbatch : 0);
@@ -79,7 +79,7 @@ int main() {
             const gft::SeriesBatch& g = a.g;
             std::printf("OK nd=%d items=%u inplace=%d", g.nd, g.items, g.inplace);
             list("ext", g.ext, g.nd), list("xs", g.xs, g.nd), list("ys", g.ys, g.nd), list("ss", g.ss, g.nd), list("rs", g.rs, g.nd);
-            std::printf(" planes=%d,%zu,%zu,%zu,%zu rows=%zu,%zu,%zu\n", a.pl.w, a.pl.x, a.pl.y, a.pl.s, a.pl.r, a.d.xr, a.d.yr, a.d.rr);
+            std::printf(" planes=%d,%zu,%zu,%zu,%zu rows=%zu,%zu,%zu\n", a.pl.w, a.pl.x, a.pl.y, a.pl.s, a.pl.r, a.it.xs[1], a.it.ys[1], a.it.rs[1]);
         } catch (const std::exception& e) {
             std::printf("E %s\n", e.what());
         }
