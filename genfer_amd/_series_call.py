@@ -11,7 +11,8 @@ and the module's name for messages.  ``run`` works on ``t.shape[-rank:]`` and ``
 stride and its second length because those tuples are one entry longer, rank 3 its slab stride and third length likewise.
 
 Everything that needs no device is judged first, in one order for every module: type, dtype, planes, axes (per tensor), the orders,
-``out``, grad, then the placement, the devices and the library's device.
+``out``, grad, then the placement, the devices and the library's device.  ``run_chain`` is the same path for ``observe_chain``, whose
+items carry their own scalars (``x``, ``cs``).
 """
 from __future__ import annotations
 
@@ -45,6 +46,9 @@ OPS = {o.suffix: o for o in (
     _op("taylor_expansion_of_coeff", "k", long="x", var=True),
     _op("shift_down", "k", long="x", var=True),
     _op("evaluate_all_one", None, long="x"),
+    # kind "chain": the operand a, at rank 2 the axis, then the scalars x and the constants cs of every item (a pointer and batch
+    # strides each, as the seeds), nsteps and degree_p1 (run_chain)
+    _op("observe_chain", "chain", long="x", names=("a", "x", "cs"), var=True),
 )}
 F64_ONLY = ("corr", "compose_adj")  # no gfti_ twin
 RANK3 = ("mul", "div", "exp", "log", "compose", "pow")  # gft[i]_series3_*: the core operations, compose and pow
@@ -77,6 +81,8 @@ def _arguments(op, rank, view, e, var, k, tail):
     ("x", "second", "out"), the others are the parts of the scalars and of the tail (the batch shape, its length, the stream):
     ctypes for the declaration, values for a call -- one layout for both."""
     a = view("x", True)
+    if op.kind == "chain":  # (k: the two counts nsteps, degree_p1)
+        return a + (var if rank >= 2 else ()) + view("second", False) + view("cs", False) + k + view("out", True) + tail
     if op.kind == "second":
         a += view("second", True)
     elif op.kind == "seed":
@@ -107,7 +113,7 @@ def _lib():
                         f = getattr(L, pre + mid + op.suffix)
                         f.restype = C.c_int
                         f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,),
-                                                     (C.c_size_t,), (_SZP, C.c_size_t, C.c_void_p)))
+                                                     (C.c_size_t,) * (2 if op.kind == "chain" else 1), (_SZP, C.c_size_t, C.c_void_p)))
         for pre in ("gft_", "gfti_"):
             for suffix in RANK3:
                 f = getattr(L, pre + "series3_" + suffix)
@@ -287,5 +293,99 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
     fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_", "series3_")[rank - 1] + op.suffix)
     parts = {"x": x, "second": second, "out": out}
     if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (scalar,), (var,), (scalar,), tail)) != 0:
+        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
+    return out
+
+
+def _count(what, name, v):
+    """one of the chain's counts: an integer, no bool"""
+    import operator
+
+    if isinstance(v, bool):
+        raise TypeError(f"{what}: {name} must be an integer, got a bool")
+    try:
+        return operator.index(v)
+    except TypeError:
+        raise TypeError(f"{what}: {name} must be an integer, got {v!r}") from None
+
+
+def run_chain(call, a, var, x, cs, degree_p1=None, out=None):
+    """One call of gft[i]_series[2]_observe_chain: ``a`` the operand, ``var`` the axis at rank 2, ``x`` one scalar per item or None
+    (the continuous form), ``cs`` the constants ``[B..., nsteps]``.  The checks come in ``run``'s order."""
+    import torch
+
+    op, (module, rank, planes, limit, _raw) = OPS["observe_chain"], call
+    what = f"{module}.{op.label}"
+    axes, _order, _short, over_text, _out_text = _rank_rules(rank)
+    for t, w in ((a, "a"), (x, "x"), (cs, "cs"), (out, "out")):
+        if t is None and w in ("x", "out"):
+            continue
+        w = f"{what}: {w}"
+        _check(torch, t, w, planes)
+        if t is a or t is out:
+            axes(t, w, planes)
+    if cs.dim() < 1 + planes:
+        raise TaylorError(f"{what}: cs has no axis of constants; it is [{'2, ' if planes else ''}B..., nsteps]")
+    if cs.shape[-1] > 1 and cs.stride(-1) != 1:
+        raise TaylorError(f"{what}: cs: the last axis (the steps) has stride {cs.stride(-1)}; it must have unit stride")
+    shape = tuple(a.shape[-rank:])
+    count = shape[0] * shape[-1] if rank == 2 else shape[0]
+    if count > limit:
+        raise TaylorError(over_text.format(what=what, shape=shape, count=count, limit=limit).replace(": x has", ": a has"))
+    axis = -1
+    if rank == 2:
+        from .series2 import _var
+
+        axis = _var(what, var, "the variable the chain acts on is 0 (axis -2) or 1 (axis -1)") - 2
+    length, nsteps, on = shape[axis], int(cs.shape[-1]), f" on axis {axis}" if rank == 2 else ""
+    if nsteps == 0:
+        raise TaylorError(f"{what}: nsteps = 0 (cs holds no constants: a chain has at least one step)")
+    d = length - nsteps if degree_p1 is None else _count(what, "degree_p1", degree_p1)
+    if d < 2:
+        raise TaylorError(f"{what}: degree_p1 = {d} (the result needs at least two coefficients{on}: degree_p1 >= 2"
+                          + (f"; the default is {length} - nsteps)" if degree_p1 is None else ")"))
+    if d + nsteps > length:
+        raise TaylorError(f"{what}: degree_p1 + nsteps = {d} + {nsteps}, but a has {length} stored coefficients{on} (every step takes one: "
+                          f"degree_p1 + nsteps <= {length})")
+    rshape = (d,) if rank == 1 else ((d, min(shape[1], d)) if axis == -2 else (min(shape[0], d), d))
+    named = [("a", a.shape[planes:a.dim() - rank])] + ([("x", x.shape[planes:])] if x is not None else []) + [("cs", cs.shape[planes:-1])]
+    try:
+        batch = tuple(torch.broadcast_shapes(*[s for _, s in named]))
+    except RuntimeError:
+        raise TaylorError(f"{what}: the batch shapes do not broadcast: " + ", ".join(f"{n} has {tuple(s)}" for n, s in named)
+                          + " (x has the batch shape, cs the batch shape and one last axis of nsteps constants)") from None
+    if out is not None:
+        if out.dim() < planes + rank or tuple(out.shape[-rank:]) != rshape:
+            raise TaylorError(f"{what}: out has shape {tuple(out.shape)}; the result has {rshape} coefficients per item (degree_p1 = {d}{on})")
+        if tuple(out.shape[planes:out.dim() - rank]) != batch:
+            raise TaylorError(f"{what}: out has batch shape {tuple(out.shape[planes:out.dim() - rank])}; the operands broadcast to {batch}")
+    if torch.is_grad_enabled():
+        for t, w in ((a, "a"), (x, "x"), (cs, "cs")):
+            if t is not None and t.requires_grad:
+                raise TaylorError(f"{what}: {w} requires grad, and observe_chain has no autograd in this version; pass {w}.detach() or call "
+                                  "under torch.no_grad() (nothing is detached silently)")
+    tensors = [(t, w) for t, w in ((a, "a"), (x, "x"), (cs, "cs"), (out, "out")) if t is not None]
+    for t, w in tensors:
+        _placed(t, f"{what}: {w}")
+    for t, _ in tensors[1:]:
+        if t.device != a.device:
+            raise TaylorError(f"{what}: the tensors are on different devices ({a.device}, {t.device})")
+    lead, nb = (2,) * planes, len(batch)
+    if out is None:
+        out = torch.empty(lead + batch + rshape, dtype=torch.float64, device=a.device)
+    if planes:  # the plane axis stays first, missing batch axes go behind it (a view)
+        lift = lambda t, dim: t if t.dim() >= dim else t[(slice(None),) + (None,) * (dim - t.dim())]  # noqa: E731
+        a, cs = lift(a, nb + 1 + rank), lift(cs, nb + 2)
+        x = None if x is None else lift(x, nb + 1)
+    L = _lib()
+    dev = int(L.gft_device())
+    if dev >= 0 and a.device.index != dev:
+        raise TaylorError(f"{what}: the tensors are on {a.device}, but the library runs on cuda:{dev}")
+    ns = nb + planes
+    parts = {"x": a.expand(lead + batch + shape), "second": None if x is None else x.expand(lead + batch),
+             "cs": cs.expand(lead + batch + (nsteps,)), "out": out}
+    tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
+    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_")[rank - 1] + op.suffix)
+    if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (), (var,), (nsteps, d), tail)) != 0:
         raise TaylorError((L.gft_last_error() or b"unknown error").decode())
     return out

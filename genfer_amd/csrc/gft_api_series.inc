@@ -7,6 +7,8 @@
 // at the stored result shape S on the permuted item of gft::series3_dims, compose on that of gft::series3_compose_dims)
 // and the observation ops gft_series_* / gft_series2_* derivative / taylor_expansion_of_coeff / shift_down / evaluate_all_one with
 // their gfti_ twins (one operand, the result shorter by the order k on one axis; the kernels: gft_series_observe.hip)
+// and the fused observation chain gft_series_observe_chain / gft_series2_observe_chain with their gfti_ twins (every item with its
+// own scalars x and constants cs, one launch for all the steps; the kernels: gft_series_observe_chain.hip)
 // Every entry point fills one gft::SeriesCall with its rank (gft_series_args.hpp, which judges it without the device and states the
 // item of any rank as one gft::SeriesItem) and hands it to series_call, which dispatches on the rank once; pow is one driver.
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
@@ -27,6 +29,15 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
     const gft::SeriesBatch& g = a.g;
     const gft::SeriesPlanes& pl = a.pl;
     const hipStream_t cs = (hipStream_t)stream;
+    if (op == gft::SERIES_OBSERVE_CHAIN) {  // one launch for the whole chain; the derivative's factors of order 1 over the axis
+        const size_t tlen = (c.rank == 2 && c.var == 0 ? it.nx[1] : it.nx[2]) - 1;
+        Rc<Buf> tab = w == 2 ? Ops<EIv>::cached_table(TAB_DERIV, 1, tlen) : Ops<EF64>::cached_table(TAB_DERIV, 1, tlen);
+        join_caller_in(cs);
+        R.series_last = gft::series_observe_chain(R.stream, x, y, c.cs.p, res, gft::series2_dims(it), c.var, c.rank == 2, (unsigned)c.nsteps,
+                                                  (unsigned)c.degree_p1, g, pl, tab->p, tlen, R.series_force);
+        join_caller_out(cs);
+        return 0;
+    }
     if (op >= gft::SERIES_DERIVATIVE) {
         // the factors depend on (op, k, len) only: computed once with the reference's rounding (k_factor_table's functor) and kept.
         // A table is written on the library's stream, where the kernel below runs: its first use is ordered behind it.
@@ -222,8 +233,27 @@ static gft::SeriesView view(const double* p, const int64_t* bs, size_t len2, int
                                       const int64_t* rbs, const size_t* batch, size_t nbatch, void* stream) {                                 \
         GFT_SERIES_ENTRY(SERIES_EVAL_ONE, WHAT "series2_evaluate_all_one", W, 2, (c.x = view(x, xbs, nx1, xrs, nx0), c.r = view(res, rbs, 1))); \
     }
+// the fused observation chain: the operand a (at rank 2 with the axis), the scalars x (NULL: the continuous form) and the constants
+// cs of every item, then the result with degree_p1 coefficients on the axis
+#define GFT_SERIES_OBSERVE_CHAIN(PFX, WHAT, W)                                                                                                \
+    int PFX##series_observe_chain(const double* a, const int64_t* abs, size_t na, const double* x, const int64_t* xbs, const double* cs,      \
+                                  const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res, const int64_t* rbs, size_t n,             \
+                                  const size_t* batch, size_t nbatch, void* stream) {                                                         \
+        GFT_SERIES_ENTRY(SERIES_OBSERVE_CHAIN, WHAT "series_observe_chain", W, 1,                                                             \
+                         (c.x = view(a, abs, na), c.var = 1, c.y = view(x, xbs, 1), c.cs = view(cs, cbs, nsteps), c.nsteps = nsteps,          \
+                          c.degree_p1 = degree_p1, c.r = view(res, rbs, n)));                                                                 \
+    }                                                                                                                                         \
+    int PFX##series2_observe_chain(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,        \
+                                   const int64_t* xbs, const double* cs, const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res,    \
+                                   const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) { \
+        GFT_SERIES_ENTRY(SERIES_OBSERVE_CHAIN, WHAT "series2_observe_chain", W, 2,                                                            \
+                         (c.x = view(a, abs, na1, ars, na0), c.var = var, c.y = view(x, xbs, 1), c.cs = view(cs, cbs, nsteps),                \
+                          c.nsteps = nsteps, c.degree_p1 = degree_p1, c.r = view(res, rbs, n1, rrs, n0)));                                    \
+    }
 
 extern "C" {
+GFT_SERIES_OBSERVE_CHAIN(gft_, "", 1)
+GFT_SERIES_OBSERVE_CHAIN(gfti_, "interval ", 2)
 GFT_SERIES_ARITH(gft_, "", 1)
 GFT_SERIES_ARITH(gfti_, "interval ", 2)
 GFT_SERIES_OBSERVE(gft_, "", 1)
@@ -248,5 +278,6 @@ int gft_series_last_form(void) { return R.series_last; }
 #undef GFT_SERIES3_COMPOSE_POW
 #undef GFT_SERIES3_ARITH
 #undef GFT_SERIES_ARITH
+#undef GFT_SERIES_OBSERVE_CHAIN
 #undef GFT_SERIES_OBSERVE_K
 #undef GFT_SERIES_OBSERVE

@@ -114,6 +114,16 @@ void series3_compose_launch(hipStream_t st, const Series3Plan& p, const double* 
 void series_observe(hipStream_t st, int op, const double* x, double* res, const Series2Dims& d, int var, unsigned k, const SeriesBatch& g,
                     const SeriesPlanes& pl, const double* tab, size_t tab_plane, bool rank2);
 
+// ---- the fused observation chain at ranks 1 and 2 (gft_series_observe_chain.hip) -----------------------------------------------------
+// SERIES_OBSERVE_CHAIN: nsteps steps along the axis `var` of the operand `a` (d: its stored shape and row stride, the result's shape
+// and row stride), the last one at degree_p1.  `x`: one scalar per item at the batch strides g.ys (planes pl.y apart) or nullptr, the
+// continuous form; `cs`: nsteps constants per item at g.ss, unit stride (planes pl.s apart).  `tab`: the k_factor_table factors of
+// (TAB_DERIV, 1, L_0 - 1).  `force` as for series_plan: form A (one wave per line) holds up to 64 coefficients on the axis.
+// One launch, no workspace; returns the form.
+int series_observe_chain(hipStream_t st, const double* a, const double* x, const double* cs, double* res, const Series2Dims& d, int var, bool rank2,
+                         unsigned nsteps, unsigned degree_p1, const SeriesBatch& g, const SeriesPlanes& pl, const double* tab, size_t tab_plane,
+                         int force);
+
 // the element offsets of item `it` (kernels of gft_series.hip and gft_div2d.hip)
 struct SeriesOff {
     size_t x, y, s, r;

@@ -34,7 +34,11 @@ enum SeriesOp {
     SERIES_DERIVATIVE = 8,
     SERIES_COEFF = 9,
     SERIES_SHIFT_DOWN = 10,
-    SERIES_EVAL_ONE = 11
+    SERIES_EVAL_ONE = 11,
+    // The fused Poisson observation chain (gft_series_observe_chain.hip): `nsteps` steps of derivative(v, 1), truncation, the factor
+    // var(v, x) (none where x is null: the continuous rate) and the step's constant, per item; x is the operand `a` and the LONG side,
+    // y the scalars x (one element per item, as the seeds), cs the constants.  The result has degree_p1 coefficients on the axis.
+    SERIES_OBSERVE_CHAIN = 12
 };
 
 constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
@@ -103,6 +107,9 @@ struct SeriesView {
 // slab axis, 1 the row axis, 2 the unit-stride axis).  The observation ops (SERIES_DERIVATIVE ..., ranks 1 and 2): x is the one
 // operand and the LONG side, `k` the order, `var` the axis at rank 2 (at rank 1 it is 1, the series axis), and the result's shape
 // must be x's with k taken off that axis (evaluate_all_one: one element per item).  Rank 3 has mul / div / exp / log / compose / pow.
+// SERIES_OBSERVE_CHAIN (ranks 1 and 2): x is the operand a, `y` the scalars x (p may be null: the continuous form; its lengths stay
+// 1), `cs` the constants with len[2] = nsteps; the result has degree_p1 coefficients on the axis `var` and min(length, degree_p1)
+// on the other one.
 struct SeriesCall {
     int op = SERIES_MUL;
     const char* fn = "";  // the name in messages
@@ -111,9 +118,10 @@ struct SeriesCall {
     uint32_t e = 0;
     int var = 0;
     size_t k = 0;
+    size_t nsteps = 0, degree_p1 = 0;
     const size_t* batch = nullptr;
     size_t nbatch = 0;
-    SeriesView x, y, r;
+    SeriesView x, y, r, cs;
 };
 
 // What series_args makes of an accepted call: the collapsed batch, the plane strides and the item -- the lengths narrowed to
@@ -207,8 +215,9 @@ static inline void series_shapes(const SeriesCall& c) {
         for (int i = 1; i >= 3 - rank; --i) t = to_string(v.len[i]) + sep + t;
         return t;
     };
+    const bool chain = op == SERIES_OBSERVE_CHAIN;
     if (observe) {
-        if (empty(c.x)) throw std::runtime_error(f + ": x has no coefficients");
+        if (empty(c.x)) throw std::runtime_error(f + (chain ? ": a has no coefficients" : ": x has no coefficients"));
     } else if (empty(c.r)) {
         if (!r2) throw std::runtime_error(f + ": " + len.r + " == 0 (the result has no coefficients)");
         throw std::runtime_error(f + (transposed ? ": the result has no coefficients (an axis of its shape is 0)" : std::string(": ") + shape + " == 0 (the result has no coefficients)"));
@@ -218,9 +227,9 @@ static inline void series_shapes(const SeriesCall& c) {
     for (size_t i = 0, prod = 1; i < 3 && !over; ++i) over = L.len[i] > most || (prod *= L.len[i]) > most;
     if (over) {
         if (!r2)
-            throw std::runtime_error(f + ": " + Llen + " = " + to_string(L.len[2]) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
+            throw std::runtime_error(f + ": " + (chain ? "na" : Llen) + " = " + to_string(L.len[2]) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
         if (xlong)
-            throw std::runtime_error(f + ": " + Lwho + " has " + dims(L, " * ") + " coefficients, which exceeds the limit of " + to_string(most) +
+            throw std::runtime_error(f + ": " + (chain ? "a" : Lwho) + " has " + dims(L, " * ") + " coefficients, which exceeds the limit of " + to_string(most) +
                                      " coefficients per item of this version");
         throw std::runtime_error(f + ": " + shape + " = " + dims(L, " * ") + " exceeds the limit of " + to_string(most) + " coefficients per item of this version");
     }
@@ -228,6 +237,20 @@ static inline void series_shapes(const SeriesCall& c) {
         if (bad_var) throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable the operation acts on is 0 or 1)");
         if (op == SERIES_EVAL_ONE) return;
         const bool rows = r2 && c.var == 0;
+        if (chain) {  // degree_p1 + nsteps <= L_0: step t then runs at d_t = degree_p1 + (nsteps - 1 - t) on a line of d_t + 1
+            const size_t L0 = rows ? c.x.len[1] : c.x.len[2], other = rows ? c.x.len[2] : c.x.len[1], d = c.degree_p1;
+            const std::string on = r2 ? " on axis " + to_string(c.var) : std::string();
+            if (c.nsteps == 0) throw std::runtime_error(f + ": nsteps = 0 (cs holds no constants: a chain has at least one step)");
+            if (d < 2) throw std::runtime_error(f + ": degree_p1 = " + to_string(d) + " (the result needs at least two coefficients" + on + ": degree_p1 >= 2)");
+            if (d > L0 || c.nsteps > L0 - d)
+                throw std::runtime_error(f + ": degree_p1 + nsteps = " + to_string(d) + " + " + to_string(c.nsteps) + ", but a has " + to_string(L0) +
+                                         " stored coefficients" + on + " (every step takes one: degree_p1 + nsteps <= " + to_string(L0) + ")");
+            const size_t o = std::min(other, d), w0 = rows ? d : o, w1 = rows ? o : d;
+            if (c.r.len[1] != (r2 ? w0 : 1) || c.r.len[2] != w1)
+                throw std::runtime_error(f + ": the result has " + (r2 ? to_string(c.r.len[1]) + " x " : std::string()) + to_string(c.r.len[2]) +
+                                         " coefficients; with degree_p1 = " + to_string(d) + " it has " + (r2 ? to_string(w0) + " x " : std::string()) + to_string(w1));
+            return;
+        }
         const size_t n = rows ? c.x.len[1] : c.x.len[2], k = c.k;
         if (k >= n)
             throw std::runtime_error(f + ": k = " + to_string(k) + ", but x has " + to_string(n) + " stored coefficients" +
@@ -259,7 +282,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     const std::string f(c.fn);
     const int op = c.op, w = c.w;
     const bool comp = op == SERIES_COMPOSE, corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
-    const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed;
+    const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed, chain = op == SERIES_OBSERVE_CHAIN;
     const size_t* batch = c.batch;
     const size_t nbatch = c.nbatch;
     series_shapes(c);
@@ -271,9 +294,10 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         items *= batch[i];
         if (items >= ((size_t)1 << 31)) throw std::runtime_error(f + ": more than 2^31 - 1 series in one call");
     }
-    const SeriesOperand ax = series_arg(c, comp ? "f" : (corr ? "g" : (adj ? "gh" : "x")), c.x);
-    const SeriesOperand ay = series_arg(c, comp || adj ? "g" : (binary ? "y" : "the seeds"), c.y);
+    const SeriesOperand ax = series_arg(c, comp ? "f" : (corr ? "g" : (adj ? "gh" : (chain ? "a" : "x"))), c.x);
+    const SeriesOperand ay = series_arg(c, comp || adj ? "g" : (binary ? "y" : (chain ? "x" : "the seeds")), c.y);
     const SeriesOperand ar = series_arg(c, "the result", c.r);
+    const SeriesOperand ac = series_arg(c, "cs", c.cs);  // (read by the observation chain alone)
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
         struct Ax {
@@ -305,6 +329,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     }
     check_ptr(ax.p, ax.what);
     if (binary || ay.p) check_ptr(ay.p, ay.what);
+    if (chain) check_ptr(ac.p, ac.what);
     check_ptr(ar.p, ar.what);
     // the result may be an input itself (the same view: every row is read before it is written); any other overlap is refused.
     // Judged by address ranges, so two interleaved views of one buffer count as overlapping.
@@ -317,7 +342,8 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         }
         throw std::runtime_error(f + ": the result partially overlaps " + a.what + " (it may alias an operand only as the same view)");
     };
-    overlap(ax, true);
+    overlap(ax, !chain);  // (a chain's result is shorter than its operand: never the same view)
+    if (chain) overlap(ac, false);
     if (transposed) overlap(ay, false);  // corr's result may be g itself, compose_adj's gh; neither may be the second operand
     else if (binary) overlap(ay, true);
     else if (ay.p) overlap(ay, false);
@@ -326,10 +352,10 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     g.nd = 0;
     g.items = (unsigned)items;
     g.inplace = inplace;
-    const bool seeds = !binary && ay.p;
+    const bool seeds = !binary && !chain && ay.p, xscal = chain && ay.p;  // a chain: ys are the strides of x, ss those of cs
     for (size_t i = 0; i < nbatch; ++i) {
         if (batch[i] == 1) continue;
-        const size_t e = batch[i], sx = ax.st[i], sy = binary ? ay.st[i] : 0, ss = seeds ? ay.st[i] : 0, sr = ar.st[i];
+        const size_t e = batch[i], sx = ax.st[i], sy = binary || xscal ? ay.st[i] : 0, ss = seeds ? ay.st[i] : (chain ? ac.st[i] : 0), sr = ar.st[i];
         if (g.nd > 0) {
             const int p = g.nd - 1;
             // (merged extents stay below 2^31: items does)
@@ -354,8 +380,8 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     }
     out.pl.w = w;
     out.pl.x = ax.plane;
-    out.pl.y = binary ? ay.plane : 0;
-    out.pl.s = seeds ? ay.plane : 0;
+    out.pl.y = binary || xscal ? ay.plane : 0;
+    out.pl.s = seeds ? ay.plane : (chain ? ac.plane : 0);
     out.pl.r = ar.plane;
     SeriesItem& it = out.it;
     for (int i = 0; i < 3; ++i) {

@@ -90,3 +90,12 @@ def shift_down(x, k, out=None):
 def evaluate_all_one(x, out=None):
     """The ascending interval sum of every item's coefficients from ``[0, 0]``; ``[2, B...]``."""
     return _run(_OBSERVE, "evaluate_all_one", x, out=out)
+
+
+def observe_chain(a, x, cs, degree_p1=None, out=None):
+    """``series.observe_chain`` over intervals: ``a`` is ``[2, B..., L]``, ``x`` ``[2, B...]`` or ``None`` (continuous rate), ``cs``
+    ``[2, B..., nsteps]``; every product and sum is the reference's interval operation.  A scalar counts as 0 or 1 when both of its
+    bounds are."""
+    from ._series_call import run_chain
+
+    return run_chain(_OBSERVE, a, None, x, cs, degree_p1, out)

@@ -89,3 +89,11 @@ def shift_down(x, var, k, out=None):
 def evaluate_all_one(x, out=None):
     """The row-major interval sum of every item from ``[0, 0]``; ``[2, B...]``."""
     return _run(_CALL, "evaluate_all_one", x, out=out)
+
+
+def observe_chain(a, var, x, cs, degree_p1=None, out=None):
+    """``series2.observe_chain`` over intervals: ``a`` is ``[2, B..., n0, n1]``, ``x`` ``[2, B...]`` or ``None``, ``cs``
+    ``[2, B..., nsteps]``."""
+    from ._series_call import run_chain
+
+    return run_chain(_CALL, a, var, x, cs, degree_p1, out)

@@ -1,6 +1,7 @@
 """Batched univariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow``, the transposed
 product ``corr`` and the observation ops ``derivative``, ``taylor_expansion_of_coeff``, ``shift_down``, ``evaluate_all_one``
-(``gft_series_*``), all but ``corr`` differentiable by torch's autograd.
+(``gft_series_*``), all but ``corr`` differentiable by torch's autograd, and the fused Poisson observation chain ``observe_chain`` (no
+autograd).
 
 The last axis of every tensor is the series (coefficient ``k`` of ``t^k`` at index ``k``, unit stride), the leading axes are
 batch axes and broadcast by torch's rules (``expand``, no copy: one series against a whole batch has batch stride 0).
@@ -204,6 +205,18 @@ def evaluate_all_one(x, out=None):
     if _tracked("series.evaluate_all_one", (x,), out):
         return _autograd().EvalOne.apply(x)
     return _run(_CALL, "evaluate_all_one", x, out=out)
+
+
+def observe_chain(a, x, cs, degree_p1=None, out=None):
+    """The fused Poisson observation chain, ``observe k ~ Poisson(rate * X)`` with ``k = cs.shape[-1]`` steps in one launch.  Step ``t``
+    is ``(derivative(1).truncate(d_t) * var(x, d_t)) * cs[..., t]`` at ``d_t = degree_p1 + (nsteps - 1 - t)``, each step on the one
+    before (``gft_observe_chain``'s unfolding; ``include/gftaylor.h`` states the loops).  ``x``: one scalar per item (the batch shape),
+    or ``None`` for a continuous rate, where a step is ``derivative(1).truncate(d_t) * cs[..., t]``.  ``cs``: ``[B..., nsteps]``, unit
+    stride on its last axis.  ``x`` and ``cs`` broadcast against the batch.  ``degree_p1`` (default ``L - nsteps``, ``L`` the stored
+    length) is the result's length; ``degree_p1 >= 2`` and ``degree_p1 + nsteps <= L``.  No autograd in this version."""
+    from ._series_call import run_chain
+
+    return run_chain(_CALL, a, None, x, cs, degree_p1, out)
 
 
 # ---- autograd (the Functions: _series_autograd.py) ---------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Batched bivariate series on float64 device tensors: ``mul``, ``div``, ``exp``, ``log``, ``compose``, ``pow`` and the transposed
 product ``corr`` and the observation ops ``derivative``, ``taylor_expansion_of_coeff``, ``shift_down``, ``evaluate_all_one``
-(``gft_series2_*``).
+and the fused Poisson observation chain ``observe_chain`` (``gft_series2_*``).
 
 The last two axes of every tensor are the coefficient array of one ``TaylorPoly<F64>`` in two variables: axis -2 is variable 0
 (any non-negative stride), axis -1 is variable 1 (unit stride); the leading axes are batch axes and broadcast by torch's rules
@@ -169,3 +169,12 @@ def shift_down(x, var, k, out=None):
 def evaluate_all_one(x, out=None):
     """Every item at ``(1, 1)``: ``0.0 + x[b, 0, 0] + x[b, 0, 1] + ...`` in row-major order, one chain; the batch shape."""
     return _run(_CALL, "evaluate_all_one", x, out=out)
+
+
+def observe_chain(a, var, x, cs, degree_p1=None, out=None):
+    """``series.observe_chain`` along variable ``var`` (0: axis -2, 1: axis -1) of every item: each line along that axis runs the
+    chain, the other axis is cut to ``min(len, degree_p1)`` and carried along.  The result has ``degree_p1`` coefficients on the axis of
+    ``var`` (default: its stored length less ``nsteps``).  ``x``: the batch shape or ``None`` (continuous rate); ``cs``: ``[B..., nsteps]``."""
+    from ._series_call import run_chain
+
+    return run_chain(_CALL, a, var, x, cs, degree_p1, out)

@@ -422,6 +422,41 @@ int gft_series2_shift_down(const double* x, const int64_t* xbs, int64_t xrs, siz
 int gft_series2_evaluate_all_one(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, double* res,
                                  const int64_t* rbs, const size_t* batch, size_t nbatch, void* stream);
 
+/* ---- batched fused Poisson observation chains: what `observe k ~ Poisson(lambda * X)` runs (generating_function.rs:678-711), per
+ * item and in one launch -- gft_observe_chain's unfolding on caller-owned device tensors, at ranks 1 and 2.  nsteps steps; step t runs
+ * at degree d_t = degree_p1 + (nsteps - 1 - t) with the constant cs[t]:
+ *   discrete rate (x given):     (derivative(v, 1).truncate_to_degree_p1(d_t) * var(v, x, d_t)) * from(cs[t])
+ *   continuous rate (x == NULL):  derivative(v, 1).truncate_to_degree_p1(d_t) * from(cs[t])
+ * Every item has its own scalars: x has the batch shape (strides xbs), cs is [B..., nsteps] with unit stride on its last axis (batch
+ * strides cbs); both may repeat through stride 0.  An item is a set of independent lines along the acted-on axis v (rank 1: the
+ * series; rank 2: `var`, 0 is axis -2 and 1 is axis -1); every other axis is cut to min(len, d_t) at step t and carried along.  Per
+ * line, with src the previous step's output (the operand at t = 0), L its length, dl = min(L - 1, d_t), and ff the derivative's
+ * factors of order 1 (ff_0 = 1 * 1, ff_{j+1} = ff_j * (from(j + 2) / from(j + 1)), the quotient rounded first), every operation
+ * rounded once and nothing contracted:
+ *   D[j] = src[j + 1] * ff_j,  j < dl                                  (derivative, mt:471-479)
+ *   discrete form, lout = min(dl + 1, d_t), for kv < lout:
+ *       c == 0:  res = +0.0                                            (Mul's zero shortcut; the item is all +0.0 from here on)
+ *       x == 0:  res = kv == 0 ? +0.0 : D[kv - 1] * 1                  (mul_var alone, mt:619-621)
+ *       else:    A = (1 <= kv <= dl) ? D[kv - 1] * 1 : +0.0;  res = 0.0 + A;
+ *                if kv < dl:  res = res + (x == 1 ? D[kv] : x * D[kv])
+ *       if c != 1:  res = c * res
+ *   continuous form, lout = dl, for kv < lout:
+ *       res = (c == 0) ? +0.0 : (c == 1 ? D[kv] : c * D[kv])
+ * `==` compares values (-0.0 counts as zero).  The three tests of the scalars are made per item on the device and are the only
+ * data-dependent branches; non-finite scalars and data run the same sequence, and no shortcut looks at the coefficients.
+ * Shape rules, refused by name before the device is touched: degree_p1 >= 2, nsteps >= 1, degree_p1 + nsteps <= L_0 (the operand's
+ * stored length on v), so every step is full: dl == lout == d_t.  The result has degree_p1 coefficients on v and min(len, degree_p1)
+ * on the other axis of a rank-2 item, and (n | n0, n1) must say so.  The limits bound the operand (na <= 4096, na0 * na1 <= 4096).
+ * The result may not overlap a, x or cs.  Batch strides, row strides, NULL stride arrays, empty batches, the stream contract and
+ * return values: those of gft_series_mul.  One launch per call, no workspace; gft_series_last_form() reports 1 (one wave per line:
+ * L_0 <= 64) or 2 (one workgroup per line), and the option "series_form" forces 2. */
+int gft_series_observe_chain(const double* a, const int64_t* abs, size_t na, const double* x, const int64_t* xbs, const double* cs,
+                             const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res, const int64_t* rbs, size_t n,
+                             const size_t* batch, size_t nbatch, void* stream);
+int gft_series2_observe_chain(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,
+                              const int64_t* xbs, const double* cs, const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res,
+                              const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI, collectives internal to the library --------
  * The reference is single-process; a host that wants one large product spread over the GPUs of a node starts one
  * process per GPU (each with its own gft_init(device)), lets rank 0 call gft_dist_unique_id, hands the 128 bytes to
@@ -691,6 +726,16 @@ int gfti_series2_shift_down(const double* x, const int64_t* xbs, int64_t xrs, si
                             const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
 int gfti_series2_evaluate_all_one(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, double* res,
                                   const int64_t* rbs, const size_t* batch, size_t nbatch, void* stream);
+/* The observation chains over Interval<F64>: gft_series_observe_chain / gft_series2_observe_chain on (lo, hi) planes, the plane
+ * stride first in every stride array; x is [2, B...] and cs [2, B..., nsteps].  The same loops, every * and + the reference's Interval
+ * operation with its own short-circuits ([0,0] + A is A; [0,0] * finite is [+0,+0]); a scalar equals 0 or 1 when both of its bounds
+ * do.  The limits on the operand are na <= 2048 and na0 * na1 <= 2048. */
+int gfti_series_observe_chain(const double* a, const int64_t* abs, size_t na, const double* x, const int64_t* xbs, const double* cs,
+                              const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res, const int64_t* rbs, size_t n,
+                              const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_observe_chain(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,
+                               const int64_t* xbs, const double* cs, const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res,
+                               const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
 size_t gfti_len_of(const gft_poly* p, size_t v);
 int gfti_is_constant(const gft_poly* p);
 int gfti_is_zero(const gft_poly* p);
