@@ -24,8 +24,9 @@ struct DagRec {  // what the scheduler needs from a recording (implemented per k
     struct Deps {
         Buf* b[MAX_DEPS];
         int n = 0;
-        void push_back(Buf* x) {
-            if (n < MAX_DEPS) b[n++] = x;
+        void push_back(Buf* x) {  // (a dropped dependency would put a recording on its producer's level: refuse)
+            if (n >= MAX_DEPS) throw Error("internal: a recording with more than DagRec::MAX_DEPS dependencies");
+            b[n++] = x;
         }
         Buf** begin() { return b; }
         Buf** end() { return b + n; }
