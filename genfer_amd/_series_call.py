@@ -12,7 +12,7 @@ stride and its second length because those tuples are one entry longer, rank 3 i
 
 Everything that needs no device is judged first, in one order for every module: type, dtype, planes, axes (per tensor), the orders,
 ``out``, grad, then the placement, the devices and the library's device.  ``run_chain`` is the same path for ``observe_chain``, whose
-items carry their own scalars (``x``, ``cs``).
+items carry their own scalars (``x``, ``cs``), and ``run_linear`` for ``mul_linear`` and ``compose_linear`` (``c``, ``m``).
 """
 from __future__ import annotations
 
@@ -49,6 +49,10 @@ OPS = {o.suffix: o for o in (
     # kind "chain": the operand a, at rank 2 the axis, then the scalars x and the constants cs of every item (a pointer and batch
     # strides each, as the seeds), nsteps and degree_p1 (run_chain)
     _op("observe_chain", "chain", long="x", names=("a", "x", "cs"), var=True),
+    # kind "linear": the operand, at rank 2 its `var` axes (mul_linear: the factor's variable; compose_linear: var and wvar), then the
+    # scalars c and m of every item (a pointer and batch strides each, as the seeds) (run_linear)
+    _op("mul_linear", "linear", names=("a", "c", "m"), var=1),
+    _op("compose_linear", "linear", names=("f", "c", "m"), var=2),
 )}
 F64_ONLY = ("corr", "compose_adj")  # no gfti_ twin
 RANK3 = ("mul", "div", "exp", "log", "compose", "pow")  # gft[i]_series3_*: the core operations, compose and pow
@@ -83,6 +87,8 @@ def _arguments(op, rank, view, e, var, k, tail):
     a = view("x", True)
     if op.kind == "chain":  # (k: the two counts nsteps, degree_p1)
         return a + (var if rank >= 2 else ()) + view("second", False) + view("cs", False) + k + view("out", True) + tail
+    if op.kind == "linear":  # (var: op.var axes)
+        return a + (var if rank >= 2 else ()) + view("second", False) + view("cs", False) + view("out", True) + tail
     if op.kind == "second":
         a += view("second", True)
     elif op.kind == "seed":
@@ -112,7 +118,7 @@ def _lib():
                     if pre == "gft_" or op.suffix not in F64_ONLY:
                         f = getattr(L, pre + mid + op.suffix)
                         f.restype = C.c_int
-                        f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,),
+                        f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,) * int(op.var),
                                                      (C.c_size_t,) * (2 if op.kind == "chain" else 1), (_SZP, C.c_size_t, C.c_void_p)))
         for pre in ("gft_", "gfti_"):
             for suffix in RANK3:
@@ -387,5 +393,111 @@ def run_chain(call, a, var, x, cs, degree_p1=None, out=None):
     tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
     fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_")[rank - 1] + op.suffix)
     if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (), (var,), (nsteps, d), tail)) != 0:
+        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
+    return out
+
+
+def run_linear(call, name, a, var, wvar, c, m, n=None, out=None):
+    """One call of gft[i]_series[2]_mul_linear / _compose_linear: ``a`` the operand, ``var`` (and compose_linear's ``wvar``) the axes at
+    rank 2, ``c`` and ``m`` one scalar per item each, ``n`` the result's order (an int at rank 1, a pair at rank 2).  The checks come in
+    ``run``'s order."""
+    import torch
+
+    op, (module, rank, planes, limit, _raw) = OPS[name], call
+    what = f"{module}.{op.label}"
+    comp = name == "compose_linear"
+    aname = op.names[0]
+    axes, _order, _short, _over_text, _out_text = _rank_rules(rank)
+    for t, w in ((a, aname), (c, "c"), (m, "m"), (out, "out")):
+        if t is None and w == "out":
+            continue
+        w = f"{what}: {w}"
+        _check(torch, t, w, planes)
+        if t is a or t is out:
+            axes(t, w, planes)
+    shape = tuple(a.shape[-rank:])
+    v = w = rank - 1  # as positions of an item's shape
+    if rank == 2:
+        from .series2 import _var
+
+        v = w = _var(what, var, "the variable of f that is replaced is 0 (axis -2) or 1 (axis -1)" if comp
+                     else "the variable of the linear factor is 0 (axis -2) or 1 (axis -1)")
+        if comp and wvar is not None:
+            if isinstance(wvar, bool) or not isinstance(wvar, int) or wvar not in (0, 1):
+                raise TaylorError(f"{what}: wvar = {wvar!r}; the variable of the affine series is 0 (axis -2) or 1 (axis -1)")
+            w = wvar
+    # the default order: the compact stored shape of the definition -- but where wvar != var with f's own length on var, of which index 0
+    # alone is stored, because an operand lies inside the orders
+    compact = list(shape)
+    if not comp:
+        compact[w] = shape[w] + 1
+    elif w != v:
+        compact[w] = shape[w] + shape[v] - 1
+    if n is None:
+        if out is not None:
+            if out.dim() < planes + rank:
+                raise TaylorError(f"{what}: out has shape {tuple(out.shape)}; the result has {rank} series ax{'is' if rank == 1 else 'es'}")
+            order = tuple(out.shape[-rank:])
+        else:
+            order = tuple(compact)
+    else:
+        import operator
+
+        try:
+            order = (operator.index(n),) if rank == 1 else tuple(operator.index(k) for k in n)
+        except TypeError:
+            raise TypeError(f"{what}: n must be {'an integer' if rank == 1 else 'a pair of integers'}, got {n!r}") from None
+        if len(order) != rank:
+            raise TaylorError(f"{what}: n = {n!r}; the order of a bivariate result is a pair (n0, n1)")
+    on = f" on axis {w - 2}" if rank == 2 else ""
+    if order[w] < 2:
+        raise TaylorError(f"{what}: the result has {order[w]} coefficient{on} (c + m * x needs two: a substitution at one coefficient is the "
+                          "constant one, not a linear one)")
+    if any(k < 1 for k in order):
+        raise TaylorError(f"{what}: n = {order if rank == 2 else order[0]} (the result has no coefficients)")
+    if any(s > k for s, k in zip(shape, order)):
+        raise TaylorError(f"{what}: {aname} has {shape if rank == 2 else shape[0]} coefficients, the result n = {order if rank == 2 else order[0]} "
+                          "(an operand is longer than the truncation order)")
+    count = order[0] * order[-1] if rank == 2 else order[0]
+    if count > limit:
+        raise TaylorError(f"{what}: n = {order if rank == 2 else order[0]} exceeds the limit of {limit} coefficients per "
+                          f"{'item' if rank == 2 else 'series'} of this version")
+    named = [(aname, a.shape[planes:a.dim() - rank]), ("c", c.shape[planes:]), ("m", m.shape[planes:])]
+    try:
+        batch = tuple(torch.broadcast_shapes(*[s for _, s in named]))
+    except RuntimeError:
+        raise TaylorError(f"{what}: the batch shapes do not broadcast: " + ", ".join(f"{k} has {tuple(s)}" for k, s in named)
+                          + " (c and m have the batch shape: one scalar per item)") from None
+    if out is not None:
+        if out.dim() < planes + rank or tuple(out.shape[-rank:]) != order:
+            raise TaylorError(f"{what}: out has shape {tuple(out.shape)}; the result has n = {order if rank == 2 else order[0]} coefficients per item")
+        if tuple(out.shape[planes:out.dim() - rank]) != batch:
+            raise TaylorError(f"{what}: out has batch shape {tuple(out.shape[planes:out.dim() - rank])}; the operands broadcast to {batch}")
+    if torch.is_grad_enabled():
+        for t, k in ((a, aname), (c, "c"), (m, "m")):
+            if t.requires_grad:
+                raise TaylorError(f"{what}: {k} requires grad, and {op.label} has no autograd in this version; pass {k}.detach() or call "
+                                  "under torch.no_grad() (nothing is detached silently)")
+    tensors = [(a, aname), (c, "c"), (m, "m")] + ([(out, "out")] if out is not None else [])
+    for t, k in tensors:
+        _placed(t, f"{what}: {k}")
+    for t, _ in tensors[1:]:
+        if t.device != a.device:
+            raise TaylorError(f"{what}: the tensors are on different devices ({a.device}, {t.device})")
+    lead, nb = (2,) * planes, len(batch)
+    if out is None:
+        out = torch.empty(lead + batch + order, dtype=torch.float64, device=a.device)
+    if planes:  # the plane axis stays first, missing batch axes go behind it (a view)
+        lift = lambda t, dim: t if t.dim() >= dim else t[(slice(None),) + (None,) * (dim - t.dim())]  # noqa: E731
+        a, c, m = lift(a, nb + 1 + rank), lift(c, nb + 1), lift(m, nb + 1)
+    L = _lib()
+    dev = int(L.gft_device())
+    if dev >= 0 and a.device.index != dev:
+        raise TaylorError(f"{what}: the tensors are on {a.device}, but the library runs on cuda:{dev}")
+    ns = nb + planes
+    parts = {"x": a.expand(lead + batch + shape), "second": c.expand(lead + batch), "cs": m.expand(lead + batch), "out": out}
+    tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
+    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_")[rank - 1] + op.suffix)
+    if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (), (v, w)[:int(op.var)], (), tail)) != 0:
         raise TaylorError((L.gft_last_error() or b"unknown error").decode())
     return out

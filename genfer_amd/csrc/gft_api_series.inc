@@ -9,6 +9,8 @@
 // their gfti_ twins (one operand, the result shorter by the order k on one axis; the kernels: gft_series_observe.hip)
 // and the fused observation chain gft_series_observe_chain / gft_series2_observe_chain with their gfti_ twins (every item with its
 // own scalars x and constants cs, one launch for all the steps; the kernels: gft_series_observe_chain.hip)
+// and the affine substitutions gft_series_mul_linear / compose_linear, gft_series2_mul_linear / compose_linear with their gfti_ twins
+// (every item with its own scalars c and m, one launch; the kernels: gft_series_linear.hip)
 // Every entry point fills one gft::SeriesCall with its rank (gft_series_args.hpp, which judges it without the device and states the
 // item of any rank as one gft::SeriesItem) and hands it to series_call, which dispatches on the rank once; pow is one driver.
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
@@ -35,6 +37,12 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         join_caller_in(cs);
         R.series_last = gft::series_observe_chain(R.stream, x, y, c.cs.p, res, gft::series2_dims(it), c.var, c.rank == 2, (unsigned)c.nsteps,
                                                   (unsigned)c.degree_p1, g, pl, tab->p, tlen, R.series_force);
+        join_caller_out(cs);
+        return 0;
+    }
+    if (op == gft::SERIES_MUL_LINEAR || op == gft::SERIES_COMPOSE_LINEAR) {  // one launch; c and m travel as the chain's x and cs
+        join_caller_in(cs);
+        R.series_last = gft::series_linear(R.stream, op, x, y, c.cs.p, res, gft::series2_dims(it), c.var, c.wvar, g, pl, R.series_force);
         join_caller_out(cs);
         return 0;
     }
@@ -250,8 +258,39 @@ static gft::SeriesView view(const double* p, const int64_t* bs, size_t len2, int
                          (c.x = view(a, abs, na1, ars, na0), c.var = var, c.y = view(x, xbs, 1), c.cs = view(cs, cbs, nsteps),                \
                           c.nsteps = nsteps, c.degree_p1 = degree_p1, c.r = view(res, rbs, n1, rrs, n0)));                                    \
     }
+// the affine substitutions: the operand (at rank 2 with var, compose_linear also with wvar), the scalars c and m of every item, then
+// the result
+#define GFT_SERIES_LINEAR(PFX, WHAT, W)                                                                                                       \
+    int PFX##series_mul_linear(const double* a, const int64_t* abs, size_t na, const double* cv, const int64_t* cbs, const double* mv,         \
+                               const int64_t* mbs, double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,             \
+                               void* stream) {                                                                                                \
+        GFT_SERIES_ENTRY(SERIES_MUL_LINEAR, WHAT "series_mul_linear", W, 1,                                                                   \
+                         (c.x = view(a, abs, na), c.var = 1, c.wvar = 1, c.y = view(cv, cbs, 1), c.cs = view(mv, mbs, 1), c.r = view(res, rbs, n))); \
+    }                                                                                                                                         \
+    int PFX##series2_mul_linear(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* cv,          \
+                                const int64_t* cbs, const double* mv, const int64_t* mbs, double* res, const int64_t* rbs, int64_t rrs,        \
+                                size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) {                                     \
+        GFT_SERIES_ENTRY(SERIES_MUL_LINEAR, WHAT "series2_mul_linear", W, 2,                                                                  \
+                         (c.x = view(a, abs, na1, ars, na0), c.var = var, c.wvar = var, c.y = view(cv, cbs, 1), c.cs = view(mv, mbs, 1),        \
+                          c.r = view(res, rbs, n1, rrs, n0)));                                                                                \
+    }                                                                                                                                         \
+    int PFX##series_compose_linear(const double* f, const int64_t* fbs, size_t nf, const double* cv, const int64_t* cbs, const double* mv,     \
+                                   const int64_t* mbs, double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch,         \
+                                   void* stream) {                                                                                            \
+        GFT_SERIES_ENTRY(SERIES_COMPOSE_LINEAR, WHAT "series_compose_linear", W, 1,                                                           \
+                         (c.x = view(f, fbs, nf), c.var = 1, c.wvar = 1, c.y = view(cv, cbs, 1), c.cs = view(mv, mbs, 1), c.r = view(res, rbs, n))); \
+    }                                                                                                                                         \
+    int PFX##series2_compose_linear(const double* f, const int64_t* fbs, int64_t frs, size_t nf0, size_t nf1, int var, int wvar,              \
+                                    const double* cv, const int64_t* cbs, const double* mv, const int64_t* mbs, double* res,                    \
+                                    const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream) { \
+        GFT_SERIES_ENTRY(SERIES_COMPOSE_LINEAR, WHAT "series2_compose_linear", W, 2,                                                          \
+                         (c.x = view(f, fbs, nf1, frs, nf0), c.var = var, c.wvar = wvar, c.y = view(cv, cbs, 1), c.cs = view(mv, mbs, 1),       \
+                          c.r = view(res, rbs, n1, rrs, n0)));                                                                                \
+    }
 
 extern "C" {
+GFT_SERIES_LINEAR(gft_, "", 1)
+GFT_SERIES_LINEAR(gfti_, "interval ", 2)
 GFT_SERIES_OBSERVE_CHAIN(gft_, "", 1)
 GFT_SERIES_OBSERVE_CHAIN(gfti_, "interval ", 2)
 GFT_SERIES_ARITH(gft_, "", 1)
@@ -279,5 +318,6 @@ int gft_series_last_form(void) { return R.series_last; }
 #undef GFT_SERIES3_ARITH
 #undef GFT_SERIES_ARITH
 #undef GFT_SERIES_OBSERVE_CHAIN
+#undef GFT_SERIES_LINEAR
 #undef GFT_SERIES_OBSERVE_K
 #undef GFT_SERIES_OBSERVE

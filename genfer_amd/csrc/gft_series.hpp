@@ -124,6 +124,14 @@ int series_observe_chain(hipStream_t st, const double* a, const double* x, const
                          unsigned nsteps, unsigned degree_p1, const SeriesBatch& g, const SeriesPlanes& pl, const double* tab, size_t tab_plane,
                          int force);
 
+// ---- the affine substitutions at ranks 1 and 2 (gft_series_linear.hip) -----------------------------------------------------------------
+// SERIES_MUL_LINEAR: a times c + m * x_var; SERIES_COMPOSE_LINEAR: x_var := c + m * x_wvar in f.  d: the operand's stored shape and row
+// stride, the result's shape and row stride (rank 1: one row, var == wvar == 1).  `c`, `m`: one scalar per item each at the batch
+// strides g.ys / g.ss (planes pl.y / pl.s apart).  `force` as for series_plan: compose's form A (one wave per line) holds up to 64
+// coefficients on the axis of wvar.  One launch, no workspace; returns the form (SERIES_NONE for mul_linear, a streaming kernel).
+int series_linear(hipStream_t st, int op, const double* a, const double* c, const double* m, double* res, const Series2Dims& d, int var, int wvar,
+                  const SeriesBatch& g, const SeriesPlanes& pl, int force);
+
 // the element offsets of item `it` (kernels of gft_series.hip and gft_div2d.hip)
 struct SeriesOff {
     size_t x, y, s, r;

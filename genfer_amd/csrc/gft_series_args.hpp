@@ -38,7 +38,12 @@ enum SeriesOp {
     // The fused Poisson observation chain (gft_series_observe_chain.hip): `nsteps` steps of derivative(v, 1), truncation, the factor
     // var(v, x) (none where x is null: the continuous rate) and the step's constant, per item; x is the operand `a` and the LONG side,
     // y the scalars x (one element per item, as the seeds), cs the constants.  The result has degree_p1 coefficients on the axis.
-    SERIES_OBSERVE_CHAIN = 12
+    SERIES_OBSERVE_CHAIN = 12,
+    // The affine substitutions (gft_series_linear.hip, ranks 1 and 2): x is the operand (a / f), y the scalars c and cs the scalars m
+    // (one element per item each, as the seeds), the result the LONG side.  mul_linear (mt:611-623): a times c + m * x_var.
+    // compose_linear (subst_var's linear paths, mt:555-579): x_var := c + m * x_wvar.
+    SERIES_MUL_LINEAR = 13,
+    SERIES_COMPOSE_LINEAR = 14
 };
 
 constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
@@ -109,7 +114,8 @@ struct SeriesView {
 // must be x's with k taken off that axis (evaluate_all_one: one element per item).  Rank 3 has mul / div / exp / log / compose / pow.
 // SERIES_OBSERVE_CHAIN (ranks 1 and 2): x is the operand a, `y` the scalars x (p may be null: the continuous form; its lengths stay
 // 1), `cs` the constants with len[2] = nsteps; the result has degree_p1 coefficients on the axis `var` and min(length, degree_p1)
-// on the other one.
+// on the other one.  SERIES_MUL_LINEAR / SERIES_COMPOSE_LINEAR (ranks 1 and 2): x is the operand, `y` the scalars c and `cs` the
+// scalars m (their lengths stay 1), `var` (and compose_linear's `wvar`) the axes, at rank 1 both 1; the result is the long side.
 struct SeriesCall {
     int op = SERIES_MUL;
     const char* fn = "";  // the name in messages
@@ -117,6 +123,7 @@ struct SeriesCall {
     int rank = 1;
     uint32_t e = 0;
     int var = 0;
+    int wvar = 0;  // compose_linear: the variable of the affine series (mul_linear: var is that variable)
     size_t k = 0;
     size_t nsteps = 0, degree_p1 = 0;
     const size_t* batch = nullptr;
@@ -181,6 +188,40 @@ static inline bool series_same_view(const SeriesOperand& a, const SeriesOperand&
     return true;
 }
 
+// The shape rules of the affine substitutions (ranks 1 and 2; at rank 1 var == wvar == 1, the series axis): the axes, a result of at
+// least two coefficients on the affine series' axis, an operand inside the result, the limit on the result.
+static inline void series_linear_shapes(const SeriesCall& c) {
+    using std::to_string;
+    const std::string f(c.fn);
+    const bool r2 = c.rank > 1, comp = c.op == SERIES_COMPOSE_LINEAR;
+    const char* const who = comp ? "f" : "a";
+    if (r2 && (c.var < 0 || c.var > 1))
+        throw std::runtime_error(f + ": var = " + to_string(c.var) + (comp ? " (the variable of f that is replaced is 0 or 1)" : " (the variable of the linear factor is 0 or 1)"));
+    if (r2 && comp && (c.wvar < 0 || c.wvar > 1))
+        throw std::runtime_error(f + ": wvar = " + to_string(c.wvar) + " (the variable of the affine series is 0 or 1)");
+    const int w = comp ? c.wvar : c.var;
+    if (c.r.len[1] == 0 || c.r.len[2] == 0)
+        throw std::runtime_error(f + (r2 ? ": n0 * n1 == 0 (the result has no coefficients)" : ": n == 0 (the result has no coefficients)"));
+    const size_t nw = c.r.len[1 + w];
+    if (nw < 2)
+        throw std::runtime_error(f + ": the result has " + to_string(nw) + " coefficient" + (r2 ? " on axis " + to_string(w - 2) : std::string()) +
+                                 " (c + m * x needs two: a substitution at one coefficient is the constant one, not a linear one)");
+    if (c.x.len[1] == 0 || c.x.len[2] == 0) throw std::runtime_error(f + ": an operand has no coefficients");
+    if (c.x.len[1] > c.r.len[1] || c.x.len[2] > c.r.len[2]) {
+        if (r2)
+            throw std::runtime_error(f + ": " + who + " has " + to_string(c.x.len[1]) + " x " + to_string(c.x.len[2]) + " coefficients, the result " +
+                                     to_string(c.r.len[1]) + " x " + to_string(c.r.len[2]) + " (an operand is longer than the truncation order)");
+        throw std::runtime_error(f + ": n" + who + " = " + to_string(c.x.len[2]) + " > n = " + to_string(c.r.len[2]) + " (an operand is longer than the truncation order)");
+    }
+    const size_t most = series_limit(c.rank, c.w);
+    if (c.r.len[1] > most || c.r.len[2] > most || c.r.len[1] * c.r.len[2] > most) {
+        if (r2)
+            throw std::runtime_error(f + ": n0 * n1 = " + to_string(c.r.len[1]) + " * " + to_string(c.r.len[2]) + " exceeds the limit of " + to_string(most) +
+                                     " coefficients per item of this version");
+        throw std::runtime_error(f + ": n = " + to_string(c.r.len[2]) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
+    }
+}
+
 // The three shape rules, once over the call's `rank` series axes: nothing is empty, the long side carries the limit, and the short
 // sides fit inside the long side.  The long side is the result, or x for the transposed and the observation ops (ranks 1 and 2).
 // The texts are per rank: rank 1 names its lengths, the higher ranks print the last `rank` lengths of a view.
@@ -193,6 +234,7 @@ static inline void series_shapes(const SeriesCall& c) {
     // before gfti_series3_* and misleads an interval caller or one with another width -- to be retired with those pins)
     if (rank == 3 && ((c.w != 1 && c.w != 2) || op > SERIES_POW))
         throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
+    if (op == SERIES_MUL_LINEAR || op == SERIES_COMPOSE_LINEAR) return series_linear_shapes(c);
     const bool observe = op >= SERIES_DERIVATIVE, comp = op == SERIES_COMPOSE;
     const bool corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
     const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed;
@@ -283,6 +325,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     const int op = c.op, w = c.w;
     const bool comp = op == SERIES_COMPOSE, corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
     const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed, chain = op == SERIES_OBSERVE_CHAIN;
+    const bool lin = op == SERIES_MUL_LINEAR || op == SERIES_COMPOSE_LINEAR, complin = op == SERIES_COMPOSE_LINEAR;
     const size_t* batch = c.batch;
     const size_t nbatch = c.nbatch;
     series_shapes(c);
@@ -294,10 +337,10 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         items *= batch[i];
         if (items >= ((size_t)1 << 31)) throw std::runtime_error(f + ": more than 2^31 - 1 series in one call");
     }
-    const SeriesOperand ax = series_arg(c, comp ? "f" : (corr ? "g" : (adj ? "gh" : (chain ? "a" : "x"))), c.x);
-    const SeriesOperand ay = series_arg(c, comp || adj ? "g" : (binary ? "y" : (chain ? "x" : "the seeds")), c.y);
+    const SeriesOperand ax = series_arg(c, comp || complin ? "f" : (corr ? "g" : (adj ? "gh" : (chain || lin ? "a" : "x"))), c.x);
+    const SeriesOperand ay = series_arg(c, lin ? "c" : (comp || adj ? "g" : (binary ? "y" : (chain ? "x" : "the seeds"))), c.y);
     const SeriesOperand ar = series_arg(c, "the result", c.r);
-    const SeriesOperand ac = series_arg(c, "cs", c.cs);  // (read by the observation chain alone)
+    const SeriesOperand ac = series_arg(c, lin ? "m" : "cs", c.cs);  // (read by the observation chain and the affine substitutions)
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
         struct Ax {
@@ -328,8 +371,8 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
                 throw std::runtime_error(f + ": the result's series overlap each other (its strides do not separate the rows)");
     }
     check_ptr(ax.p, ax.what);
-    if (binary || ay.p) check_ptr(ay.p, ay.what);
-    if (chain) check_ptr(ac.p, ac.what);
+    if (binary || lin || ay.p) check_ptr(ay.p, ay.what);
+    if (chain || lin) check_ptr(ac.p, ac.what);
     check_ptr(ar.p, ar.what);
     // the result may be an input itself (the same view: every row is read before it is written); any other overlap is refused.
     // Judged by address ranges, so two interleaved views of one buffer count as overlapping.
@@ -342,8 +385,8 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         }
         throw std::runtime_error(f + ": the result partially overlaps " + a.what + " (it may alias an operand only as the same view)");
     };
-    overlap(ax, !chain);  // (a chain's result is shorter than its operand: never the same view)
-    if (chain) overlap(ac, false);
+    overlap(ax, !chain && !lin);  // (a chain's result is shorter than its operand: never the same view; a substitution's is no operand)
+    if (chain || lin) overlap(ac, false);
     if (transposed) overlap(ay, false);  // corr's result may be g itself, compose_adj's gh; neither may be the second operand
     else if (binary) overlap(ay, true);
     else if (ay.p) overlap(ay, false);
@@ -352,10 +395,11 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     g.nd = 0;
     g.items = (unsigned)items;
     g.inplace = inplace;
-    const bool seeds = !binary && !chain && ay.p, xscal = chain && ay.p;  // a chain: ys are the strides of x, ss those of cs
+    // a chain: ys are the strides of x, ss those of cs; an affine substitution: ys those of c, ss those of m
+    const bool seeds = !binary && !chain && !lin && ay.p, xscal = (chain && ay.p) || lin, cscal = chain || lin;
     for (size_t i = 0; i < nbatch; ++i) {
         if (batch[i] == 1) continue;
-        const size_t e = batch[i], sx = ax.st[i], sy = binary || xscal ? ay.st[i] : 0, ss = seeds ? ay.st[i] : (chain ? ac.st[i] : 0), sr = ar.st[i];
+        const size_t e = batch[i], sx = ax.st[i], sy = binary || xscal ? ay.st[i] : 0, ss = seeds ? ay.st[i] : (cscal ? ac.st[i] : 0), sr = ar.st[i];
         if (g.nd > 0) {
             const int p = g.nd - 1;
             // (merged extents stay below 2^31: items does)
@@ -381,7 +425,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     out.pl.w = w;
     out.pl.x = ax.plane;
     out.pl.y = binary || xscal ? ay.plane : 0;
-    out.pl.s = seeds ? ay.plane : (chain ? ac.plane : 0);
+    out.pl.s = seeds ? ay.plane : (cscal ? ac.plane : 0);
     out.pl.r = ar.plane;
     SeriesItem& it = out.it;
     for (int i = 0; i < 3; ++i) {

@@ -99,3 +99,18 @@ def observe_chain(a, x, cs, degree_p1=None, out=None):
     from ._series_call import run_chain
 
     return run_chain(_OBSERVE, a, None, x, cs, degree_p1, out)
+
+
+def mul_linear(a, c, m, n=None, out=None):
+    """``series.mul_linear`` over intervals: ``a`` is ``[2, B..., L]``, ``c`` and ``m`` ``[2, B...]``; every product and sum is the
+    reference's interval operation, and ``c`` counts as 0 when both of its bounds are."""
+    from ._series_call import run_linear
+
+    return run_linear(_OBSERVE, "mul_linear", a, None, None, c, m, n, out)
+
+
+def compose_linear(f, c, m, n=None, out=None):
+    """``series.compose_linear`` over intervals: ``f`` is ``[2, B..., nf]``, ``c`` and ``m`` ``[2, B...]``."""
+    from ._series_call import run_linear
+
+    return run_linear(_OBSERVE, "compose_linear", f, None, None, c, m, n, out)

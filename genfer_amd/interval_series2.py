@@ -97,3 +97,17 @@ def observe_chain(a, var, x, cs, degree_p1=None, out=None):
     from ._series_call import run_chain
 
     return run_chain(_CALL, a, var, x, cs, degree_p1, out)
+
+
+def mul_linear(a, var, c, m, n=None, out=None):
+    """``series2.mul_linear`` over intervals: ``a`` is ``[2, B..., n0, n1]``, ``c`` and ``m`` ``[2, B...]``."""
+    from ._series_call import run_linear
+
+    return run_linear(_CALL, "mul_linear", a, var, None, c, m, n, out)
+
+
+def compose_linear(f, var, c, m, wvar=None, n=None, out=None):
+    """``series2.compose_linear`` over intervals: ``f`` is ``[2, B..., n0, n1]``, ``c`` and ``m`` ``[2, B...]``."""
+    from ._series_call import run_linear
+
+    return run_linear(_CALL, "compose_linear", f, var, wvar, c, m, n, out)

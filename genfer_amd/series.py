@@ -219,8 +219,28 @@ def observe_chain(a, x, cs, degree_p1=None, out=None):
     return run_chain(_CALL, a, None, x, cs, degree_p1, out)
 
 
-# ---- autograd (the Functions: _series_autograd.py) ---------------------------------------------------------------------------
+def mul_linear(a, c, m, n=None, out=None):
+    """``a`` times the linear series ``c + m * t`` as the reference multiplies by one (``mul_linear``; ``include/gftaylor.h`` states the
+    loop): ``out[j] = a[j-1] * m + c * a[j]``, the sum and the second product absent where ``c == 0`` (by value, per item).  ``c``, ``m``:
+    one scalar per item (the batch shape; they broadcast against it).  ``n`` (default ``L + 1``, ``L`` the stored length)
+    is the result's order.  No autograd in this version."""
+    from ._series_call import run_linear
 
+    return run_linear(_CALL, "mul_linear", a, None, None, c, m, n, out)
+
+
+def compose_linear(f, c, m, n=None, out=None):
+    """``f(c + m * t)`` as the reference substitutes an affine series (``subst_var``'s linear paths; ``include/gftaylor.h`` states the
+    loops): where ``c == 0`` (by value, per item) coefficient ``i`` times ``m^i`` from a running table, else Horner's loop with
+    ``mul_linear`` as its product.  ``c``, ``m``: one scalar per item.  ``n`` (default: ``f``'s stored length) is the
+    result's order.  One launch, about ``nf * n`` multiply-adds per item; ``compose(f, [c, m])`` has other bits and ``nf * n^2 / 2``.
+    No autograd in this version."""
+    from ._series_call import run_linear
+
+    return run_linear(_CALL, "compose_linear", f, None, None, c, m, n, out)
+
+
+# ---- autograd (the Functions: _series_autograd.py) ---------------------------------------------------------------------------
 
 def _tracked(what, operands, out, seed=None):
     """Whether the call records a grad_fn: grad mode is on and an operand requires grad.  Refuses what cannot be differentiated."""

@@ -178,3 +178,21 @@ def observe_chain(a, var, x, cs, degree_p1=None, out=None):
     from ._series_call import run_chain
 
     return run_chain(_CALL, a, var, x, cs, degree_p1, out)
+
+
+def mul_linear(a, var, c, m, n=None, out=None):
+    """``a`` times the linear series ``c + m * x_var`` (``var`` 0: axis -2, 1: axis -1): ``series.mul_linear`` on every line along that
+    axis.  ``n`` (default: ``a``'s shape with one more on the axis) is the result's order, a pair."""
+    from ._series_call import run_linear
+
+    return run_linear(_CALL, "mul_linear", a, var, None, c, m, n, out)
+
+
+def compose_linear(f, var, c, m, wvar=None, n=None, out=None):
+    """``f`` with ``x_var := c + m * x_wvar`` (``wvar`` defaults to ``var``).  ``wvar == var``: ``series.compose_linear`` on every line
+    along the axis.  Otherwise the slices of ``f`` along ``var`` are the Horner coefficients and the result keeps index 0 alone on that
+    axis.  ``n`` (default: the stored shape of the result, with ``f``'s own length on ``var`` where ``wvar != var``) is the result's order,
+    a pair."""
+    from ._series_call import run_linear
+
+    return run_linear(_CALL, "compose_linear", f, var, wvar, c, m, n, out)

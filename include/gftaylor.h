@@ -457,6 +457,44 @@ int gft_series2_observe_chain(const double* a, const int64_t* abs, int64_t ars, 
                               const int64_t* xbs, const double* cs, const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res,
                               const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
 
+/* ---- batched affine substitutions: what the reference runs wherever a series is multiplied by, or a variable replaced with, the
+ * affine series c + m * x_w (X ~ Binomial(Y, p), X += Y, thinning, marginalising to a point, a Taylor shift) -- mul_linear
+ * (mt:611-623) and subst_var's two linear paths (mt:555-579) on caller-owned device tensors, per item and in one launch, at ranks 1
+ * and 2.  Every item has its own scalars: c and m have the batch shape (strides cbs, mbs) and may repeat through stride 0.  Axes are
+ * counted as `var`: 0 is axis -2 and 1 is axis -1 of a rank-2 item; at rank 1 there is the series axis alone.  An operand lies inside
+ * the orders (na <= n, per axis), the result has (n | n0, n1) coefficients, at least two on the axis w of the affine series, and the
+ * limits bound the result (n <= 4096, n0 * n1 <= 4096).  Every operation is rounded once, nothing is contracted, and an absent term
+ * is absent, not an added zero.
+ *   mul_linear(a, c, m; w; n), a with L stored coefficients on w.  The compact result has L' = min(n_w, L + 1) on w and a's lengths
+ *   on the other axis; per line along w:
+ *       t[0] = +0.0,  t[j] = a[j - 1] * m                              1 <= j < L'      (mul_var, mt:589-608)
+ *       c == 0:  out[j] = t[j]
+ *       else:    out[j] = t[j] + (c * a[j])  for j < L,  out[L] = t[L] where L < L'
+ *   and everything of n outside the compact result is +0.0.
+ *   compose_linear(f, v, c, m, w; n): x_v := c + m * x_w.  S_i is slice i of f along v (i < nf_v).
+ *       w == v and c == 0:  out slice i = S_i * p_i,  p_0 = 1,  p_{i+1} = p_i * m          (the running power table, mt:557-565)
+ *       else:  res = 0.0 + S_{nf_v - 1};  for i = nf_v - 2 ... 0:                          (Horner, mt:569-579)
+ *                  res = mul_linear(res, c, m; w; n) at its compact shape;  res[k] = res[k] + S_i[k] over the stored positions of S_i
+ *   The result is res inside +0.0 at the orders n; for w != v only index 0 along v is ever stored.  The compact shape: f's for
+ *   w == v; else 1 on v and min(n_w, nf_w + nf_v - 1) on w.
+ * `c == 0` compares the value (-0.0 counts as zero), per item on the device: the only data-dependent branch.  Non-finite scalars
+ * and data run the same sequence and no shortcut looks at the coefficients; gft_series_compose(f, [c, m]) is the general product's
+ * operation order, other bits, and about nf * n^2 / 2 multiply-adds per item where this is nf * n.
+ * The result may not overlap the operand, c or m (not even as the same view).  Batch strides, row strides, NULL stride arrays, empty
+ * batches, the stream contract and return values: those of gft_series_mul.  One launch per call, no workspace.  After
+ * compose_linear gft_series_last_form() reports 1 (one wave per line along w: n_w <= 64) or 2 (one workgroup per line), and the
+ * option "series_form" forces 2; mul_linear is one streaming kernel and reports 0. */
+int gft_series_mul_linear(const double* a, const int64_t* abs, size_t na, const double* c, const int64_t* cbs, const double* m,
+                          const int64_t* mbs, double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gft_series2_mul_linear(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* c,
+                           const int64_t* cbs, const double* m, const int64_t* mbs, double* res, const int64_t* rbs, int64_t rrs, size_t n0,
+                           size_t n1, const size_t* batch, size_t nbatch, void* stream);
+int gft_series_compose_linear(const double* f, const int64_t* fbs, size_t nf, const double* c, const int64_t* cbs, const double* m,
+                              const int64_t* mbs, double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gft_series2_compose_linear(const double* f, const int64_t* fbs, int64_t frs, size_t nf0, size_t nf1, int var, int wvar, const double* c,
+                               const int64_t* cbs, const double* m, const int64_t* mbs, double* res, const int64_t* rbs, int64_t rrs, size_t n0,
+                               size_t n1, const size_t* batch, size_t nbatch, void* stream);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI, collectives internal to the library --------
  * The reference is single-process; a host that wants one large product spread over the GPUs of a node starts one
  * process per GPU (each with its own gft_init(device)), lets rank 0 call gft_dist_unique_id, hands the 128 bytes to
@@ -736,6 +774,20 @@ int gfti_series_observe_chain(const double* a, const int64_t* abs, size_t na, co
 int gfti_series2_observe_chain(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,
                                const int64_t* xbs, const double* cs, const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res,
                                const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+/* The affine substitutions over Interval<F64>: gft_series_mul_linear / gft_series_compose_linear and their rank-2 twins on (lo, hi)
+ * planes, the plane stride first in every stride array; c and m are [2, B...].  The same loops, every * and + the reference's Interval
+ * operation with its own short-circuits; c equals 0 when both of its bounds do.  The limits on the result are n <= 2048 and
+ * n0 * n1 <= 2048. */
+int gfti_series_mul_linear(const double* a, const int64_t* abs, size_t na, const double* c, const int64_t* cbs, const double* m,
+                           const int64_t* mbs, double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_mul_linear(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* c,
+                            const int64_t* cbs, const double* m, const int64_t* mbs, double* res, const int64_t* rbs, int64_t rrs, size_t n0,
+                            size_t n1, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series_compose_linear(const double* f, const int64_t* fbs, size_t nf, const double* c, const int64_t* cbs, const double* m,
+                               const int64_t* mbs, double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_compose_linear(const double* f, const int64_t* fbs, int64_t frs, size_t nf0, size_t nf1, int var, int wvar, const double* c,
+                                const int64_t* cbs, const double* m, const int64_t* mbs, double* res, const int64_t* rbs, int64_t rrs, size_t n0,
+                                size_t n1, const size_t* batch, size_t nbatch, void* stream);
 size_t gfti_len_of(const gft_poly* p, size_t v);
 int gfti_is_constant(const gft_poly* p);
 int gfti_is_zero(const gft_poly* p);
