@@ -4,15 +4,17 @@ autograd Functions of ``series`` and ``series2_grad``) describe a call by data a
 
 ``OPS`` is the table of the operations: one row says what travels between the first operand and the result, which side is the long
 one, the operands' names in messages and whether ``var`` travels at ranks 2 and 3.  The same rows build the ctypes declarations of every
-``gft[i]_series[2]_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart.  A ``Call``
+``gft[i]_series[2]_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart; the C layer's
+counterpart is ``gft::SERIES_OPS`` (gft_series_args.hpp), and tests/test_series_refusals.py holds the two tables together.  A ``Call``
 says the rest: the rank (1: the last axis is the series, 2 / 3: the last two / three axes are the coefficient array), ``planes`` (1: interval
 tensors ``[2, B..., item]``, the plane axis travelling as the first entry of every batch-stride array), the limit of the long side
 and the module's name for messages.  ``run`` works on ``t.shape[-rank:]`` and ``t.stride()[-rank:-1]``: rank 2 contributes its row
 stride and its second length because those tuples are one entry longer, rank 3 its slab stride and third length likewise.
 
 Everything that needs no device is judged first, in one order for every module: type, dtype, planes, axes (per tensor), the orders,
-``out``, grad, then the placement, the devices and the library's device.  ``run_chain`` is the same path for ``observe_chain``, whose
-items carry their own scalars (``x``, ``cs``), and ``run_linear`` for ``mul_linear`` and ``compose_linear`` (``c``, ``m``).
+``out``, grad, then the placement, the devices and the library's device.  ``run``, ``run_chain`` (``observe_chain``, whose items
+carry their own scalars ``x``, ``cs``) and ``run_linear`` (``mul_linear`` and ``compose_linear``: ``c``, ``m``) hold the shape rules
+of their operations and end in the one tail ``_launch``; ``_axes`` is the one check of the series axes, by the rank.
 """
 from __future__ import annotations
 
@@ -147,38 +149,19 @@ def _check(torch, t, what, planes=0):
         raise TaylorError(f"{what}: the tensor has {lead}; an interval tensor is stacked [2, ...] = (lo, hi) along its first axis")
 
 
-def _axes1(t, what, planes=0):
-    """the series axis of an operand or of ``out``"""
-    if t.dim() < 1 + planes:
-        raise TaylorError(f"{what}: a 0-dimensional tensor has no series axis")
-    if t.shape[-1] > 1 and t.stride(-1) != 1:
-        raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
-    if t.shape[-1] == 0:
-        raise TaylorError(f"{what}: the series (last) axis is empty")
-
-
-def _axes2(t, what, planes=0):
-    """the two series axes of an operand or of ``out``"""
-    if t.dim() < 2 + planes:
+def _axes(rank, t, what, planes=0):
+    """the ``rank`` series axes of an operand or of ``out``: enough axes, none empty, the last one with unit stride"""
+    kind, count = (None, "bivariate", "trivariate")[rank - 1], (None, "two", "three")[rank - 1]
+    if t.dim() < rank + planes:
+        if rank == 1:
+            raise TaylorError(f"{what}: a 0-dimensional tensor has no series axis")
         if planes:
-            raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate interval series needs at least 3 (the first holds the two "
-                              "planes, the last two are the coefficient array)")
-        raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a bivariate series needs at least 2 (the last two are the coefficient array)")
-    if t.shape[-1] == 0 or t.shape[-2] == 0:
-        raise TaylorError(f"{what}: a series axis is empty (the last two axes are {tuple(t.shape[-2:])})")
-    if t.shape[-1] > 1 and t.stride(-1) != 1:
-        raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
-
-
-def _axes3(t, what, planes=0):
-    """the three series axes of an operand or of ``out``"""
-    if t.dim() < 3 + planes:
-        if planes:
-            raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a trivariate interval series needs at least 4 (the first holds the two "
-                              "planes, the last three are the coefficient array)")
-        raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a trivariate series needs at least 3 (the last three are the coefficient array)")
-    if 0 in t.shape[-3:]:
-        raise TaylorError(f"{what}: a series axis is empty (the last three axes are {tuple(t.shape[-3:])})")
+            raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a {kind} interval series needs at least {rank + 1} (the first holds the two "
+                              f"planes, the last {count} are the coefficient array)")
+        raise TaylorError(f"{what}: the tensor has {t.dim()} axes; a {kind} series needs at least {rank} (the last {count} are the coefficient array)")
+    if 0 in t.shape[-rank:]:
+        raise TaylorError(f"{what}: the series (last) axis is empty" if rank == 1 else
+                          f"{what}: a series axis is empty (the last {count} axes are {tuple(t.shape[-rank:])})")
     if t.shape[-1] > 1 and t.stride(-1) != 1:
         raise TaylorError(f"{what}: the series (last) axis has stride {t.stride(-1)}; it must have unit stride")
 
@@ -187,24 +170,63 @@ _rank = {}
 
 
 def _rank_rules(rank):
-    """What differs by rank: the checks of the series axes, the order helpers (they stay with their modules, series._order ... and
+    """What differs by rank beyond _axes: the order helpers (they stay with their modules, series._order ... and
     series2._orders ...; here they take and give item shapes) and the texts that count "per series" or "per item"."""
     if not _rank:
         from .series import _order, _order_short
         from .series2 import _orders, _orders_short
         from .series3 import _orders as _orders3
 
-        _rank[1] = (_axes1, lambda what, n, limit, *items: (_order(what, n, *[i[0] for i in items], max_n=limit),),
+        _rank[1] = (lambda what, n, limit, *items: (_order(what, n, *[i[0] for i in items], max_n=limit),),
                     lambda what, n, names, g, y: (_order_short(what, n, g[0], y[0], names),),
                     "{what}: x has {count} coefficients, which exceeds the limit of {limit} per series of this version",
                     "{what}: out has {got[0]} coefficients per series, the result has n = {want[0]}")
-        _rank[2] = (_axes2, lambda what, n, limit, *items: _orders(what, n, *items, max_elems=limit),
+        _rank[2] = (lambda what, n, limit, *items: _orders(what, n, *items, max_elems=limit),
                     lambda what, n, names, g, y: _orders_short(what, n, g, y, names),
                     "{what}: x has {shape[0]} * {shape[1]} = {count} coefficients, which exceeds the limit of {limit} per item of this version",
                     "{what}: out has {got} coefficients per item, the result has n = {want}")
-        _rank[3] = (_axes3, lambda what, n, limit, *items: _orders3(what, n, *items, max_elems=limit), None, None,
+        _rank[3] = (lambda what, n, limit, *items: _orders3(what, n, *items, max_elems=limit), None, None,
                     "{what}: out has {got} coefficients per item, the result has n = {want}")  # (no transposed or observation op at rank 3)
     return _rank[rank]
+
+
+def _launch(what, op, call, named, out, batch, rshape, scalars):
+    """The tail of every call, once.  ``named``: the operands as (the part's key for ``_arguments``, the name in messages, the tensor
+    or None, the item shape it is expanded to behind the batch), in the order they are judged; ``out`` (None: allocated here) follows
+    them.  ``scalars``: the ``e``, ``var`` and ``k`` parts of the argument list.  In this order: the placement of every tensor, one
+    device, ``out``, the interval operands lifted to the batch's axes, the library's device, the expansion, the call, its error."""
+    import torch
+
+    _module, rank, planes, _limit, _raw = call
+    given = [(t, name) for _, name, t, _ in named if t is not None] + ([(out, "out")] if out is not None else [])
+    for t, name in given:
+        _placed(t, f"{what}: {name}")
+    device = given[0][0].device
+    for t, _ in given[1:]:
+        if t.device != device:
+            raise TaylorError(f"{what}: the tensors are on different devices ({device}, {t.device})")
+    lead, nb = (2,) * planes, len(batch)
+    if out is None:
+        out = torch.empty(lead + batch + rshape, dtype=torch.float64, device=device)
+    parts = {key: t for key, _, t, _ in named}
+    if planes:  # torch aligns shapes from the right: the plane axis stays first, missing batch axes go behind it (a view)
+        for key, _, t, item in named:
+            if t is not None and t.dim() < nb + 1 + len(item):
+                parts[key] = t[(slice(None),) + (None,) * (nb + 1 + len(item) - t.dim())]
+    L = _lib()
+    dev = int(L.gft_device())
+    if dev >= 0 and device.index != dev:
+        raise TaylorError(f"{what}: the tensors are on {device}, but the library runs on cuda:{dev}")
+    for key, _, t, item in named:
+        if t is not None:
+            parts[key] = parts[key].expand(lead + batch + item)
+    parts["out"] = out
+    ns = nb + planes  # entries of a batch-stride array
+    tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_", "series3_")[rank - 1] + op.suffix)
+    if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), *scalars, tail)) != 0:
+        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
+    return out
 
 
 def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
@@ -214,7 +236,7 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
 
     op, (module, rank, planes, limit, raw) = OPS[name], call
     what = f"{module}.{op.label}"
-    axes, order, short, over_text, out_text = _rank_rules(rank)
+    order, short, over_text, out_text = _rank_rules(rank)
     observe, seeded = op.kind in ("k", None), op.kind == "seed"
     xname, sname = op.names[0], "seed" if seeded else op.names[1]
     # everything that needs no device first: types, shapes, strides, orders, out, grad -- then the placement
@@ -223,7 +245,7 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
             w = f"{what}: {w}"
             _check(torch, t, w, planes)
             if item:
-                axes(t, w, planes)
+                _axes(rank, t, w, planes)
     shape = tuple(x.shape[-rank:])
     if observe:
         count = shape[0] * shape[-1] if rank == 2 else shape[0]
@@ -244,7 +266,7 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
         rshape = short(what, n, op.names, shape, tuple(second.shape[-rank:]))
     else:
         rshape = order(what, n, limit, shape, *((tuple(second.shape[-rank:]),) if op.kind == "second" else ()))
-    lead, nr = (2,) * planes, len(rshape)
+    nr = len(rshape)
     shapes = [x.shape[planes:-rank]]
     if second is not None:
         shapes.append(second.shape[planes:] if seeded else second.shape[planes:-rank])
@@ -271,36 +293,8 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
     if raw and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, second)):
         raise TaylorError(f"{what}: an operand requires grad, and this version of {module} has no autograd; pass {xname}.detach() or call under "
                           "torch.no_grad() (nothing is detached silently)")
-    _placed(x, f"{what}: {xname}")
-    if second is not None:
-        _placed(second, f"{what}: {sname}")
-    if out is not None:
-        _placed(out, f"{what}: out")
-    for t in (second, out):
-        if t is not None and t.device != x.device:
-            raise TaylorError(f"{what}: the tensors are on different devices ({x.device}, {t.device})")
-    if out is None:
-        out = torch.empty(lead + batch + rshape, dtype=torch.float64, device=x.device)
-    nb = len(batch)
-    if planes:  # torch aligns shapes from the right: the plane axis stays first, missing batch axes go behind it (a view)
-        lift = lambda t, dim: t if t.dim() >= dim else t[(slice(None),) + (None,) * (dim - t.dim())]  # noqa: E731
-        x = lift(x, nb + 1 + rank)
-        if second is not None:
-            second = lift(second, nb + 1 + (0 if seeded else rank))
-    L = _lib()
-    dev = int(L.gft_device())
-    if dev >= 0 and x.device.index != dev:
-        raise TaylorError(f"{what}: the tensors are on {x.device}, but the library runs on cuda:{dev}")
-    ns = nb + planes  # entries of a batch-stride array
-    x = x.expand(lead + batch + shape)
-    if second is not None:
-        second = second.expand(lead + batch + (() if seeded else tuple(second.shape[-rank:])))
-    tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_", "series3_")[rank - 1] + op.suffix)
-    parts = {"x": x, "second": second, "out": out}
-    if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (scalar,), (var,), (scalar,), tail)) != 0:
-        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
-    return out
+    named = (("x", xname, x, shape), ("second", sname, second, () if seeded or second is None else tuple(second.shape[-rank:])))
+    return _launch(what, op, call, named, out, batch, rshape, ((scalar,), (var,), (scalar,)))
 
 
 def _count(what, name, v):
@@ -322,14 +316,14 @@ def run_chain(call, a, var, x, cs, degree_p1=None, out=None):
 
     op, (module, rank, planes, limit, _raw) = OPS["observe_chain"], call
     what = f"{module}.{op.label}"
-    axes, _order, _short, over_text, _out_text = _rank_rules(rank)
+    over_text = _rank_rules(rank)[2]
     for t, w in ((a, "a"), (x, "x"), (cs, "cs"), (out, "out")):
         if t is None and w in ("x", "out"):
             continue
         w = f"{what}: {w}"
         _check(torch, t, w, planes)
         if t is a or t is out:
-            axes(t, w, planes)
+            _axes(rank, t, w, planes)
     if cs.dim() < 1 + planes:
         raise TaylorError(f"{what}: cs has no axis of constants; it is [{'2, ' if planes else ''}B..., nsteps]")
     if cs.shape[-1] > 1 and cs.stride(-1) != 1:
@@ -370,31 +364,8 @@ def run_chain(call, a, var, x, cs, degree_p1=None, out=None):
             if t is not None and t.requires_grad:
                 raise TaylorError(f"{what}: {w} requires grad, and observe_chain has no autograd in this version; pass {w}.detach() or call "
                                   "under torch.no_grad() (nothing is detached silently)")
-    tensors = [(t, w) for t, w in ((a, "a"), (x, "x"), (cs, "cs"), (out, "out")) if t is not None]
-    for t, w in tensors:
-        _placed(t, f"{what}: {w}")
-    for t, _ in tensors[1:]:
-        if t.device != a.device:
-            raise TaylorError(f"{what}: the tensors are on different devices ({a.device}, {t.device})")
-    lead, nb = (2,) * planes, len(batch)
-    if out is None:
-        out = torch.empty(lead + batch + rshape, dtype=torch.float64, device=a.device)
-    if planes:  # the plane axis stays first, missing batch axes go behind it (a view)
-        lift = lambda t, dim: t if t.dim() >= dim else t[(slice(None),) + (None,) * (dim - t.dim())]  # noqa: E731
-        a, cs = lift(a, nb + 1 + rank), lift(cs, nb + 2)
-        x = None if x is None else lift(x, nb + 1)
-    L = _lib()
-    dev = int(L.gft_device())
-    if dev >= 0 and a.device.index != dev:
-        raise TaylorError(f"{what}: the tensors are on {a.device}, but the library runs on cuda:{dev}")
-    ns = nb + planes
-    parts = {"x": a.expand(lead + batch + shape), "second": None if x is None else x.expand(lead + batch),
-             "cs": cs.expand(lead + batch + (nsteps,)), "out": out}
-    tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_")[rank - 1] + op.suffix)
-    if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (), (var,), (nsteps, d), tail)) != 0:
-        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
-    return out
+    named = (("x", "a", a, shape), ("second", "x", x, ()), ("cs", "cs", cs, (nsteps,)))
+    return _launch(what, op, call, named, out, batch, rshape, ((), (var,), (nsteps, d)))
 
 
 def run_linear(call, name, a, var, wvar, c, m, n=None, out=None):
@@ -407,14 +378,13 @@ def run_linear(call, name, a, var, wvar, c, m, n=None, out=None):
     what = f"{module}.{op.label}"
     comp = name == "compose_linear"
     aname = op.names[0]
-    axes, _order, _short, _over_text, _out_text = _rank_rules(rank)
     for t, w in ((a, aname), (c, "c"), (m, "m"), (out, "out")):
         if t is None and w == "out":
             continue
         w = f"{what}: {w}"
         _check(torch, t, w, planes)
         if t is a or t is out:
-            axes(t, w, planes)
+            _axes(rank, t, w, planes)
     shape = tuple(a.shape[-rank:])
     v = w = rank - 1  # as positions of an item's shape
     if rank == 2:
@@ -478,26 +448,5 @@ def run_linear(call, name, a, var, wvar, c, m, n=None, out=None):
             if t.requires_grad:
                 raise TaylorError(f"{what}: {k} requires grad, and {op.label} has no autograd in this version; pass {k}.detach() or call "
                                   "under torch.no_grad() (nothing is detached silently)")
-    tensors = [(a, aname), (c, "c"), (m, "m")] + ([(out, "out")] if out is not None else [])
-    for t, k in tensors:
-        _placed(t, f"{what}: {k}")
-    for t, _ in tensors[1:]:
-        if t.device != a.device:
-            raise TaylorError(f"{what}: the tensors are on different devices ({a.device}, {t.device})")
-    lead, nb = (2,) * planes, len(batch)
-    if out is None:
-        out = torch.empty(lead + batch + order, dtype=torch.float64, device=a.device)
-    if planes:  # the plane axis stays first, missing batch axes go behind it (a view)
-        lift = lambda t, dim: t if t.dim() >= dim else t[(slice(None),) + (None,) * (dim - t.dim())]  # noqa: E731
-        a, c, m = lift(a, nb + 1 + rank), lift(c, nb + 1), lift(m, nb + 1)
-    L = _lib()
-    dev = int(L.gft_device())
-    if dev >= 0 and a.device.index != dev:
-        raise TaylorError(f"{what}: the tensors are on {a.device}, but the library runs on cuda:{dev}")
-    ns = nb + planes
-    parts = {"x": a.expand(lead + batch + shape), "second": c.expand(lead + batch), "cs": m.expand(lead + batch), "out": out}
-    tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_")[rank - 1] + op.suffix)
-    if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), (), (v, w)[:int(op.var)], (), tail)) != 0:
-        raise TaylorError((L.gft_last_error() or b"unknown error").decode())
-    return out
+    named = (("x", aname, a, shape), ("second", "c", c, ()), ("cs", "m", m, ()))
+    return _launch(what, op, call, named, out, batch, order, ((), (v, w)[:int(op.var)], ()))

@@ -12,7 +12,8 @@
 // and the affine substitutions gft_series_mul_linear / compose_linear, gft_series2_mul_linear / compose_linear with their gfti_ twins
 // (every item with its own scalars c and m, one launch; the kernels: gft_series_linear.hip)
 // Every entry point fills one gft::SeriesCall with its rank (gft_series_args.hpp, which judges it without the device and states the
-// item of any rank as one gft::SeriesItem) and hands it to series_call, which dispatches on the rank once; pow is one driver.
+// item of any rank as one gft::SeriesItem) and hands it to series_call, which dispatches on the family of the op's row in
+// gft::SERIES_OPS and, for the arithmetic family, on the rank; pow is one driver.
 // (the planner and the kernels: gft_series.hpp, gft_series.hip; included by gft_api.hip after the device interop, whose
 // pointer check and stream joins it shares)
 // ------------------------------------------------------------------------------------------
@@ -31,7 +32,9 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
     const gft::SeriesBatch& g = a.g;
     const gft::SeriesPlanes& pl = a.pl;
     const hipStream_t cs = (hipStream_t)stream;
-    if (op == gft::SERIES_OBSERVE_CHAIN) {  // one launch for the whole chain; the derivative's factors of order 1 over the axis
+    const gft::SeriesOpRow& row = gft::SERIES_OPS[op];
+    switch (row.family) {
+    case gft::SERIES_CHAIN: {  // one launch for the whole chain; the derivative's factors of order 1 over the axis
         const size_t tlen = (c.rank == 2 && c.var == 0 ? it.nx[1] : it.nx[2]) - 1;
         Rc<Buf> tab = w == 2 ? Ops<EIv>::cached_table(TAB_DERIV, 1, tlen) : Ops<EF64>::cached_table(TAB_DERIV, 1, tlen);
         join_caller_in(cs);
@@ -40,13 +43,13 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         join_caller_out(cs);
         return 0;
     }
-    if (op == gft::SERIES_MUL_LINEAR || op == gft::SERIES_COMPOSE_LINEAR) {  // one launch; c and m travel as the chain's x and cs
+    case gft::SERIES_LINEAR: {  // one launch; c and m travel as the chain's x and cs
         join_caller_in(cs);
         R.series_last = gft::series_linear(R.stream, op, x, y, c.cs.p, res, gft::series2_dims(it), c.var, c.wvar, g, pl, R.series_force);
         join_caller_out(cs);
         return 0;
     }
-    if (op >= gft::SERIES_DERIVATIVE) {
+    case gft::SERIES_OBSERVE: {
         // the factors depend on (op, k, len) only: computed once with the reference's rounding (k_factor_table's functor) and kept.
         // A table is written on the library's stream, where the kernel below runs: its first use is ordered behind it.
         Rc<Buf> tab;
@@ -62,12 +65,14 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         R.series_last = gft::SERIES_NONE;
         return 0;
     }
-    if (op == gft::SERIES_POW) {  // one driver for every rank
+    case gft::SERIES_POWER: {  // one driver for every rank
         Rc<Buf> ws = alloc_doubles(gft::series_pow_workspace(g.items, it.n, w));  // (returned to the pool on exit: later launches follow)
         join_caller_in(cs);
         R.series_last = gft::series_pow(R.stream, c.rank, x, c.e, res, it, g, ws->p, R.series_force, pl);
         join_caller_out(cs);
         return 0;
+    }
+    case gft::SERIES_ARITH: break;  // by the rank, below
     }
     // ranks 2 and 3 have one form, planned before the streams are joined (the planner may refuse)
     if (c.rank == 3) {  // on the permuted item of the stored result shape S (compose: of the chain's final shape)
@@ -96,8 +101,7 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         return 0;
     }
     const unsigned nx = it.nx[2], ny = it.ny[2], n = it.n[2];
-    const bool transposed = op == gft::SERIES_CORR || op == gft::SERIES_COMPOSE_ADJ;  // their planner sizes the long rows: x's
-    const int form = gft::series_plan(op, g.items, transposed ? nx : n, R.series_force, w);
+    const int form = gft::series_plan(op, g.items, row.xlong ? nx : n, R.series_force, w);  // (the planner sizes the long rows)
     const size_t wsn = gft::series_workspace(op, form, g.items, nx, n, w);
     Rc<Buf> ws;
     if (wsn) ws = alloc_doubles(wsn);  // (returned to the pool on exit: later launches follow these on the one stream)

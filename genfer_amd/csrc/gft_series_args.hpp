@@ -2,6 +2,10 @@
 // and planned with (one SeriesCall in, one SeriesItem out), and everything that is judged about a call without touching device
 // state -- the shape rules, the batch, the strides, the result's distinct addresses, the overlap proof and the collapse of the
 // batch axes into a SeriesBatch; then what is planned from the shapes alone: the rank-3 item, compose's chain and pow's steps.
+// What an operation IS -- its family, its highest rank, its operands' names and roles, its long side, what its result may alias --
+// is stated once, in the rows of SERIES_OPS; series_shapes, series_args and the caller's dispatch read the row.  Rules of one op
+// (the chain's counts, series_linear_shapes, the observation ops' k, pow's cap on batch axes, corr's and compose_adj's length names)
+// stay code, keyed on the op or the family.
 // No HIP include: this header compiles with a plain host compiler (tests/series_args_main.cpp replays refusals through it).
 // The device side (planners, launches, __device__ helpers) is gft_series.hpp; the caller with the device is gft_api_series.inc.
 #pragma once
@@ -43,8 +47,54 @@ enum SeriesOp {
     // (one element per item each, as the seeds), the result the LONG side.  mul_linear (mt:611-623): a times c + m * x_var.
     // compose_linear (subst_var's linear paths, mt:555-579): x_var := c + m * x_wvar.
     SERIES_MUL_LINEAR = 13,
-    SERIES_COMPOSE_LINEAR = 14
+    SERIES_COMPOSE_LINEAR = 14,
+    SERIES_OP_COUNT  // (no operation: the length of SERIES_OPS)
 };
+
+// One row per SeriesOp.  family: what series_call dispatches on.  ranks: the highest rank the op exists at.  x / y / cs: the
+// operands' names in the stride, pointer and overlap messages ("-": the op has no such operand; its view stays the default one,
+// about which nothing can be refused).  yrole: y is a second series; the optional seeds (null allowed; their strides travel as
+// ss / pl.s); or one scalar per item (its strides travel as ys / pl.y; optional for the chain, whose continuous form has none).
+// csrole: cs is the chain's constants or the substitutions' scalar m (either way its strides travel as ss / pl.s).  xlong: x, not
+// the result, is the long side.  alias_x / alias_y: the result may be that operand itself, as the same view.
+enum SeriesFamily { SERIES_ARITH, SERIES_POWER, SERIES_OBSERVE, SERIES_CHAIN, SERIES_LINEAR };
+enum SeriesYRole { SERIES_Y_NONE, SERIES_Y_SERIES, SERIES_Y_SEEDS, SERIES_Y_SCALAR };
+enum SeriesCsRole { SERIES_CS_NONE, SERIES_CS_CONSTANTS, SERIES_CS_SCALAR };
+struct SeriesOpRow {
+    SeriesOp op;
+    SeriesFamily family;
+    int ranks;
+    const char *x, *y, *cs;
+    SeriesYRole yrole;
+    SeriesCsRole csrole;
+    bool xlong, alias_x, alias_y;
+};
+constexpr SeriesOpRow SERIES_OPS[] = {
+    {SERIES_MUL, SERIES_ARITH, 3, "x", "y", "-", SERIES_Y_SERIES, SERIES_CS_NONE, false, true, true},
+    {SERIES_DIV, SERIES_ARITH, 3, "x", "y", "-", SERIES_Y_SERIES, SERIES_CS_NONE, false, true, true},
+    {SERIES_EXP, SERIES_ARITH, 3, "x", "the seeds", "-", SERIES_Y_SEEDS, SERIES_CS_NONE, false, true, false},
+    {SERIES_LOG, SERIES_ARITH, 3, "x", "the seeds", "-", SERIES_Y_SEEDS, SERIES_CS_NONE, false, true, false},
+    {SERIES_COMPOSE, SERIES_ARITH, 3, "f", "g", "-", SERIES_Y_SERIES, SERIES_CS_NONE, false, true, true},
+    {SERIES_POW, SERIES_POWER, 3, "x", "-", "-", SERIES_Y_NONE, SERIES_CS_NONE, false, true, false},
+    // (corr's result may be g itself, compose_adj's gh; neither may be the second operand)
+    {SERIES_CORR, SERIES_ARITH, 2, "g", "y", "-", SERIES_Y_SERIES, SERIES_CS_NONE, true, true, false},
+    {SERIES_COMPOSE_ADJ, SERIES_ARITH, 2, "gh", "g", "-", SERIES_Y_SERIES, SERIES_CS_NONE, true, true, false},
+    {SERIES_DERIVATIVE, SERIES_OBSERVE, 2, "x", "-", "-", SERIES_Y_NONE, SERIES_CS_NONE, true, true, false},
+    {SERIES_COEFF, SERIES_OBSERVE, 2, "x", "-", "-", SERIES_Y_NONE, SERIES_CS_NONE, true, true, false},
+    {SERIES_SHIFT_DOWN, SERIES_OBSERVE, 2, "x", "-", "-", SERIES_Y_NONE, SERIES_CS_NONE, true, true, false},
+    {SERIES_EVAL_ONE, SERIES_OBSERVE, 2, "x", "-", "-", SERIES_Y_NONE, SERIES_CS_NONE, true, true, false},
+    // (a chain's result is shorter than its operand: never the same view; a substitution's result is no operand)
+    {SERIES_OBSERVE_CHAIN, SERIES_CHAIN, 2, "a", "x", "cs", SERIES_Y_SCALAR, SERIES_CS_CONSTANTS, true, false, false},
+    {SERIES_MUL_LINEAR, SERIES_LINEAR, 2, "a", "c", "m", SERIES_Y_SCALAR, SERIES_CS_SCALAR, false, false, false},
+    {SERIES_COMPOSE_LINEAR, SERIES_LINEAR, 2, "f", "c", "m", SERIES_Y_SCALAR, SERIES_CS_SCALAR, false, false, false},
+};
+constexpr bool series_ops_in_enum_order() {
+    for (int i = 0; i < (int)(sizeof(SERIES_OPS) / sizeof(SERIES_OPS[0])); ++i)
+        if (SERIES_OPS[i].op != i) return false;
+    return true;
+}
+static_assert(sizeof(SERIES_OPS) / sizeof(SERIES_OPS[0]) == SERIES_OP_COUNT && series_ops_in_enum_order(),
+              "SERIES_OPS has one row per SeriesOp, in the enum's order (tests/make_series_refusals.py indexes the ops by position)");
 
 constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
 // Interval<F64> series (gfti_series_*): two planes per row, so the same LDS footprints are reached at half the order
@@ -105,17 +155,14 @@ struct SeriesView {
 };
 
 // One call of rank 1, 2 or 3 (gft[i]_series_*, _series2_*, _series3_*): the limit bounds the product of the long side's lengths.
-// `y`: the second operand (mul, div; compose: x is f, y is g) or the seeds (exp, log; p may be null; one double per item, so its
-// lengths stay 1); pow has neither, and `e`.  corr (x is g, y is y) and compose_adj (x is gh, y is g, the result has nf
-// coefficients) are the transposed operations (ranks 1 and 2): their result is the SHORT side, so x bounds y and the result, and
-// the rows the planner sizes are x's.  `var`: compose's variable above rank 1, counted over the call's own axes (rank 3: 0 the
-// slab axis, 1 the row axis, 2 the unit-stride axis).  The observation ops (SERIES_DERIVATIVE ..., ranks 1 and 2): x is the one
-// operand and the LONG side, `k` the order, `var` the axis at rank 2 (at rank 1 it is 1, the series axis), and the result's shape
-// must be x's with k taken off that axis (evaluate_all_one: one element per item).  Rank 3 has mul / div / exp / log / compose / pow.
-// SERIES_OBSERVE_CHAIN (ranks 1 and 2): x is the operand a, `y` the scalars x (p may be null: the continuous form; its lengths stay
-// 1), `cs` the constants with len[2] = nsteps; the result has degree_p1 coefficients on the axis `var` and min(length, degree_p1)
-// on the other one.  SERIES_MUL_LINEAR / SERIES_COMPOSE_LINEAR (ranks 1 and 2): x is the operand, `y` the scalars c and `cs` the
-// scalars m (their lengths stay 1), `var` (and compose_linear's `wvar`) the axes, at rank 1 both 1; the result is the long side.
+// What x, y and cs are to the op, which side is long and up to which rank the op exists: its row of SERIES_OPS.  Seeds and scalars
+// are one double per item, so their lengths stay 1.  The transposed operations corr and compose_adj (whose result has nf
+// coefficients) have the SHORT side as their result, so x bounds y and the result, and the rows the planner sizes are x's.
+// `var`: compose's variable above rank 1, counted over the call's own axes (rank 3: 0 the slab axis, 1 the row axis, 2 the
+// unit-stride axis).  The observation ops: `k` the order, `var` the axis at rank 2 (at rank 1 it is 1, the series axis), and the
+// result's shape must be x's with k taken off that axis (evaluate_all_one: one element per item).  SERIES_OBSERVE_CHAIN: cs has
+// len[2] = nsteps; the result has degree_p1 coefficients on the axis `var` and min(length, degree_p1) on the other one.
+// SERIES_MUL_LINEAR / SERIES_COMPOSE_LINEAR: `var` (and compose_linear's `wvar`) the axes, at rank 1 both 1.
 struct SeriesCall {
     int op = SERIES_MUL;
     const char* fn = "";  // the name in messages
@@ -194,7 +241,7 @@ static inline void series_linear_shapes(const SeriesCall& c) {
     using std::to_string;
     const std::string f(c.fn);
     const bool r2 = c.rank > 1, comp = c.op == SERIES_COMPOSE_LINEAR;
-    const char* const who = comp ? "f" : "a";
+    const char* const who = SERIES_OPS[c.op].x;
     if (r2 && (c.var < 0 || c.var > 1))
         throw std::runtime_error(f + ": var = " + to_string(c.var) + (comp ? " (the variable of f that is replaced is 0 or 1)" : " (the variable of the linear factor is 0 or 1)"));
     if (r2 && comp && (c.wvar < 0 || c.wvar > 1))
@@ -229,49 +276,49 @@ static inline void series_linear_shapes(const SeriesCall& c) {
 static inline void series_shapes(const SeriesCall& c) {
     using std::to_string;
     const std::string f(c.fn);
+    const SeriesOpRow& row = SERIES_OPS[c.op];
     const int op = c.op, rank = c.rank;
     // (the text is pinned byte for byte by tests/series3_compose_args_main.cpp and tests/series_refusals.json; its "on f64" dates from
     // before gfti_series3_* and misleads an interval caller or one with another width -- to be retired with those pins)
-    if (rank == 3 && ((c.w != 1 && c.w != 2) || op > SERIES_POW))
+    if (rank == 3 && ((c.w != 1 && c.w != 2) || row.ranks < 3))
         throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
-    if (op == SERIES_MUL_LINEAR || op == SERIES_COMPOSE_LINEAR) return series_linear_shapes(c);
-    const bool observe = op >= SERIES_DERIVATIVE, comp = op == SERIES_COMPOSE;
-    const bool corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
-    const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed;
+    if (row.family == SERIES_LINEAR) return series_linear_shapes(c);
+    const bool chain = row.family == SERIES_CHAIN, observe = chain || row.family == SERIES_OBSERVE;
+    const bool corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, binary = row.yrole == SERIES_Y_SERIES, xlong = row.xlong;
     const bool r2 = rank > 1, bad_var = r2 && (c.var < 0 || c.var >= rank);
-    if (bad_var && (comp || adj))
+    if (bad_var && (op == SERIES_COMPOSE || adj))
         throw std::runtime_error(f + ": var = " + to_string(c.var) + " (the variable of f that g replaces is " + (rank == 3 ? "0, 1 or 2)" : "0 or 1)"));
     struct Names {
-        const char *x, *y, *r;
+        std::string x, y, r;
     };
-    const Names len = corr ? Names{"ng", "ny", "m"} : (adj ? Names{"n", "ng", "nf"} : Names{"nx", "ny", "n"});  // rank 1: the lengths' names
-    const Names who = corr ? Names{"g", "y", "the result"}
-                           : (adj ? Names{"gh", "g", "the result"} : (rank == 3 && comp ? Names{"f", "g", "the result"} : Names{"x", "y", "the result"}));
+    // the row's names -- but compose, f / g everywhere else, is x / y in these texts below rank 3 (pinned as found)
+    const bool xy = op == SERIES_COMPOSE && rank < 3;
+    const Names who{xy ? "x" : row.x, xy ? "y" : row.y, "the result"};
+    // rank 1 names its lengths: n and the operand's name, the result's n; corr's result has m, compose_adj's gh has n and its result nf
+    const Names len{adj ? "n" : "n" + who.x, "n" + who.y, corr ? "m" : (adj ? "nf" : "n")};
     const char* const shape = rank == 3 ? "n0 * n1 * n2" : "n0 * n1";  // above rank 1: the result's lengths by name
-    const bool xlong = transposed || observe;
     const SeriesView& L = xlong ? c.x : c.r;
-    const char *Llen = xlong ? len.x : len.r, *Lwho = xlong ? who.x : who.r;
+    const std::string &Llen = xlong ? len.x : len.r, &Lwho = xlong ? who.x : who.r;
     auto empty = [](const SeriesView& v) { return v.len[0] == 0 || v.len[1] == 0 || v.len[2] == 0; };
     auto dims = [rank](const SeriesView& v, const char* sep) {  // the last `rank` lengths
         std::string t = to_string(v.len[2]);
         for (int i = 1; i >= 3 - rank; --i) t = to_string(v.len[i]) + sep + t;
         return t;
     };
-    const bool chain = op == SERIES_OBSERVE_CHAIN;
     if (observe) {
-        if (empty(c.x)) throw std::runtime_error(f + (chain ? ": a has no coefficients" : ": x has no coefficients"));
+        if (empty(c.x)) throw std::runtime_error(f + ": " + who.x + " has no coefficients");
     } else if (empty(c.r)) {
         if (!r2) throw std::runtime_error(f + ": " + len.r + " == 0 (the result has no coefficients)");
-        throw std::runtime_error(f + (transposed ? ": the result has no coefficients (an axis of its shape is 0)" : std::string(": ") + shape + " == 0 (the result has no coefficients)"));
+        throw std::runtime_error(f + (xlong ? ": the result has no coefficients (an axis of its shape is 0)" : std::string(": ") + shape + " == 0 (the result has no coefficients)"));
     }
     const size_t most = series_limit(rank, c.w);
     bool over = false;  // a length or a partial product of the lengths (none overflows: every factor is within the limit)
     for (size_t i = 0, prod = 1; i < 3 && !over; ++i) over = L.len[i] > most || (prod *= L.len[i]) > most;
     if (over) {
         if (!r2)
-            throw std::runtime_error(f + ": " + (chain ? "na" : Llen) + " = " + to_string(L.len[2]) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
+            throw std::runtime_error(f + ": " + Llen + " = " + to_string(L.len[2]) + " exceeds the limit of " + to_string(most) + " coefficients per series of this version");
         if (xlong)
-            throw std::runtime_error(f + ": " + (chain ? "a" : Lwho) + " has " + dims(L, " * ") + " coefficients, which exceeds the limit of " + to_string(most) +
+            throw std::runtime_error(f + ": " + Lwho + " has " + dims(L, " * ") + " coefficients, which exceeds the limit of " + to_string(most) +
                                      " coefficients per item of this version");
         throw std::runtime_error(f + ": " + shape + " = " + dims(L, " * ") + " exceeds the limit of " + to_string(most) + " coefficients per item of this version");
     }
@@ -304,13 +351,13 @@ static inline void series_shapes(const SeriesCall& c) {
         return;
     }
     if (empty(c.x) || (binary && empty(c.y))) throw std::runtime_error(f + ": an operand has no coefficients");
-    auto fits = [&](const SeriesView& s, const char* slen, const char* swho) {
+    auto fits = [&](const SeriesView& s, const std::string& slen, const std::string& swho) {
         if (s.len[0] <= L.len[0] && s.len[1] <= L.len[1] && s.len[2] <= L.len[2]) return;
         const char* why = &s == &c.r ? "the result of a transposed operation is its short side" : "an operand is longer than the truncation order";
         if (r2) throw std::runtime_error(f + ": " + swho + " has " + dims(s, " x ") + " coefficients, " + Lwho + " " + dims(L, " x ") + " (" + why + ")");
         throw std::runtime_error(f + ": " + slen + " = " + to_string(s.len[2]) + " > " + Llen + " = " + to_string(L.len[2]) + " (" + why + ")");
     };
-    if (transposed) fits(c.r, len.r, who.r);
+    if (xlong) fits(c.r, len.r, who.r);  // (the transposed ops: the observation ops have returned)
     else fits(c.x, len.x, who.x);
     if (binary) fits(c.y, len.y, who.y);
 }
@@ -322,10 +369,8 @@ static inline void series_shapes(const SeriesCall& c) {
 template <class CheckPtr>
 static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& check_ptr) {
     const std::string f(c.fn);
-    const int op = c.op, w = c.w;
-    const bool comp = op == SERIES_COMPOSE, corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, transposed = corr || adj;
-    const bool binary = op == SERIES_MUL || op == SERIES_DIV || comp || transposed, chain = op == SERIES_OBSERVE_CHAIN;
-    const bool lin = op == SERIES_MUL_LINEAR || op == SERIES_COMPOSE_LINEAR, complin = op == SERIES_COMPOSE_LINEAR;
+    const SeriesOpRow& row = SERIES_OPS[c.op];
+    const int w = c.w;
     const size_t* batch = c.batch;
     const size_t nbatch = c.nbatch;
     series_shapes(c);
@@ -337,10 +382,13 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         items *= batch[i];
         if (items >= ((size_t)1 << 31)) throw std::runtime_error(f + ": more than 2^31 - 1 series in one call");
     }
-    const SeriesOperand ax = series_arg(c, comp || complin ? "f" : (corr ? "g" : (adj ? "gh" : (chain || lin ? "a" : "x"))), c.x);
-    const SeriesOperand ay = series_arg(c, lin ? "c" : (comp || adj ? "g" : (binary ? "y" : (chain ? "x" : "the seeds"))), c.y);
+    const SeriesOperand ax = series_arg(c, row.x, c.x);
+    const SeriesOperand ay = series_arg(c, row.y, c.y);
     const SeriesOperand ar = series_arg(c, "the result", c.r);
-    const SeriesOperand ac = series_arg(c, lin ? "m" : "cs", c.cs);  // (read by the observation chain and the affine substitutions)
+    const SeriesOperand ac = series_arg(c, row.cs, c.cs);
+    // y is read where the op has one and, where it is optional (the seeds, the chain's x), it is given; cs where the op has one
+    const bool optional = row.yrole == SERIES_Y_SEEDS || row.family == SERIES_CHAIN;
+    const bool has_y = row.yrole != SERIES_Y_NONE && (ay.p || !optional), has_cs = row.csrole != SERIES_CS_NONE;
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
         struct Ax {
@@ -371,8 +419,8 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
                 throw std::runtime_error(f + ": the result's series overlap each other (its strides do not separate the rows)");
     }
     check_ptr(ax.p, ax.what);
-    if (binary || lin || ay.p) check_ptr(ay.p, ay.what);
-    if (chain || lin) check_ptr(ac.p, ac.what);
+    if (has_y) check_ptr(ay.p, ay.what);
+    if (has_cs) check_ptr(ac.p, ac.what);
     check_ptr(ar.p, ar.what);
     // the result may be an input itself (the same view: every row is read before it is written); any other overlap is refused.
     // Judged by address ranges, so two interleaved views of one buffer count as overlapping.
@@ -385,47 +433,37 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         }
         throw std::runtime_error(f + ": the result partially overlaps " + a.what + " (it may alias an operand only as the same view)");
     };
-    overlap(ax, !chain && !lin);  // (a chain's result is shorter than its operand: never the same view; a substitution's is no operand)
-    if (chain || lin) overlap(ac, false);
-    if (transposed) overlap(ay, false);  // corr's result may be g itself, compose_adj's gh; neither may be the second operand
-    else if (binary) overlap(ay, true);
-    else if (ay.p) overlap(ay, false);
+    overlap(ax, row.alias_x);
+    if (has_cs) overlap(ac, false);
+    if (has_y) overlap(ay, row.alias_y);
     // collapse the batch: unit axes go, axes contiguous with their inner neighbour on every operand merge
     SeriesBatch& g = out.g;
     g.nd = 0;
     g.items = (unsigned)items;
     g.inplace = inplace;
-    // a chain: ys are the strides of x, ss those of cs; an affine substitution: ys those of c, ss those of m
-    const bool seeds = !binary && !chain && !lin && ay.p, xscal = (chain && ay.p) || lin, cscal = chain || lin;
+    // what travels as ys / pl.y and as ss / pl.s: a second series or a scalar y as y; the seeds, else cs, as s
+    const SeriesOperand* const as_y = has_y && row.yrole != SERIES_Y_SEEDS ? &ay : nullptr;
+    const SeriesOperand* const as_s = has_y && row.yrole == SERIES_Y_SEEDS ? &ay : (has_cs ? &ac : nullptr);
     for (size_t i = 0; i < nbatch; ++i) {
         if (batch[i] == 1) continue;
-        const size_t e = batch[i], sx = ax.st[i], sy = binary || xscal ? ay.st[i] : 0, ss = seeds ? ay.st[i] : (cscal ? ac.st[i] : 0), sr = ar.st[i];
-        if (g.nd > 0) {
-            const int p = g.nd - 1;
-            // (merged extents stay below 2^31: items does)
-            if (g.xs[p] == sx * e && g.ys[p] == sy * e && g.ss[p] == ss * e && g.rs[p] == sr * e) {
-                g.ext[p] *= (unsigned)e;
-                g.xs[p] = sx;
-                g.ys[p] = sy;
-                g.ss[p] = ss;
-                g.rs[p] = sr;
-                continue;
-            }
+        const size_t e = batch[i], sx = ax.st[i], sy = as_y ? as_y->st[i] : 0, ss = as_s ? as_s->st[i] : 0, sr = ar.st[i];
+        int p = g.nd - 1;
+        // (merged extents stay below 2^31: items does)
+        if (p >= 0 && g.xs[p] == sx * e && g.ys[p] == sy * e && g.ss[p] == ss * e && g.rs[p] == sr * e) {
+            g.ext[p] *= (unsigned)e;
+        } else {
+            // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow's copy every series axis of the rank)
+            const int most = IMAXD - w - (row.family == SERIES_POWER ? c.rank - 1 : 0);
+            if (g.nd == most) throw std::runtime_error(f + ": the batch has more than " + std::to_string(most) + " non-contiguous axes");
+            p = g.nd++;
+            g.ext[p] = (unsigned)e;
         }
-        // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow's copy every series axis of the rank)
-        const int most = IMAXD - w - (op == SERIES_POW ? c.rank - 1 : 0);
-        if (g.nd == most) throw std::runtime_error(f + ": the batch has more than " + std::to_string(most) + " non-contiguous axes");
-        g.ext[g.nd] = (unsigned)e;
-        g.xs[g.nd] = sx;
-        g.ys[g.nd] = sy;
-        g.ss[g.nd] = ss;
-        g.rs[g.nd] = sr;
-        ++g.nd;
+        g.xs[p] = sx, g.ys[p] = sy, g.ss[p] = ss, g.rs[p] = sr;
     }
     out.pl.w = w;
     out.pl.x = ax.plane;
-    out.pl.y = binary || xscal ? ay.plane : 0;
-    out.pl.s = seeds ? ay.plane : (cscal ? ac.plane : 0);
+    out.pl.y = as_y ? as_y->plane : 0;
+    out.pl.s = as_s ? as_s->plane : 0;
     out.pl.r = ar.plane;
     SeriesItem& it = out.it;
     for (int i = 0; i < 3; ++i) {

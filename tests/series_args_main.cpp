@@ -3,6 +3,7 @@
 // call: "E <message>" for a refusal, "EMPTY" for an empty batch, else the collapsed batch and the plane strides.
 //   op w rank2 e var k  nbatch|null b...  <x> <y> <r>  : fn
 //   a view is  off|null  nbs|null s...  rst len0 len1      (off: doubles into one buffer that is never read)
+// With the argument "ops" it reads nothing and prints the table of the operations, one row of gft::SERIES_OPS per line (names "|"-separated).
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -43,7 +44,13 @@ static void list(const char* name, const T* a, int n) {
     std::printf("]");
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "ops") {  // the rows of gft::SERIES_OPS: index family ranks long x y cs
+        const char* const family[] = {"arith", "pow", "observe", "chain", "linear"};
+        for (const gft::SeriesOpRow& r : gft::SERIES_OPS)
+            std::printf("%d %s %d %s %s|%s|%s\n", (int)r.op, family[r.family], r.ranks, r.xlong ? "x" : "result", r.x, r.y, r.cs);
+        return 0;
+    }
     std::string line;
     while (std::getline(std::cin, line)) {
         if (line.empty()) continue;

@@ -57,6 +57,22 @@ def test_accepted_calls_collapse_as_recorded(program):
     assert sum(line.startswith("OK ") for line in lines) >= 5
 
 
+def test_the_two_operation_tables_agree(program):
+    """gft::SERIES_OPS (the program's "ops" mode) and _series_call.OPS, row by row in the enum's order: as many operations, the same
+    long side, the same name of the first operand, the same operations at rank 3"""
+    from genfer_amd import _series_call
+
+    rows = [line.split(" ", 4) for line in subprocess.check_output([program, "ops"], text=True).splitlines()]
+    ops = list(_series_call.OPS.values())
+    assert len(rows) == len(ops) and [int(r[0]) for r in rows] == list(range(len(ops)))
+    assert [o.suffix for o in ops][:len(table.OPS)] == table.OPS  # (the generator states an op by its position in the enum)
+    for (_, _family, ranks, long, names), o in zip(rows, ops):
+        assert long == o.long, o.suffix
+        assert names.split("|")[0] == o.names[0], o.suffix
+        assert (int(ranks) == 3) == (o.suffix in _series_call.RANK3), o.suffix
+        assert int(ranks) in (2, 3), o.suffix
+
+
 @pytest.mark.gpu
 def test_c_layer_messages_on_the_gpu():
     checked = []
