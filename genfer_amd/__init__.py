@@ -22,6 +22,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
 from . import series  # noqa: F401  (batched series on device tensors; loads the library on first use)
 from . import interval_series  # noqa: F401  (the same over Interval<F64>: [2, B..., n] tensors)
+from . import bigfloat_series  # noqa: F401  (series' six arithmetic ops over BigFloat: [2, B..., n] = (factor, exponent) tensors)
 from . import series2  # noqa: F401  (batched bivariate series: [B..., n0, n1] tensors)
 from . import series3  # noqa: F401  (batched trivariate series: [B..., n0, n1, n2] tensors; mul / div / exp / log / compose / pow)
 from . import interval_series2  # noqa: F401  (the same over Interval<F64>: [2, B..., n0, n1] tensors)

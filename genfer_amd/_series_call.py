@@ -4,11 +4,12 @@ autograd Functions of ``series`` and ``series2_grad``) describe a call by data a
 
 ``OPS`` is the table of the operations: one row says what travels between the first operand and the result, which side is the long
 one, the operands' names in messages and whether ``var`` travels at ranks 2 and 3.  The same rows build the ctypes declarations of every
-``gft[i]_series[2]_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart; the C layer's
+``gft[i]_series[2]_*`` and ``gftb_series_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart; the C layer's
 counterpart is ``gft::SERIES_OPS`` (gft_series_args.hpp), and tests/test_series_refusals.py holds the two tables together.  A ``Call``
 says the rest: the rank (1: the last axis is the series, 2 / 3: the last two / three axes are the coefficient array), ``planes`` (1: interval
 tensors ``[2, B..., item]``, the plane axis travelling as the first entry of every batch-stride array), the limit of the long side
-and the module's name for messages.  ``run`` works on ``t.shape[-rank:]`` and ``t.stride()[-rank:-1]``: rank 2 contributes its row
+and the module's name for messages, and ``elem``, what the planes hold (``ELEMS``: the symbol prefix and the words of the messages; ``"bigfloat"``
+is ``bigfloat_series``, rank 1's six arithmetic ops).  ``run`` works on ``t.shape[-rank:]`` and ``t.stride()[-rank:-1]``: rank 2 contributes its row
 stride and its second length because those tuples are one entry longer, rank 3 its slab stride and third length likewise.
 
 Everything that needs no device is judged first, in one order for every module: type, dtype, planes, axes (per tensor), the orders,
@@ -28,7 +29,20 @@ from .taylor import TaylorError
 # others -- the result, or x for the transposed and the observation ops.  names: the operands (and, transposed, the result's
 # order) in messages.  var: the variable travels at ranks 2 and 3, behind the operands.  label: the function's name in messages.
 Op = namedtuple("Op", "suffix kind long names var label")
-Call = namedtuple("Call", "module rank planes limit raw")  # raw: the module has no autograd and refuses an operand that requires grad
+# raw: the module has no autograd and refuses an operand that requires grad.  elem: what the planes hold, a key of ELEMS (None: by the
+# planes alone -- float64 or Interval<F64>)
+Call = namedtuple("Call", "module rank planes limit raw elem", defaults=(None,))
+# per element kind: the symbol prefix, what a tensor is called and what its two planes are, and whether a plane stride of 0 is a value
+# (a point interval) or a mistake (a factor plane is not its own exponent plane)
+Elem = namedtuple("Elem", "prefix noun planes point")
+ELEMS = {"interval": Elem("gfti_", "an interval tensor", "(lo, hi)", True),
+         "bigfloat": Elem("gftb_", "a BigFloat tensor", "(factor, exponent)", False)}
+BIGFLOAT_OPS = ("mul", "div", "exp", "log", "compose", "pow")  # gftb_series_*: rank 1 only
+
+
+def _elem(call):
+    """the Elem of a call with planes (None: one plane, float64)"""
+    return ELEMS[call.elem or "interval"] if call.planes else None
 
 
 def _op(suffix, kind, long="result", names=("x", "y"), var=False, label=None):
@@ -122,6 +136,11 @@ def _lib():
                         f.restype = C.c_int
                         f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,) * int(op.var),
                                                      (C.c_size_t,) * (2 if op.kind == "chain" else 1), (_SZP, C.c_size_t, C.c_void_p)))
+        for suffix in BIGFLOAT_OPS:  # the BigFloat family: gfti_series_*'s argument lists, from the same rows
+            f = getattr(L, ELEMS["bigfloat"].prefix + "series_" + suffix)
+            f.restype = C.c_int
+            f.argtypes = list(_arguments(OPS[suffix], 1, lambda which, lens: _view_types(1, lens), (C.c_uint32,), (), (C.c_size_t,),
+                                         (_SZP, C.c_size_t, C.c_void_p)))
         for pre in ("gft_", "gfti_"):
             for suffix in RANK3:
                 f = getattr(L, pre + "series3_" + suffix)
@@ -138,15 +157,19 @@ def _placed(t, what):
         raise TaylorError(f"{what}: the tensor is on {t.device}; it must be in device memory of the library's GPU")
 
 
-def _check(torch, t, what, planes=0):
-    """type, dtype and, for an interval tensor, the leading axis of the two planes"""
+def _check(torch, t, what, planes=0, elem=None):
+    """type, dtype and, for a tensor of two planes (``elem``: its Elem), the leading axis of the planes and its stride"""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what}: expected a torch.Tensor, got {type(t).__name__}")
     if t.dtype != torch.float64:
         raise TaylorError(f"{what}: the tensor is {t.dtype}; only torch.float64 is accepted (no implicit conversion)")
     if planes and (t.dim() < 1 or t.shape[0] != 2):
         lead = "no axes" if t.dim() < 1 else f"a first axis of {t.shape[0]}"
-        raise TaylorError(f"{what}: the tensor has {lead}; an interval tensor is stacked [2, ...] = (lo, hi) along its first axis")
+        elem = elem or ELEMS["interval"]
+        raise TaylorError(f"{what}: the tensor has {lead}; {elem.noun} is stacked [2, ...] = {elem.planes} along its first axis")
+    if planes and elem is not None and not elem.point and t.stride(0) == 0:
+        raise TaylorError(f"{what}: the tensor has plane stride 0 (an expanded first axis); the two planes of {elem.noun} are {elem.planes}, "
+                          "and a factor plane cannot be its own exponent plane")
 
 
 def _axes(rank, t, what, planes=0):
@@ -197,7 +220,7 @@ def _launch(what, op, call, named, out, batch, rshape, scalars):
     device, ``out``, the interval operands lifted to the batch's axes, the library's device, the expansion, the call, its error."""
     import torch
 
-    _module, rank, planes, _limit, _raw = call
+    _module, rank, planes, _limit, _raw, _kind = call
     given = [(t, name) for _, name, t, _ in named if t is not None] + ([(out, "out")] if out is not None else [])
     for t, name in given:
         _placed(t, f"{what}: {name}")
@@ -223,7 +246,7 @@ def _launch(what, op, call, named, out, batch, rshape, scalars):
     parts["out"] = out
     ns = nb + planes  # entries of a batch-stride array
     tail = ((C.c_size_t * max(nb, 1))(*batch), nb, C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    fn = getattr(L, ("gfti_" if planes else "gft_") + ("series_", "series2_", "series3_")[rank - 1] + op.suffix)
+    fn = getattr(L, (_elem(call).prefix if planes else "gft_") + ("series_", "series2_", "series3_")[rank - 1] + op.suffix)
     if fn(*_arguments(op, rank, lambda which, lens: _view(rank, parts[which], ns, lens), *scalars, tail)) != 0:
         raise TaylorError((L.gft_last_error() or b"unknown error").decode())
     return out
@@ -234,8 +257,9 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
     op's ``k``; ``var``: the variable at ranks 2 and 3 (already judged by series2._var / series3._var where it is compose's)."""
     import torch
 
-    op, (module, rank, planes, limit, raw) = OPS[name], call
+    op, (module, rank, planes, limit, raw, _kind) = OPS[name], call
     what = f"{module}.{op.label}"
+    elem = _elem(call)
     order, short, over_text, out_text = _rank_rules(rank)
     observe, seeded = op.kind in ("k", None), op.kind == "seed"
     xname, sname = op.names[0], "seed" if seeded else op.names[1]
@@ -243,7 +267,7 @@ def run(call, name, x, second=None, n=None, out=None, scalar=None, var=None):
     for t, w, item in ((x, xname, True), (second, sname, not seeded), (out, "out", op.kind is not None)):
         if t is not None:
             w = f"{what}: {w}"
-            _check(torch, t, w, planes)
+            _check(torch, t, w, planes, elem)
             if item:
                 _axes(rank, t, w, planes)
     shape = tuple(x.shape[-rank:])
@@ -314,7 +338,7 @@ def run_chain(call, a, var, x, cs, degree_p1=None, out=None):
     (the continuous form), ``cs`` the constants ``[B..., nsteps]``.  The checks come in ``run``'s order."""
     import torch
 
-    op, (module, rank, planes, limit, _raw) = OPS["observe_chain"], call
+    op, (module, rank, planes, limit, _raw, _kind) = OPS["observe_chain"], call
     what = f"{module}.{op.label}"
     over_text = _rank_rules(rank)[2]
     for t, w in ((a, "a"), (x, "x"), (cs, "cs"), (out, "out")):
@@ -374,7 +398,7 @@ def run_linear(call, name, a, var, wvar, c, m, n=None, out=None):
     ``run``'s order."""
     import torch
 
-    op, (module, rank, planes, limit, _raw) = OPS[name], call
+    op, (module, rank, planes, limit, _raw, _kind) = OPS[name], call
     what = f"{module}.{op.label}"
     comp = name == "compose_linear"
     aname = op.names[0]

@@ -11,6 +11,8 @@
 // own scalars x and constants cs, one launch for all the steps; the kernels: gft_series_observe_chain.hip)
 // and the affine substitutions gft_series_mul_linear / compose_linear, gft_series2_mul_linear / compose_linear with their gfti_ twins
 // (every item with its own scalars c and m, one launch; the kernels: gft_series_linear.hip)
+// and the BigFloat family gftb_series_mul / div / exp / log / compose / pow (rank 1 only; w == 2 with the element kind
+// gft::SERIES_ELEM_BIGFLOAT: every stride array starts with the factor -> exponent plane stride)
 // Every entry point fills one gft::SeriesCall with its rank (gft_series_args.hpp, which judges it without the device and states the
 // item of any rank as one gft::SeriesItem) and hands it to series_call, which dispatches on the family of the op's row in
 // gft::SERIES_OPS and, for the arithmetic family, on the rank; pow is one driver.
@@ -101,7 +103,7 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         return 0;
     }
     const unsigned nx = it.nx[2], ny = it.ny[2], n = it.n[2];
-    const int form = gft::series_plan(op, g.items, row.xlong ? nx : n, R.series_force, w);  // (the planner sizes the long rows)
+    const int form = gft::series_plan(op, g.items, row.xlong ? nx : n, R.series_force, w, c.elem);  // (the planner sizes the long rows)
     const size_t wsn = gft::series_workspace(op, form, g.items, nx, n, w);
     Rc<Buf> ws;
     if (wsn) ws = alloc_doubles(wsn);  // (returned to the pool on exit: later launches follow these on the one stream)
@@ -124,24 +126,27 @@ static gft::SeriesView view(const double* p, const int64_t* bs, size_t len2, int
 
 }  // namespace
 
-// An entry point: the descriptor `c` with the call's common fields, FILL names the rest (the operands, e, var, k).
-#define GFT_SERIES_ENTRY(OP, FN, W, RANK, FILL)                                    \
+// An entry point: the descriptor `c` with the call's common fields, FILL names the rest (the operands, e, var, k).  ELEM: what the W
+// planes hold (gft::SeriesElem); the entry points without one take it from the width.
+#define GFT_SERIES_ENTRY_ELEM(OP, FN, W, ELEM, RANK, FILL)                         \
     return guard_int([&] {                                                         \
         gft::SeriesCall c;                                                         \
-        c.op = gft::OP, c.fn = FN, c.w = W, c.rank = RANK, c.batch = batch, c.nbatch = nbatch; \
+        c.op = gft::OP, c.fn = FN, c.w = W, c.elem = gft::ELEM, c.rank = RANK, c.batch = batch, c.nbatch = nbatch; \
         FILL;                                                                      \
         return series_call(c, stream);                                             \
     })
+#define GFT_SERIES_ENTRY(OP, FN, W, RANK, FILL) GFT_SERIES_ENTRY_ELEM(OP, FN, W, SERIES_ELEM_BY_WIDTH, RANK, FILL)
 // the argument lists the arithmetic ops share: two operands (at rank 2 with or without compose's var), an operand and its seeds
-#define GFT_SERIES_BINARY(SYM, OP, FN, W)                                                                                                     \
+#define GFT_SERIES_BINARY_ELEM(SYM, OP, FN, W, ELEM)                                                                                          \
     int SYM(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny, double* res, const int64_t* rbs,  \
             size_t n, const size_t* batch, size_t nbatch, void* stream) {                                                                     \
-        GFT_SERIES_ENTRY(OP, FN, W, 1, (c.x = view(x, xbs, nx), c.y = view(y, ybs, ny), c.r = view(res, rbs, n)));                            \
+        GFT_SERIES_ENTRY_ELEM(OP, FN, W, ELEM, 1, (c.x = view(x, xbs, nx), c.y = view(y, ybs, ny), c.r = view(res, rbs, n)));                 \
     }
-#define GFT_SERIES_SEEDED(SYM, OP, FN, W)                                                                                                     \
+#define GFT_SERIES_BINARY(SYM, OP, FN, W) GFT_SERIES_BINARY_ELEM(SYM, OP, FN, W, SERIES_ELEM_BY_WIDTH)
+#define GFT_SERIES_SEEDED_ELEM(SYM, OP, FN, W, ELEM)                                                                                          \
     int SYM(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs, double* res, const int64_t* rbs, size_t n, \
             const size_t* batch, size_t nbatch, void* stream) {                                                                               \
-        GFT_SERIES_ENTRY(OP, FN, W, 1, (c.x = view(x, xbs, nx), c.y = view(seed, sbs, 1), c.r = view(res, rbs, n)));                          \
+        GFT_SERIES_ENTRY_ELEM(OP, FN, W, ELEM, 1, (c.x = view(x, xbs, nx), c.y = view(seed, sbs, 1), c.r = view(res, rbs, n)));               \
     }
 #define GFT_SERIES2_BINARY(SYM, OP, FN, W)                                                                                                    \
     int SYM(const double* x, const int64_t* xbs, int64_t xrs, size_t nx0, size_t nx1, const double* y, const int64_t* ybs, int64_t yrs,       \
@@ -203,16 +208,19 @@ static gft::SeriesView view(const double* p, const int64_t* bs, size_t len2, int
     GFT_SERIES3_COMPOSE_POW(PFX, WHAT, W)
 // The arithmetic ops at both ranks.  Interval<F64> (gfti_, W == 2): the same calls on (lo, hi) planes; every batch-stride array has
 // nbatch + 1 entries, the plane stride first.  Rank 2: the last two axes are an item's coefficient array, with a row stride each.
-#define GFT_SERIES_ARITH(PFX, WHAT, W)                                                                                                        \
-    GFT_SERIES_BINARY(PFX##series_mul, SERIES_MUL, WHAT "series_mul", W)                                                                      \
-    GFT_SERIES_BINARY(PFX##series_div, SERIES_DIV, WHAT "series_div", W)                                                                      \
-    GFT_SERIES_SEEDED(PFX##series_exp, SERIES_EXP, WHAT "series_exp", W)                                                                      \
-    GFT_SERIES_SEEDED(PFX##series_log, SERIES_LOG, WHAT "series_log", W)                                                                      \
-    GFT_SERIES_BINARY(PFX##series_compose, SERIES_COMPOSE, WHAT "series_compose", W)                                                          \
+// (rank 1 is its own macro: the BigFloat family has no other rank)
+#define GFT_SERIES1_ARITH(PFX, WHAT, W, ELEM)                                                                                                 \
+    GFT_SERIES_BINARY_ELEM(PFX##series_mul, SERIES_MUL, WHAT "series_mul", W, ELEM)                                                           \
+    GFT_SERIES_BINARY_ELEM(PFX##series_div, SERIES_DIV, WHAT "series_div", W, ELEM)                                                           \
+    GFT_SERIES_SEEDED_ELEM(PFX##series_exp, SERIES_EXP, WHAT "series_exp", W, ELEM)                                                           \
+    GFT_SERIES_SEEDED_ELEM(PFX##series_log, SERIES_LOG, WHAT "series_log", W, ELEM)                                                           \
+    GFT_SERIES_BINARY_ELEM(PFX##series_compose, SERIES_COMPOSE, WHAT "series_compose", W, ELEM)                                               \
     int PFX##series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,                \
                         const size_t* batch, size_t nbatch, void* stream) {                                                                   \
-        GFT_SERIES_ENTRY(SERIES_POW, WHAT "series_pow", W, 1, (c.x = view(x, xbs, nx), c.e = e, c.r = view(res, rbs, n)));                    \
-    }                                                                                                                                         \
+        GFT_SERIES_ENTRY_ELEM(SERIES_POW, WHAT "series_pow", W, ELEM, 1, (c.x = view(x, xbs, nx), c.e = e, c.r = view(res, rbs, n)));         \
+    }
+#define GFT_SERIES_ARITH(PFX, WHAT, W)                                                                                                        \
+    GFT_SERIES1_ARITH(PFX, WHAT, W, SERIES_ELEM_BY_WIDTH)                                                                                     \
     GFT_SERIES2_BINARY(PFX##series2_mul, SERIES_MUL, WHAT "series2_mul", W)                                                                   \
     GFT_SERIES2_BINARY(PFX##series2_div, SERIES_DIV, WHAT "series2_div", W)                                                                   \
     GFT_SERIES2_SEEDED(PFX##series2_exp, SERIES_EXP, WHAT "series2_exp", W)                                                                   \
@@ -299,6 +307,8 @@ GFT_SERIES_OBSERVE_CHAIN(gft_, "", 1)
 GFT_SERIES_OBSERVE_CHAIN(gfti_, "interval ", 2)
 GFT_SERIES_ARITH(gft_, "", 1)
 GFT_SERIES_ARITH(gfti_, "interval ", 2)
+// BigFloat (gftb_, W == 2 planes: factor, exponent): rank 1's six arithmetic operations and nothing else
+GFT_SERIES1_ARITH(gftb_, "bigfloat ", 2, SERIES_ELEM_BIGFLOAT)
 GFT_SERIES_OBSERVE(gft_, "", 1)
 GFT_SERIES_OBSERVE(gfti_, "interval ", 2)
 // the transposed operations (f64 only): g / gh is the long side, the result the short one
@@ -310,9 +320,12 @@ GFT_SERIES3_ARITH(gft_, "", 1)
 GFT_SERIES3_ARITH(gfti_, "interval ", 2)
 int gft_series_last_form(void) { return R.series_last; }
 }
+#undef GFT_SERIES_ENTRY_ELEM
 #undef GFT_SERIES_ENTRY
+#undef GFT_SERIES_BINARY_ELEM
 #undef GFT_SERIES_BINARY
-#undef GFT_SERIES_SEEDED
+#undef GFT_SERIES_SEEDED_ELEM
+#undef GFT_SERIES1_ARITH
 #undef GFT_SERIES2_BINARY
 #undef GFT_SERIES2_BINARY_VAR
 #undef GFT_SERIES2_SEEDED

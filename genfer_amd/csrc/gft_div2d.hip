@@ -99,6 +99,8 @@ template <>
 __device__ inline double bcast_lane<EF64>(double v, unsigned j) { return bcast_f64(v, j); }
 template <>
 __device__ inline Iv bcast_lane<EIv>(Iv v, unsigned j) { return Iv{bcast_f64(v.lo, j), bcast_f64(v.hi, j)}; }
+template <>
+__device__ inline Bf bcast_lane<EBig>(Bf v, unsigned j) { return Bf{bcast_f64(v.f, j), bcast_f64(v.e, j)}; }
 
 template <class E>
 struct SlabDiv {  // generic element type: the functor's own division
@@ -588,7 +590,10 @@ __device__ __forceinline__ void div_1d_wave_body(const double* __restrict__ xs, 
     // starts at +0 and only adds) — so the pass is exact unless a non-finite quotient coefficient appears, which is
     // noted and settled by redoing the row with the bounds as selects (the reference's own case analysis).
     // The divisor values of step j + 1 are requested before the quotient of step j is formed: no LDS wait in the chain.
-    bool bad = false;
+    // Where zero is not neutral (BigFloat: cur + q * 0 rescales cur and drops it at exponent <= -1024) there is no fast pass: the
+    // row runs with the bounds as selects from the start.
+    bool bad = !E::ZERO_NEUTRAL;
+    if constexpr (E::ZERO_NEUTRAL) {
 #pragma unroll
     for (int oe = 0; oe < DIV1D_WSEG; ++oe) {
         const unsigned j0 = 64u * oe, j1 = n < j0 + 64 ? n : j0 + 64;
@@ -612,6 +617,7 @@ __device__ __forceinline__ void div_1d_wave_body(const double* __restrict__ xs, 
                 yv[e] = yn[e];
             }
         }
+    }
     }
     if (bad) {  // (wave-uniform: every lane saw the same quotient coefficients)
 #pragma unroll
@@ -712,7 +718,8 @@ static void div_rows(hipStream_t st, const double* x, unsigned nx, const double*
 }
 void series_div_rows(hipStream_t st, const double* x, unsigned nx, const double* y, unsigned ny, double* res, unsigned n,
                      const SeriesBatch& g, const SeriesPlanes& pl) {
-    if (pl.w == 2) div_rows<EIv>(st, x, nx, y, ny, res, n, g, pl);
+    if (pl.elem == SERIES_ELEM_BIGFLOAT) div_rows<EBig>(st, x, nx, y, ny, res, n, g, pl);
+    else if (pl.w == 2) div_rows<EIv>(st, x, nx, y, ny, res, n, g, pl);
     else div_rows<EF64>(st, x, nx, y, ny, res, n, g, pl);
 }
 template bool K<EF64>::div_1d(hipStream_t, const double*, size_t, unsigned, const double*, size_t, unsigned, double*, size_t, unsigned, int);

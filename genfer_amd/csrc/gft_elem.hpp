@@ -64,6 +64,9 @@ struct EF64 {
     GFT_HD static V mulw(V a, V b) { return a * b; }   // "wave-checked" variants: plain ops for f64
     GFT_HD static V addw(V a, V b) { return a + b; }
     GFT_HD static V add0(V b) { return 0.0 + b; }      // (0 + b): turns -0 into +0, so it is not skipped
+    // acc + x * zero() == acc for every finite x, and zero() + s == s for every sum s formed from zero(): a kernel may run a
+    // term its bounds exclude as a product with a staged zero, and need not add a finished sum onto a zeroed result
+    static constexpr bool ZERO_NEUTRAL = true;
     // positive-regime interface of the interval functor (no such regime for plain f64)
     static constexpr bool HAS_POS = false;
     GFT_HD static bool pos_ok(V) { return false; }
@@ -202,6 +205,7 @@ struct EIv {
         return add(a, b);
     }
     GFT_HD static V add0(V b) { return b; }  // [0,0] + b returns b unchanged (interval.rs:126-139)
+    static constexpr bool ZERO_NEUTRAL = true;  // (as EF64's: [0,0] is add's short-circuit and a finite operand times [0,0] is [0,0])
     // ---- positive regime ------------------------------------------------------------------------------------------
     // Probability-like tensors are strictly positive.  For operands with 0 < lo <= hi < inf that are not the point
     // interval [1,1] the reference's product (interval.rs:164-190) takes no short-circuit, its min / max of the four
@@ -355,7 +359,31 @@ struct EBig {
     GFT_HD static V mulw(V a, V b) { return mul(a, b); }
     GFT_HD static V addw(V a, V b) { return add(a, b); }
     GFT_HD static V add0(V b) { return add(zero(), b); }  // the real 0 + b: it drops b when b.exponent <= -1024
+    // Not neutral: {0, 0} + b rescales b by powi(2, b.exponent) -- it loses b's last bit at exponent -1023 and all of b below --
+    // so a kernel performs every addition of zero the reference performs and no other
+    static constexpr bool ZERO_NEUTRAL = false;
     static constexpr bool HAS_POS = false;
+    // :158-163.  x = to_f64(a) * LOG2_E, k = x `as i64` (saturating, NaN -> 0; kept as a double: exact below 2^63, and where it
+    // saturates the factor is 0 or non-finite), then normalize(2^(x - k), k).  The host pass takes libm's pow as the reference does, the
+    // device pass the device library's exp2: a few ulps apart, as EF64::exp -- exact bits come from the caller's seeds.
+    GFT_HD static V exp(V a) {
+        const double x = a.f * bf_pow2(a.e) * 1.4426950408889634;
+        const double lim = 9223372036854775808.0;  // 2^63
+        const double k = x != x ? 0.0 : __builtin_trunc(__builtin_fmax(__builtin_fmin(x, lim), -lim));
+#if defined(__HIP_DEVICE_COMPILE__)
+        return normalize(::exp2(x - k), k);
+#else
+        return normalize(std::pow(2.0, x - k), k);
+#endif
+    }
+    // :175-180
+    GFT_HD static V log(V a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return normalize((::log2(a.f) + a.e) * 0.6931471805599453, 0.0);
+#else
+        return normalize((std::log2(a.f) + a.e) * 0.6931471805599453, 0.0);
+#endif
+    }
 };
 
 }  // namespace gft

@@ -26,12 +26,15 @@
 // Horner loop) is compose form B run backwards; it has no form A.
 //
 // Every function below is a template over the element functor: EF64 serves gft_series_*, EIv (Interval<F64>, the planes lo and hi
-// a plane stride apart on every operand) gfti_series_*.  The entry points of gft_series.hpp pick the instantiation by the width.
+// a plane stride apart on every operand) gfti_series_*, EBig (BigFloat, the planes factor and exponent) gftb_series_*.  The entry
+// points of gft_series.hpp pick the instantiation by the width and the element kind (by_elem).  EBig has the six arithmetic
+// operations: the transposed kernels (corr, compose_adj) are not instantiated on it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <stdexcept>
+#include <type_traits>
 
 #include "gft_elem.hpp"
 #include "gft_launch.hpp"
@@ -63,7 +66,11 @@ constexpr unsigned SA_BUDGET_KB_PLAIN = 64;
 // The interval kernels keep it: the two forms were not timed against each other for intervals.
 constexpr unsigned SA_MIN_ITEMS = 256;
 
-// what the runtime granted, asked once per element type (the EIv kernels are functions of their own)
+// the transposed operations exist on F64 (and are instantiated on Interval<F64>); BigFloat has none
+template <class E>
+constexpr bool HAS_TRANSPOSED = !std::is_same<E, EBig>::value;
+
+// what the runtime granted, asked once per element type (the EIv and the EBig kernels are functions of their own)
 template <class E>
 struct Granted {
     static unsigned budget_kb;  // 0: not asked yet
@@ -92,9 +99,10 @@ template <class E>
 unsigned budget_kb() {
     unsigned& kb = Granted<E>::budget_kb;
     if (kb) return kb;
-    const void* ks[] = {(const void*)k_series_mul_a<E>, (const void*)k_series_div_a<E>, (const void*)k_series_explog_a<E, false>,
-                        (const void*)k_series_explog_a<E, true>, (const void*)k_series_compose_a<E>, (const void*)k_series_corr_a<E>};
-    kb = (unsigned)(grant_dynamic_lds(ks, sizeof(ks) / sizeof(*ks), SA_BUDGET_KB * 1024, SA_BUDGET_KB_PLAIN * 1024) / 1024);
+    const void* ks[6] = {(const void*)k_series_mul_a<E>, (const void*)k_series_div_a<E>, (const void*)k_series_explog_a<E, false>,
+                         (const void*)k_series_explog_a<E, true>, (const void*)k_series_compose_a<E>, nullptr};
+    if constexpr (HAS_TRANSPOSED<E>) ks[5] = (const void*)k_series_corr_a<E>;
+    kb = (unsigned)(grant_dynamic_lds(ks, HAS_TRANSPOSED<E> ? 6 : 5, SA_BUDGET_KB * 1024, SA_BUDGET_KB_PLAIN * 1024) / 1024);
     return kb;
 }
 
@@ -198,7 +206,10 @@ void launch(hipStream_t st, int op, int form, const double* x, unsigned nx, cons
             case SERIES_MUL: GFT_LAUNCH(k_series_mul_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
             case SERIES_DIV: GFT_LAUNCH(k_series_div_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
             case SERIES_COMPOSE: GFT_LAUNCH(k_series_compose_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
-            case SERIES_CORR: GFT_LAUNCH(k_series_corr_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g); break;
+            case SERIES_CORR:
+                if constexpr (HAS_TRANSPOSED<E>) GFT_LAUNCH(k_series_corr_a<E>, grid, block, lds, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, pitch, lg, g);
+                else throw std::runtime_error("series: no transposed product on this element");
+                break;
             case SERIES_COMPOSE_ADJ: throw std::runtime_error("series: compose_adj has no form A");
             case SERIES_EXP: GFT_LAUNCH((k_series_explog_a<E, false>), grid, block, lds, st, x, pl.x, nx, y, pl.s, res, pl.r, n, pitch, lg, g); break;
             default: GFT_LAUNCH((k_series_explog_a<E, true>), grid, block, lds, st, x, pl.x, nx, y, pl.s, res, pl.r, n, pitch, lg, g); break;
@@ -216,24 +227,28 @@ void launch(hipStream_t st, int op, int form, const double* x, unsigned nx, cons
                    y, pl.y, ny, res, pl.r, n, g);
         return;
     }
-    if (op == SERIES_CORR) {  // mul's geometry over the m = n outputs
-        const unsigned half = (n + 1) / 2;
-        const bool spread = !g.inplace && g.items < SA_MIN_ITEMS;
-        const unsigned threads = spread ? 64u : std::min(256u, (half + 63) / 64 * 64);
-        const unsigned shares = g.inplace ? 1u : (half + threads - 1) / threads;
-        GFT_LAUNCH(k_series_corr_b<E>, dim3(g.items, shares), dim3(threads), (size_t)E::W * ((size_t)nx + ny) * sizeof(double), st, x, pl.x, nx,
-                   y, pl.y, ny, res, pl.r, n, g);
-        return;
-    }
-    if (op == SERIES_COMPOSE_ADJ) {  // x = gh (nx = the order n), y = g, n = nf outputs
-        const unsigned full = (n - 1) * (ny - 1) + 1, l0 = std::min(full, nx);
-        const unsigned threads = std::min(256u, ((l0 + 1) / 2 + 63) / 64 * 64);
-        const size_t rows = (size_t)2 * E::W * l0 * sizeof(double), all = rows + (size_t)E::W * ny * sizeof(double);
-        if (all <= 64 * 1024 || compose_adj_big<E>())
-            GFT_LAUNCH((k_series_compose_adj_b<E, true>), dim3(g.items), dim3(threads), all, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
-        else
-            GFT_LAUNCH((k_series_compose_adj_b<E, false>), dim3(g.items), dim3(threads), rows, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
-        return;
+    if constexpr (!HAS_TRANSPOSED<E>) {
+        if (op == SERIES_CORR || op == SERIES_COMPOSE_ADJ) throw std::runtime_error("series: no transposed operation on this element");
+    } else {
+        if (op == SERIES_CORR) {  // mul's geometry over the m = n outputs
+            const unsigned half = (n + 1) / 2;
+            const bool spread = !g.inplace && g.items < SA_MIN_ITEMS;
+            const unsigned threads = spread ? 64u : std::min(256u, (half + 63) / 64 * 64);
+            const unsigned shares = g.inplace ? 1u : (half + threads - 1) / threads;
+            GFT_LAUNCH(k_series_corr_b<E>, dim3(g.items, shares), dim3(threads), (size_t)E::W * ((size_t)nx + ny) * sizeof(double), st, x, pl.x, nx,
+                       y, pl.y, ny, res, pl.r, n, g);
+            return;
+        }
+        if (op == SERIES_COMPOSE_ADJ) {  // x = gh (nx = the order n), y = g, n = nf outputs
+            const unsigned full = (n - 1) * (ny - 1) + 1, l0 = std::min(full, nx);
+            const unsigned threads = std::min(256u, ((l0 + 1) / 2 + 63) / 64 * 64);
+            const size_t rows = (size_t)2 * E::W * l0 * sizeof(double), all = rows + (size_t)E::W * ny * sizeof(double);
+            if (all <= 64 * 1024 || compose_adj_big<E>())
+                GFT_LAUNCH((k_series_compose_adj_b<E, true>), dim3(g.items), dim3(threads), all, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
+            else
+                GFT_LAUNCH((k_series_compose_adj_b<E, false>), dim3(g.items), dim3(threads), rows, st, x, pl.x, nx, y, pl.y, ny, res, pl.r, n, g);
+            return;
+        }
     }
     if (op == SERIES_COMPOSE) {
         const unsigned threads = std::min(256u, ((n + 1) / 2 + 63) / 64 * 64);
@@ -277,6 +292,7 @@ template <class E>
 int pow_steps(hipStream_t st, int rank, const double* x, unsigned e, double* res, const SeriesItem& it, const SeriesBatch& g, double* ws, int force,
               const SeriesPlanes& pl) {
     int form = rank == 1 ? SERIES_NONE : SERIES_FORM_B;
+    if (std::is_same<E, EBig>::value && rank != 1) throw std::runtime_error("series: BigFloat pow exists at rank 1 only");  // (series_shapes refuses it)
     if (g.items == 0) return form;
     const unsigned* n = it.n;
     const unsigned N = n[0] * n[1] * n[2];
@@ -324,7 +340,7 @@ int pow_steps(hipStream_t st, int rank, const double* x, unsigned e, double* res
         double* out = slot[s.out];
         const SeriesBatch w = ws_batch(g, s.a == POW_UNIT ? 0 : (size_t)sa[0] * sa[1] * sa[2], (size_t)sb[0] * sb[1] * sb[2], s.last ? 0 : lc[0] * s.L[0]);
         SeriesPlanes wpl;
-        wpl.w = E::W;
+        wpl.w = E::W, wpl.elem = pl.elem;
         if (E::W == 2) wpl.x = wpl.y = wp, wpl.r = s.last ? pl.r : wp;  // (one plane: the strides stay 0)
         if (rank == 1) {
             form = plan<E>(SERIES_MUL, g.items, lo[2], force);
@@ -340,10 +356,18 @@ int pow_steps(hipStream_t st, int rank, const double* x, unsigned e, double* res
     return form;
 }
 
+// the instantiation of a call: BigFloat by the element kind, else by the width
+template <class F>
+auto by_elem(int w, int elem, F&& f) {
+    if (elem == SERIES_ELEM_BIGFLOAT) return f(EBig());
+    if (w == 2) return f(EIv());
+    return f(EF64());
+}
+
 }  // namespace
 
-int series_plan(int op, unsigned items, unsigned n, int force, int w) {
-    return w == 2 ? plan<EIv>(op, items, n, force) : plan<EF64>(op, items, n, force);
+int series_plan(int op, unsigned items, unsigned n, int force, int w, int elem) {
+    return by_elem(w, elem, [&](auto e) { return plan<decltype(e)>(op, items, n, force); });
 }
 
 size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n, int w) {
@@ -353,15 +377,14 @@ size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned 
 
 void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
                    unsigned n, const SeriesBatch& g, double* ws, const SeriesPlanes& pl) {
-    if (pl.w == 2) launch<EIv>(st, op, form, x, nx, y, ny, res, n, g, ws, pl);
-    else launch<EF64>(st, op, form, x, nx, y, ny, res, n, g, ws, pl);
+    by_elem(pl.w, pl.elem, [&](auto e) { launch<decltype(e)>(st, op, form, x, nx, y, ny, res, n, g, ws, pl); });
 }
 
 size_t series_pow_workspace(unsigned items, const unsigned* n, int w) { return (size_t)w * (3 * (size_t)items * n[0] * n[1] * n[2] + 1); }
 
 int series_pow(hipStream_t st, int rank, const double* x, unsigned e, double* res, const SeriesItem& it, const SeriesBatch& g, double* ws,
                int force, const SeriesPlanes& pl) {
-    return pl.w == 2 ? pow_steps<EIv>(st, rank, x, e, res, it, g, ws, force, pl) : pow_steps<EF64>(st, rank, x, e, res, it, g, ws, force, pl);
+    return by_elem(pl.w, pl.elem, [&](auto el) { return pow_steps<decltype(el)>(st, rank, x, e, res, it, g, ws, force, pl); });
 }
 
 }  // namespace gft

@@ -28,12 +28,14 @@ enum SeriesForm { SERIES_NONE = 0, SERIES_FORM_A = 1, SERIES_FORM_B = 2 };
 
 // The form a call takes.  force: 0 = by the thresholds, SERIES_FORM_A = form A whenever the rows fit its LDS budget,
 // SERIES_FORM_B = never form A (gft_set_option("series_form")).
-int series_plan(int op, unsigned items, unsigned n, int force, int w = 1);
+// `w`, `elem`: the planes per tensor and what they hold (SeriesElem: Interval<F64> and BigFloat are both w == 2).
+int series_plan(int op, unsigned items, unsigned n, int force, int w = 1, int elem = SERIES_ELEM_BY_WIDTH);
 // doubles of device workspace the call needs (form B of exp / log: the transposed operand and result, each of w planes), else 0.
 // Not for SERIES_POW (series_pow_workspace).
 size_t series_workspace(int op, int form, unsigned items, unsigned nx, unsigned n, int w = 1);
 // Launches the call on `st`.  `y`: the second operand of mul / div / compose (x is f, y is g); for exp / log the seeds or nullptr
 // (seeds formed on the device by the HIP device library's exp / log).  `ws`: series_workspace() doubles.  Not for SERIES_POW.
+// `pl`: the planes, their strides and the element kind (pl.elem == SERIES_ELEM_BIGFLOAT: rank 1's six arithmetic ops only).
 // corr and compose_adj: the result is the SHORT side, n <= nx, and series_plan takes the long side nx (the rows held in LDS).
 void series_launch(hipStream_t st, int op, int form, const double* x, unsigned nx, const double* y, unsigned ny, double* res,
                    unsigned n, const SeriesBatch& g, double* ws, const SeriesPlanes& pl = SeriesPlanes());

@@ -111,11 +111,18 @@ inline unsigned series_limit(int rank, int w) {
     return most[rank - 1][w == 2];
 }
 
+// What the planes of a tensor hold.  SERIES_ELEM_BY_WIDTH, the default: the width alone says it -- w = 1 is F64, w = 2 is
+// Interval<F64>, (lo, hi).  SERIES_ELEM_BIGFLOAT (w = 2): BigFloat (src/number/big_float.rs), the factor plane and the exponent plane
+// (integral doubles); gftb_series_*, rank 1, the six arithmetic operations.
+enum SeriesElem { SERIES_ELEM_BY_WIDTH = 0, SERIES_ELEM_BIGFLOAT = 1 };
+
 // The element of a call: w = 1 is F64 (one plane, the strides below unused), w = 2 is Interval<F64>, stored as the planes
-// (lo, hi) x / y / s / r elements apart (operands, seeds, result; 0 on an operand: a point interval read twice).
+// (lo, hi) x / y / s / r elements apart (operands, seeds, result; 0 on an operand: a point interval read twice), or with
+// elem == SERIES_ELEM_BIGFLOAT a BigFloat's (factor, exponent), where no plane stride is 0.
 struct SeriesPlanes {
     int w = 1;
     size_t x = 0, y = 0, s = 0, r = 0;
+    int elem = SERIES_ELEM_BY_WIDTH;
 };
 
 // The collapsed batch: item (i_0, ..., i_{nd-1}), row-major over ext, has its rows at x + sum i_a * xs[a] (elements), and
@@ -167,6 +174,7 @@ struct SeriesCall {
     int op = SERIES_MUL;
     const char* fn = "";  // the name in messages
     int w = 1;
+    int elem = SERIES_ELEM_BY_WIDTH;  // what the w planes hold
     int rank = 1;
     uint32_t e = 0;
     int var = 0;
@@ -278,6 +286,11 @@ static inline void series_shapes(const SeriesCall& c) {
     const std::string f(c.fn);
     const SeriesOpRow& row = SERIES_OPS[c.op];
     const int op = c.op, rank = c.rank;
+    if (c.elem == SERIES_ELEM_BIGFLOAT) {  // the BigFloat family: rank 1, the six arithmetic operations, two planes
+        if (rank != 1) throw std::runtime_error(f + ": BigFloat series exist at rank 1 only in this version (rank " + to_string(rank) + " was asked for)");
+        if (op > SERIES_POW) throw std::runtime_error(f + ": no such operation on BigFloat series in this version (mul / div / exp / log / compose / pow)");
+        if (c.w != 2) throw std::runtime_error(f + ": a BigFloat tensor has two planes (factor, exponent), not " + to_string(c.w));
+    }
     // (the text is pinned byte for byte by tests/series3_compose_args_main.cpp and tests/series_refusals.json; its "on f64" dates from
     // before gfti_series3_* and misleads an interval caller or one with another width -- to be retired with those pins)
     if (rank == 3 && ((c.w != 1 && c.w != 2) || row.ranks < 3))
@@ -389,6 +402,12 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     // y is read where the op has one and, where it is optional (the seeds, the chain's x), it is given; cs where the op has one
     const bool optional = row.yrole == SERIES_Y_SEEDS || row.family == SERIES_CHAIN;
     const bool has_y = row.yrole != SERIES_Y_NONE && (ay.p || !optional), has_cs = row.csrole != SERIES_CS_NONE;
+    if (c.elem == SERIES_ELEM_BIGFLOAT) {  // a point interval reads one plane twice; a factor plane cannot be its own exponent plane
+        const SeriesOperand* const read[2] = {&ax, has_y ? &ay : nullptr};  // (the result's is refused below, for intervals too)
+        for (const SeriesOperand* a : read)
+            if (a && a->plane == 0)
+                throw std::runtime_error(f + ": zero plane stride on " + a->what + " (the factor plane of a BigFloat tensor cannot be its own exponent plane)");
+    }
     // the result's elements are distinct addresses: no zero stride, and sorted by stride every axis steps over the ones below it
     {
         struct Ax {
@@ -461,6 +480,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
         g.xs[p] = sx, g.ys[p] = sy, g.ss[p] = ss, g.rs[p] = sr;
     }
     out.pl.w = w;
+    out.pl.elem = c.elem;
     out.pl.x = ax.plane;
     out.pl.y = as_y ? as_y->plane : 0;
     out.pl.s = as_s ? as_s->plane : 0;

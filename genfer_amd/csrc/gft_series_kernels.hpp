@@ -25,6 +25,17 @@ struct ColWs {  // item's column of a transposed workspace: [plane][n][items]
     __device__ void st(unsigned i, typename E::V v) const { E::st(p, plane, (size_t)i * items, v); }
 };
 
+// The reference's product does not store the sums of mul_1d: mul_rec adds them onto the zeroed result, z[k] = z[k] + out[k] with
+// z[k] == 0 (mt:984-1012).  Where zero is neutral (F64: a sum formed from +0 is never -0; Interval<F64>: [0,0] + b returns b) that
+// addition returns its operand and the kernels never performed it.  BigFloat's {0, 0} + s rescales s by powi(2, s.exponent), which
+// changes s at exponent -1023 and drops it below: there the addition is performed (EBig::add0).  The sums of div, exp and log are
+// stored as they are formed (mt:1162-1192, 1271-1283, 1319-1333): no such addition there.
+template <class E>
+__device__ inline typename E::V onto_zero(typename E::V sum) {
+    if constexpr (E::ZERO_NEUTRAL) return sum;
+    else return E::add0(sum);
+}
+
 // ---- the recurrences, one series per lane (the loops of k_exp_1d / k_log_1d / k_div_1d_serial / k_conv_* reference order) ----
 // z[k] = 0 + sum_{j = lo .. hi-1} x[j] * y[k-j], ascending j (mul_1d, mt:972-982).  k runs downwards and z[k] overwrites y[k]:
 // the outputs still to come read y[0 .. k-1] only.
@@ -36,7 +47,7 @@ __device__ inline void rec_mul(const AX x, const AY y, unsigned nx, unsigned ny,
         V sum = E::zero();
 #pragma unroll 4
         for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(x.ld(j), y.ld(k - j)));
-        y.st(k, sum);
+        y.st(k, onto_zero<E>(sum));
     }
 }
 // One Horner step of compose in place: r <- r * g truncated at L <= lr + ng - 1, r holding lr coefficients on entry (the same sums as
@@ -49,7 +60,7 @@ __device__ inline void rec_horner_step(const AR r, const AG g, unsigned lr, unsi
         V sum = E::zero();
 #pragma unroll 4
         for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(r.ld(j), g.ld(k - j)));
-        r.st(k, sum);
+        r.st(k, onto_zero<E>(sum));
     }
 }
 // The transposed product, c[i] = 0 + sum_k g[k] * y[k-i] with k DESCENDING from min(ng-1, i+ny-1) to i: the sums of mul_1d on the
@@ -269,7 +280,7 @@ __global__ __launch_bounds__(256) void k_series_mul_b(const double* x, size_t xp
             V sum = E::zero();
 #pragma unroll 4
             for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(E::ld(xl, nx, j), E::ld(yl, ny, k - j)));
-            E::st(res + o.r, rp, k, sum);
+            E::st(res + o.r, rp, k, onto_zero<E>(sum));
         }
     }
 }
@@ -313,6 +324,7 @@ __global__ __launch_bounds__(256) void k_series_compose_b(const double* f, size_
                 V sum = E::zero();
 #pragma unroll 4
                 for (unsigned j = lo; j < hi; ++j) sum = E::add(sum, E::mul(E::ld(r0, n, j), E::ld(gsrc, gplane, k - j)));
+                sum = onto_zero<E>(sum);
                 if (k == 0) sum = E::add(sum, fi);
                 E::st(r1, n, k, sum);
             }

@@ -671,6 +671,33 @@ int gfti_series_compose(const double* f, const int64_t* fbs, size_t nf, const do
                         double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
 int gfti_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
                     const size_t* batch, size_t nbatch, void* stream);
+/* Batched series over BigFloat (big_float.rs): gft_series_mul / div / exp / log / compose / pow on tensors [2, B..., n] =
+ * (factor, exponent).  These six are the whole BigFloat surface of the library: there is no handle family, no other rank and no
+ * observation op.  The argument lists are those of gfti_series_*: every stride array (xbs / ybs / sbs / rbs) has nbatch + 1
+ * entries, the FIRST the factor -> exponent plane stride in elements, the batch strides behind it; NULL = C-contiguous rows with
+ * the two planes back to back.  No plane stride may be 0 (a factor plane cannot be its own exponent plane): refused on every operand,
+ * on the seeds and on the result.  Everything else is judged as for gfti_series_*: the overlap test covers both planes, the result may
+ * be an operand only as the same view (plane stride included), n <= 2048.  Seeds are [2, B...]; NULL: formed on the device
+ * (exp2 / log2 of the device library: a few ulps from a host libm's, so exact bits need the caller's seeds).
+ * The element contract: a coefficient is factor * 2^exponent; the factor is in +-[1, 2), or 0 with exponent 0, or non-finite (its
+ * exponent is kept); the exponent is an integral double with |e| < 2^52; exponent differences of 2^31 or more are unsupported (the
+ * reference truncates them to 32 bits).  Inputs are not scanned: values outside the contract give unspecified values, never an
+ * out-of-bounds access.  Per item the results are the reference's general algorithms in BigFloat arithmetic, every factor and
+ * exponent with the oracle's bits -- including every addition of zero the reference performs: 0 + b drops b at exponent <= -1024,
+ * so mul adds each finished sum onto a zero (mul_rec onto its zeroed result), as do the products inside compose and pow.
+ * gft_series_last_form and the "series_form" option serve this family too. */
+int gftb_series_mul(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gftb_series_div(const double* x, const int64_t* xbs, size_t nx, const double* y, const int64_t* ybs, size_t ny,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gftb_series_exp(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gftb_series_log(const double* x, const int64_t* xbs, size_t nx, const double* seed, const int64_t* sbs,
+                    double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gftb_series_compose(const double* f, const int64_t* fbs, size_t nf, const double* g, const int64_t* gbs, size_t ng,
+                        double* res, const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gftb_series_pow(const double* x, const int64_t* xbs, size_t nx, uint32_t e, double* res, const int64_t* rbs, size_t n,
+                    const size_t* batch, size_t nbatch, void* stream);
 /* Batched bivariate series over Interval<F64>: gft_series2_* on tensors [2, B..., n0, n1] = (lo, hi).  The argument lists are those
  * of gft_series2_* (row strides `xrs` / `yrs` / `rrs` included, one per operand: both planes share it); the stride-array convention
  * is gfti_series_*'s: every batch-stride array (xbs / ybs / sbs / rbs) has nbatch + 1 entries, the lo -> hi plane stride FIRST, NULL =

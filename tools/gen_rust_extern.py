@@ -32,7 +32,7 @@ def declarations():
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = text[text.index('extern "C" {'):]
     out = []
-    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_ ]*?\**)\s*\b(gfti?_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_ ]*?\**)\s*\b(gft[ib]?_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):  # (gftb_: the BigFloat series)
         ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
         params = []
         if args and args != "void":
