@@ -2,7 +2,7 @@
 ``interval_series3`` (and the
 autograd Functions of ``series`` and ``series2_grad``) describe a call by data and hand it to ``run``.
 
-``OPS`` is the table of the operations: one row says what travels between the first operand and the result, which side is the long
+``OPS`` (and ``MORE_OPS``, the operations added behind it) is the table of the operations: one row says what travels between the first operand and the result, which side is the long
 one, the operands' names in messages and whether ``var`` travels at ranks 2 and 3.  The same rows build the ctypes declarations of every
 ``gft[i]_series[2]_*`` and ``gftb_series_*`` entry point and the argument tuple of a call (``_arguments``), so the two cannot drift apart; the C layer's
 counterpart is ``gft::SERIES_OPS`` (gft_series_args.hpp), and tests/test_series_refusals.py holds the two tables together.  A ``Call``
@@ -70,6 +70,16 @@ OPS = {o.suffix: o for o in (
     _op("mul_linear", "linear", names=("a", "c", "m"), var=1),
     _op("compose_linear", "linear", names=("f", "c", "m"), var=2),
 )}
+# The operations behind the table (gft::SERIES_MORE_OPS): OPS ends with the affine substitutions -- tests/test_series_linear_cpu.py pins
+# them as its last rows, and tests/test_series_refusals.py holds OPS to gft::SERIES_OPS row by row -- so later operations are stated here.
+MORE_OPS = {o.suffix: o for o in (
+    # kind "negbin": the chain's layout with the scalars p behind x (a pointer and batch strides), the row ls where the chain has cs,
+    # and the two counts nls = order + 1 and degree_p1 (run_negbinomial)
+    _op("observe_negbinomial", "negbin", long="x", names=("a", "x", "ls"), var=True),
+    # kind "lah": the scalars p (a pointer and batch strides), the order, the result (run_lah_row).  One entry point per element
+    # type, gft[i]_series_lah_row: the operand has no series axis, so there is no series2_ spelling
+    _op("lah_row", "lah", names=("p", None)),
+)}
 F64_ONLY = ("corr", "compose_adj")  # no gfti_ twin
 RANK3 = ("mul", "div", "exp", "log", "compose", "pow")  # gft[i]_series3_*: the core operations, compose and pow
 
@@ -103,6 +113,10 @@ def _arguments(op, rank, view, e, var, k, tail):
     a = view("x", True)
     if op.kind == "chain":  # (k: the two counts nsteps, degree_p1)
         return a + (var if rank >= 2 else ()) + view("second", False) + view("cs", False) + k + view("out", True) + tail
+    if op.kind == "negbin":  # (k: the two counts nls, degree_p1)
+        return a + (var if rank >= 2 else ()) + view("second", False) + view("p", False) + view("cs", False) + k + view("out", True) + tail
+    if op.kind == "lah":  # (k: the order)
+        return view("x", False) + k + view("out", False) + tail
     if op.kind == "linear":  # (var: op.var axes)
         return a + (var if rank >= 2 else ()) + view("second", False) + view("cs", False) + view("out", True) + tail
     if op.kind == "second":
@@ -130,12 +144,14 @@ def _lib():
         L = lib()
         for pre in ("gft_", "gfti_"):  # the interval twins take the same argument lists
             for rank, mid in ((1, "series_"), (2, "series2_")):
-                for op in OPS.values():
+                for op in list(OPS.values()) + list(MORE_OPS.values()):
+                    if op.kind == "lah" and rank == 2:
+                        continue
                     if pre == "gft_" or op.suffix not in F64_ONLY:
                         f = getattr(L, pre + mid + op.suffix)
                         f.restype = C.c_int
                         f.argtypes = list(_arguments(op, rank, lambda which, lens: _view_types(rank, lens), (C.c_uint32,), (C.c_int,) * int(op.var),
-                                                     (C.c_size_t,) * (2 if op.kind == "chain" else 1), (_SZP, C.c_size_t, C.c_void_p)))
+                                                     (C.c_size_t,) * (2 if op.kind in ("chain", "negbin") else 1), (_SZP, C.c_size_t, C.c_void_p)))
         for suffix in BIGFLOAT_OPS:  # the BigFloat family: gfti_series_*'s argument lists, from the same rows
             f = getattr(L, ELEMS["bigfloat"].prefix + "series_" + suffix)
             f.restype = C.c_int
@@ -474,3 +490,95 @@ def run_linear(call, name, a, var, wvar, c, m, n=None, out=None):
                                   "under torch.no_grad() (nothing is detached silently)")
     named = (("x", aname, a, shape), ("second", "c", c, ()), ("cs", "m", m, ()))
     return _launch(what, op, call, named, out, batch, order, ((), (v, w)[:int(op.var)], ()))
+
+
+NEGBIN_MAX = {0: 8192, 1: 4096}  # gft_series_args.hpp SERIES_NEGBIN_MAX / _IV, by the planes: the limit on 3 * degree_p1 + order
+
+
+def run_negbinomial(call, a, var, x, p, ls, degree_p1=None, out=None):
+    """One call of gft[i]_series[2]_observe_negbinomial: ``a`` the operand, ``var`` the axis at rank 2, ``x`` and ``p`` one scalar per
+    item each, ``ls`` the row ``[B..., order + 1]``.  The checks come in ``run_chain``'s order."""
+    import torch
+
+    op, (module, rank, planes, limit, _raw, _kind) = MORE_OPS["observe_negbinomial"], call
+    what = f"{module}.{op.label}"
+    over_text = _rank_rules(rank)[2]
+    for t, w in ((a, "a"), (x, "x"), (p, "p"), (ls, "ls"), (out, "out")):
+        if t is None and w == "out":
+            continue
+        w = f"{what}: {w}"
+        _check(torch, t, w, planes)
+        if t is a or t is out:
+            _axes(rank, t, w, planes)
+    if ls.dim() < 1 + planes:
+        raise TaylorError(f"{what}: ls has no axis of entries; it is [{'2, ' if planes else ''}B..., order + 1]")
+    if ls.shape[-1] > 1 and ls.stride(-1) != 1:
+        raise TaylorError(f"{what}: ls: the last axis (the entries) has stride {ls.stride(-1)}; it must have unit stride")
+    shape = tuple(a.shape[-rank:])
+    count = shape[0] * shape[-1] if rank == 2 else shape[0]
+    if count > limit:
+        raise TaylorError(over_text.format(what=what, shape=shape, count=count, limit=limit).replace(": x has", ": a has"))
+    axis = -1
+    if rank == 2:
+        from .series2 import _var
+
+        axis = _var(what, var, "the variable the observation acts on is 0 (axis -2) or 1 (axis -1)") - 2
+    length, nls, on = shape[axis], int(ls.shape[-1]), f" on axis {axis}" if rank == 2 else ""
+    if nls == 0:
+        raise TaylorError(f"{what}: ls holds no entry (a row of order K has K + 1 >= 1 entries)")
+    order = nls - 1
+    d = length - order if degree_p1 is None else _count(what, "degree_p1", degree_p1)
+    if d < 3:
+        raise TaylorError(f"{what}: degree_p1 = {d} (the result needs at least three coefficients{on}: degree_p1 >= 3"
+                          + (f"; the default is {length} - order)" if degree_p1 is None else ")"))
+    if d + order > length:
+        raise TaylorError(f"{what}: degree_p1 + order = {d} + {order}, but a has {length} stored coefficients{on} (every pass takes one: "
+                          f"degree_p1 + order <= {length})")
+    if 3 * d + order > NEGBIN_MAX[planes]:
+        raise TaylorError(f"{what}: 3 * degree_p1 + order = 3 * {d} + {order} exceeds the limit of {NEGBIN_MAX[planes]} of this operation")
+    rshape = (d,) if rank == 1 else ((d, min(shape[1], d)) if axis == -2 else (min(shape[0], d), d))
+    named = [("a", a.shape[planes:a.dim() - rank]), ("x", x.shape[planes:]), ("p", p.shape[planes:]), ("ls", ls.shape[planes:-1])]
+    try:
+        batch = tuple(torch.broadcast_shapes(*[s for _, s in named]))
+    except RuntimeError:
+        raise TaylorError(f"{what}: the batch shapes do not broadcast: " + ", ".join(f"{n} has {tuple(s)}" for n, s in named)
+                          + " (x and p have the batch shape, ls the batch shape and one last axis of order + 1 entries)") from None
+    if out is not None:
+        if out.dim() < planes + rank or tuple(out.shape[-rank:]) != rshape:
+            raise TaylorError(f"{what}: out has shape {tuple(out.shape)}; the result has {rshape} coefficients per item (degree_p1 = {d}{on})")
+        if tuple(out.shape[planes:out.dim() - rank]) != batch:
+            raise TaylorError(f"{what}: out has batch shape {tuple(out.shape[planes:out.dim() - rank])}; the operands broadcast to {batch}")
+    if torch.is_grad_enabled():
+        for t, w in ((a, "a"), (x, "x"), (p, "p"), (ls, "ls")):
+            if t.requires_grad:
+                raise TaylorError(f"{what}: {w} requires grad, and observe_negbinomial has no autograd in this version; pass {w}.detach() or "
+                                  "call under torch.no_grad() (nothing is detached silently)")
+    named = (("x", "a", a, shape), ("second", "x", x, ()), ("p", "p", p, ()), ("cs", "ls", ls, (nls,)))
+    return _launch(what, op, call, named, out, batch, rshape, ((), (var,), (nls, d)))
+
+
+def run_lah_row(call, p, order, out=None):
+    """One call of gft[i]_series_lah_row: ``p`` one scalar per item, the result ``[B..., order + 1]``."""
+    import torch
+
+    op, (module, _rank, planes, limit, _raw, _kind) = MORE_OPS["lah_row"], call
+    what = f"{module}.{op.label}"
+    _check(torch, p, f"{what}: p", planes)
+    if out is not None:
+        _check(torch, out, f"{what}: out", planes)
+        _axes(1, out, f"{what}: out", planes)
+    order = _count(what, "order", order)
+    if order < 0:
+        raise TaylorError(f"{what}: order = {order} (a row has order + 1 >= 1 entries)")
+    if order + 1 > limit:
+        raise TaylorError(f"{what}: order + 1 = {order + 1} exceeds the limit of {limit} coefficients per series of this version")
+    batch = tuple(p.shape[planes:])
+    if out is not None:
+        if out.shape[-1] != order + 1:
+            raise TaylorError(f"{what}: out has shape {tuple(out.shape)}; the result has {order + 1} entries per item (order = {order})")
+        if tuple(out.shape[planes:-1]) != batch:
+            raise TaylorError(f"{what}: out has batch shape {tuple(out.shape[planes:-1])}; p has {batch}")
+    if torch.is_grad_enabled() and p.requires_grad:
+        raise TaylorError(f"{what}: p requires grad, and lah_row has no autograd in this version; pass p.detach() or call under "
+                          "torch.no_grad() (nothing is detached silently)")
+    return _launch(what, op, call, (("x", "p", p, ()),), out, batch, (order + 1,), ((), (), (order,)))

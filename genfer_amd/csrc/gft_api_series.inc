@@ -11,6 +11,9 @@
 // own scalars x and constants cs, one launch for all the steps; the kernels: gft_series_observe_chain.hip)
 // and the affine substitutions gft_series_mul_linear / compose_linear, gft_series2_mul_linear / compose_linear with their gfti_ twins
 // (every item with its own scalars c and m, one launch; the kernels: gft_series_linear.hip)
+// and the fused negative-binomial observation gft_series_observe_negbinomial / gft_series2_observe_negbinomial with the Lah row
+// gft_series_lah_row and their gfti_ twins (every item with its own scalars x and p and its own row; the kernels:
+// gft_series_observe_negbinomial.hip)
 // and the BigFloat family gftb_series_mul / div / exp / log / compose / pow (rank 1 only; w == 2 with the element kind
 // gft::SERIES_ELEM_BIGFLOAT: every stride array starts with the factor -> exponent plane stride)
 // Every entry point fills one gft::SeriesCall with its rank (gft_series_args.hpp, which judges it without the device and states the
@@ -34,12 +37,18 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
     const gft::SeriesBatch& g = a.g;
     const gft::SeriesPlanes& pl = a.pl;
     const hipStream_t cs = (hipStream_t)stream;
-    const gft::SeriesOpRow& row = gft::SERIES_OPS[op];
+    const gft::SeriesOpRow& row = gft::series_op_row(op);
     switch (row.family) {
     case gft::SERIES_CHAIN: {  // one launch for the whole chain; the derivative's factors of order 1 over the axis
         const size_t tlen = (c.rank == 2 && c.var == 0 ? it.nx[1] : it.nx[2]) - 1;
         Rc<Buf> tab = w == 2 ? Ops<EIv>::cached_table(TAB_DERIV, 1, tlen) : Ops<EF64>::cached_table(TAB_DERIV, 1, tlen);
         join_caller_in(cs);
+        if (op == gft::SERIES_OBSERVE_NEGBINOMIAL) {  // the same table; p travels beside the batch
+            R.series_last = gft::series_observe_negbinomial(R.stream, x, y, c.p.p, a.ps, a.pp, c.cs.p, res, gft::series2_dims(it), c.var, c.rank == 2,
+                                                            (unsigned)(c.cs.len[2] - 1), (unsigned)c.degree_p1, g, pl, tab->p, tlen, R.series_force);
+            join_caller_out(cs);
+            return 0;
+        }
         R.series_last = gft::series_observe_chain(R.stream, x, y, c.cs.p, res, gft::series2_dims(it), c.var, c.rank == 2, (unsigned)c.nsteps,
                                                   (unsigned)c.degree_p1, g, pl, tab->p, tlen, R.series_force);
         join_caller_out(cs);
@@ -52,6 +61,12 @@ static int series_call(const gft::SeriesCall& c, void* stream) {
         return 0;
     }
     case gft::SERIES_OBSERVE: {
+        if (op == gft::SERIES_LAH_ROW) {  // no table: the row is a recurrence on the item's own p
+            join_caller_in(cs);
+            R.series_last = gft::series_lah_row(R.stream, x, res, (unsigned)(c.r.len[2] - 1), g, pl, R.series_force);
+            join_caller_out(cs);
+            return 0;
+        }
         // the factors depend on (op, k, len) only: computed once with the reference's rounding (k_factor_table's functor) and kept.
         // A table is written on the library's stream, where the kernel below runs: its first use is ordered behind it.
         Rc<Buf> tab;
@@ -270,6 +285,28 @@ static gft::SeriesView view(const double* p, const int64_t* bs, size_t len2, int
                          (c.x = view(a, abs, na1, ars, na0), c.var = var, c.y = view(x, xbs, 1), c.cs = view(cs, cbs, nsteps),                \
                           c.nsteps = nsteps, c.degree_p1 = degree_p1, c.r = view(res, rbs, n1, rrs, n0)));                                    \
     }
+// the negative-binomial observation: the operand a (at rank 2 with the axis), the scalars x and p and the row ls (order + 1 entries)
+// of every item, then the result with degree_p1 coefficients on the axis; and the row itself from p
+#define GFT_SERIES_OBSERVE_NEGBINOMIAL(PFX, WHAT, W)                                                                                          \
+    int PFX##series_observe_negbinomial(const double* a, const int64_t* abs, size_t na, const double* x, const int64_t* xbs, const double* p,  \
+                                        const int64_t* pbs, const double* ls, const int64_t* lbs, size_t nls, size_t degree_p1, double* res,  \
+                                        const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream) {                     \
+        GFT_SERIES_ENTRY(SERIES_OBSERVE_NEGBINOMIAL, WHAT "series_observe_negbinomial", W, 1,                                                 \
+                         (c.x = view(a, abs, na), c.var = 1, c.y = view(x, xbs, 1), c.p = view(p, pbs, 1), c.cs = view(ls, lbs, nls),         \
+                          c.nsteps = nls, c.degree_p1 = degree_p1, c.r = view(res, rbs, n)));                                                 \
+    }                                                                                                                                         \
+    int PFX##series2_observe_negbinomial(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,  \
+                                         const int64_t* xbs, const double* p, const int64_t* pbs, const double* ls, const int64_t* lbs,       \
+                                         size_t nls, size_t degree_p1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1,    \
+                                         const size_t* batch, size_t nbatch, void* stream) {                                                  \
+        GFT_SERIES_ENTRY(SERIES_OBSERVE_NEGBINOMIAL, WHAT "series2_observe_negbinomial", W, 2,                                                \
+                         (c.x = view(a, abs, na1, ars, na0), c.var = var, c.y = view(x, xbs, 1), c.p = view(p, pbs, 1),                       \
+                          c.cs = view(ls, lbs, nls), c.nsteps = nls, c.degree_p1 = degree_p1, c.r = view(res, rbs, n1, rrs, n0)));            \
+    }                                                                                                                                         \
+    int PFX##series_lah_row(const double* p, const int64_t* pbs, size_t order, double* res, const int64_t* rbs, const size_t* batch,          \
+                            size_t nbatch, void* stream) {                                                                                    \
+        GFT_SERIES_ENTRY(SERIES_LAH_ROW, WHAT "series_lah_row", W, 1, (c.x = view(p, pbs, 1), c.var = 1, c.r = view(res, rbs, order + 1)));   \
+    }
 // the affine substitutions: the operand (at rank 2 with var, compose_linear also with wvar), the scalars c and m of every item, then
 // the result
 #define GFT_SERIES_LINEAR(PFX, WHAT, W)                                                                                                       \
@@ -305,6 +342,8 @@ GFT_SERIES_LINEAR(gft_, "", 1)
 GFT_SERIES_LINEAR(gfti_, "interval ", 2)
 GFT_SERIES_OBSERVE_CHAIN(gft_, "", 1)
 GFT_SERIES_OBSERVE_CHAIN(gfti_, "interval ", 2)
+GFT_SERIES_OBSERVE_NEGBINOMIAL(gft_, "", 1)
+GFT_SERIES_OBSERVE_NEGBINOMIAL(gfti_, "interval ", 2)
 GFT_SERIES_ARITH(gft_, "", 1)
 GFT_SERIES_ARITH(gfti_, "interval ", 2)
 // BigFloat (gftb_, W == 2 planes: factor, exponent): rank 1's six arithmetic operations and nothing else
@@ -335,6 +374,7 @@ int gft_series_last_form(void) { return R.series_last; }
 #undef GFT_SERIES3_ARITH
 #undef GFT_SERIES_ARITH
 #undef GFT_SERIES_OBSERVE_CHAIN
+#undef GFT_SERIES_OBSERVE_NEGBINOMIAL
 #undef GFT_SERIES_LINEAR
 #undef GFT_SERIES_OBSERVE_K
 #undef GFT_SERIES_OBSERVE

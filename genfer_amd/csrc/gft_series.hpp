@@ -126,6 +126,19 @@ int series_observe_chain(hipStream_t st, const double* a, const double* x, const
                          unsigned nsteps, unsigned degree_p1, const SeriesBatch& g, const SeriesPlanes& pl, const double* tab, size_t tab_plane,
                          int force);
 
+// ---- the fused negative-binomial observation at ranks 1 and 2, and the Lah row (gft_series_observe_negbinomial.hip) ---------------------
+// SERIES_OBSERVE_NEGBINOMIAL: order + 1 passes along the axis `var` of the operand `a` (d as for the chain), the result at degree_p1.
+// `x`, `p`: one scalar per item each, x at the batch strides g.ys (planes pl.y apart), p at `pstrides` over the same collapsed axes
+// (planes pplane apart); `ls`: order + 1 entries per item at g.ss, unit stride (planes pl.s apart).  `tab`: the k_factor_table
+// factors of (TAB_DERIV, 1, at least degree_p1 + order - 1).  `force` as for series_plan: form A (one wave per line) holds up to 64
+// coefficients of degree_p1 + order.  One launch, no workspace; returns the form.
+int series_observe_negbinomial(hipStream_t st, const double* a, const double* x, const double* p, const size_t* pstrides, size_t pplane, const double* ls,
+                               double* res, const Series2Dims& d, int var, bool rank2, unsigned order, unsigned degree_p1, const SeriesBatch& g,
+                               const SeriesPlanes& pl, const double* tab, size_t tab_plane, int force);
+// SERIES_LAH_ROW: `p` one scalar per item at g.xs (planes pl.x apart), the result order + 1 entries per item at g.rs.  Form A (one
+// wave per item) holds rows of up to 64 entries.  One launch; returns the form.
+int series_lah_row(hipStream_t st, const double* p, double* res, unsigned order, const SeriesBatch& g, const SeriesPlanes& pl, int force);
+
 // ---- the affine substitutions at ranks 1 and 2 (gft_series_linear.hip) -----------------------------------------------------------------
 // SERIES_MUL_LINEAR: a times c + m * x_var; SERIES_COMPOSE_LINEAR: x_var := c + m * x_wvar in f.  d: the operand's stored shape and row
 // stride, the result's shape and row stride (rank 1: one row, var == wvar == 1).  `c`, `m`: one scalar per item each at the batch

@@ -48,7 +48,20 @@ enum SeriesOp {
     // compose_linear (subst_var's linear paths, mt:555-579): x_var := c + m * x_wvar.
     SERIES_MUL_LINEAR = 13,
     SERIES_COMPOSE_LINEAR = 14,
-    SERIES_OP_COUNT  // (no operation: the length of SERIES_OPS)
+    SERIES_OP_COUNT,  // (no operation: the length of SERIES_OPS, the table the Python layer's OPS mirrors row by row)
+    // The operations behind the table: their rows are SERIES_MORE_OPS.  SERIES_OPS ends with the affine substitutions -- the tests of
+    // that layer pin them as the last rows of the Python table, and the two tables are held together row by row -- so an operation
+    // added later is stated here, and series_op_row() finds the row of either kind.
+    // The fused negative-binomial observation (gft_series_observe_negbinomial.hip; generating_function.rs:731-750): order + 1 passes of
+    // the scaling substitution x_v := p * x_v, the product with (p * x + p * x_v)^i, the scaling by the row's entry, the accumulation
+    // and a derivative.  x is the operand `a` and the LONG side, y the scalars x and the view `p` the scalars p (one element per item
+    // each), cs the row ls with len[2] = order + 1.  Of the chain's family: the result has degree_p1 coefficients on the axis.
+    SERIES_OBSERVE_NEGBINOMIAL = SERIES_OP_COUNT + 1,
+    // The row of scaled Lah numbers such an observation sums with (generating_function.rs:713-730): x is the scalar p of every item
+    // (no series axis: len 1), the result the row of order + 1 entries.  One entry point (gft[i]_series_lah_row): the operand has no
+    // rank, and `ranks` below only says that rank 3 keeps its refusal.
+    SERIES_LAH_ROW,
+    SERIES_OP_END  // (no operation: one past the last of SERIES_MORE_OPS)
 };
 
 // One row per SeriesOp.  family: what series_call dispatches on.  ranks: the highest rank the op exists at.  x / y / cs: the
@@ -88,6 +101,13 @@ constexpr SeriesOpRow SERIES_OPS[] = {
     {SERIES_MUL_LINEAR, SERIES_LINEAR, 2, "a", "c", "m", SERIES_Y_SCALAR, SERIES_CS_SCALAR, false, false, false},
     {SERIES_COMPOSE_LINEAR, SERIES_LINEAR, 2, "f", "c", "m", SERIES_Y_SCALAR, SERIES_CS_SCALAR, false, false, false},
 };
+// the rows of the operations behind SERIES_OP_COUNT, in the enum's order
+constexpr SeriesOpRow SERIES_MORE_OPS[] = {
+    // (the negative-binomial observation: the chain's family with its own rules and a required x; its fourth operand is SeriesCall::p)
+    {SERIES_OBSERVE_NEGBINOMIAL, SERIES_CHAIN, 2, "a", "x", "ls", SERIES_Y_SCALAR, SERIES_CS_CONSTANTS, true, false, false},
+    // (one operand, as the observation ops; the result is the long side and never the operand)
+    {SERIES_LAH_ROW, SERIES_OBSERVE, 2, "p", "-", "-", SERIES_Y_NONE, SERIES_CS_NONE, false, false, false},
+};
 constexpr bool series_ops_in_enum_order() {
     for (int i = 0; i < (int)(sizeof(SERIES_OPS) / sizeof(SERIES_OPS[0])); ++i)
         if (SERIES_OPS[i].op != i) return false;
@@ -95,6 +115,15 @@ constexpr bool series_ops_in_enum_order() {
 }
 static_assert(sizeof(SERIES_OPS) / sizeof(SERIES_OPS[0]) == SERIES_OP_COUNT && series_ops_in_enum_order(),
               "SERIES_OPS has one row per SeriesOp, in the enum's order (tests/make_series_refusals.py indexes the ops by position)");
+static_assert(sizeof(SERIES_MORE_OPS) / sizeof(SERIES_MORE_OPS[0]) == SERIES_OP_END - SERIES_OBSERVE_NEGBINOMIAL &&
+                  SERIES_MORE_OPS[0].op == SERIES_OBSERVE_NEGBINOMIAL && SERIES_MORE_OPS[1].op == SERIES_LAH_ROW,
+              "SERIES_MORE_OPS has one row per operation behind SERIES_OP_COUNT, in the enum's order");
+// the row of an operation of either table (an op outside both: std::logic_error, a caller's mistake and no refusal)
+inline const SeriesOpRow& series_op_row(int op) {
+    if (op >= 0 && op < SERIES_OP_COUNT) return SERIES_OPS[op];
+    if (op >= SERIES_OBSERVE_NEGBINOMIAL && op < SERIES_OP_END) return SERIES_MORE_OPS[op - SERIES_OBSERVE_NEGBINOMIAL];
+    throw std::logic_error("series_op_row: no such operation");
+}
 
 constexpr unsigned SERIES_MAX_N = 4096;  // the limit of this first version (form B's mul and div hold a row pair in 64 KB of LDS)
 // Interval<F64> series (gfti_series_*): two planes per row, so the same LDS footprints are reached at half the order
@@ -105,6 +134,10 @@ constexpr unsigned SERIES2_MAX_ELEMS_IV = 2048;
 constexpr unsigned SERIES3_MAX_ELEMS = 4096;  // n0 * n1 * n2 of the result: the two-arrays-in-64-KB footprint of rank 2
 // Interval<F64> items (gfti_series3_*): 16-byte LDS elements, the same 64 KB at half that
 constexpr unsigned SERIES3_MAX_ELEMS_IV = 2048;
+// SERIES_OBSERVE_NEGBINOMIAL's own limit on 3 * degree_p1 + order: the lines D (degree_p1 + order elements), S and P (degree_p1 each)
+// of its form B lie in the 64 KB of dynamic LDS every kernel may have (8-byte elements, 16-byte for Interval<F64>)
+constexpr unsigned SERIES_NEGBIN_MAX = 8192;
+constexpr unsigned SERIES_NEGBIN_MAX_IV = 4096;
 // the most coefficients of an item's long side, by the rank (1, 2, 3) and the element width (1: F64, 2: Interval<F64>)
 inline unsigned series_limit(int rank, int w) {
     constexpr unsigned most[3][2] = {{SERIES_MAX_N, SERIES_MAX_N_IV}, {SERIES2_MAX_ELEMS, SERIES2_MAX_ELEMS_IV}, {SERIES3_MAX_ELEMS, SERIES3_MAX_ELEMS_IV}};
@@ -184,14 +217,18 @@ struct SeriesCall {
     const size_t* batch = nullptr;
     size_t nbatch = 0;
     SeriesView x, y, r, cs;
+    SeriesView p;  // SERIES_OBSERVE_NEGBINOMIAL: the scalars p, one element per item as y
 };
 
 // What series_args makes of an accepted call: the collapsed batch, the plane strides and the item -- the lengths narrowed to
 // unsigned (exact: the limits have been judged) with the strides of the series axes.
+// `ps` / `pp`: the batch strides of SeriesCall::p over the collapsed axes and its plane stride (zeros where the op has no p).
 struct SeriesArgs {
     SeriesBatch g;
     SeriesPlanes pl;
     SeriesItem it;
+    size_t ps[IMAXD] = {};
+    size_t pp = 0;
 };
 
 struct SeriesOperand {  // a view with its strides judged: batch strides in elements, the span it covers
@@ -249,7 +286,7 @@ static inline void series_linear_shapes(const SeriesCall& c) {
     using std::to_string;
     const std::string f(c.fn);
     const bool r2 = c.rank > 1, comp = c.op == SERIES_COMPOSE_LINEAR;
-    const char* const who = SERIES_OPS[c.op].x;
+    const char* const who = series_op_row(c.op).x;
     if (r2 && (c.var < 0 || c.var > 1))
         throw std::runtime_error(f + ": var = " + to_string(c.var) + (comp ? " (the variable of f that is replaced is 0 or 1)" : " (the variable of the linear factor is 0 or 1)"));
     if (r2 && comp && (c.wvar < 0 || c.wvar > 1))
@@ -284,7 +321,7 @@ static inline void series_linear_shapes(const SeriesCall& c) {
 static inline void series_shapes(const SeriesCall& c) {
     using std::to_string;
     const std::string f(c.fn);
-    const SeriesOpRow& row = SERIES_OPS[c.op];
+    const SeriesOpRow& row = series_op_row(c.op);
     const int op = c.op, rank = c.rank;
     if (c.elem == SERIES_ELEM_BIGFLOAT) {  // the BigFloat family: rank 1, the six arithmetic operations, two planes
         if (rank != 1) throw std::runtime_error(f + ": BigFloat series exist at rank 1 only in this version (rank " + to_string(rank) + " was asked for)");
@@ -296,6 +333,14 @@ static inline void series_shapes(const SeriesCall& c) {
     if (rank == 3 && ((c.w != 1 && c.w != 2) || row.ranks < 3))
         throw std::runtime_error(f + ": no such operation at rank 3 in this version (mul / div / exp / log on f64)");
     if (row.family == SERIES_LINEAR) return series_linear_shapes(c);
+    if (op == SERIES_LAH_ROW) {  // the one rule: order + 1 entries within the rank-1 limit (the operand is one scalar per item)
+        const size_t most = series_limit(1, c.w);
+        if (c.r.len[2] == 0 || c.r.len[2] > most)
+            throw std::runtime_error(f + ": order + 1 = " + (c.r.len[2] ? to_string(c.r.len[2]) : std::string("2^64")) + " exceeds the limit of " + to_string(most) +
+                                     " coefficients per series of this version");
+        return;
+    }
+    const bool negbin = op == SERIES_OBSERVE_NEGBINOMIAL;
     const bool chain = row.family == SERIES_CHAIN, observe = chain || row.family == SERIES_OBSERVE;
     const bool corr = op == SERIES_CORR, adj = op == SERIES_COMPOSE_ADJ, binary = row.yrole == SERIES_Y_SERIES, xlong = row.xlong;
     const bool r2 = rank > 1, bad_var = r2 && (c.var < 0 || c.var >= rank);
@@ -342,6 +387,24 @@ static inline void series_shapes(const SeriesCall& c) {
         if (chain) {  // degree_p1 + nsteps <= L_0: step t then runs at d_t = degree_p1 + (nsteps - 1 - t) on a line of d_t + 1
             const size_t L0 = rows ? c.x.len[1] : c.x.len[2], other = rows ? c.x.len[2] : c.x.len[1], d = c.degree_p1;
             const std::string on = r2 ? " on axis " + to_string(c.var) : std::string();
+            if (negbin) {  // order = K: pass i reads d coefficients of the i-th derivative, so degree_p1 + K <= L_0; the powers need d >= 3
+                const size_t n = c.cs.len[2], own = c.w == 2 ? SERIES_NEGBIN_MAX_IV : SERIES_NEGBIN_MAX;
+                if (n == 0) throw std::runtime_error(f + ": ls holds no entry (a row of order K has K + 1 >= 1 entries)");
+                if (d < 3)
+                    throw std::runtime_error(f + ": degree_p1 = " + to_string(d) + " (the result needs at least three coefficients" + on +
+                                             ": degree_p1 >= 3; at two the reference multiplies by a linear power in every pass, a form this version leaves out)");
+                if (d > L0 || n - 1 > L0 - d)
+                    throw std::runtime_error(f + ": degree_p1 + order = " + to_string(d) + " + " + to_string(n - 1) + ", but a has " + to_string(L0) +
+                                             " stored coefficients" + on + " (every pass takes one: degree_p1 + order <= " + to_string(L0) + ")");
+                if (3 * d + (n - 1) > own)
+                    throw std::runtime_error(f + ": 3 * degree_p1 + order = 3 * " + to_string(d) + " + " + to_string(n - 1) + " exceeds the limit of " + to_string(own) +
+                                             " of this operation (three lines of a pass lie in 64 KB of LDS)");
+                const size_t o = std::min(other, d), w0 = rows ? d : o, w1 = rows ? o : d;
+                if (c.r.len[1] != (r2 ? w0 : 1) || c.r.len[2] != w1)
+                    throw std::runtime_error(f + ": the result has " + (r2 ? to_string(c.r.len[1]) + " x " : std::string()) + to_string(c.r.len[2]) +
+                                             " coefficients; with degree_p1 = " + to_string(d) + " it has " + (r2 ? to_string(w0) + " x " : std::string()) + to_string(w1));
+                return;
+            }
             if (c.nsteps == 0) throw std::runtime_error(f + ": nsteps = 0 (cs holds no constants: a chain has at least one step)");
             if (d < 2) throw std::runtime_error(f + ": degree_p1 = " + to_string(d) + " (the result needs at least two coefficients" + on + ": degree_p1 >= 2)");
             if (d > L0 || c.nsteps > L0 - d)
@@ -382,7 +445,7 @@ static inline void series_shapes(const SeriesCall& c) {
 template <class CheckPtr>
 static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& check_ptr) {
     const std::string f(c.fn);
-    const SeriesOpRow& row = SERIES_OPS[c.op];
+    const SeriesOpRow& row = series_op_row(c.op);
     const int w = c.w;
     const size_t* batch = c.batch;
     const size_t nbatch = c.nbatch;
@@ -399,8 +462,10 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     const SeriesOperand ay = series_arg(c, row.y, c.y);
     const SeriesOperand ar = series_arg(c, "the result", c.r);
     const SeriesOperand ac = series_arg(c, row.cs, c.cs);
+    const bool has_p = c.op == SERIES_OBSERVE_NEGBINOMIAL;
+    const SeriesOperand ap = series_arg(c, "p", c.p);  // (the default view where the op has none: nothing about it can be refused)
     // y is read where the op has one and, where it is optional (the seeds, the chain's x), it is given; cs where the op has one
-    const bool optional = row.yrole == SERIES_Y_SEEDS || row.family == SERIES_CHAIN;
+    const bool optional = row.yrole == SERIES_Y_SEEDS || (row.family == SERIES_CHAIN && !has_p);
     const bool has_y = row.yrole != SERIES_Y_NONE && (ay.p || !optional), has_cs = row.csrole != SERIES_CS_NONE;
     if (c.elem == SERIES_ELEM_BIGFLOAT) {  // a point interval reads one plane twice; a factor plane cannot be its own exponent plane
         const SeriesOperand* const read[2] = {&ax, has_y ? &ay : nullptr};  // (the result's is refused below, for intervals too)
@@ -440,6 +505,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     check_ptr(ax.p, ax.what);
     if (has_y) check_ptr(ay.p, ay.what);
     if (has_cs) check_ptr(ac.p, ac.what);
+    if (has_p) check_ptr(ap.p, ap.what);
     check_ptr(ar.p, ar.what);
     // the result may be an input itself (the same view: every row is read before it is written); any other overlap is refused.
     // Judged by address ranges, so two interleaved views of one buffer count as overlapping.
@@ -455,6 +521,7 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     overlap(ax, row.alias_x);
     if (has_cs) overlap(ac, false);
     if (has_y) overlap(ay, row.alias_y);
+    if (has_p) overlap(ap, false);
     // collapse the batch: unit axes go, axes contiguous with their inner neighbour on every operand merge
     SeriesBatch& g = out.g;
     g.nd = 0;
@@ -466,9 +533,10 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
     for (size_t i = 0; i < nbatch; ++i) {
         if (batch[i] == 1) continue;
         const size_t e = batch[i], sx = ax.st[i], sy = as_y ? as_y->st[i] : 0, ss = as_s ? as_s->st[i] : 0, sr = ar.st[i];
+        const size_t sp = has_p ? ap.st[i] : 0;
         int p = g.nd - 1;
         // (merged extents stay below 2^31: items does)
-        if (p >= 0 && g.xs[p] == sx * e && g.ys[p] == sy * e && g.ss[p] == ss * e && g.rs[p] == sr * e) {
+        if (p >= 0 && g.xs[p] == sx * e && g.ys[p] == sy * e && g.ss[p] == ss * e && g.rs[p] == sr * e && out.ps[p] == sp * e) {
             g.ext[p] *= (unsigned)e;
         } else {
             // (the workspace copies add the series axis, and for intervals the plane axis, to these; pow's copy every series axis of the rank)
@@ -477,8 +545,9 @@ static inline bool series_args(const SeriesCall& c, SeriesArgs& out, CheckPtr&& 
             p = g.nd++;
             g.ext[p] = (unsigned)e;
         }
-        g.xs[p] = sx, g.ys[p] = sy, g.ss[p] = ss, g.rs[p] = sr;
+        g.xs[p] = sx, g.ys[p] = sy, g.ss[p] = ss, g.rs[p] = sr, out.ps[p] = sp;
     }
+    out.pp = has_p ? ap.plane : 0;
     out.pl.w = w;
     out.pl.elem = c.elem;
     out.pl.x = ax.plane;

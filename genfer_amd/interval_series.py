@@ -101,6 +101,21 @@ def observe_chain(a, x, cs, degree_p1=None, out=None):
     return run_chain(_OBSERVE, a, None, x, cs, degree_p1, out)
 
 
+def lah_row(p, order, out=None):
+    """``series.lah_row`` over intervals: ``p`` is ``[2, B...]``, the result ``[2, B..., order + 1]``."""
+    from ._series_call import run_lah_row
+
+    return run_lah_row(_OBSERVE, p, order, out)
+
+
+def observe_negbinomial(a, x, p, ls, degree_p1=None, out=None):
+    """``series.observe_negbinomial`` over intervals: ``a`` is ``[2, B..., L]``, ``x`` and ``p`` ``[2, B...]``, ``ls``
+    ``[2, B..., k + 1]``; ``3 * degree_p1 + k <= 4096``.  A scalar counts as 0 or 1 when both of its bounds are."""
+    from ._series_call import run_negbinomial
+
+    return run_negbinomial(_OBSERVE, a, None, x, p, ls, degree_p1, out)
+
+
 def mul_linear(a, c, m, n=None, out=None):
     """``series.mul_linear`` over intervals: ``a`` is ``[2, B..., L]``, ``c`` and ``m`` ``[2, B...]``; every product and sum is the
     reference's interval operation, and ``c`` counts as 0 when both of its bounds are."""

@@ -99,6 +99,14 @@ def observe_chain(a, var, x, cs, degree_p1=None, out=None):
     return run_chain(_CALL, a, var, x, cs, degree_p1, out)
 
 
+def observe_negbinomial(a, var, x, p, ls, degree_p1=None, out=None):
+    """``series2.observe_negbinomial`` over intervals: ``a`` is ``[2, B..., n0, n1]``, ``x`` and ``p`` ``[2, B...]``, ``ls``
+    ``[2, B..., k + 1]`` (from ``interval_series.lah_row``)."""
+    from ._series_call import run_negbinomial
+
+    return run_negbinomial(_CALL, a, var, x, p, ls, degree_p1, out)
+
+
 def mul_linear(a, var, c, m, n=None, out=None):
     """``series2.mul_linear`` over intervals: ``a`` is ``[2, B..., n0, n1]``, ``c`` and ``m`` ``[2, B...]``."""
     from ._series_call import run_linear

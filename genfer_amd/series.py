@@ -219,6 +219,27 @@ def observe_chain(a, x, cs, degree_p1=None, out=None):
     return run_chain(_CALL, a, None, x, cs, degree_p1, out)
 
 
+def lah_row(p, order, out=None):
+    """The row of scaled Lah numbers ``observe k ~ NegBinomial(X, p)`` sums with (generating_function.rs:713-730): ``p`` is ``[B...]``
+    (any strides), the result ``[B..., order + 1]``.  ``row_0 = [1]`` and ``row_d[i] = ((1 - p) / d) * (row_{d-1}[i] * (d + i - 1) +
+    row_{d-1}[i - 1])`` with the absent entries zero, multiplied by and added all the same.  One launch; no autograd."""
+    from ._series_call import run_lah_row
+
+    return run_lah_row(_CALL, p, order, out)
+
+
+def observe_negbinomial(a, x, p, ls, degree_p1=None, out=None):
+    """The fused negative-binomial observation ``observe k ~ NegBinomial(X, p)`` with ``k = ls.shape[-1] - 1`` in one launch: ``a`` is
+    the inner generating function evaluated at ``p * x`` to ``degree_p1 + k`` coefficients, ``x`` and ``p`` one scalar per item,
+    ``ls`` the row ``[B..., k + 1]`` (usually ``lah_row(p, k)``).  Pass ``i`` scales coefficient ``j`` of the ``i``-th derivative by
+    ``p ** j``, multiplies by ``(p * x + p * t) ** i``, scales by ``ls[..., i]`` and adds (``include/gftaylor.h`` states the loops).
+    ``degree_p1`` (default ``L - k``) is the result's length; ``degree_p1 >= 3``, ``degree_p1 + k <= L`` and
+    ``3 * degree_p1 + k <= 8192``.  No autograd in this version."""
+    from ._series_call import run_negbinomial
+
+    return run_negbinomial(_CALL, a, None, x, p, ls, degree_p1, out)
+
+
 def mul_linear(a, c, m, n=None, out=None):
     """``a`` times the linear series ``c + m * t`` as the reference multiplies by one (``mul_linear``; ``include/gftaylor.h`` states the
     loop): ``out[j] = a[j-1] * m + c * a[j]``, the sum and the second product absent where ``c == 0`` (by value, per item).  ``c``, ``m``:

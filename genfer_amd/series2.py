@@ -180,6 +180,14 @@ def observe_chain(a, var, x, cs, degree_p1=None, out=None):
     return run_chain(_CALL, a, var, x, cs, degree_p1, out)
 
 
+def observe_negbinomial(a, var, x, p, ls, degree_p1=None, out=None):
+    """``series.observe_negbinomial`` along variable ``var`` (0: axis -2, 1: axis -1) of every item: each line along that axis runs the
+    passes, the other axis is cut to ``min(len, degree_p1)``.  The row comes from ``series.lah_row``."""
+    from ._series_call import run_negbinomial
+
+    return run_negbinomial(_CALL, a, var, x, p, ls, degree_p1, out)
+
+
 def mul_linear(a, var, c, m, n=None, out=None):
     """``a`` times the linear series ``c + m * x_var`` (``var`` 0: axis -2, 1: axis -1): ``series.mul_linear`` on every line along that
     axis.  ``n`` (default: ``a``'s shape with one more on the axis) is the result's order, a pair."""

@@ -457,6 +457,50 @@ int gft_series2_observe_chain(const double* a, const int64_t* abs, int64_t ars, 
                               const int64_t* xbs, const double* cs, const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res,
                               const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
 
+/* ---- batched fused negative-binomial observation: what `observe k ~ NegBinomial(X, p)` runs (generating_function.rs:712-751), per
+ * item and in one launch each: the row of scaled Lah numbers, and the sum over it.
+ *
+ * gft_series_lah_row: p has the batch shape (strides pbs, stride 0 allowed), the result is [B..., order + 1] (unit stride on its last
+ * axis, batch strides rbs).  row_0 = [1];  for d = 1 .. order, i = 0 .. d:
+ *       row_d[i] = ((1 - p) / from(d)) * (row_{d-1}[i] * from(d + i - 1) + row_{d-1}[i - 1])
+ * where an entry row_{d-1} does not have is zero -- and is multiplied by and added all the same (-0.0, intervals).  order + 1 <= 4096.
+ * The result may not overlap p.  gft_series_last_form(): 1 (one wave per item: order + 1 <= 64) or 2 (one workgroup per item).
+ *
+ * gft_series_observe_negbinomial / gft_series2_observe_negbinomial: a is the inner generating function evaluated at p * x to
+ * degree_p1 + K coefficients on the acted-on axis v (rank 1: the series; rank 2: `var`), x and p one scalar per item each (strides
+ * xbs, pbs), ls [B..., nls] the row, nls = K + 1 (unit stride on its last axis, batch strides lbs; usually gft_series_lah_row(p, K),
+ * but any row).  With d = degree_p1 and L the stored length on v, per item:
+ *   c = p * x, m = p * 1 -- but c = x, m = 1 where p == 1                     (from(p) * var(v, x, d): Mul returns var itself)
+ *   pf[0] = 1, pf[j + 1] = pf[j] * m                                          (subst_var's power table, mt:555-567)
+ *   P_1 = [c, m];  P_{i+1} = mul_linear(P_i, c, m) at length min(d, i + 2)    (gft_series_mul_linear's loops)
+ * and per line along v (of a rank-2 item the first min(other axis, d) lines), D_0 = a[0 .. d + K):
+ *   for i = 0 .. K:
+ *       S[j] = D_i[j] * pf[j],  j < d
+ *       i == 0:  U = S;   i == 1:  U = mul_linear(S, c, m) at length d
+ *       i >= 2:  U[j] = 0 + (((0 + S[lo] * P_i[j - lo]) + ...) + S[j] * P_i[0]),  lo = max(0, j + 1 - len P_i)   (mul_1d, mt:971-982)
+ *                -- but where the lines are the columns of a rank-2 item with more than one line the product walks the rows, every
+ *                term passes through a sum of its own:  U[j] = ((0 + (0 + S[lo] * P_i[j - lo])) + ...) + (0 + S[j] * P_i[0])
+ *       V = ls[i] == 1 ? U : ls[i] * U;   ls[i] == 0:  V is the one-coefficient zero
+ *       i == 0:  sum = V (all +0.0 for the zero), then sum[first] = sum[first] + 0 on the item's first element
+ *       i >= 1:  sum[j] = (0 + sum[j]) + V[j];  against the zero only sum[first] = sum[first] + 0
+ *       D_{i+1}[j] = D_i[j + 1] * ff_j                                        (derivative, the chain's ff; not after the last pass)
+ * `==` compares values (-0.0 counts as zero; an interval equals 0 or 1 when both bounds do).  The tests of p, c and ls[i] are made per
+ * item on the device and are the only data-dependent branches; no shortcut looks at the coefficients.
+ * Shape rules, refused by name before the device is touched, in this order: nls >= 1, degree_p1 >= 3, degree_p1 + K <= L,
+ * 3 * degree_p1 + K <= 8192, and the result's shape: degree_p1 coefficients on v and min(len, degree_p1) on the other axis of a rank-2
+ * item.  The limits bound the operand (na <= 4096, na0 * na1 <= 4096).  The result may not overlap a, x, p or ls.  Strides, empty
+ * batches, the stream contract and return values: those of gft_series_mul.  One launch per call, no workspace;
+ * gft_series_last_form() reports 1 (one wave per line: degree_p1 + K <= 64) or 2 (one workgroup per line), "series_form" forces 2. */
+int gft_series_lah_row(const double* p, const int64_t* pbs, size_t order, double* res, const int64_t* rbs, const size_t* batch, size_t nbatch,
+                       void* stream);
+int gft_series_observe_negbinomial(const double* a, const int64_t* abs, size_t na, const double* x, const int64_t* xbs, const double* p,
+                                   const int64_t* pbs, const double* ls, const int64_t* lbs, size_t nls, size_t degree_p1, double* res,
+                                   const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gft_series2_observe_negbinomial(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,
+                                    const int64_t* xbs, const double* p, const int64_t* pbs, const double* ls, const int64_t* lbs, size_t nls,
+                                    size_t degree_p1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch,
+                                    size_t nbatch, void* stream);
+
 /* ---- batched affine substitutions: what the reference runs wherever a series is multiplied by, or a variable replaced with, the
  * affine series c + m * x_w (X ~ Binomial(Y, p), X += Y, thinning, marginalising to a point, a Taylor shift) -- mul_linear
  * (mt:611-623) and subst_var's two linear paths (mt:555-579) on caller-owned device tensors, per item and in one launch, at ranks 1
@@ -801,6 +845,18 @@ int gfti_series_observe_chain(const double* a, const int64_t* abs, size_t na, co
 int gfti_series2_observe_chain(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,
                                const int64_t* xbs, const double* cs, const int64_t* cbs, size_t nsteps, size_t degree_p1, double* res,
                                const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch, size_t nbatch, void* stream);
+/* The negative-binomial observation over Interval<F64>: the three calls above on (lo, hi) planes, the plane stride first in every
+ * stride array; p and x are [2, B...], ls and the Lah row [2, B..., K + 1].  The same loops in the reference's Interval operations.
+ * The limits: order + 1 <= 2048; na <= 2048, na0 * na1 <= 2048 and 3 * degree_p1 + K <= 4096. */
+int gfti_series_lah_row(const double* p, const int64_t* pbs, size_t order, double* res, const int64_t* rbs, const size_t* batch, size_t nbatch,
+                        void* stream);
+int gfti_series_observe_negbinomial(const double* a, const int64_t* abs, size_t na, const double* x, const int64_t* xbs, const double* p,
+                                    const int64_t* pbs, const double* ls, const int64_t* lbs, size_t nls, size_t degree_p1, double* res,
+                                    const int64_t* rbs, size_t n, const size_t* batch, size_t nbatch, void* stream);
+int gfti_series2_observe_negbinomial(const double* a, const int64_t* abs, int64_t ars, size_t na0, size_t na1, int var, const double* x,
+                                     const int64_t* xbs, const double* p, const int64_t* pbs, const double* ls, const int64_t* lbs, size_t nls,
+                                     size_t degree_p1, double* res, const int64_t* rbs, int64_t rrs, size_t n0, size_t n1, const size_t* batch,
+                                     size_t nbatch, void* stream);
 /* The affine substitutions over Interval<F64>: gft_series_mul_linear / gft_series_compose_linear and their rank-2 twins on (lo, hi)
  * planes, the plane stride first in every stride array; c and m are [2, B...].  The same loops, every * and + the reference's Interval
  * operation with its own short-circuits; c equals 0 when both of its bounds do.  The limits on the result are n <= 2048 and
